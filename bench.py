@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of one MTLoRA train step (BASELINE.json metric) on N MI355X.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3 [--config c2]
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--config c2] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,13 +10,18 @@ HRNet heads + weighted multi-task loss, backward, [RCCL all-reduce of the traina
 AdamW, zero_grad -- dropout 0.05 and DropPath 0.2 active (train mode).  Per-GPU batch is fixed (weak scaling); inputs
 are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps (`ms_per_step` = their wall
+time / K), the optional --dump-outputs DIR (the last timed step's loss, gradient norm and updated model state as .npy;
+model, batch and RNG are seeded, so the same arguments give the same inputs on every run), the line.  --full adds the
+objects below, each measured after the timed steps.
+
 --config selects a row of mtlora_amd.mtl_harness.CONFIGS (the BASELINE.json configs):
     c2 (default)  Swin-T/448, 4 tasks, r_shared 64 / r_task 4, B=32      <- the configuration the metric is quoted on
     c1            Swin-T/224, 1 task, r=4, B=2 (the reference's CPU-runnable plumbing case)
     c4            Swin-B/448, 4 tasks, r=128 shared and per task, B=16   (near machine balance)
     c5:<r>        Swin-T/448, 8 synthetic tasks, r in {4,16,64,256}      (skinny-GEMM HBM regime)
 
-Extra objects in the line (this tier's contract):
+Extra objects in the line with --full (this tier's contract):
   roofline      the dominant HIP kernel (k_nt, the fused MTLoRALinear GEMM), HOT-PATH launches only (the callers' plain
                 rank-0 GEMMs have their own kinds): SURVEY 8(d) algorithmic bytes / their HIP-event durations, measured
                 over extra profiled steps right after the timed region (events on the launch stream; mtlora_prof_begin).
@@ -55,6 +60,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c2", help="c1 | c2 (default, the BASELINE metric) | c4 | c5:<r>")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs around the headline figure: roofline, other_configs, eager_gpu, cpu_baseline "
+                         "(each can be dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step left to its caller as DIR/<name>.npy (float32, < 64 MB)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--roofline-steps", type=int, default=0, help="steps of the profiled leg (default: min(max(steps, 2), 5); tools/pmc.sh uses 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -71,7 +81,7 @@ def parse():
                          "and letting them migrate over a 256-core host costs 0.4-2.5 %% (DESIGN.md 7); 0 = leave the affinity alone")
     ap.add_argument("--eager-leg", default="", help=argparse.SUPPRESS)  # child process of the eager_gpu leg: --eager-leg <config> --batch B
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short c4 / c5:4 legs the default (c2, 1 GPU) run appends under `other_configs`")
+                    help="skip the short c4 / c5:4 legs a --full c2 run on 1 GPU appends under `other_configs`")
     return ap.parse_args()
 
 
@@ -97,14 +107,16 @@ def barrier(world):
 
 
 def time_steps(step_fn, steps, warmup, world):
+    """(wall time of `steps` steps, host issue time, what the last timed step returned)"""
     for _ in range(warmup):
         step_fn()
     barrier(world)
     t0 = time.perf_counter()
     host = 0.0
+    out = None
     for _ in range(steps):
         h0 = time.perf_counter()
-        step_fn()
+        out = step_fn()
         host += time.perf_counter() - h0   # time the host spends ISSUING a step (no sync inside the step)
     t_issue = time.perf_counter() - t0
     barrier(world)
@@ -114,7 +126,32 @@ def time_steps(step_fn, steps, warmup, world):
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
-    return dt, t_issue
+    return dt, t_issue, out
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # (--dump-outputs stays under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, model, last):
+    """--dump-outputs: what a caller of the timed step holds after its last step, as float32 .npy files: the loss and the clipped
+    gradient norm it returns, and the model state it updated in place (every trainable parameter after AdamW, the BatchNorm running
+    statistics).  Above DUMP_BUDGET_BYTES every tensor is reduced to the same fraction of its elements, picked by a fixed seed."""
+    import numpy as np
+    loss, norm = last if isinstance(last, tuple) else (last, None)
+    arrays = {"loss": loss}
+    if norm is not None:
+        arrays["grad_norm"] = norm
+    arrays.update(("param." + n, p) for n, p in model.named_parameters() if p.requires_grad)
+    arrays.update(("buffer." + n, b) for n, b in model.named_buffers() if n.endswith(("running_mean", "running_var")))
+    frac = min(1.0, DUMP_BUDGET_BYTES / (4.0 * sum(t.numel() for t in arrays.values())))
+    g = torch.Generator().manual_seed(0)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        if frac < 1.0 and t.numel() > 1:
+            t = t.reshape(-1)[torch.randperm(t.numel(), generator=g)[:max(1, int(t.numel() * frac))].sort().values]
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+    print(f"bench: {len(arrays)} arrays ({frac:.4f} of their elements) written to {out_dir}", file=sys.stderr)
 
 
 def _static_traffic(cfg_name, n_hot, n_all):
@@ -331,8 +368,9 @@ def cpu_baseline(cfgrow):
             "sample": f"{cfgrow['what']}: train step, B={B}, fp32, 1 warm-up + {k} timed steps ({dt:.2f} s/step)"}
 
 
-def run_config(args, name, rank, world, dev, steps, warmup, want_roofline, batch=0):
-    """build the config's model, time `steps` train steps, optionally profile the library launches.  Returns (row, B, ips, fields)."""
+def run_config(args, name, rank, world, dev, steps, warmup, want_roofline, batch=0, dump_dir=""):
+    """build the config's model, time `steps` train steps, optionally dump the last step's outputs and profile the library launches.
+    Returns (row, B, ips, fields)."""
     from mtlora_amd import mtl_harness as H
     from mtlora_amd.ddp import GradReducer
     row = H.config(name)
@@ -352,8 +390,8 @@ def run_config(args, name, rank, world, dev, steps, warmup, want_roofline, batch
     torch.manual_seed(1234 + rank)
 
     def eager_step():
-        H.train_step(model, crit, opt, img, tg, clip_grad=5.0, reducer=reducer, amp_dtype=torch.bfloat16,
-                     fused_loss=not args.no_fused_loss)
+        return H.train_step(model, crit, opt, img, tg, clip_grad=5.0, reducer=reducer, amp_dtype=torch.bfloat16,
+                            fused_loss=not args.no_fused_loss)
 
     graph_info = {"enabled": False, "why": "eager multi-stream step (default; --graph replays a captured HIP graph)"}
     step = eager_step
@@ -366,7 +404,10 @@ def run_config(args, name, rank, world, dev, steps, warmup, want_roofline, batch
             print(f"bench: HIP-graph replay not used, running eagerly: {gstep.why}", file=sys.stderr)
         step = gstep
 
-    dt, t_issue = time_steps(step, steps, warmup, world)
+    dt, t_issue, last = time_steps(step, steps, warmup, world)
+    if dump_dir and rank == 0:
+        torch.cuda.synchronize()
+        dump_outputs(dump_dir, model, last)
     ips = B * world * steps / dt
     n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
     fields = {
@@ -409,7 +450,8 @@ def main():
     if world > 1 and n_pin <= 0:  # N ranks share one host: keep each rank's intra-op CPU pool small (no CPU-side compute)
         torch.set_num_threads(max(1, min(4, usable_cores() // world)))
 
-    row, B, ips, fields = run_config(args, args.config, rank, world, dev, args.steps, args.warmup, not args.no_roofline, args.batch)
+    row, B, ips, fields = run_config(args, args.config, rank, world, dev, args.steps, args.warmup, args.full and not args.no_roofline,
+                                     args.batch, args.dump_outputs)
     default = args.config == "c2"
     result = {
         "metric": "images/sec (train step) Swin-T/448 r=64 4-task" if default else f"images/sec (train step) {args.config}",
@@ -420,7 +462,7 @@ def main():
     }
     if "roofline" in fields:
         result["roofline"] = fields["roofline"]
-    if default and world == 1 and not args.no_other_configs and not args.batch:
+    if args.full and default and world == 1 and not args.no_other_configs and not args.batch:
         # (before the eager / CPU baseline legs: the CPU leg's thread pools keep spinning and cost the host-heavy c4 step 15 %)
         # the other single-GPU BASELINE configs, short legs (8 steps after 3 warm-up steps, no baselines): Swin-B r=128 and the 8-task r=4 sweep point
         others = {}
@@ -441,9 +483,9 @@ def main():
     if n_pin > 0:  # the comparator legs get the whole host back (the eager leg is a child process and inherits the mask)
         os.sched_setaffinity(0, full_mask)
         torch.set_num_threads(full_threads)
-    if rank == 0 and world == 1 and not args.no_eager_gpu:
+    if args.full and rank == 0 and world == 1 and not args.no_eager_gpu:
         result["eager_gpu"] = eager_gpu(args.config, B, ips)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(row)
     if world > 1:
         barrier(world)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kind kernel time of two bench.py lines side by side:  python tools/ab_kinds.py a.json b.json"""
+"""Per-kind kernel time of two `bench.py --full` lines side by side:  python tools/ab_kinds.py a.json b.json"""
 import json, sys
 a, b = (json.loads(open(p).read().strip().splitlines()[-1]) for p in sys.argv[1:3])
 print(f"{'':24s} {'A':>9s} {'B':>9s}   (ms/step)   step: {a['ms_per_step']:.2f} vs {b['ms_per_step']:.2f}   {a['value']:.1f} vs {b['value']:.1f}")

@@ -9,11 +9,11 @@ PART=${1:-1}
 if [ "$PART" = "1" ]; then
   timeout 2400 python -m pytest tests -q -m gpu > $OUT/pytest.txt 2>&1; grep -E "passed|failed" $OUT/pytest.txt | tail -1
   cp gpurun_out/model_parity.jsonl $OUT/model_parity.jsonl 2>/dev/null
-  python bench.py > $OUT/bench_default.json 2>/dev/null; cut -c1-160 $OUT/bench_default.json
+  python bench.py --full > $OUT/bench_default.json 2>/dev/null; cut -c1-160 $OUT/bench_default.json
   for c in c1 c4 c5:4 c5:16 c5:64 c5:256; do
-    python bench.py --config $c --no-cpu-baseline --no-other-configs > $OUT/bench_${c/:/_}.json 2>/dev/null; cut -c1-120 $OUT/bench_${c/:/_}.json
+    python bench.py --full --config $c --no-cpu-baseline --no-other-configs > $OUT/bench_${c/:/_}.json 2>/dev/null; cut -c1-120 $OUT/bench_${c/:/_}.json
   done
-  python bench.py --config c1 --graph --no-cpu-baseline --no-eager-gpu --no-other-configs > $OUT/bench_c1_graph.json 2>/dev/null; cut -c1-120 $OUT/bench_c1_graph.json
+  python bench.py --full --config c1 --graph --no-cpu-baseline --no-eager-gpu --no-other-configs > $OUT/bench_c1_graph.json 2>/dev/null; cut -c1-120 $OUT/bench_c1_graph.json
   python bench.py --cores 2 --no-cpu-baseline --no-eager-gpu --no-other-configs --no-roofline > $OUT/bench_c2_cores2_eager.json 2>/dev/null; cut -c1-120 $OUT/bench_c2_cores2_eager.json
   python bench.py --cores 2 --graph --no-cpu-baseline --no-eager-gpu --no-other-configs --no-roofline > $OUT/bench_c2_cores2_graph.json 2>/dev/null; cut -c1-120 $OUT/bench_c2_cores2_graph.json
 else
@@ -31,7 +31,7 @@ else
   python - $OUT/pmc_traffic.json <<'PY' || { echo "pmc_traffic.json: hot-path launch count differs from bench.py's -- re-run tools/pmc.sh after the kernel change"; exit 1; }
 import json, subprocess, sys
 pm = json.load(open(sys.argv[1]))
-line = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-eager-gpu", "--no-other-configs"],
+line = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-eager-gpu", "--no-other-configs"],
                       capture_output=True, text=True).stdout.strip().splitlines()[-1]
 n_bench = json.loads(line)["roofline"]["launches_per_step"]
 n_pmc = pm["hot_path"]["launches_per_step"]

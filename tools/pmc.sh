@@ -15,7 +15,7 @@ mkdir -p $REPO/gpurun_out
 # tools/pmc_traffic.py can attribute the counters to launch kinds (hot-path launches vs the callers' rank-0 GEMMs of the same kernels)
 if [ "${KINDS:-0}" = "1" ]; then
   export MTLORA_PROF_DUMP=$REPO/gpurun_out/pmc_${TAG}_kinds.csv
-  ROOF="--roofline-steps 1"
+  ROOF="--full --roofline-steps 1"
 else
   ROOF="--no-roofline"
 fi
