@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MTLORA_ABI_VERSION 8
+#define MTLORA_ABI_VERSION 9
 #define MTLORA_MAX_TASKS 8
 
 typedef enum mtlora_dtype {
@@ -386,7 +386,9 @@ int mtlora_residual_droppath_bwd(int n, const void* const* g, void* const* dy, v
  *   kind 1  NormalsLoss(normalize=True, L1, size_average) (:162-220): label (B,C,H,W), C <= 4;
  *           stat[0] = sum of the validity mask (label != ignore_index)
  *   kind 2  BalancedCrossEntropyLoss(size_average) (:42-89): C = 1, label (B,1,H,W);
- *           stat[0] = w = mean(1 - (label >= 0.5))
+ *           stat[0] = w = mean(1 - (label >= 0.5)), or the constant pos_weight (edge: 0.95, :243-245)
+ *   kind 3  DepthLoss('l1') (:132-148): C = 1, label (B,1,H,W), |up - label| over label != ignore_index, mean over the
+ *           valid pixels; stat[0] = number of valid pixels
  * low (B,h,w,C) is the channels-last low-resolution prediction, H = scale*h, W = scale*w (integer scale 1..32,
  * align_corners=False; larger scales: MTLORA_ERR_UNSUPPORTED / a negative count).  Writes dlow = d loss / d low (dtype of
  * low) and `mtlora_upsample_loss_partials(B, h, w, scale)` fp32 partial loss values (one per tile of the launch) whose sum
@@ -395,6 +397,38 @@ int mtlora_residual_droppath_bwd(int n, const void* const* g, void* const* dy, v
 int64_t mtlora_upsample_loss_partials(int64_t B, int h, int w, int scale);
 int mtlora_upsample_loss(int kind, const void* low, const float* label, const float* stat, void* dlow, float* partials,
                          int64_t B, int h, int w, int C, int scale, int dtype, float ignore_index, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Validation end of an epoch, fused (ABI v9): replaces, for one task and one batch, the final
+ * F.interpolate(pred, img_size, mode="bilinear") of models/swin_mtl.py:245 TOGETHER WITH get_output
+ * (evaluation/evaluate_utils.py:20-38), the task's meter update and the task's loss of main.py:439-528 validate().
+ * Forward only; the upsampled prediction never exists and nothing is copied to the host.
+ *   kind 0  softmax (SemsegMeter eval_semseg.py:109-120, HumanPartsMeter eval_human_parts.py:96-106, SoftMaxwithLoss), C <= 48
+ *           counts: tp[C], predicted[C], ground truth[C] among label != ignore_index (fp = predicted - tp, fn = gt - tp),
+ *           then the valid count: 3 C + 1.  float quantities: loss.  stat[0] = number of valid pixels
+ *   kind 1  normals (NormalsMeterV1 eval_normals_v1.py:29-54, NormalsMeterV2 eval_normals_v2.py:32-44, NormalsLoss), C <= 4
+ *           counts: n_v1, #{deg < 11.25}, #{deg < 22.5}, #{deg < 30}, n_v2.  float quantities: loss, sum of V1 degrees, sum
+ *           of V2 degrees.  stat[0] = sum of the validity mask
+ *   kind 2  saliency (SaliencyMeterWithBeta eval_sal_beta.py:29-70, SaliencyMeterWithNoBeta eval_sal_no_beta.py:33-50 with
+ *           jaccard.py, BalancedCrossEntropyLoss), C = 1.  stat[0] = w, stat[1..16) the 15 per-image thresholds,
+ *           stat[16..35) the 19 global thresholds (the caller builds them the way the meters do, so they are the same floats)
+ *           counts: [19][tp, predicted, actual] over label != ignore_index, then [B][15][tp, fp, fn] per image: 57 + 45 B.
+ *           float quantities: loss
+ *   kind 3  depth (DepthMeter eval_depth.py:71-89, DepthLoss), C = 1.  counts: valid.  float quantities: loss,
+ *           sum (gt - p)^2, sum (log gt - log p)^2 with p = max(up, 1e-9).  stat[0] = number of valid pixels
+ *   kind 4  edge (EdgeMeter eval_edge.py:31-37, BalancedCrossEntropyLoss(pos_weight)), C = 1.  no counts.  float quantities:
+ *           loss, and the meter's value (the same loss applied to the PROCESSED prediction, as the reference does).
+ *           stat[0] = pos_weight
+ * low, label, scale, dtype, ignore_index as mtlora_upsample_loss.  `counts` (n_int64 values) is ADDED to with integer
+ * atomics -- zero it, or hand in a meter's running state; `fpartials` receives n_float_partials fp32 values laid out
+ * [quantity][tile] (n_float_partials / number of quantities per row), to be summed by the caller in a fixed order.
+ * Deterministic: no float atomics.  mtlora_upsample_metrics_sizes reports both sizes (pure host call).
+ * ------------------------------------------------------------------------------------------ */
+int mtlora_upsample_metrics_sizes(int kind, int64_t B, int h, int w, int C, int scale, int64_t* n_int64,
+                                  int64_t* n_float_partials);
+int mtlora_upsample_metrics(int kind, const void* low, const float* label, const float* stat, int64_t* counts,
+                            float* fpartials, int64_t B, int h, int w, int C, int scale, int dtype, float ignore_index,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Small deterministic reductions of the callers (two launches each: per-block partials, fixed-order combine; no atomics and

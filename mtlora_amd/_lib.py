@@ -12,7 +12,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int6
 import torch
 
 MAX_TASKS = 8
-ABI_VERSION = 8
+ABI_VERSION = 9
 F32, BF16, F16 = 0, 1, 2
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -163,6 +163,9 @@ _SIGS = {
     "mtlora_label_stat": (c_int, [c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
     "mtlora_upsample_loss": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                      c_int, c_int, ctypes.c_float, c_void_p]),
+    "mtlora_upsample_metrics_sizes": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "mtlora_upsample_metrics": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                        c_int, c_int, ctypes.c_float, c_void_p]),
     "mtlora_upsample_cl_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int64, c_int, c_void_p]),
     "mtlora_upsample_cl_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int64, c_int, c_void_p]),
     "mtlora_block_save_bytes": (c_int64, [POINTER(BlockDesc)]),

@@ -27,9 +27,12 @@
 //
 //   kind 0  SoftMaxwithLoss        (mtl_loss_schemes.py:22-39)  cross entropy, ignore_index, mean over valid pixels
 //   kind 1  NormalsLoss            (:162-220, normalize=True, L1, size_average)
-//   kind 2  BalancedCrossEntropy   (:42-89, size_average)       stat[0] = w = mean(1 - labels)
+//   kind 2  BalancedCrossEntropy   (:42-89, size_average)       stat[0] = w = mean(1 - labels), or the constant pos_weight
+//   kind 3  DepthLoss l1           (:132-148)                   |up - label| over label != ignore, mean over valid pixels
+// (the per-pixel formulas live in up_pixel.h, shared with metrics.hip)
 // Label-only statistics (valid count, mask sum, w) come from the caller (they do not depend on the prediction).
 #include "common.h"
+#include "up_pixel.h"
 
 namespace {
 
@@ -47,76 +50,6 @@ struct UpLossParams {
 // latencies; at B = 32, 56 x 56 -> 448 x 448 the kernel times are flat over TR = 2 .. 8 (more waves and more rim cancel), at B = 8
 // TR = 2 is 1.8 x faster than TR = 8, at B = 64 6 % slower
 constexpr int UL_TR = 4;
-
-// per-output-pixel loss gradient g[c] = d loss / d up[c] (normalised), returns the pixel's share of the loss value;
-// lab: the pixel's label (kinds 0, 2) or its C label channels (kind 1)
-template <int KIND, int CMAX>
-__device__ __forceinline__ float up_pixel(float (&up)[CMAX], float (&g)[CMAX], const float (&lab)[KIND == 1 ? CMAX : 1], int C,
-                                          float ignore, float norm, float wneg) {
-    float loss = 0.f;
-    if (KIND == 0) {
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) g[c] = 0.f;
-        if (lab[0] != ignore) {
-            const int cls = (int)lab[0];
-            float m = -3.0e38f;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) m = c < C ? fmaxf(m, up[c]) : m;
-            float sum = 0.f, ucls = 0.f;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) {
-                up[c] = c < C ? __expf(up[c] - m) : 0.f;
-                sum += up[c];
-            }
-            const float inv = 1.f / sum;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) {
-                const float pc = up[c] * inv;
-                ucls = c == cls ? pc : ucls;
-                g[c] = norm * (pc - (c == cls ? 1.f : 0.f));
-            }
-            loss = -__logf(ucls) * norm;
-        }
-    } else if (KIND == 1) {
-        float mk[CMAX];
-        float r2 = 0.f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            mk[c] = (c < C && lab[c < (KIND == 1 ? CMAX : 1) ? c : 0] != ignore) ? 1.f : 0.f;
-            r2 += up[c] * up[c];
-        }
-        const float r = sqrtf(r2), n = r + 1e-12f;
-        float gc[CMAX], dot = 0.f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            const float d = up[c] / n - (c < C ? lab[c < (KIND == 1 ? CMAX : 1) ? c : 0] : 0.f);
-            gc[c] = (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * mk[c] * norm;
-            dot += gc[c] * up[c];
-            loss += fabsf(d) * mk[c] * norm;
-        }
-        const float k2 = r > 0.f ? dot / (r * n * n) : 0.f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) g[c] = gc[c] / n - k2 * up[c];
-    } else {
-        const float lb = lab[0] >= 0.5f ? 1.f : 0.f;
-        const float coef = (wneg * lb + (1.f - wneg) * (1.f - lb)) * norm;
-        const float o = up[0], gz = o >= 0.f ? 1.f : 0.f;
-        const float lv = o * (lb - gz) - log1pf(__expf(o - 2.f * o * gz));
-        const float sg = 1.f / (1.f + __expf(-o));
-        g[0] = -coef * (lb - sg);
-        loss = -coef * lv;
-    }
-    return loss;
-}
-
-// weight of output index o for low-res index q along one axis (PyTorch's source index arithmetic)
-__device__ __forceinline__ float up_weight(int o, int q, float rs, int n_in) {
-    float s = ((float)o + 0.5f) * rs - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    const int i0 = (int)s, i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-    const float f = s - (float)i0;
-    return (i0 == q ? 1.f - f : 0.f) + (i1 == q ? f : 0.f);
-}
 
 struct UpTile {
     int TQ, tiles_x, tiles_y;
@@ -169,6 +102,8 @@ __global__ __launch_bounds__(64) void k_up_loss(const UpLossParams p) {
         norm = 1.f / p.stat[0];
     else if (KIND == 1)
         norm = 1.f / fmaxf(p.stat[0], 1e-6f);
+    else if (KIND == 3)
+        norm = 1.f / fmaxf(p.stat[0], 1.f);
     else
         norm = 1.f / ((float)p.B * (float)H * (float)W);
     const float wneg = KIND == 2 ? p.stat[0] : 0.f;
@@ -341,6 +276,9 @@ static int dispatch_up(int kind, const UpLossParams& p, int64_t blocks, hipStrea
     } else if (kind == 2) {
         if (p.C != 1) return MTLORA_ERR_UNSUPPORTED;
         launch_up<T, 2, 1>(p, blocks, s);
+    } else if (kind == 3) {
+        if (p.C != 1) return MTLORA_ERR_UNSUPPORTED;
+        launch_up<T, 3, 1>(p, blocks, s);
     } else {
         return MTLORA_ERR_UNSUPPORTED;
     }

@@ -1440,16 +1440,17 @@ def label_stat(lab: torch.Tensor, kind: int, ignore_index: float) -> torch.Tenso
 # ----------------------------------------------------------------------------------------------
 # loss end of the train step: bilinear upsample (integer scale, align_corners=False) + per-task loss, fused
 # ----------------------------------------------------------------------------------------------
-LOSS_KINDS = {"softmax": 0, "normals": 1, "balanced_bce": 2}
+LOSS_KINDS = {"softmax": 0, "normals": 1, "balanced_bce": 2, "l1_masked": 3}
 
 
 class UpsampleLossFn(torch.autograd.Function):
     """loss_kind( F.interpolate(low.permute(0,3,1,2), scale_factor=scale, mode="bilinear"), label ) as ONE kernel that also
     produces d loss / d low (csrc/loss.hip); the upsampled prediction never exists.  ``low`` is (B, h, w, C)
-    channels-last (fp32 / bf16), ``label`` (B, 1 | C, scale*h, scale*w)."""
+    channels-last (fp32 / bf16), ``label`` (B, 1 | C, scale*h, scale*w).  ``pos_weight`` (``balanced_bce`` only): the constant
+    weight of BalancedCrossEntropyLoss(pos_weight=...) instead of the label statistic (edge: 0.95)."""
 
     @staticmethod
-    def forward(ctx, kind: str, low, label, scale: int, ignore_index: float = 255.0):
+    def forward(ctx, kind: str, low, label, scale: int, ignore_index: float = 255.0, pos_weight: Optional[float] = None):
         L.require_gpu(low, label)
         B, h, w, C = low.shape
         H, W = h * scale, w * scale
@@ -1466,9 +1467,14 @@ class UpsampleLossFn(torch.autograd.Function):
         elif kind == "normals":
             stat = label_stat(lab, 0, ignore_index)
         elif kind == "balanced_bce":
-            stat = label_stat(lab, 1, ignore_index)
+            stat = (label_stat(lab, 1, ignore_index) if pos_weight is None
+                    else torch.full((1,), float(pos_weight), dtype=torch.float32, device=lab.device))
+        elif kind == "l1_masked":
+            stat = label_stat(lab, 0, ignore_index)
         else:
             raise RuntimeError(f"mtlora_amd: unknown fused loss kind {kind!r}")
+        if pos_weight is not None and kind != "balanced_bce":
+            raise RuntimeError(f"mtlora_amd: pos_weight applies to 'balanced_bce', not {kind!r}")
         lib = L.lib()
         n = lib.mtlora_upsample_loss_partials(B, h, w, int(scale))
         if n < 0:
@@ -1485,7 +1491,74 @@ class UpsampleLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (dlow,) = ctx.saved_tensors
-        return None, (dlow * g.to(dlow.dtype)).to(ctx.in_dtype), None, None, None
+        return None, (dlow * g.to(dlow.dtype)).to(ctx.in_dtype), None, None, None, None
+
+
+# validation end: bilinear upsample + get_output + meter update + loss, fused and forward-only (csrc/metrics.hip)
+METRIC_KINDS = {"softmax": 0, "normals": 1, "saliency": 2, "l1_masked": 3, "edge": 4}
+METRIC_FLOATS = {"softmax": 1, "normals": 3, "saliency": 1, "l1_masked": 3, "edge": 2}  # float quantities per kind, loss first
+SAL_THRESHOLDS = 15, 19
+_sal_thr: dict = {}
+
+
+def saliency_thresholds(device=None):
+    """the 15 + 19 thresholds of the reference's two saliency meters as the fp32 values its comparisons see:
+    ``np.linspace(0.2, 0.9, 15)`` compared as Python floats against fp32 tensors (eval_sal_no_beta.py:27), and
+    ``torch.arange(0.05, 1, 0.05)`` (eval_sal_beta.py:23).  Built on the CPU once; cached per device."""
+    key = str(device)
+    if key not in _sal_thr:
+        import numpy as np
+        t = torch.cat([torch.tensor(np.linspace(0.2, 0.9, 15), dtype=torch.float64).float(), torch.arange(0.05, 1, 0.05)])
+        _sal_thr[key] = t if device is None else t.to(device)
+    return _sal_thr[key]
+
+
+def upsample_metrics_sizes(kind: str, B: int, h: int, w: int, C: int, scale: int):
+    """(number of int64 counts, number of fp32 partials) of ``upsample_metrics``; pure host call, raises on a geometry the
+    kernel does not take."""
+    ni, nf = ctypes.c_int64(0), ctypes.c_int64(0)
+    L.check(L.lib().mtlora_upsample_metrics_sizes(METRIC_KINDS[kind], B, h, w, C, int(scale), ctypes.byref(ni), ctypes.byref(nf)),
+            "mtlora_upsample_metrics_sizes")
+    return ni.value, nf.value
+
+
+@torch.no_grad()
+def upsample_metrics(kind: str, low, label, scale: int, counts=None, ignore_index: float = 255.0, pos_weight: float = 0.95):
+    """meter counters and loss of ``F.interpolate(low.permute(0,3,1,2), scale_factor=scale, mode="bilinear")`` against ``label``
+    in ONE launch (csrc/metrics.hip; layouts in include/mtlora_hip.h).  ``low`` (B, h, w, C) channels-last fp32 / bf16.
+    Returns ``(counts, sums)``: ``counts`` int64 -- the given tensor, ADDED to in place, or a fresh zeroed one -- and ``sums``
+    the kind's float quantities as fp64 (loss first), summed over the tiles' partials in a fixed order.  No host sync."""
+    L.require_gpu(low, label)
+    B, h, w, C = low.shape
+    H, W = h * scale, w * scale
+    lab = label.detach().float().contiguous()
+    exp_c = C if kind == "normals" else 1
+    if tuple(lab.shape) != (B, exp_c, H, W):
+        raise RuntimeError(f"mtlora_amd: label shape {tuple(lab.shape)} does not match prediction {(B, exp_c, H, W)}")
+    lo = low.detach().contiguous()
+    if lo.dtype not in (torch.float32, torch.bfloat16):
+        lo = lo.float()
+    if kind in ("softmax", "normals", "l1_masked"):
+        stat = label_stat(lab, 0, ignore_index)
+    elif kind == "saliency":
+        stat = torch.cat([label_stat(lab, 1, ignore_index), saliency_thresholds(lab.device)])
+    elif kind == "edge":
+        stat = torch.full((1,), float(pos_weight), dtype=torch.float32, device=lab.device)
+    else:
+        raise RuntimeError(f"mtlora_amd: unknown fused metrics kind {kind!r}")
+    ni, nfp = upsample_metrics_sizes(kind, B, h, w, C, scale)
+    if counts is None:
+        counts = torch.zeros(max(ni, 1), dtype=torch.int64, device=lo.device)
+    elif counts.dtype != torch.int64 or counts.numel() < ni or not counts.is_contiguous() or counts.device != lo.device:
+        raise RuntimeError(f"mtlora_amd: counts must be a contiguous int64 tensor of at least {ni} elements on {lo.device}")
+    nq = METRIC_FLOATS[kind]
+    part = torch.empty(max(nfp, nq), dtype=torch.float32, device=lo.device)
+    st = L.lib().mtlora_upsample_metrics(METRIC_KINDS[kind], L.ptr(lo), L.ptr(lab), L.ptr(stat), L.ptr(counts), L.ptr(part), B, h,
+                                         w, C, int(scale), L.dtype_code(lo), float(ignore_index), L.stream_ptr())
+    L.check(st, "mtlora_upsample_metrics")
+    if nfp == 0:
+        return counts, torch.zeros(nq, dtype=torch.float64, device=lo.device)
+    return counts, part[:nfp].view(nq, nfp // nq).sum(1, dtype=torch.float64)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -28,6 +28,9 @@ from .lora import MTLoRALinear, mark_only_lora_as_trainable
 from .swin_transformer_mtlora import SwinTransformerMTLoRA
 
 NUM_OUTPUT = {"semseg": 21, "normals": 3, "sal": 1, "human_parts": 7, "depth": 1, "edge": 1}  # data/mtl_ds.py:749-780
+EDGE_POS_WEIGHT = 0.95  # get_loss's default edge_w (mtl_loss_schemes.py:243-245), also EdgeMeter's (evaluate_utils.py:122)
+NYUD4 = ("semseg", "depth", "normals", "edge")  # the reference's NYUD task set (data/mtl_ds.py:744-804), 40 semseg classes
+NYUD_NUM_OUTPUT = {"semseg": 40}
 LOSS_WEIGHTS = {"depth": 1.0, "semseg": 1.0, "human_parts": 2.0, "sal": 5.0, "edge": 50.0, "normals": 10.0}
 
 
@@ -293,6 +296,11 @@ def task_loss(task: str, out: torch.Tensor, label: torch.Tensor) -> torch.Tensor
     if task == "depth":                             # DepthLoss l1 (:132-148)
         mask = (label != 255).to(out.dtype)
         return ((out - label).abs() * mask).sum() / mask.sum().clamp_min(1.0)
+    if task == "edge":                              # BalancedCrossEntropyLoss(size_average, pos_weight=0.95) (:243-245)
+        labels = (label >= 0.5).to(out.dtype)
+        gz = (out >= 0).to(out.dtype)
+        lv = out * (labels - gz) - torch.log(1 + torch.exp(out - 2 * out * gz))
+        return (EDGE_POS_WEIGHT * (-(labels * lv)).sum() + (1 - EDGE_POS_WEIGHT) * (-((1.0 - labels) * lv)).sum()) / labels.numel()
     raise NotImplementedError(task)
 
 
@@ -310,7 +318,8 @@ class MultiTaskLoss(nn.Module):
         per["total"] = total
         return total, per
 
-    FUSED_KIND = {"semseg": "softmax", "human_parts": "softmax", "normals": "normals", "sal": "balanced_bce"}
+    FUSED_KIND = {"semseg": "softmax", "human_parts": "softmax", "normals": "normals", "sal": "balanced_bce",
+                  "depth": "l1_masked", "edge": "balanced_bce"}
 
     def task_low(self, t, lo, lab):
         """loss of task t from its LOW-resolution (B, h, w, C) prediction (fused upsample + loss + backward where it applies)"""
@@ -318,6 +327,8 @@ class MultiTaskLoss(nn.Module):
         H, W = lab.shape[-2:]
         kind = self.FUSED_KIND.get(task_kind(t))
         if kind is not None and lo.is_cuda and H % h == 0 and W % w == 0 and H // h == W // w:
+            if task_kind(t) == "edge":  # the constant weight instead of the label statistic
+                return UpsampleLossFn.apply(kind, lo, lab, H // h, 255.0, EDGE_POS_WEIGHT)
             return UpsampleLossFn.apply(kind, lo, lab, H // h)
         return task_loss(t, F.interpolate(lo.permute(0, 3, 1, 2), (H, W), mode="bilinear"), lab)
 
@@ -330,24 +341,25 @@ class MultiTaskLoss(nn.Module):
     def forward_low(self, low, gt):
         """same value and gradients as ``forward(upsampled prediction, gt)`` from the LOW-resolution (B, h, w, C)
         predictions of ``model(x, upsample=False)``: bilinear upsample + loss + backward fused (csrc/loss.hip).
-        Tasks without a fused kernel (depth, edge) and non-integer scales take the plain path."""
+        Non-integer scales and CPU tensors take the plain path."""
         return self.combine({t: self.task_low(t, low[t], gt[t]) for t in self.tasks})
 
 
 # --------------------------------------------------------------------------------------------------
 def build_model(img_size=448, tasks=("semseg", "normals", "sal", "human_parts"), embed_dim=96, depths=(2, 2, 6, 2),
                 num_heads=(3, 6, 12, 24), r_shared=64, r_task=4, drop_path_rate=0.2, lora_b_std=0.02, seed=0,
-                freeze=True, **mt_over) -> MultiTaskSwin:
+                freeze=True, num_outputs: Optional[Mapping[str, int]] = None, **mt_over) -> MultiTaskSwin:
     """random-init model of the BASELINE configs: trunc_normal(.02) weights (reference :717-724),
     lora_*_B ~ N(0, lora_b_std) so that the LoRA paths are numerically live, and the reference's
-    trainable set (mark_only_lora_as_trainable with every freeze flag False, main.py:257-262)."""
+    trainable set (mark_only_lora_as_trainable with every freeze flag False, main.py:257-262).
+    ``num_outputs`` overrides the channel count of named tasks (NYUD: ``{"semseg": 40}``)."""
     torch.manual_seed(seed)
     mt = mtlora_namespace(tasks, r_shared, r_task, n_stages=len(depths), **mt_over)
     bb = SwinTransformerMTLoRA(img_size=img_size, patch_size=4, in_chans=3, num_classes=0, embed_dim=embed_dim,
                                depths=list(depths), num_heads=list(num_heads), window_size=7, mlp_ratio=4.0,
                                qkv_bias=True, drop_rate=0.0, drop_path_rate=drop_path_rate, ape=False, patch_norm=True,
                                tasks=list(tasks), mtlora=mt)
-    model = MultiTaskSwin(bb, tasks, {t: num_output(t) for t in tasks})
+    model = MultiTaskSwin(bb, tasks, {t: int((num_outputs or {}).get(t, num_output(t))) for t in tasks})
     if lora_b_std > 0:
         with torch.no_grad():
             for n, p in model.named_parameters():
@@ -378,16 +390,17 @@ def build_optimizer(model: nn.Module, lr=5e-4, weight_decay=0.05, fused: Optiona
                              capturable=bool(capturable and fused))
 
 
-def synthetic_batch(B: int, S: int, tasks: Sequence[str], seed: int, device="cpu"):
+def synthetic_batch(B: int, S: int, tasks: Sequence[str], seed: int, device="cpu", num_outputs: Optional[Mapping[str, int]] = None):
     """SURVEY 8d synthetic inputs: image ~ N(0,1); semseg/human_parts class ids with 5 % 255; sal Bernoulli(.3);
-    normals unit vectors with 5 % pixels 255."""
+    normals unit vectors with 5 % pixels 255; depth uniform in [0, 10); edge Bernoulli(.1) (edge maps are sparse: about
+    one pixel in ten of a dilated NYUD / PASCAL boundary map is on).  ``num_outputs`` as ``build_model``."""
     g = torch.Generator(device="cpu").manual_seed(seed)
     img = torch.randn(B, 3, S, S, generator=g)
     tg = {}
     for t in tasks:
         k = task_kind(t)
         if k in ("semseg", "human_parts"):
-            lab = torch.randint(0, NUM_OUTPUT[k], (B, 1, S, S), generator=g).float()
+            lab = torch.randint(0, int((num_outputs or {}).get(t, NUM_OUTPUT[k])), (B, 1, S, S), generator=g).float()
             lab[torch.rand(B, 1, S, S, generator=g) < 0.05] = 255.0
         elif k == "sal":
             lab = (torch.rand(B, 1, S, S, generator=g) < 0.3).float()
@@ -397,6 +410,8 @@ def synthetic_batch(B: int, S: int, tasks: Sequence[str], seed: int, device="cpu
             lab = torch.where(ign, torch.full_like(lab, 255.0), lab)
         elif k == "depth":
             lab = torch.rand(B, 1, S, S, generator=g) * 10
+        elif k == "edge":
+            lab = (torch.rand(B, 1, S, S, generator=g) < 0.1).float()
         else:
             raise NotImplementedError(t)
         tg[t] = lab.to(device)
@@ -480,6 +495,48 @@ def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 
     optimizer.step()
     optimizer.zero_grad(set_to_none=True)
     return loss.detach(), norm
+
+
+def validate_step(model, criterion, meter, images, targets, amp_dtype: Optional[torch.dtype] = torch.bfloat16):
+    """one batch of the reference's ``validate()`` (main.py:439-528): eval-mode forward under ``torch.no_grad()``, the weighted
+    multi-task loss and the meter update.  On a GPU each task's head runs on its side stream as in ``MultiTaskSwin.forward``
+    and ends in ONE launch (``meter.update_task_low``: final upsample + get_output + meter + loss, csrc/metrics.hip); the
+    full-resolution predictions never exist and nothing is copied to the host.  Returns ``(weighted loss, per-task losses)``
+    as device tensors.  ``model.training`` is restored; parameters, buffers, hooks and the merged state are not touched."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            ctx = (torch.autocast("cuda", dtype=amp_dtype) if (amp_dtype is not None and images.is_cuda)
+                   else contextlib.nullcontext())
+            with ctx:
+                if isinstance(model, MultiTaskSwin):
+                    conc = images.is_cuda and _TASK_STREAMS and len(model.tasks) > 1 and _streams_allowed()
+                    per = model(images, upsample=False, concurrent=conc,
+                                per_task_fn=lambda t, lo: meter.update_task_low(t, lo, targets[t]))
+                else:
+                    low = model(images, upsample=False)
+                    per = {t: meter.update_task_low(t, low[t], targets[t]) for t in criterion.tasks}
+            return criterion.combine({t: per[t].float() for t in criterion.tasks})
+    finally:
+        model.train(was_training)
+
+
+def validate(model, batches, criterion=None, meter=None, database: str = "PASCALContext",
+             amp_dtype: Optional[torch.dtype] = torch.bfloat16, verbose: bool = False):
+    """the reference's ``validate()`` over ``batches`` (an iterable of ``(images, targets)``): ``validate_step`` per batch,
+    ONE ``meter.get_score()`` -- the only device-to-host copy -- at the end.  Returns ``(scores, mean weighted loss)``."""
+    from .evaluation import PerformanceMeter
+    tasks = list(model.tasks)
+    criterion = criterion if criterion is not None else MultiTaskLoss(tasks)
+    meter = meter if meter is not None else PerformanceMeter(tasks, database)
+    total, n = None, 0
+    for images, targets in batches:
+        loss, _ = validate_step(model, criterion, meter, images, targets, amp_dtype)
+        total = loss.double() if total is None else total + loss.double()
+        n += 1
+    scores = meter.get_score(verbose)
+    return scores, (float(total) / n if n else float("nan"))
 
 
 class GraphedTrainStep:
