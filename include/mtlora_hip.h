@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MTLORA_ABI_VERSION 9
+#define MTLORA_ABI_VERSION 10
 #define MTLORA_MAX_TASKS 8
 
 typedef enum mtlora_dtype {
@@ -527,6 +527,57 @@ int mtlora_block_fwd(const mtlora_block_desc* d, const mtlora_block_params* p, c
 int mtlora_block_bwd(const mtlora_block_desc* d, const mtlora_block_params* p, const void* x, const void* normed,
                      const void* x_out, const void* g_x_out, const void* g_normed_out, const void* save, int64_t save_bytes,
                      const mtlora_block_grads* g, void* scratch, int64_t scratch_bytes, int phase, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The parameter update of the train step, fused (ABI v10): replaces, for ALL trainable tensors at once, what the
+ * reference's NativeScalerWithGradNormCount.__call__ does after backward (utils.py:348-375, called at main.py:347-353):
+ * GradScaler.unscale_, torch.nn.utils.clip_grad_norm_, the AdamW step over the decay / no-decay groups of
+ * optimizer.py:71-85, and GradScaler.update -- three launches on `stream`, no host synchronisation, nothing read back.
+ * fp32 parameters, gradients and state only; no amsgrad, no maximize.
+ *
+ * Tensors are cut into chunks of MTLORA_ADAMW_CHUNK elements, one workgroup per chunk.
+ *   mtlora_adamw_sizes   pure host call: for n_tensors element counts, the number of chunks, the bytes of the device table
+ *                        and the bytes of per-call scratch (two words per chunk).
+ *   mtlora_adamw_table   pure host call: fills `host_table` (table_bytes of HOST memory) from the tensors' DEVICE pointers
+ *                        p / m (exp_avg) / v (exp_avg_sq), element counts and parameter-group indices
+ *                        (< MTLORA_ADAMW_MAX_GROUPS); the caller copies it to the device once.  Pointers 4-byte aligned; the
+ *                        kernels use 16-byte accesses where a tensor's pointers are 16-byte aligned and scalar ones elsewhere.
+ *   mtlora_adamw_update  one optimizer step.  `table`: the device copy of that table.  `grads`: DEVICE array of n_tensors
+ *                        gradient pointers, re-uploaded by the caller whenever they change (autograd allocates fresh
+ *                        gradients after zero_grad(set_to_none=True)); a null entry = no gradient this step: that tensor,
+ *                        its state and nothing else of it is read or written (torch skips such parameters too).
+ *                        `groups`: n_groups HOST structs, passed on to the kernels by value (lr moves every step under a
+ *                        scheduler).  max_norm <= 0: no clipping.  `scale` / `growth_tracker`: DEVICE words of a GradScaler
+ *                        (fp32 / int32), both null = no loss scaling; the gradients are multiplied by 1 / *scale, then
+ *                        the scale is updated with growth_factor / backoff_factor / growth_interval as
+ *                        torch.amp.GradScaler.update does.  `norm_out`: optional DEVICE fp32 word, receives the total norm.
+ *                        `ctrl`: MTLORA_ADAMW_CTRL_WORDS fp32 DEVICE words owned by the optimizer, zero before the first
+ *                        step, persistent:
+ *                            [0] total 2-norm of the UNSCALED gradients before clipping   [1] found_inf (0 / 1)
+ *                            [2] clip coefficient min(1, max_norm / (norm + 1e-6))         [3] [2] / *scale
+ *                            [4] the step counter t (counts the steps that were not skipped)
+ *                            [8 + 2 g], [9 + 2 g]  1 - beta1^t and sqrt(1 - beta2^t) of group g
+ *                        A gradient holding inf / nan sets found_inf: the step is skipped ON THE DEVICE (parameters, state
+ *                        and t stay bitwise unchanged; with a scaler the scale backs off) -- with or without a scaler.
+ *                        Otherwise, per element: g' = g [3]; p *= 1 - lr wd; m = b1 m + (1 - b1) g';
+ *                        v = b2 v + (1 - b2) g'^2; p -= lr / (1 - b1^t) m / (sqrt(v) / sqrt(1 - b2^t) + eps).
+ * Deterministic: no float atomics; the norm is summed in a fixed order (per-chunk fp32 partials, combined in double).
+ * ------------------------------------------------------------------------------------------ */
+#define MTLORA_ADAMW_CHUNK 4096
+#define MTLORA_ADAMW_MAX_GROUPS 16
+#define MTLORA_ADAMW_CTRL_WORDS 64
+typedef struct mtlora_adamw_group {
+    double lr, beta1, beta2, eps, weight_decay; /* doubles, as torch holds them: 1 - beta, 1 - lr wd and the powers are formed in
+                                                   double and rounded once */
+} mtlora_adamw_group;
+int mtlora_adamw_sizes(int64_t n_tensors, const int64_t* numel, int64_t* n_chunks, int64_t* table_bytes,
+                       int64_t* scratch_bytes);
+int mtlora_adamw_table(int64_t n_tensors, const int64_t* numel, const int32_t* group, void* const* p, void* const* m,
+                       void* const* v, void* host_table, int64_t table_bytes);
+int mtlora_adamw_update(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks,
+                        const mtlora_adamw_group* groups, int n_groups, float max_norm, float* ctrl, float* norm_out,
+                        float* scale, int32_t* growth_tracker, float growth_factor, float backoff_factor,
+                        int growth_interval, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Hardware self-test: writes the lane->element maps of the MFMA / LDS-transpose primitives the

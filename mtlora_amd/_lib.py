@@ -7,12 +7,12 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p
 
 import torch
 
 MAX_TASKS = 8
-ABI_VERSION = 9
+ABI_VERSION = 10
 F32, BF16, F16 = 0, 1, 2
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -61,6 +61,13 @@ class BlockGrads(Structure):
                 ("d_norm2_b", c_void_p), ("d_next_g", c_void_p), ("d_next_b", c_void_p), ("dA", c_void_p * 4), ("dB", c_void_p * 4),
                 ("dbias", c_void_p)]
 
+
+class AdamwGroup(Structure):
+    """mtlora_adamw_group (ABI v10): one parameter group's hyper-parameters, passed by value every step"""
+    _fields_ = [("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double)]
+
+
+ADAMW_CHUNK, ADAMW_MAX_GROUPS, ADAMW_CTRL_WORDS = 4096, 16, 64
 
 PROF_KINDS = 24
 
@@ -175,6 +182,11 @@ _SIGS = {
                                  c_void_p, c_int64, c_void_p]),
     "mtlora_block_bwd": (c_int, [POINTER(BlockDesc), POINTER(BlockParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_int64, POINTER(BlockGrads), c_void_p, c_int64, c_int, c_void_p]),
+    "mtlora_adamw_sizes": (c_int, [c_int64, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "mtlora_adamw_table": (c_int, [c_int64, POINTER(c_int64), POINTER(c_int32), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                   c_void_p, c_int64]),
+    "mtlora_adamw_update": (c_int, [c_void_p, c_void_p, c_int64, c_int64, POINTER(AdamwGroup), c_int, c_float, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_float, c_float, c_int, c_void_p, c_int64, c_void_p]),
     "mtlora_selftest_layouts": (c_int, [c_void_p, c_void_p]),
     "mtlora_prof_begin": (c_int, [c_int]),
     "mtlora_prof_end": (c_int, [POINTER(ProfSummary)]),

@@ -1,0 +1,383 @@
+// optim.hip -- the parameter update of the reference train step (main.py:347-353 with utils.py:348-375 and the AdamW of
+// optimizer.py:71-85), fused: GradScaler.unscale_ + clip_grad_norm_ + AdamW.step + GradScaler.update over ALL trainable
+// tensors as three launches, with no host synchronisation and no per-tensor work on the host.  fp32 parameters, gradients and state.
+//
+// The tensors are cut into chunks of MTLORA_ADAMW_CHUNK elements; one 256-thread workgroup owns one chunk.  A device table
+// (built on the host by mtlora_adamw_table, uploaded once) maps chunk -> (tensor, chunk index inside it) and tensor ->
+// (p, m, v, numel, group).  The gradient pointers live in a table of their own, because they change from step to step
+// (zero_grad(set_to_none=True) lets autograd allocate fresh gradients): the caller re-uploads that one array per step.  A null
+// gradient pointer switches the tensor's chunks off: nothing of it is read or written.
+//
+//   k_optim_norm    partials[chunk] = sum of g^2 over the chunk, of the gradients AS STORED (still multiplied by the loss scale);
+//                   flags[chunk] = 1 if a value of the chunk is inf / nan.  16-byte loads where the chunk's base is 16-byte
+//                   aligned (the last n % 4 elements, and every element of a misaligned tensor, go through the scalar path).
+//                   No float atomics: every workgroup owns its two words.
+//   k_optim_finish  ONE workgroup: partials summed in a fixed order in double (thread t takes t, t + 256, ...; then a fixed
+//                   tree), so the norm is bit-reproducible from run to run.  Writes the control block (unscaled norm, found_inf,
+//                   clip coefficient, the factor coef / scale the update applies to the raw gradients, the step counter --
+//                   incremented only when the step is not skipped -- and each group's bias corrections, powers in double) and
+//                   performs GradScaler.update: on found_inf scale *= backoff and the growth tracker returns to 0; otherwise the
+//                   tracker counts up and at growth_interval scale *= growth (kept only if finite, as ATen) and the tracker resets.
+//   k_optim_step    the same chunk grid.  found_inf set: returns before touching memory -- parameters and state stay bitwise
+//                   unchanged.  Otherwise torch's AdamW, decoupled weight decay, per element:
+//                       g' = g * (coef / scale);  p *= 1 - lr wd;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;
+//                       p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)
+//                   lr, wd, betas, eps per parameter group, BY VALUE in the launch arguments (lr moves every step under a
+//                   scheduler; nothing to upload).
+#include "common.h"
+
+namespace {
+
+constexpr int OPT_CHUNK = MTLORA_ADAMW_CHUNK;
+constexpr int OPT_THREADS = 256;
+constexpr int OPT_VPT = OPT_CHUNK / (4 * OPT_THREADS);  // 16-byte vectors per thread and chunk
+constexpr int OPT_MAXG = MTLORA_ADAMW_MAX_GROUPS;
+static_assert(OPT_CHUNK % (4 * OPT_THREADS) == 0, "chunk = whole vectors per thread");
+
+// the device table: [n_tensors] OptTensor, then [n_chunks] OptChunk
+struct OptTensor {
+    float* p;
+    float* m;
+    float* v;
+    int64_t n;
+    int32_t group;
+    int32_t pad_;
+};
+struct OptChunk {
+    int32_t tensor;
+    int32_t index;  // element offset = index * OPT_CHUNK
+};
+static_assert(sizeof(OptTensor) == 40 && sizeof(OptChunk) == 8, "table layout");
+
+struct OptGroups {  // kernel argument.  The hyper-parameters arrive as doubles (as torch holds them); what is derived from them is
+    // formed in double on the host and rounded once: 1 - 0.999f is 1.3e-5 away from 1 - 0.999
+    float lr[OPT_MAXG], decay[OPT_MAXG], b1[OPT_MAXG], omb1[OPT_MAXG], b2[OPT_MAXG], omb2[OPT_MAXG], eps[OPT_MAXG];
+    double b1d[OPT_MAXG], b2d[OPT_MAXG];
+    int n;
+};
+
+// control block words (floats), MTLORA_ADAMW_CTRL_WORDS of them
+enum { OC_NORM = 0, OC_FOUND_INF = 1, OC_COEF = 2, OC_GMUL = 3, OC_STEP = 4, OC_BC = 8 };  // OC_BC + 2 g: bc1, sqrt(bc2) of group g
+static_assert(OC_BC + 2 * OPT_MAXG <= MTLORA_ADAMW_CTRL_WORDS, "control block");
+
+__device__ __forceinline__ bool opt_nonfinite(float x) { return (__builtin_bit_cast(uint32_t, x) & 0x7F800000u) == 0x7F800000u; }
+
+// fixed-order sum over the workgroup's 4 waves; the result is valid in thread 0
+__device__ __forceinline__ float opt_block_sum(float s, float* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void k_optim_norm(const OptTensor* __restrict__ tens, const OptChunk* __restrict__ chunks,
+                                                            const float* const* __restrict__ grads, float* __restrict__ partials,
+                                                            uint32_t* __restrict__ flags) {
+    __shared__ float red[4];
+    __shared__ int bad_any;
+    const int tid = threadIdx.x;
+    const OptChunk ck = chunks[blockIdx.x];
+    const float* g = grads[ck.tensor];
+    if (!g) {  // (workgroup-uniform) no gradient this step
+        if (tid == 0) {
+            partials[blockIdx.x] = 0.f;
+            flags[blockIdx.x] = 0u;
+        }
+        return;
+    }
+    const int64_t off = (int64_t)ck.index * OPT_CHUNK;
+    const int64_t left = tens[ck.tensor].n - off;
+    const int n = left < OPT_CHUNK ? (int)left : OPT_CHUNK;
+    g += off;
+    if (tid == 0) bad_any = 0;
+    float s = 0.f;
+    bool bad = false;
+    if (((uintptr_t)g & 15u) == 0) {
+        const int nv = n >> 2;
+        f32x4 x[OPT_VPT];
+#pragma unroll
+        for (int k = 0; k < OPT_VPT; ++k) {
+            const int i = k * OPT_THREADS + tid;
+            x[k] = i < nv ? *reinterpret_cast<const f32x4*>(g + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int k = 0; k < OPT_VPT; ++k)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                s += x[k][e] * x[k][e];
+                bad |= opt_nonfinite(x[k][e]);
+            }
+        const int i = 4 * nv + tid;  // the last n % 4 elements
+        if (tid < 4 && i < n) {
+            const float t = g[i];
+            s += t * t;
+            bad |= opt_nonfinite(t);
+        }
+    } else {
+        for (int i = tid; i < n; i += OPT_THREADS) {
+            const float t = g[i];
+            s += t * t;
+            bad |= opt_nonfinite(t);
+        }
+    }
+    __syncthreads();  // bad_any = 0 is visible
+    if (bad) bad_any = 1;  // (LDS; every writer stores the same value)
+    const float tot = opt_block_sum(s, red);  // (its barrier also orders bad_any)
+    if (tid == 0) {
+        partials[blockIdx.x] = tot;
+        flags[blockIdx.x] = bad_any ? 1u : 0u;
+    }
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __restrict__ partials, const uint32_t* __restrict__ flags,
+                                                              int n_chunks, const OptGroups grp, float max_norm, float* __restrict__ ctrl,
+                                                              float* __restrict__ norm_out, float* __restrict__ scale,
+                                                              int32_t* __restrict__ tracker, float growth, float backoff, int interval) {
+    __shared__ double red[OPT_THREADS];
+    __shared__ uint32_t fl[OPT_THREADS];
+    __shared__ float step_new;
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    uint32_t f = 0u;
+    for (int i = tid; i < n_chunks; i += OPT_THREADS) {
+        s += (double)partials[i];
+        f |= flags[i];
+    }
+    red[tid] = s;
+    fl[tid] = f;
+    __syncthreads();
+    for (int w = OPT_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) {
+            red[tid] += red[tid + w];
+            fl[tid] |= fl[tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const bool found = fl[0] != 0u;
+        const float sc = scale ? *scale : 1.f;
+        const float inv = (float)(1.0 / (double)sc);  // GradScaler.unscale_: the reciprocal in double, applied in fp32
+        const float norm = (float)(sqrt(red[0]) * (double)inv);
+        const float coef = max_norm > 0.f ? fminf(1.f, max_norm / (norm + 1e-6f)) : 1.f;  // clip_grad_norm_
+        const float st = ctrl[OC_STEP] + (found ? 0.f : 1.f);
+        ctrl[OC_NORM] = norm;
+        ctrl[OC_FOUND_INF] = found ? 1.f : 0.f;
+        ctrl[OC_COEF] = coef;
+        ctrl[OC_GMUL] = coef * inv;
+        ctrl[OC_STEP] = st;
+        step_new = st;
+        if (norm_out) *norm_out = norm;
+        if (scale) {  // GradScaler.update (ATen amp_update_scale)
+            if (found) {
+                *scale = sc * backoff;
+                *tracker = 0;
+            } else {
+                const int ok = *tracker + 1;
+                if (ok == interval) {
+                    const float grown = sc * growth;
+                    if (!opt_nonfinite(grown)) *scale = grown;
+                    *tracker = 0;
+                } else {
+                    *tracker = ok;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < grp.n) {
+        const double t = (double)step_new;
+        ctrl[OC_BC + 2 * tid] = (float)(1.0 - pow(grp.b1d[tid], t));
+        ctrl[OC_BC + 2 * tid + 1] = (float)sqrt(1.0 - pow(grp.b2d[tid], t));
+    }
+}
+
+struct OptCoef {
+    float gmul, decay, b1, omb1, b2, omb2, step_size, inv_bc2s, eps;
+};
+
+__device__ __forceinline__ void opt_adamw(float& p, float g, float& m, float& v, const OptCoef& c) {
+    g *= c.gmul;
+    p *= c.decay;
+    m = c.b1 * m + c.omb1 * g;
+    v = c.b2 * v + c.omb2 * g * g;
+    p -= c.step_size * (m / (sqrtf(v) * c.inv_bc2s + c.eps));
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void k_optim_step(const OptTensor* __restrict__ tens, const OptChunk* __restrict__ chunks,
+                                                            const float* const* __restrict__ grads, const float* __restrict__ ctrl,
+                                                            const OptGroups grp) {
+    if (ctrl[OC_FOUND_INF] != 0.f) return;  // skipped step: nothing is written
+    const int tid = threadIdx.x;
+    const OptChunk ck = chunks[blockIdx.x];
+    const float* g = grads[ck.tensor];
+    if (!g) return;
+    const OptTensor t = tens[ck.tensor];
+    const int64_t off = (int64_t)ck.index * OPT_CHUNK;
+    const int64_t left = t.n - off;
+    const int n = left < OPT_CHUNK ? (int)left : OPT_CHUNK;
+    g += off;
+    float* p = t.p + off;
+    float* m = t.m + off;
+    float* v = t.v + off;
+    const int gi = t.group;
+    OptCoef c;
+    c.gmul = ctrl[OC_GMUL];
+    c.decay = grp.decay[gi];
+    c.b1 = grp.b1[gi];
+    c.omb1 = grp.omb1[gi];
+    c.b2 = grp.b2[gi];
+    c.omb2 = grp.omb2[gi];
+    c.step_size = grp.lr[gi] / ctrl[OC_BC + 2 * gi];
+    c.inv_bc2s = 1.f / ctrl[OC_BC + 2 * gi + 1];
+    c.eps = grp.eps[gi];
+    if ((((uintptr_t)g | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15u) == 0) {
+        const int nv = n >> 2;
+        f32x4 xg[OPT_VPT], xp[OPT_VPT], xm[OPT_VPT], xv[OPT_VPT];
+#pragma unroll
+        for (int k = 0; k < OPT_VPT; ++k) {
+            const int i = k * OPT_THREADS + tid;
+            if (i < nv) {
+                xg[k] = *reinterpret_cast<const f32x4*>(g + 4 * i);
+                xp[k] = *reinterpret_cast<const f32x4*>(p + 4 * i);
+                xm[k] = *reinterpret_cast<const f32x4*>(m + 4 * i);
+                xv[k] = *reinterpret_cast<const f32x4*>(v + 4 * i);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < OPT_VPT; ++k) {
+            const int i = k * OPT_THREADS + tid;
+            if (i < nv) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float pp = xp[k][e], mm = xm[k][e], vv = xv[k][e];
+                    opt_adamw(pp, xg[k][e], mm, vv, c);
+                    xp[k][e] = pp;
+                    xm[k][e] = mm;
+                    xv[k][e] = vv;
+                }
+                *reinterpret_cast<f32x4*>(p + 4 * i) = xp[k];
+                *reinterpret_cast<f32x4*>(m + 4 * i) = xm[k];
+                *reinterpret_cast<f32x4*>(v + 4 * i) = xv[k];
+            }
+        }
+        const int i = 4 * nv + tid;  // the last n % 4 elements
+        if (tid < 4 && i < n) {
+            float pp = p[i], mm = m[i], vv = v[i];
+            opt_adamw(pp, g[i], mm, vv, c);
+            p[i] = pp;
+            m[i] = mm;
+            v[i] = vv;
+        }
+    } else {
+        for (int i = tid; i < n; i += OPT_THREADS) {
+            float pp = p[i], mm = m[i], vv = v[i];
+            opt_adamw(pp, g[i], mm, vv, c);
+            p[i] = pp;
+            m[i] = mm;
+            v[i] = vv;
+        }
+    }
+}
+
+static int opt_count(int64_t n_tensors, const int64_t* numel, int64_t* n_chunks) {
+    if (n_tensors <= 0 || n_tensors >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
+    if (!numel) return MTLORA_ERR_NULL;
+    int64_t nc = 0;
+    for (int64_t i = 0; i < n_tensors; ++i) {
+        if (numel[i] < 0 || numel[i] >= ((int64_t)1 << 42)) return MTLORA_ERR_SHAPE;
+        nc += mtl_ceil_div(numel[i], OPT_CHUNK);
+    }
+    if (nc >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
+    *n_chunks = nc;
+    return MTLORA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtlora_adamw_sizes(int64_t n_tensors, const int64_t* numel, int64_t* n_chunks, int64_t* table_bytes, int64_t* scratch_bytes) {
+    if (!n_chunks || !table_bytes || !scratch_bytes) return MTLORA_ERR_NULL;
+    int64_t nc = 0;
+    const int rc = opt_count(n_tensors, numel, &nc);
+    if (rc != MTLORA_OK) return rc;
+    *n_chunks = nc;
+    *table_bytes = n_tensors * (int64_t)sizeof(OptTensor) + nc * (int64_t)sizeof(OptChunk);
+    *scratch_bytes = nc * 8;  // partials (fp32) + flags
+    return MTLORA_OK;
+}
+
+int mtlora_adamw_table(int64_t n_tensors, const int64_t* numel, const int32_t* group, void* const* p, void* const* m, void* const* v,
+                       void* host_table, int64_t table_bytes) {
+    int64_t nc = 0;
+    const int rc = opt_count(n_tensors, numel, &nc);
+    if (rc != MTLORA_OK) return rc;
+    if (!group || !p || !m || !v || !host_table) return MTLORA_ERR_NULL;
+    if (table_bytes < n_tensors * (int64_t)sizeof(OptTensor) + nc * (int64_t)sizeof(OptChunk)) return MTLORA_ERR_WORKSPACE;
+    OptTensor* te = reinterpret_cast<OptTensor*>(host_table);
+    OptChunk* ce = reinterpret_cast<OptChunk*>(te + n_tensors);
+    int64_t c = 0;
+    for (int64_t i = 0; i < n_tensors; ++i) {
+        if (group[i] < 0 || group[i] >= OPT_MAXG) return MTLORA_ERR_SHAPE;
+        if (numel[i] > 0 && (!p[i] || !m[i] || !v[i])) return MTLORA_ERR_NULL;
+        if (((uintptr_t)p[i] | (uintptr_t)m[i] | (uintptr_t)v[i]) & 3u) return MTLORA_ERR_ALIGN;
+        te[i].p = reinterpret_cast<float*>(p[i]);
+        te[i].m = reinterpret_cast<float*>(m[i]);
+        te[i].v = reinterpret_cast<float*>(v[i]);
+        te[i].n = numel[i];
+        te[i].group = group[i];
+        te[i].pad_ = 0;
+        const int64_t k = mtl_ceil_div(numel[i], OPT_CHUNK);
+        for (int64_t j = 0; j < k; ++j, ++c) {
+            ce[c].tensor = (int32_t)i;
+            ce[c].index = (int32_t)j;
+        }
+    }
+    return MTLORA_OK;
+}
+
+int mtlora_adamw_update(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const mtlora_adamw_group* groups,
+                        int n_groups, float max_norm, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker,
+                        float growth_factor, float backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes,
+                        void* stream) {
+    if (n_tensors <= 0 || n_tensors >= ((int64_t)1 << 31) || n_chunks < 0 || n_chunks >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
+    if (n_groups < 1 || n_groups > OPT_MAXG) return MTLORA_ERR_UNSUPPORTED;
+    if (!table || !grads || !groups || !ctrl || !scratch) return MTLORA_ERR_NULL;
+    if ((scale == nullptr) != (growth_tracker == nullptr)) return MTLORA_ERR_NULL;
+    if (((uintptr_t)table | (uintptr_t)grads | (uintptr_t)scratch) & 7u) return MTLORA_ERR_ALIGN;
+    if (((uintptr_t)ctrl | (uintptr_t)norm_out | (uintptr_t)scale | (uintptr_t)growth_tracker) & 3u) return MTLORA_ERR_ALIGN;
+    if (scratch_bytes < n_chunks * 8) return MTLORA_ERR_WORKSPACE;
+    if (scale && (growth_interval < 1 || !(growth_factor > 1.f) || !(backoff_factor > 0.f && backoff_factor < 1.f))) return MTLORA_ERR_SHAPE;
+    OptGroups g = {};
+    g.n = n_groups;
+    for (int i = 0; i < n_groups; ++i) {
+        const mtlora_adamw_group& s = groups[i];
+        if (!(s.lr >= 0.0) || !(s.eps >= 0.0) || !(s.weight_decay >= 0.0) || !(s.beta1 >= 0.0 && s.beta1 < 1.0) ||
+            !(s.beta2 >= 0.0 && s.beta2 < 1.0))
+            return MTLORA_ERR_SHAPE;
+        g.lr[i] = (float)s.lr;
+        g.decay[i] = (float)(1.0 - s.lr * s.weight_decay);
+        g.b1[i] = (float)s.beta1;
+        g.omb1[i] = (float)(1.0 - s.beta1);
+        g.b2[i] = (float)s.beta2;
+        g.omb2[i] = (float)(1.0 - s.beta2);
+        g.eps[i] = (float)s.eps;
+        g.b1d[i] = s.beta1;
+        g.b2d[i] = s.beta2;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const OptTensor* te = reinterpret_cast<const OptTensor*>(table);
+    const OptChunk* ce = reinterpret_cast<const OptChunk*>(te + n_tensors);
+    const float* const* gp = reinterpret_cast<const float* const*>(grads);
+    float* partials = reinterpret_cast<float*>(scratch);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(partials + n_chunks);
+    if (n_chunks > 0) hipLaunchKernelGGL(k_optim_norm, dim3((unsigned)n_chunks), dim3(OPT_THREADS), 0, s, te, ce, gp, partials, flags);
+    hipLaunchKernelGGL(k_optim_finish, dim3(1), dim3(OPT_THREADS), 0, s, partials, flags, (int)n_chunks, g, max_norm, ctrl, norm_out, scale,
+                       growth_tracker, growth_factor, backoff_factor, growth_interval);
+    if (n_chunks > 0) hipLaunchKernelGGL(k_optim_step, dim3((unsigned)n_chunks), dim3(OPT_THREADS), 0, s, te, ce, gp, ctrl, g);
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
+}  // extern "C"

@@ -25,6 +25,7 @@ import torch.nn.functional as F
 from . import functional as Fn
 from .functional import BatchNormReluFn, UpsampleLossFn
 from .lora import MTLoRALinear, mark_only_lora_as_trainable
+from .optim import FusedAdamW
 from .swin_transformer_mtlora import SwinTransformerMTLoRA
 
 NUM_OUTPUT = {"semseg": 21, "normals": 3, "sal": 1, "human_parts": 7, "depth": 1, "edge": 1}  # data/mtl_ds.py:749-780
@@ -371,10 +372,13 @@ def build_model(img_size=448, tasks=("semseg", "normals", "sal", "human_parts"),
 
 
 def build_optimizer(model: nn.Module, lr=5e-4, weight_decay=0.05, fused: Optional[bool] = None,
-                    capturable: bool = False) -> torch.optim.Optimizer:
+                    capturable: bool = False, impl: str = "torch") -> torch.optim.Optimizer:
     """AdamW(betas .9/.999, eps 1e-8, wd .05) with the no-decay set of optimizer.py:71-85 (1-D tensors, biases,
     relative_position_bias_table); only trainable tensors are handed over (frozen ones never get a grad in the
-    reference either)."""
+    reference either).  ``impl="hip"``: the same two groups under ``optim.FusedAdamW`` (clip + unscale + AdamW as
+    three launches, csrc/optim.hip; ``fused`` / ``capturable`` do not apply)."""
+    if impl not in ("torch", "hip"):
+        raise ValueError(f"build_optimizer: impl must be 'torch' or 'hip', got {impl!r}")
     decay, no_decay = [], []
     for n, p in model.named_parameters():
         if not p.requires_grad:
@@ -384,6 +388,8 @@ def build_optimizer(model: nn.Module, lr=5e-4, weight_decay=0.05, fused: Optiona
         else:
             decay.append(p)
     groups = [{"params": decay}, {"params": no_decay, "weight_decay": 0.0}]
+    if impl == "hip":
+        return FusedAdamW(groups, lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay)
     if fused is None:
         fused = all(p.is_cuda for p in decay + no_decay)
     return torch.optim.AdamW(groups, lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay, fused=fused,
@@ -452,10 +458,17 @@ def _factor_packer(model):
 
 
 def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 5.0, reducer=None,
-               amp_dtype: Optional[torch.dtype] = torch.bfloat16, fused_loss: bool = True):
+               amp_dtype: Optional[torch.dtype] = torch.bfloat16, fused_loss: bool = True, loss_scaler=None,
+               update_grad: bool = True):
     """one reference train step (main.py:329-354): autocast fwd + weighted multi-task loss, backward,
     [gradient all-reduce], clip_grad_norm_(5.0), AdamW, zero_grad.  bf16 autocast needs no GradScaler
-    (the reference's scaler exists for its fp16 default)."""
+    (the reference's scaler exists for its fp16 default: ``loss_scaler``, an ``optim.LossScaler``, scales the loss before
+    backward and is unscaled / updated inside the ``optim.FusedAdamW`` update).  ``update_grad=False`` is a gradient-accumulation
+    micro-step (main.py:349): forward and backward only, the gradients stay and ``(loss, None)`` is returned.  With a
+    ``FusedAdamW`` the clip, the step and the scaler update are ``clip_and_step``'s three launches."""
+    fused_opt = isinstance(optimizer, FusedAdamW)
+    if loss_scaler is not None and not fused_opt:
+        raise TypeError("train_step: loss_scaler needs the HIP optimizer (build_optimizer(impl='hip'))")
     def fwd():
         if fused_loss:  # final upsample + losses (+ their backward) as one kernel per task, inside the task's stream
             if isinstance(model, MultiTaskSwin):
@@ -482,7 +495,7 @@ def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 
         reducer.prepare()
     Fn.set_factor_stream(side)
     try:
-        loss.backward()
+        (loss if loss_scaler is None else loss_scaler.scale(loss)).backward()
     finally:
         Fn.set_factor_stream(None)
     if side is not None:
@@ -490,6 +503,12 @@ def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 
         Fn.factor_stream_joined()
     if reducer is not None:
         reducer.finish()
+    if not update_grad:
+        return loss.detach(), None
+    if fused_opt:
+        norm = optimizer.clip_and_step(clip_grad or None, loss_scaler)
+        optimizer.zero_grad(set_to_none=True)
+        return loss.detach(), norm
     params = [p for g in optimizer.param_groups for p in g["params"] if p.grad is not None]
     norm = torch.nn.utils.clip_grad_norm_(params, clip_grad, foreach=True) if clip_grad else None
     optimizer.step()

@@ -1,0 +1,255 @@
+"""The parameter update of the train step on the HIP path (csrc/optim.hip): gradient norm, clip, loss-scale unscale, inf / nan
+skip, AdamW and the scaler update as THREE launches for all trainable tensors, with no host synchronisation.
+
+Replaces the reference's ``NativeScalerWithGradNormCount`` + ``torch.optim.AdamW`` pair (utils.py:348-375, optimizer.py:71-85,
+called at main.py:347-353):
+
+    optimizer = FusedAdamW(param_groups, lr=..., weight_decay=...)
+    loss_scaler = LossScaler()
+    grad_norm = loss_scaler(loss, optimizer, clip_grad=5.0, update_grad=(idx + 1) % accumulation_steps == 0)
+
+fp32 parameters, gradients and state only; there is no fallback: anything else raises.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Any, Dict, List, Optional
+
+import torch
+
+from . import _lib
+
+__all__ = ["FusedAdamW", "LossScaler", "uniform_step"]
+
+_STATE_ALIGN = 4  # elements: every tensor's slice of the flat state buffers starts 16-byte aligned
+
+
+def uniform_step(state: Dict[Any, Dict[str, Any]]) -> float:
+    """the one step count of an AdamW ``state`` mapping (``state_dict()["state"]`` or ``optimizer.state``); 0 if it is empty.
+    The kernels keep ONE device counter for all parameters, so a state whose per-parameter steps differ cannot be represented."""
+    steps = {float(s["step"]) for s in state.values() if "step" in s}
+    if len(steps) > 1:
+        raise ValueError(f"mtlora_amd: FusedAdamW keeps one step counter for all parameters; this state has steps {sorted(steps)}")
+    return steps.pop() if steps else 0.0
+
+
+class FusedAdamW(torch.optim.Optimizer):
+    """``torch.optim.AdamW`` (decoupled weight decay) whose ``step`` is the multi-tensor HIP update.
+
+    * ``step()`` is plain AdamW; ``clip_and_step(max_norm, scaler)`` is the fused clip_grad_norm_ + unscale + AdamW + scaler update.
+    * ``exp_avg`` / ``exp_avg_sq`` live in two flat fp32 buffers; ``state[p]`` holds views into them and a 0-d view of the single
+      device step counter.  A parameter gets its ``state`` entry the first time it has a gradient, as in torch.
+    * ``state_dict()`` / ``load_state_dict()`` use torch AdamW's format, so checkpoints interchange with ``torch.optim.AdamW``
+      (``state_dict()`` returns copies, not views).  The one restriction: all parameters share ONE step counter.
+    * A gradient holding inf / nan skips the whole step on the device (parameters, state and the counter stay bitwise unchanged),
+      with or without a scaler; the returned norm is then non-finite.
+    * Every parameter that had a gradient gets its ``_version`` bumped after each call -- the kernels write through raw pointers,
+      and ``MTLoRALinear`` / ``FactorPacker`` judge freshness by ``_version``.  This includes skipped steps (the skip is decided
+      on the device; the host cannot know).
+    """
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 amsgrad: bool = False, maximize: bool = False):
+        if amsgrad or maximize:
+            raise ValueError("mtlora_amd: FusedAdamW supports neither amsgrad nor maximize")
+        if isinstance(lr, torch.Tensor):
+            raise ValueError("mtlora_amd: FusedAdamW takes lr as a Python number (it travels in the launch arguments)")
+        if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"mtlora_amd: invalid AdamW hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
+        # torch AdamW's group keys, so that the two state_dict formats interchange
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
+                        capturable=False, differentiable=False, fused=None, decoupled_weight_decay=True)
+        super().__init__(params, defaults)
+        if len(self.param_groups) > _lib.ADAMW_MAX_GROUPS:
+            raise ValueError(f"mtlora_amd: FusedAdamW supports up to {_lib.ADAMW_MAX_GROUPS} parameter groups")
+        self._params: List[torch.Tensor] = []
+        group_of: List[int] = []
+        for gi, g in enumerate(self.param_groups):
+            if g.get("amsgrad") or g.get("maximize"):
+                raise ValueError("mtlora_amd: FusedAdamW supports neither amsgrad nor maximize")
+            for p in g["params"]:
+                if p.dtype != torch.float32:
+                    raise TypeError(f"mtlora_amd: FusedAdamW updates fp32 parameters only (got {p.dtype}); keep fp32 masters "
+                                    "and run the model under autocast")
+                self._params.append(p)
+                group_of.append(gi)
+        _lib.require_gpu(*self._params)
+        for p in self._params:
+            if not p.is_contiguous():
+                raise ValueError("mtlora_amd: FusedAdamW needs contiguous parameters")
+            if p.device != self._params[0].device:
+                raise ValueError("mtlora_amd: FusedAdamW needs all parameters on one device")
+        self._build(group_of)
+
+    # ---- device side -------------------------------------------------------------------------------------------------------
+    def _build(self, group_of: List[int]) -> None:
+        L, dev, nt = _lib.lib(), self._params[0].device, len(self._params)
+        self._offsets, total = [], 0
+        for p in self._params:
+            self._offsets.append(total)
+            total += -(-p.numel() // _STATE_ALIGN) * _STATE_ALIGN
+        self._exp_avg = torch.zeros(max(total, 1), dtype=torch.float32, device=dev)
+        self._exp_avg_sq = torch.zeros(max(total, 1), dtype=torch.float32, device=dev)
+        self._ctrl = torch.zeros(_lib.ADAMW_CTRL_WORDS, dtype=torch.float32, device=dev)
+        self._has_state = [False] * nt
+        numel = (ctypes.c_int64 * nt)(*[p.numel() for p in self._params])
+        nc, tb, sb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(L.mtlora_adamw_sizes(nt, numel, ctypes.byref(nc), ctypes.byref(tb), ctypes.byref(sb)), "adamw_sizes")
+        self._n_chunks, self._scratch_bytes = nc.value, sb.value
+        host = torch.zeros(tb.value // 8, dtype=torch.int64)
+        PA = ctypes.c_void_p * nt
+        mp, vp = self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr()
+        _lib.check(L.mtlora_adamw_table(nt, numel, (ctypes.c_int32 * nt)(*group_of), PA(*[p.data_ptr() for p in self._params]),
+                                        PA(*[mp + 4 * o for o in self._offsets]), PA(*[vp + 4 * o for o in self._offsets]),
+                                        ctypes.c_void_p(host.data_ptr()), tb.value), "adamw_table")
+        self._table = host.to(dev)
+        self._param_ptrs = [p.data_ptr() for p in self._params]  # (the table holds them: a re-allocated .data is an error)
+        self._grad_ptrs = torch.zeros(nt, dtype=torch.int64, device=dev)
+        self._scratch = torch.empty(max(self._scratch_bytes // 4, 1), dtype=torch.float32, device=dev)
+        self._groups = (_lib.AdamwGroup * len(self.param_groups))()
+
+    def _slot(self, i: int, buf: torch.Tensor) -> torch.Tensor:
+        p = self._params[i]
+        return buf[self._offsets[i]:self._offsets[i] + p.numel()].view(p.shape)
+
+    def _init_state(self, i: int) -> None:
+        self.state[self._params[i]] = {"step": self._ctrl[4], "exp_avg": self._slot(i, self._exp_avg),
+                                       "exp_avg_sq": self._slot(i, self._exp_avg_sq)}
+        self._has_state[i] = True
+
+    # ---- the update --------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def clip_and_step(self, max_norm: Optional[float] = None, scaler: Optional["LossScaler"] = None) -> torch.Tensor:
+        """unscale (``scaler``) + clip_grad_norm_(``max_norm``) + AdamW + scaler update; returns the total norm of the unscaled
+        gradients before clipping as a 0-d device tensor (no ``.item()``, no synchronisation)."""
+        params, ptrs, live, has = self._params, [], [], self._has_state
+        _lib.require_gpu(params[0])
+        for i, p in enumerate(params):
+            g = p.grad
+            if g is None:
+                ptrs.append(0)
+                continue
+            if not g.is_contiguous():  # (dtype, device and shape are the parameter's: torch checks them when .grad is set)
+                raise RuntimeError(f"mtlora_amd: FusedAdamW needs dense contiguous gradients (parameter {i}: strides {g.stride()})")
+            if p.data_ptr() != self._param_ptrs[i]:
+                raise RuntimeError(f"mtlora_amd: parameter {i} was re-allocated after FusedAdamW was built; build a new optimizer")
+            if not has[i]:
+                self._init_state(i)
+            ptrs.append(g.data_ptr())
+            live.append(p)
+        dev = params[0].device
+        # pinned staging from torch's caching host allocator: the block is not reused before this copy has run
+        host = torch.empty(len(ptrs), dtype=torch.int64, pin_memory=True)
+        host.copy_(torch.tensor(ptrs, dtype=torch.int64))
+        self._grad_ptrs.copy_(host, non_blocking=True)
+        for gi, g in enumerate(self.param_groups):
+            s = self._groups[gi]
+            s.lr, (s.beta1, s.beta2), s.eps, s.weight_decay = g["lr"], g["betas"], g["eps"], g["weight_decay"]
+        norm = torch.empty((), dtype=torch.float32, device=dev)
+        if scaler is not None:
+            scaler._lazy_init(dev)
+            sc, tr = scaler._scale.data_ptr(), scaler._growth_tracker.data_ptr()
+            gf, bf, gint = scaler._growth_factor, scaler._backoff_factor, scaler._growth_interval
+        else:
+            sc, tr, gf, bf, gint = 0, 0, 2.0, 0.5, 1
+        _lib.check(_lib.lib().mtlora_adamw_update(
+            self._table.data_ptr(), self._grad_ptrs.data_ptr(), len(params), self._n_chunks, self._groups, len(self.param_groups),
+            float(max_norm) if max_norm else 0.0, self._ctrl.data_ptr(), norm.data_ptr(), sc, tr, gf, bf, gint,
+            self._scratch.data_ptr(), self._scratch_bytes, _lib.stream_ptr()), "adamw_update")
+        if live:
+            torch.autograd.graph.increment_version(live)
+        self._opt_called = True  # (what torch's LR schedulers look at to order scheduler.step() after optimizer.step())
+        return norm
+
+    def step(self, closure=None):
+        """plain AdamW (no clip, no scaler)"""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self.clip_and_step()
+        return loss
+
+    # ---- checkpoints -------------------------------------------------------------------------------------------------------
+    def state_dict(self) -> Dict[str, Any]:
+        """torch AdamW's format; the tensors are copies (torch's ``load_state_dict`` keeps same-device tensors as they are, and a
+        torch optimizer loaded from views would update this optimizer's buffers and step counter in place)"""
+        sd = super().state_dict()
+        sd["state"] = {k: {n: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for n, v in s.items()}
+                       for k, s in sd["state"].items()}
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict: Dict[str, Any]) -> None:
+        step = uniform_step(state_dict["state"])  # before anything is touched
+        for g in state_dict["param_groups"]:
+            if g.get("amsgrad") or g.get("maximize"):
+                raise ValueError("mtlora_amd: FusedAdamW supports neither amsgrad nor maximize")
+        super().load_state_dict(state_dict)
+        index = {id(p): i for i, p in enumerate(self._params)}
+        loaded = dict(self.state)
+        self.state.clear()
+        self._exp_avg.zero_()
+        self._exp_avg_sq.zero_()
+        self._has_state = [False] * len(self._params)
+        for p, s in loaded.items():
+            i = index[id(p)]
+            self._slot(i, self._exp_avg).copy_(s["exp_avg"])
+            self._slot(i, self._exp_avg_sq).copy_(s["exp_avg_sq"])
+            self._init_state(i)
+        self._ctrl.zero_()
+        self._ctrl[4] = step
+
+
+class LossScaler:
+    """The reference's ``NativeScalerWithGradNormCount`` (utils.py:348-375) for ``FusedAdamW``: the scale and the growth tracker
+    live on the device and are read / updated by the optimizer's kernels (``torch.amp.GradScaler`` semantics: a step with inf /
+    nan gradients is skipped and the scale backs off; ``growth_interval`` good steps in a row grow it).  ``state_dict`` has
+    ``GradScaler``'s keys."""
+    state_dict_key = "amp_scaler"
+
+    def __init__(self, init_scale: float = 2.0 ** 16, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                 growth_interval: int = 2000):
+        if growth_factor <= 1.0 or not 0.0 < backoff_factor < 1.0 or growth_interval < 1:
+            raise ValueError("mtlora_amd: LossScaler needs growth_factor > 1, 0 < backoff_factor < 1, growth_interval >= 1")
+        self._init_scale, self._init_growth_tracker = float(init_scale), 0
+        self._growth_factor, self._backoff_factor, self._growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        self._scale: Optional[torch.Tensor] = None
+        self._growth_tracker: Optional[torch.Tensor] = None
+
+    def _lazy_init(self, device) -> None:
+        if self._scale is None:
+            _lib.require_gpu(torch.empty(0, device=device))
+            self._scale = torch.full((), self._init_scale, dtype=torch.float32, device=device)
+            self._growth_tracker = torch.full((), self._init_growth_tracker, dtype=torch.int32, device=device)
+
+    def scale(self, loss: torch.Tensor) -> torch.Tensor:
+        self._lazy_init(loss.device)
+        return loss * self._scale.to(loss.dtype)
+
+    def get_scale(self) -> float:
+        return self._init_scale if self._scale is None else float(self._scale.item())
+
+    def __call__(self, loss, optimizer, clip_grad=None, parameters=None, create_graph=False, update_grad=True):
+        """scaled backward, then (``update_grad``) the fused update; returns the gradient norm, or None when the gradients are
+        only accumulated.  ``parameters`` is accepted for the reference's signature: what is clipped is the optimizer's own set."""
+        if not isinstance(optimizer, FusedAdamW):
+            raise TypeError("mtlora_amd: LossScaler drives FusedAdamW only (build_optimizer(impl='hip')); "
+                            f"got {type(optimizer).__name__}")
+        self.scale(loss).backward(create_graph=create_graph)
+        return optimizer.clip_and_step(max_norm=clip_grad, scaler=self) if update_grad else None
+
+    def state_dict(self) -> Dict[str, Any]:
+        tracker = self._init_growth_tracker if self._growth_tracker is None else int(self._growth_tracker.item())
+        return {"scale": self.get_scale(), "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
+                "growth_interval": self._growth_interval, "_growth_tracker": tracker}
+
+    def load_state_dict(self, state_dict: Dict[str, Any]) -> None:
+        if len(state_dict) == 0:
+            raise RuntimeError("mtlora_amd: the source state dict is empty, possibly because it was saved from a disabled GradScaler")
+        self._init_scale = float(state_dict["scale"])
+        self._growth_factor, self._backoff_factor = float(state_dict["growth_factor"]), float(state_dict["backoff_factor"])
+        self._growth_interval, self._init_growth_tracker = int(state_dict["growth_interval"]), int(state_dict["_growth_tracker"])
+        if self._scale is not None:
+            self._scale.fill_(self._init_scale)
+            self._growth_tracker.fill_(self._init_growth_tracker)
