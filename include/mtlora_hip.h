@@ -27,15 +27,16 @@
 extern "C" {
 #endif
 
-#define MTLORA_ABI_VERSION 10
+#define MTLORA_ABI_VERSION 11
 #define MTLORA_MAX_TASKS 8
 
 typedef enum mtlora_dtype {
     MTLORA_F32 = 0,  /* exact-f32 MFMA path (v_mfma_f32_32x32x2_f32) */
     MTLORA_BF16 = 1, /* bf16 in/out, fp32 accumulate (v_mfma_f32_32x32x16_bf16) */
-    MTLORA_F16 = 2   /* fp16 in/out, fp32 accumulate (v_mfma_f32_32x32x16_f16): MTLoRALinear, window attention, gemm_tn, the
+    MTLORA_F16 = 2,  /* fp16 in/out, fp32 accumulate (v_mfma_f32_32x32x16_f16): MTLoRALinear, window attention, gemm_tn, the
                         window_process copies and the block glue (LayerNorm family, residual + DropPath, BatchNorm + ReLU) -- the
                         reference's default autocast dtype (main.py:341); upsample / loss / column-sum entries take fp32 / bf16 */
+    MTLORA_U8 = 3    /* OUTPUT dtype of mtlora_upsample_predict only (ABI v11): class ids and [0, 255] images */
 } mtlora_dtype;
 
 typedef enum mtlora_status {
@@ -429,6 +430,24 @@ int mtlora_upsample_metrics_sizes(int kind, int64_t B, int h, int w, int C, int 
 int mtlora_upsample_metrics(int kind, const void* low, const float* label, const float* stat, int64_t* counts,
                             float* fpartials, int64_t B, int h, int w, int C, int scale, int dtype, float ignore_index,
                             void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Full-resolution predictions, fused (ABI v11): replaces, for one task and one batch, the final
+ * F.interpolate(pred, img_size, mode="bilinear") of models/swin_mtl.py:245 TOGETHER WITH get_output
+ * (evaluation/evaluate_utils.py:20-38) -- what utils.py:405-439 save_imgs_mtl and any offline scoring (the edge benchmark)
+ * take.  Forward only, no label; the upsampled logits never exist, only the processed prediction is written.
+ *   kind 0  argmax (semseg, human_parts), C <= 48: out (B,H,W) MTLORA_U8, the index of the FIRST maximum (torch.max(dim)[1])
+ *   kind 1  normals, C <= 4: out (B,H,W,C), (up / max(|up|, 1e-12) + 1) * 255 / 2 (F.normalize's form)
+ *   kind 2  sigmoid (sal, edge), C = 1: out (B,H,W), 255 / (1 + exp(-up))
+ *   kind 3  identity (depth), C = 1: out (B,H,W,1) MTLORA_F32, up
+ * out_dtype of kinds 1 and 2: MTLORA_F32 (get_output's value) or MTLORA_U8 (the same fp32 value truncated, as
+ * tensor.to(torch.uint8) converts a value in [0, 255]).  low (B,h,w,C) channels-last fp32 / bf16 / fp16, H = scale*h,
+ * W = scale*w, integer scale 1..32, align_corners=False as mtlora_upsample_loss.  A C or scale out of range, an unknown kind
+ * or a kind / out_dtype pair not listed: MTLORA_ERR_UNSUPPORTED before any launch.  `out` is contiguous and aligned to its
+ * element; every element of it is written exactly once and nothing else is.  Deterministic; no atomics, no memset.
+ * ------------------------------------------------------------------------------------------ */
+int mtlora_upsample_predict(int kind, const void* low, void* out, int64_t B, int h, int w, int C, int scale, int dtype,
+                            int out_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Small deterministic reductions of the callers (two launches each: per-block partials, fixed-order combine; no atomics and

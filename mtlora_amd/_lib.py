@@ -12,8 +12,8 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 import torch
 
 MAX_TASKS = 8
-ABI_VERSION = 10
-F32, BF16, F16 = 0, 1, 2
+ABI_VERSION = 11
+F32, BF16, F16, U8 = 0, 1, 2, 3  # (U8: output dtype of mtlora_upsample_predict only)
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -173,6 +173,7 @@ _SIGS = {
     "mtlora_upsample_metrics_sizes": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "mtlora_upsample_metrics": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                         c_int, c_int, ctypes.c_float, c_void_p]),
+    "mtlora_upsample_predict": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mtlora_upsample_cl_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int64, c_int, c_void_p]),
     "mtlora_upsample_cl_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int64, c_int, c_void_p]),
     "mtlora_block_save_bytes": (c_int64, [POINTER(BlockDesc)]),

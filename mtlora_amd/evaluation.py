@@ -53,6 +53,23 @@ def get_output(output: torch.Tensor, task: str) -> torch.Tensor:
     raise ValueError("Select one of the valid tasks")
 
 
+PREDICT_KIND = {"semseg": "argmax", "human_parts": "argmax", "normals": "normals", "sal": "sigmoid", "edge": "sigmoid",
+                "depth": "identity"}
+
+
+def get_output_low(low: torch.Tensor, task: str, scale: int, uint8: bool = False) -> torch.Tensor:
+    """the fused twin of ``get_output``: ``get_output(F.interpolate(low.permute(0, 3, 1, 2), scale_factor=scale,
+    mode="bilinear"), task)`` from the LOW-resolution (B, h, w, C) head output of ``model(x, upsample=False)`` in one launch
+    (csrc/predict.hip); the full-resolution logits never exist.  GPU only.  Shapes are ``get_output``'s for B > 1 -- the batch
+    axis of one image is kept, where the reference's ``squeeze()`` drops it -- and class maps are uint8 (``PerformanceMeter.update``
+    takes them).  ``uint8=True``: the [0, 255] images of normals / sal / edge truncated to uint8, ready to be written out."""
+    from . import functional as Fn
+    if task not in PREDICT_KIND:
+        raise ValueError("Select one of the valid tasks")
+    kind = PREDICT_KIND[task]
+    return Fn.upsample_predict(kind, low, scale, out_dtype=torch.uint8 if (uint8 and kind in ("normals", "sigmoid")) else None)
+
+
 class _Meter:
     """state: ``counts`` (int64) and ``sums`` (fp64) tensors, created on the device of the first batch"""
     n_counts, n_sums = 0, 0

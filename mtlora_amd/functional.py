@@ -1561,6 +1561,41 @@ def upsample_metrics(kind: str, low, label, scale: int, counts=None, ignore_inde
     return counts, part[:nfp].view(nq, nfp // nq).sum(1, dtype=torch.float64)
 
 
+PREDICT_KINDS = {"argmax": 0, "normals": 1, "sigmoid": 2, "identity": 3}
+_PREDICT_OUT = {"argmax": (torch.uint8,), "normals": (torch.float32, torch.uint8), "sigmoid": (torch.float32, torch.uint8),
+                "identity": (torch.float32,)}  # the kind's output dtypes, default first
+
+
+@torch.no_grad()
+def upsample_predict(kind: str, low, scale: int, out_dtype=None, out=None):
+    """``get_output(F.interpolate(low.permute(0,3,1,2), scale_factor=scale, mode="bilinear"), task)`` in ONE launch
+    (csrc/predict.hip; include/mtlora_hip.h): ``low`` (B, h, w, C) channels-last fp32 / bf16 / fp16, the result at H = scale h,
+    W = scale w.  ``argmax``: uint8 (B, H, W) class ids; ``normals``: (B, H, W, C) in [0, 255]; ``sigmoid``: (B, H, W) in
+    [0, 255]; ``identity``: fp32 (B, H, W, 1).  ``out_dtype`` of normals / sigmoid: fp32 (default, get_output's values) or uint8
+    (truncated, as ``.to(torch.uint8)``).  ``out``: a contiguous tensor of that shape and dtype to write into.  No host sync."""
+    if kind not in PREDICT_KINDS:
+        raise RuntimeError(f"mtlora_amd: unknown fused prediction kind {kind!r}")
+    L.require_gpu(low, out)
+    B, h, w, C = low.shape
+    H, W = h * int(scale), w * int(scale)
+    if out_dtype is None:
+        out_dtype = _PREDICT_OUT[kind][0] if out is None else out.dtype
+    if out_dtype not in _PREDICT_OUT[kind]:
+        raise RuntimeError(f"mtlora_amd: fused prediction kind {kind!r} writes {_PREDICT_OUT[kind]}, not {out_dtype}")
+    shape = {"argmax": (B, H, W), "normals": (B, H, W, C), "sigmoid": (B, H, W), "identity": (B, H, W, 1)}[kind]
+    lo = low.detach().contiguous()
+    if lo.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        lo = lo.float()
+    if out is None:
+        out = torch.empty(shape, dtype=out_dtype, device=lo.device)
+    elif tuple(out.shape) != shape or out.dtype != out_dtype or not out.is_contiguous() or out.device != lo.device:
+        raise RuntimeError(f"mtlora_amd: out must be a contiguous {out_dtype} tensor of shape {shape} on {lo.device}")
+    st = L.lib().mtlora_upsample_predict(PREDICT_KINDS[kind], L.ptr(lo), L.ptr(out), B, h, w, C, int(scale), L.dtype_code(lo),
+                                         L.U8 if out_dtype == torch.uint8 else L.F32, L.stream_ptr())
+    L.check(st, "mtlora_upsample_predict")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # plain (library) GEMM linears with a huge row count: weight gradient as a batched GEMM over row chunks
 # ----------------------------------------------------------------------------------------------

@@ -558,6 +558,52 @@ def validate(model, batches, criterion=None, meter=None, database: str = "PASCAL
     return scores, (float(total) / n if n else float("nan"))
 
 
+def predict_step(model, images, tasks=None, uint8=False, amp_dtype=torch.bfloat16):
+    """the full-resolution predictions of one batch, as ``get_output`` of the reference's ``model(images)`` gives them
+    (evaluate_utils.py:20-38; what utils.py:405-439 save_imgs_mtl writes): eval-mode forward under ``torch.no_grad()`` with
+    ``upsample=False``; each task's head runs on its side stream as in ``validate_step`` and ends in ONE launch
+    (``evaluation.get_output_low``: final upsample + get_output, csrc/predict.hip), so the full-resolution logits never exist.
+    Returns ``{task: prediction}`` for ``tasks`` (default: all of the model's): uint8 class maps, fp32 [0, 255] images (uint8
+    with ``uint8=True``), fp32 depth.  GPU only; no host sync.  ``model.training`` is restored; parameters, buffers, hooks and
+    the merged state are not touched."""
+    from .evaluation import get_output_low
+    wanted = list(model.tasks if tasks is None else tasks)
+    H, W = images.shape[-2:]
+
+    def finish(t, lo):
+        if t not in wanted:
+            return lo
+        h, w = lo.shape[1:3]
+        if H % h or W % w or H // h != W // w:
+            raise RuntimeError(f"mtlora_amd: predict_step needs an integer scale, got {(h, w)} -> {(H, W)} for {t}")
+        return get_output_low(lo, t, H // h, uint8)
+
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            ctx = (torch.autocast("cuda", dtype=amp_dtype) if (amp_dtype is not None and images.is_cuda)
+                   else contextlib.nullcontext())
+            with ctx:
+                if isinstance(model, MultiTaskSwin):
+                    conc = images.is_cuda and _TASK_STREAMS and len(model.tasks) > 1 and _streams_allowed()
+                    per = model(images, upsample=False, concurrent=conc, per_task_fn=finish)
+                else:
+                    low = model(images, upsample=False)
+                    per = {t: finish(t, low[t]) for t in wanted}
+            return {t: per[t] for t in wanted}
+    finally:
+        model.train(was_training)
+
+
+def predict(model, batches, tasks=None, uint8=False, amp_dtype=torch.bfloat16):
+    """``predict_step`` over ``batches`` (an iterable of image tensors, or of ``(images, ...)`` tuples as a validation loader
+    yields them): a generator of one ``{task: prediction}`` dict per batch."""
+    for batch in batches:
+        images = batch[0] if isinstance(batch, (tuple, list)) else batch
+        yield predict_step(model, images, tasks, uint8, amp_dtype)
+
+
 class GraphedTrainStep:
     """The SAME train step as ``train_step``, captured once as HIP graph(s) and replayed: the step issues ~1500 kernel
     launches plus the Python / autograd / ctypes work behind them (~50 ms of host time against ~55 ms of GPU time at
