@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MTLORA_ABI_VERSION 11
+#define MTLORA_ABI_VERSION 12
 #define MTLORA_MAX_TASKS 8
 
 typedef enum mtlora_dtype {
@@ -36,7 +36,8 @@ typedef enum mtlora_dtype {
     MTLORA_F16 = 2,  /* fp16 in/out, fp32 accumulate (v_mfma_f32_32x32x16_f16): MTLoRALinear, window attention, gemm_tn, the
                         window_process copies and the block glue (LayerNorm family, residual + DropPath, BatchNorm + ReLU) -- the
                         reference's default autocast dtype (main.py:341); upsample / loss / column-sum entries take fp32 / bf16 */
-    MTLORA_U8 = 3    /* OUTPUT dtype of mtlora_upsample_predict only (ABI v11): class ids and [0, 255] images */
+    MTLORA_U8 = 3    /* OUTPUT dtype of mtlora_upsample_predict (ABI v11): class ids and [0, 255] images; SOURCE dtype of the
+                        image and class-map jobs of mtlora_ingest_batch (ABI v12) */
 } mtlora_dtype;
 
 typedef enum mtlora_status {
@@ -597,6 +598,52 @@ int mtlora_adamw_update(const void* table, const void* grads, int64_t n_tensors,
                         const mtlora_adamw_group* groups, int n_groups, float max_norm, float* ctrl, float* norm_out,
                         float* scale, int32_t* growth_tracker, float growth_factor, float backoff_factor,
                         int growth_interval, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Batch ingest (ABI v12): the tail of the reference's loader pipelines on the device -- RandomHorizontalFlip,
+ * AddIgnoreRegions, ToTensor and Normalize of data/custom_transforms.py:192-209 and :266-341 -- for one batch in the
+ * narrowest lossless host format ("wire format": uint8 HWC image, uint8 class / binary maps, fp32 or fp16 HWC normals,
+ * fp32 depth), written as the fp32 (B, C, H, W) tensors the train, validation and prediction steps take.
+ *
+ * One job per tensor, at most MTLORA_INGEST_MAX_JOBS, passed by value in the launch arguments.  Per sample b, in this order:
+ *   flip[b] != 0: mirror along W; normals channel 0 changes sign
+ *   MTLORA_INGEST_IMAGE                 u8 (B,H,W,3) -> f32 (B,3,H,W), dst = lut[c * 256 + src]; `lut` is the caller's
+ *                                       (3, 256) table ((v / 255) - mean[c]) / std[c], so no division happens here
+ *   MTLORA_INGEST_CLASS                 u8 (B,H,W)   -> f32 (B,1,H,W), the value itself
+ *   MTLORA_INGEST_CLASS_ALLZERO_IGNORE  as CLASS; a sample that is 0 everywhere becomes 255 everywhere (human_parts)
+ *   MTLORA_INGEST_NORMALS               f32 or f16 (B,H,W,3) -> f32 (B,3,H,W); a pixel whose three components are all +-0
+ *                                       becomes 255 in all three channels
+ *   MTLORA_INGEST_DEPTH                 f32 (B,H,W)  -> f32 (B,1,H,W); +-0 becomes 255
+ * `C` is the channel count of the job (3 for IMAGE and NORMALS, 1 otherwise), `src_dtype` MTLORA_U8 / MTLORA_F32 /
+ * MTLORA_F16 as listed, `reserved` is ignored.  `src` may sit at any multiple of its element size (a uint8 source at any
+ * byte), `dst` is contiguous and 4-byte aligned; no input is written, every element of every dst is written exactly once.
+ *
+ * At most three launches on `stream`, no host synchronisation: with a CLASS_ALLZERO_IGNORE job a zeroing launch for the
+ * per-sample flag words in `scratch` and a pass that ORs "any non-zero" into them (integer atomic OR), then the main launch
+ * over all jobs.  Without such a job `scratch` is not touched (it may be NULL).  Deterministic; no float atomics.
+ * mtlora_ingest_scratch_bytes is a pure host call (negative status for arguments out of range).
+ *
+ * Rejected before any launch: n_jobs outside 1..8, an unknown kind, a C the kind does not take, B, H or W < 1, a null
+ * `jobs`, src or dst, an IMAGE job without `lut` (all MTLORA_ERR_UNSUPPORTED); a src_dtype the kind does not take
+ * (MTLORA_ERR_DTYPE); a src or dst off its element's alignment (MTLORA_ERR_ALIGN); a `scratch` that is needed and
+ * missing or too small (MTLORA_ERR_WORKSPACE).
+ * ------------------------------------------------------------------------------------------ */
+#define MTLORA_INGEST_MAX_JOBS 8
+typedef enum mtlora_ingest_kind {
+    MTLORA_INGEST_IMAGE = 0,
+    MTLORA_INGEST_CLASS = 1,
+    MTLORA_INGEST_CLASS_ALLZERO_IGNORE = 2,
+    MTLORA_INGEST_NORMALS = 3,
+    MTLORA_INGEST_DEPTH = 4
+} mtlora_ingest_kind;
+typedef struct mtlora_ingest_job {
+    const void* src;
+    void* dst;
+    int32_t kind, src_dtype, C, reserved;
+} mtlora_ingest_job;
+int64_t mtlora_ingest_scratch_bytes(int n_jobs, int64_t B);
+int mtlora_ingest_batch(const mtlora_ingest_job* jobs, int n_jobs, int64_t B, int32_t H, int32_t W, const uint8_t* flip,
+                        const float* lut, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Hardware self-test: writes the lane->element maps of the MFMA / LDS-transpose primitives the

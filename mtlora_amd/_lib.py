@@ -12,8 +12,8 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 import torch
 
 MAX_TASKS = 8
-ABI_VERSION = 11
-F32, BF16, F16, U8 = 0, 1, 2, 3  # (U8: output dtype of mtlora_upsample_predict only)
+ABI_VERSION = 12
+F32, BF16, F16, U8 = 0, 1, 2, 3  # (U8: output dtype of mtlora_upsample_predict, source dtype of mtlora_ingest_batch)
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -66,6 +66,15 @@ class AdamwGroup(Structure):
     """mtlora_adamw_group (ABI v10): one parameter group's hyper-parameters, passed by value every step"""
     _fields_ = [("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double)]
 
+
+class IngestJob(Structure):
+    """mtlora_ingest_job (ABI v12): one tensor of a host batch in wire format, passed by value"""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("kind", c_int32), ("src_dtype", c_int32), ("C", c_int32),
+                ("reserved", c_int32)]
+
+
+INGEST_MAX_JOBS = 8
+INGEST_IMAGE, INGEST_CLASS, INGEST_CLASS_ALLZERO_IGNORE, INGEST_NORMALS, INGEST_DEPTH = 0, 1, 2, 3, 4
 
 ADAMW_CHUNK, ADAMW_MAX_GROUPS, ADAMW_CTRL_WORDS = 4096, 16, 64
 
@@ -188,6 +197,9 @@ _SIGS = {
                                    c_void_p, c_int64]),
     "mtlora_adamw_update": (c_int, [c_void_p, c_void_p, c_int64, c_int64, POINTER(AdamwGroup), c_int, c_float, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_float, c_float, c_int, c_void_p, c_int64, c_void_p]),
+    "mtlora_ingest_scratch_bytes": (c_int64, [c_int, c_int64]),
+    "mtlora_ingest_batch": (c_int, [POINTER(IngestJob), c_int, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
+                                    c_void_p]),
     "mtlora_selftest_layouts": (c_int, [c_void_p, c_void_p]),
     "mtlora_prof_begin": (c_int, [c_int]),
     "mtlora_prof_end": (c_int, [POINTER(ProfSummary)]),

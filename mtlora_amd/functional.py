@@ -1597,6 +1597,56 @@ def upsample_predict(kind: str, low, scale: int, out_dtype=None, out=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# batch ingest: wire-format tensors on the device -> the fp32 (B, C, H, W) tensors of the steps (csrc/ingest.hip)
+# ----------------------------------------------------------------------------------------------
+INGEST_KINDS = {"image": L.INGEST_IMAGE, "class": L.INGEST_CLASS, "class_allzero_ignore": L.INGEST_CLASS_ALLZERO_IGNORE,
+                "normals": L.INGEST_NORMALS, "depth": L.INGEST_DEPTH}
+_INGEST_SRC = {torch.uint8: L.U8, torch.float32: L.F32, torch.float16: L.F16}
+
+
+def ingest_batch(jobs, flip=None, lut=None):
+    """one ``mtlora_ingest_batch`` call (include/mtlora_hip.h) on the current stream: ``jobs`` is a sequence of
+    ``(kind, src)`` with ``kind`` in ``INGEST_KINDS`` and ``src`` a contiguous device tensor in wire format -- image uint8
+    (B, H, W, 3), class maps uint8 (B, H, W), normals fp32 / fp16 (B, H, W, 3), depth fp32 (B, H, W) -- all of one B, H, W;
+    ``flip`` uint8 (B,) or None; ``lut`` the (3, 256) fp32 table of the image job (data.image_table).  Allocates the outputs
+    (fp32 (B, C, H, W), returned in job order) and the flag scratch.  The library validates kinds, dtypes and channel counts;
+    no host sync."""
+    jobs = list(jobs)
+    srcs = [s for _, s in jobs]
+    L.require_gpu(*srcs, flip, lut)
+    if not jobs:
+        raise RuntimeError("mtlora_amd: ingest_batch needs at least one job")
+    B, H, W = srcs[0].shape[:3]
+    arr = (L.IngestJob * max(len(jobs), 1))()
+    outs = []
+    for i, (kind, src) in enumerate(jobs):
+        if kind not in INGEST_KINDS:
+            raise RuntimeError(f"mtlora_amd: unknown ingest kind {kind!r}")
+        C = src.shape[3] if src.dim() == 4 else 1
+        if src.dim() not in (3, 4) or tuple(src.shape[:3]) != (B, H, W) or not src.is_contiguous():
+            raise RuntimeError(f"mtlora_amd: ingest job {i} ({kind}) must be a contiguous (B, H, W[, C]) tensor with "
+                               f"B, H, W = {(B, H, W)}, got {tuple(src.shape)}")
+        if src.dtype not in _INGEST_SRC:
+            raise RuntimeError(f"mtlora_amd: unsupported dtype {src.dtype} for an ingest source (uint8, fp32 and fp16 are supported)")
+        out = torch.empty((B, C, H, W), dtype=torch.float32, device=src.device)
+        outs.append(out)
+        arr[i].src, arr[i].dst, arr[i].kind, arr[i].src_dtype, arr[i].C = src.data_ptr(), out.data_ptr(), INGEST_KINDS[kind], \
+            _INGEST_SRC[src.dtype], C
+    if flip is not None and (flip.dtype != torch.uint8 or tuple(flip.shape) != (B,) or not flip.is_contiguous()):
+        raise RuntimeError(f"mtlora_amd: flip must be a contiguous uint8 tensor of shape ({B},)")
+    if lut is not None and (lut.dtype != torch.float32 or tuple(lut.shape) != (3, 256) or not lut.is_contiguous()):
+        raise RuntimeError("mtlora_amd: lut must be a contiguous fp32 tensor of shape (3, 256)")
+    scratch, nbytes = None, 0
+    if any(kind == "class_allzero_ignore" for kind, _ in jobs):
+        nbytes = int(L.lib().mtlora_ingest_scratch_bytes(len(jobs), B))
+        if nbytes > 0:
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=srcs[0].device)
+    st = L.lib().mtlora_ingest_batch(arr, len(jobs), B, H, W, L.ptr(flip), L.ptr(lut), L.ptr(scratch), nbytes, L.stream_ptr())
+    L.check(st, "mtlora_ingest_batch")
+    return outs
+
+
+# ----------------------------------------------------------------------------------------------
 # plain (library) GEMM linears with a huge row count: weight gradient as a batched GEMM over row chunks
 # ----------------------------------------------------------------------------------------------
 def _layout_weight(weight, bias, cdtype, col_index, n_cols, pad_rows):
