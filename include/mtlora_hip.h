@@ -646,6 +646,58 @@ int mtlora_ingest_batch(const mtlora_ingest_job* jobs, int n_jobs, int64_t B, in
                         const float* lut, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Geometric augmentation (added under ABI v12, additive): the head of the reference's training pipeline on the device --
+ * ScaleNRotate (data/custom_transforms.py:24-88: cv2.getRotationMatrix2D about (w / 2, h / 2), cv2.warpAffine with
+ * BORDER_CONSTANT 0, the in-plane rotation of the normals :74-80, depth / sc :83-84) composed with FixedResize (:94-154, the
+ * renormalisation of the normals :144-150), as data/mtl_ds.py:846-859 chains them (and :866-867 for the resize-only test
+ * pipeline: rotation 0, scale 1) -- for one batch of decoded, un-resampled samples in "canvas format": every tensor stacked as
+ * (B, Hc, Wc[, 3]) with the dtypes of the wire format, sample b occupying the top-left size[b] = (h, w) rectangle of its
+ * canvas.  The outputs are the wire-format tensors at (Ho, Wo) that the batch ingest above takes.  ONE resample per pixel
+ * where the reference has two (it warps at source size and resizes afterwards).
+ *
+ * `size`  int32 (B, 2): h, w with 1 <= h <= Hc, 1 <= w <= Wc (clamped to the canvas on the device: no value makes the kernel
+ *         read outside a source).  Canvas pixels outside the rectangle are never read; they count as border (0).
+ * `geom`  int64 (B, 6): ax, bx, cx, ay, by, cy with MTLORA_AUGMENT_GEOM_BITS fraction bits; the source coordinate of output
+ *         pixel (u, v) is X = ax (2u + 1) + bx (2v + 1) + cx and Y likewise, in int64.  The caller composes them in float64.
+ * `side`  fp32 (B, 3): cos(rot), sin(rot), sc.  Needed by NORMALS and DEPTH jobs.
+ * `cubic_q15` int32 (32, 4), `cubic_f32` fp32 (32, 4): the four cubic weights (Keys, a = -0.75) at the fractions f / 32, rows
+ *         of the Q15 form summing to 32768.  Needed by IMAGE (q15) and NORMALS (f32) jobs.
+ *
+ * One job per tensor, at most MTLORA_INGEST_MAX_JOBS, passed by value in the launch arguments:
+ *   MTLORA_AUGMENT_IMAGE_CUBIC_U8     u8 (B,Hc,Wc,3) -> u8 (B,Ho,Wo,3); coordinate rounded to 1/32 pixel, 4 x 4 taps, integer
+ *                                     accumulation, clamp((acc + 2^29) >> 30, 0, 255)
+ *   MTLORA_AUGMENT_CLASS_NEAREST_U8   u8 (B,Hc,Wc) -> u8 (B,Ho,Wo); coordinate rounded half up to the source pixel
+ *   MTLORA_AUGMENT_NORMALS_CUBIC_F32  f32 (B,Hc,Wc,3) -> f32 (B,Ho,Wo,3); the same taps in fp32 (horizontal left to right, then
+ *                                     vertical top to bottom, no contraction), x' = x cos + y sin, y' = y cos - x sin, then
+ *                                     n / (|n| + 2^-52) unless MTLORA_AUGMENT_FLAG_NO_RENORM is set in `flags`
+ *   MTLORA_AUGMENT_DEPTH_NEAREST_F32  f32 (B,Hc,Wc) -> f32 (B,Ho,Wo); the nearest sample divided by sc
+ * A tap or a nearest sample outside [0, w) x [0, h) counts as 0.  `src` may sit at any multiple of its element size (a uint8
+ * source at any byte), `dst` is contiguous and 16-byte aligned; no input is written, every element of every dst is written
+ * exactly once.  One launch on `stream`, no host synchronisation, no scratch buffer; deterministic, plain vector stores.
+ *
+ * Rejected before any launch: n_jobs outside 1..8, an unknown kind or flag, B, Hc, Wc, Ho or Wo < 1, a null `jobs`, src, dst,
+ * `size` or `geom`, a job without the table or the side table it needs (all MTLORA_ERR_UNSUPPORTED); a src off its element's
+ * alignment, a dst off 16 bytes, a table off its element's alignment (MTLORA_ERR_ALIGN); more than 65535 samples or 2^31
+ * output pixels per sample (MTLORA_ERR_SHAPE).
+ * ------------------------------------------------------------------------------------------ */
+#define MTLORA_AUGMENT_GEOM_BITS 24
+#define MTLORA_AUGMENT_FLAG_NO_RENORM 1
+typedef enum mtlora_augment_kind {
+    MTLORA_AUGMENT_IMAGE_CUBIC_U8 = 0,
+    MTLORA_AUGMENT_CLASS_NEAREST_U8 = 1,
+    MTLORA_AUGMENT_NORMALS_CUBIC_F32 = 2,
+    MTLORA_AUGMENT_DEPTH_NEAREST_F32 = 3
+} mtlora_augment_kind;
+typedef struct mtlora_augment_job {
+    const void* src;
+    void* dst;
+    int32_t kind, flags;
+} mtlora_augment_job;
+int mtlora_augment_batch(const mtlora_augment_job* jobs, int n_jobs, int64_t B, int32_t Hc, int32_t Wc, int32_t Ho, int32_t Wo,
+                         const int32_t* size, const int64_t* geom, const float* side, const int32_t* cubic_q15,
+                         const float* cubic_f32, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hardware self-test: writes the lane->element maps of the MFMA / LDS-transpose primitives the
  * kernels rely on into `out` (int32[4096]) so a GPU test can assert them (tests/test_gpu_layouts.py).
  * ------------------------------------------------------------------------------------------ */

@@ -73,7 +73,14 @@ class IngestJob(Structure):
                 ("reserved", c_int32)]
 
 
+class AugmentJob(Structure):
+    """mtlora_augment_job: one tensor of a raw (canvas-format) batch and the wire-format tensor it becomes, passed by value"""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("kind", c_int32), ("flags", c_int32)]
+
+
 INGEST_MAX_JOBS = 8
+AUGMENT_IMAGE_CUBIC_U8, AUGMENT_CLASS_NEAREST_U8, AUGMENT_NORMALS_CUBIC_F32, AUGMENT_DEPTH_NEAREST_F32 = 0, 1, 2, 3
+AUGMENT_GEOM_BITS, AUGMENT_FLAG_NO_RENORM = 24, 1
 INGEST_IMAGE, INGEST_CLASS, INGEST_CLASS_ALLZERO_IGNORE, INGEST_NORMALS, INGEST_DEPTH = 0, 1, 2, 3, 4
 
 ADAMW_CHUNK, ADAMW_MAX_GROUPS, ADAMW_CTRL_WORDS = 4096, 16, 64
@@ -200,6 +207,8 @@ _SIGS = {
     "mtlora_ingest_scratch_bytes": (c_int64, [c_int, c_int64]),
     "mtlora_ingest_batch": (c_int, [POINTER(IngestJob), c_int, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                     c_void_p]),
+    "mtlora_augment_batch": (c_int, [POINTER(AugmentJob), c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "mtlora_selftest_layouts": (c_int, [c_void_p, c_void_p]),
     "mtlora_prof_begin": (c_int, [c_int]),
     "mtlora_prof_end": (c_int, [POINTER(ProfSummary)]),

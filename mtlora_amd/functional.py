@@ -1647,6 +1647,53 @@ def ingest_batch(jobs, flip=None, lut=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# geometric augmentation: raw canvas-format tensors on the device -> wire-format tensors at the output size (csrc/augment.hip)
+# ----------------------------------------------------------------------------------------------
+AUGMENT_KINDS = {"image_cubic_u8": L.AUGMENT_IMAGE_CUBIC_U8, "class_nearest_u8": L.AUGMENT_CLASS_NEAREST_U8,
+                 "normals_cubic_f32": L.AUGMENT_NORMALS_CUBIC_F32, "depth_nearest_f32": L.AUGMENT_DEPTH_NEAREST_F32}
+_AUGMENT_FORM = {"image_cubic_u8": (torch.uint8, 3), "class_nearest_u8": (torch.uint8, 1), "normals_cubic_f32": (torch.float32, 3),
+                 "depth_nearest_f32": (torch.float32, 1)}
+
+
+def augment_batch(jobs, size, coef, side, out_size, cubic_q15=None, cubic_f32=None, renormalize=True):
+    """one ``mtlora_augment_batch`` call (include/mtlora_hip.h) on the current stream: ``jobs`` is a sequence of ``(kind, src)``
+    with ``kind`` in ``AUGMENT_KINDS`` and ``src`` a contiguous device tensor on the canvas -- image uint8 (B, Hc, Wc, 3), class
+    maps uint8 (B, Hc, Wc), normals fp32 (B, Hc, Wc, 3), depth fp32 (B, Hc, Wc) -- all of one B, Hc, Wc; ``size`` int32 (B, 2),
+    ``coef`` int64 (B, 6), ``side`` fp32 (B, 3) and the two (32, 4) weight tables (data.cubic_table) on the device.  Allocates the
+    outputs ((B, Ho, Wo[, 3]) in the source's dtype, returned in job order); ``renormalize=False`` leaves the normals as the
+    interpolation and the in-plane rotation give them.  One launch, no host sync."""
+    jobs = list(jobs)
+    srcs = [s for _, s in jobs]
+    L.require_gpu(*srcs, size, coef, side, cubic_q15, cubic_f32)
+    if not jobs:
+        raise RuntimeError("mtlora_amd: augment_batch needs at least one job")
+    B, Hc, Wc = srcs[0].shape[:3]
+    Ho, Wo = int(out_size[0]), int(out_size[1])
+    for name, t, dt, shape in (("size", size, torch.int32, (B, 2)), ("coef", coef, torch.int64, (B, 6)), ("side", side, torch.float32, (B, 3)),
+                               ("cubic_q15", cubic_q15, torch.int32, (32, 4)), ("cubic_f32", cubic_f32, torch.float32, (32, 4))):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise RuntimeError(f"mtlora_amd: {name} must be a contiguous {dt} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    arr = (L.AugmentJob * max(len(jobs), 1))()
+    outs = []
+    for i, (kind, src) in enumerate(jobs):
+        if kind not in AUGMENT_KINDS:
+            raise RuntimeError(f"mtlora_amd: unknown augment kind {kind!r}")
+        dt, C = _AUGMENT_FORM[kind]
+        want = (B, Hc, Wc, 3) if C == 3 else (B, Hc, Wc)
+        if src.dtype != dt or tuple(src.shape) != want or not src.is_contiguous():
+            raise RuntimeError(f"mtlora_amd: augment job {i} ({kind}) must be a contiguous {dt} tensor of shape {want}, got "
+                               f"{src.dtype} {tuple(src.shape)}")
+        out = torch.empty((B, Ho, Wo, 3) if C == 3 else (B, Ho, Wo), dtype=dt, device=src.device)
+        outs.append(out)
+        arr[i].src, arr[i].dst, arr[i].kind = src.data_ptr(), out.data_ptr(), AUGMENT_KINDS[kind]
+        arr[i].flags = 0 if renormalize else L.AUGMENT_FLAG_NO_RENORM
+    st = L.lib().mtlora_augment_batch(arr, len(jobs), B, Hc, Wc, Ho, Wo, L.ptr(size), L.ptr(coef), L.ptr(side), L.ptr(cubic_q15),
+                                      L.ptr(cubic_f32), L.stream_ptr())
+    L.check(st, "mtlora_augment_batch")
+    return outs
+
+
+# ----------------------------------------------------------------------------------------------
 # plain (library) GEMM linears with a huge row count: weight gradient as a batched GEMM over row chunks
 # ----------------------------------------------------------------------------------------------
 def _layout_weight(weight, bias, cdtype, col_index, n_cols, pad_rows):
