@@ -14,8 +14,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["window_process.hip", "linear.hip", "attention.hip", "glue.hip", "loss.hip", "metrics.hip", "predict.hip", "upsample.hip", "reduce.hip", "selftest.hip", "block.hip", "hid.hip", "optim.hip", "ingest.hip", "augment.hip"]
 LIB = os.path.join(HERE, "libmtlora_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
-if os.environ.get("MTLORA_ABLATE") == "1":  # developer build: MTLORA_NT_DBG ablation toggles in the NT kernels (use --force)
-    FLAGS.append("-DMTL_NT_ABLATE=1")
 
 
 def _hipcc():
@@ -33,7 +31,7 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=True):
-    hdrs = [os.path.join(HERE, f) for f in sorted(os.listdir(HERE)) if f.endswith(".h")]  # common.h, panel.h, ...
+    hdrs = [os.path.join(HERE, f) for f in sorted(os.listdir(HERE)) if f.endswith(".h")]  # common.h, nt.h, stream.h, ...: every header is a dependency of every source
     hdrs.append(os.path.join(HERE, "..", "..", "include", "mtlora_hip.h"))
     objs, jobs = [], []
     for src in SOURCES:

@@ -1,6 +1,6 @@
 // dense.h -- k_ntd: the MFMA-dense single-output launches of MTLoRALinear (bf16): stage-2 / 3 forward outputs and dX, the decoder
 // heads' and PatchMerging GEMMs -- every launch whose reduction is long enough for a pipeline to pay (K + R >= 256) and that has
-// enough tiles.  Included by linear.hip after stream.h (sp_dma16 / SP_WAIT_VM / sp_mma1) inside its anonymous namespace.
+// enough tiles.  Included by linear.hip after stream.h (sp_dma16 / SP_WAIT_VM / sp_mma1).
 //
 // What was wrong with k_ntl on these shapes (400-460 TFLOP/s, MFMA pipe 17 % busy): ONE k-tile of register prefetch,
 // two barriers per k-tile, and a workgroup's serial chain  global -> registers -> LDS -> barrier -> fragments -> MFMA  exposed once
@@ -31,6 +31,11 @@
 // (Starting each column tile's base k loop at a different k-tile, so that the workgroups of a row block do not ask for the same lines
 // at once: +-0.)
 #pragma once
+
+#include "nt.h"
+#include "stream.h"
+
+namespace {
 
 constexpr int ND_TM = 256, ND_TN = 128, ND_KE = 64;
 constexpr int ND_ROWS = ND_TM + ND_TN;                 // rows of a stage: [weights 0..127 | activation 128..383]
@@ -63,7 +68,6 @@ __global__ __launch_bounds__(512, 2) void k_ntd(const NlParams P) {
     const int use_base = P.use_base;
     DropoutCfg drop = P.drop;
     mtl_dropout_resolve(drop);
-    const int dbg = P.dbg & NT_DBG_MASK;  // developer ablation bits (0 at compile time unless -DMTL_NT_ABLATE=1): 1 no stores, 2 no stage loads, 4 no MFMA, 8 no epilogue
     const __amdgpu_buffer_rsrc_t orsrc = sp_rsrc(P.out, (int64_t)M * P.ld_out * 2);
     const __amdgpu_buffer_rsrc_t arsrc = sp_rsrc(P.act2, ACT ? (int64_t)M * P.ld_out * 2 : 0);
     const __amdgpu_buffer_rsrc_t grsrc = sp_rsrc(const_cast<bf16*>(P.gate), GATE ? (int64_t)M * P.ld_out * 2 : 0);
@@ -113,7 +117,6 @@ __global__ __launch_bounds__(512, 2) void k_ntd(const NlParams P) {
         }
     };
     auto issue = [&](int i, int slot) __attribute__((always_inline)) {  // k-tile i of the tile whose rows are in rowc -> ring slot
-        if (dbg & 2) return;
         const bool lr = i < n1;
         const int k0 = lr ? seg_lo + i * ND_KE : (i - n1) * ND_KE;
         const int khi = lr ? seg_hi : Kb;
@@ -209,14 +212,12 @@ __global__ __launch_bounds__(512, 2) void k_ntd(const NlParams P) {
                     fw[ks][bq] = *reinterpret_cast<const u32x4*>(sw + bq * 32 * 128 + co[ks]);
                     fa[ks][bq] = *reinterpret_cast<const u32x4*>(sa + bq * 32 * 128 + co[ks]);
                 }
-            if (!(dbg & 4)) {
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks)
+            for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-                    for (int sn = 0; sn < 2; ++sn)
+                for (int sn = 0; sn < 2; ++sn)
 #pragma unroll
-                        for (int sm = 0; sm < 2; ++sm) sp_mma1<bf16>(fw[ks][sn], fa[ks][sm], acc[sn][sm]);
-            }
+                    for (int sm = 0; sm < 2; ++sm) sp_mma1<bf16>(fw[ks][sn], fa[ks][sm], acc[sn][sm]);
             if constexpr (MLR) {
                 if (i + 1 == n1 && drop.thr16 != 0) {  // the rank part is complete: acc *= keep(m, n)
 #pragma unroll
@@ -276,40 +277,38 @@ __global__ __launch_bounds__(512, 2) void k_ntd(const NlParams P) {
         // ---- epilogue: the wave's 64 (m) x 64 (n) tile, 32 rows at a time, through a private image in the ring slot of the last
         // k-tile (free once every wave has left the k loop); then whole 128-byte row segments per 8 lanes.  EPI_OPS operations.
         __syncthreads();
-        if (!(dbg & 8)) {
-            unsigned char* img = smem + img_slot * ND_STAGE + wave * (32 * ND_ORS);
-            const int c16 = lane & 7;
-            const int n = n0c + wn * 64 + c16 * 8;
+        unsigned char* img = smem + img_slot * ND_STAGE + wave * (32 * ND_ORS);
+        const int c16 = lane & 7;
+        const int n = n0c + wn * 64 + c16 * 8;
 #pragma unroll
-            for (int sm = 0; sm < 2; ++sm) {
+        for (int sm = 0; sm < 2; ++sm) {
 #pragma unroll
-                for (int sn = 0; sn < 2; ++sn)
+            for (int sn = 0; sn < 2; ++sn)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int nl = sn * 32 + 8 * q + 4 * h;
-                        u32x2 pk = {mtl_pack_bf16(acc[sn][sm][q * 4], acc[sn][sm][q * 4 + 1]),
-                                    mtl_pack_bf16(acc[sn][sm][q * 4 + 2], acc[sn][sm][q * 4 + 3])};
-                        *reinterpret_cast<u32x2*>(img + rl * ND_ORS + nl * 2) = pk;
-                    }
-                __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the image is private to this wave
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    const int ml = it * 8 + (lane >> 3);
-                    const int m = m0c + wm * 64 + sm * 32 + ml;
-                    u32x4 v = *reinterpret_cast<const u32x4*>(img + ml * ND_ORS + c16 * 16);
-                    const uint32_t off = (m < M && n < n_rows && !(dbg & 1)) ? (uint32_t)m * ldo2 + (uint32_t)n * 2u : 0xFFFFFFFFu;
-                    if constexpr (GATE) {  // the bf16-rounded gradient times gelu'(pre-activation), rounded once (as ATen does)
-                        v = mtl_gelu_gate_pk4<bf16, false>(v, hv[sm][it]);
-                    }
-                    sp_bstore(v, orsrc, off);
-                    if constexpr (ACT) {
-                        const u32x4 av = mtl_gelu_pk4<bf16, false>(v);
-                        sp_bstore(av, arsrc, off);
-                    }
+                for (int q = 0; q < 4; ++q) {
+                    const int nl = sn * 32 + 8 * q + 4 * h;
+                    u32x2 pk = {mtl_pack_bf16(acc[sn][sm][q * 4], acc[sn][sm][q * 4 + 1]),
+                                mtl_pack_bf16(acc[sn][sm][q * 4 + 2], acc[sn][sm][q * 4 + 3])};
+                    *reinterpret_cast<u32x2*>(img + rl * ND_ORS + nl * 2) = pk;
                 }
-                __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the image is private to this wave
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int ml = it * 8 + (lane >> 3);
+                const int m = m0c + wm * 64 + sm * 32 + ml;
+                u32x4 v = *reinterpret_cast<const u32x4*>(img + ml * ND_ORS + c16 * 16);
+                const uint32_t off = (m < M && n < n_rows) ? (uint32_t)m * ldo2 + (uint32_t)n * 2u : 0xFFFFFFFFu;
+                if constexpr (GATE) {  // the bf16-rounded gradient times gelu'(pre-activation), rounded once (as ATen does)
+                    v = mtl_gelu_gate_pk4<bf16, false>(v, hv[sm][it]);
+                }
+                sp_bstore(v, orsrc, off);
+                if constexpr (ACT) {
+                    const u32x4 av = mtl_gelu_pk4<bf16, false>(v);
+                    sp_bstore(av, arsrc, off);
+                }
             }
+            __builtin_amdgcn_wave_barrier();
         }
     }
 }
@@ -356,7 +355,6 @@ __global__ __launch_bounds__(256, 2) void k_nte(const NlParams P) {
     const int use_base = P.use_base;
     DropoutCfg drop = P.drop;
     mtl_dropout_resolve(drop);
-    const int dbg = P.dbg & NT_DBG_MASK;  // developer ablation bits as in k_ntd (0 at compile time in the shipped library)
     const __amdgpu_buffer_rsrc_t orsrc = sp_rsrc(P.out, (int64_t)M * P.ld_out * 2);
     const __amdgpu_buffer_rsrc_t arsrc = sp_rsrc(P.act2, ACT ? (int64_t)M * P.ld_out * 2 : 0);
     const __amdgpu_buffer_rsrc_t grsrc = sp_rsrc(const_cast<bf16*>(P.gate), GATE ? (int64_t)M * P.ld_out * 2 : 0);
@@ -404,7 +402,6 @@ __global__ __launch_bounds__(256, 2) void k_nte(const NlParams P) {
         }
     };
     auto issue = [&](int i, int slot) __attribute__((always_inline)) {
-        if (dbg & 2) return;
         const bool lr = i < n1;
         const int k0 = lr ? seg_lo + i * NE_KE : (i - n1) * NE_KE;
         const int khi = lr ? seg_hi : Kb;
@@ -482,12 +479,10 @@ __global__ __launch_bounds__(256, 2) void k_nte(const NlParams P) {
                 for (int bq = 0; bq < 2; ++bq) fw[bq] = *reinterpret_cast<const u32x4*>(sw + bq * 32 * 64 + co[ks]);
 #pragma unroll
                 for (int bq = 0; bq < 4; ++bq) fa[bq] = *reinterpret_cast<const u32x4*>(sa + bq * 32 * 64 + co[ks]);
-                if (!(dbg & 4)) {
 #pragma unroll
-                    for (int sm = 0; sm < 4; ++sm)
+                for (int sm = 0; sm < 4; ++sm)
 #pragma unroll
-                        for (int sn = 0; sn < 2; ++sn) sp_mma1<bf16>(fw[sn], fa[sm], acc[sn][sm]);
-                }
+                    for (int sn = 0; sn < 2; ++sn) sp_mma1<bf16>(fw[sn], fa[sm], acc[sn][sm]);
             }
             if constexpr (MLR) {
                 if (i + 1 == n1 && drop.thr16 != 0) {  // the rank part is complete: acc *= keep(m, n)
@@ -545,51 +540,50 @@ __global__ __launch_bounds__(256, 2) void k_nte(const NlParams P) {
         // ---- epilogue: the wave's 128 (m) x 64 (n) tile, 32 rows at a time, through a private image in the ring slot of the last
         // k-tile (free once every wave has left the k loop); whole 128-byte row segments per 8 lanes.  EPI_OPS operations.
         __syncthreads();
-        if (!(dbg & 8)) {
-            unsigned char* img = smem + img_slot * NE_STAGE + wave * (32 * NE_ORS);
-            const int c16 = lane & 7;
-            const int n = n0c + wn * 64 + c16 * 8;
+        unsigned char* img = smem + img_slot * NE_STAGE + wave * (32 * NE_ORS);
+        const int c16 = lane & 7;
+        const int n = n0c + wn * 64 + c16 * 8;
 #pragma unroll
-            for (int sm = 0; sm < 4; ++sm) {
-                u32x4 hv[4];
-                (void)hv;
-                if constexpr (GATE) {  // pre-activations of this 32-row block, in the order the stores below use them
-#pragma unroll
-                    for (int it = 0; it < 4; ++it) {
-                        const int m = m0c + wm * 128 + sm * 32 + it * 8 + (lane >> 3);
-                        const uint32_t off = (m < M && n < n_rows) ? (uint32_t)m * ldo2 + (uint32_t)n * 2u : 0xFFFFFFFFu;
-                        hv[it] = __builtin_amdgcn_raw_buffer_load_b128(grsrc, (int)off, 0, 0);
-                    }
-                }
-#pragma unroll
-                for (int sn = 0; sn < 2; ++sn)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int nl = sn * 32 + 8 * q + 4 * h;
-                        u32x2 pk = {mtl_pack_bf16(acc[sn][sm][q * 4], acc[sn][sm][q * 4 + 1]),
-                                    mtl_pack_bf16(acc[sn][sm][q * 4 + 2], acc[sn][sm][q * 4 + 3])};
-                        *reinterpret_cast<u32x2*>(img + rl * NE_ORS + nl * 2) = pk;
-                    }
-                __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the image is private to this wave
-                __builtin_amdgcn_wave_barrier();
+        for (int sm = 0; sm < 4; ++sm) {
+            u32x4 hv[4];
+            (void)hv;
+            if constexpr (GATE) {  // pre-activations of this 32-row block, in the order the stores below use them
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-                    const int ml = it * 8 + (lane >> 3);
-                    const int m = m0c + wm * 128 + sm * 32 + ml;
-                    u32x4 v = *reinterpret_cast<const u32x4*>(img + ml * NE_ORS + c16 * 16);
+                    const int m = m0c + wm * 128 + sm * 32 + it * 8 + (lane >> 3);
                     const uint32_t off = (m < M && n < n_rows) ? (uint32_t)m * ldo2 + (uint32_t)n * 2u : 0xFFFFFFFFu;
-                    if constexpr (GATE) {
-                        v = mtl_gelu_gate_pk4<bf16, false>(v, hv[it]);
-                    }
-                    sp_bstore(v, orsrc, off);
-                    if constexpr (ACT) {
-                        const u32x4 av = mtl_gelu_pk4<bf16, false>(v);
-                        sp_bstore(av, arsrc, off);
-                    }
+                    hv[it] = __builtin_amdgcn_raw_buffer_load_b128(grsrc, (int)off, 0, 0);
                 }
-                __builtin_amdgcn_wave_barrier();
             }
+#pragma unroll
+            for (int sn = 0; sn < 2; ++sn)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int nl = sn * 32 + 8 * q + 4 * h;
+                    u32x2 pk = {mtl_pack_bf16(acc[sn][sm][q * 4], acc[sn][sm][q * 4 + 1]),
+                                mtl_pack_bf16(acc[sn][sm][q * 4 + 2], acc[sn][sm][q * 4 + 3])};
+                    *reinterpret_cast<u32x2*>(img + rl * NE_ORS + nl * 2) = pk;
+                }
+            __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the image is private to this wave
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int ml = it * 8 + (lane >> 3);
+                const int m = m0c + wm * 128 + sm * 32 + ml;
+                u32x4 v = *reinterpret_cast<const u32x4*>(img + ml * NE_ORS + c16 * 16);
+                const uint32_t off = (m < M && n < n_rows) ? (uint32_t)m * ldo2 + (uint32_t)n * 2u : 0xFFFFFFFFu;
+                if constexpr (GATE) {
+                    v = mtl_gelu_gate_pk4<bf16, false>(v, hv[it]);
+                }
+                sp_bstore(v, orsrc, off);
+                if constexpr (ACT) {
+                    const u32x4 av = mtl_gelu_pk4<bf16, false>(v);
+                    sp_bstore(av, arsrc, off);
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
         }
     }
 }
 
+}  // namespace

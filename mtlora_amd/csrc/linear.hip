@@ -1,5 +1,7 @@
-// linear.hip -- MTLoRALinear forward / backward on CDNA4 (gfx950).
+// linear.hip -- MTLoRALinear forward / backward on CDNA4 (gfx950): the HOST side (validation, kernel selection, launchers, the C ABI).
 // Replaces the ATen sequence of models/lora.py:253-284 and its autograd backward.
+// The kernels live in the headers included below, all in this one translation unit: nt.h (k_pack, k_nt, k_ntl), stream.h (k_sp_*),
+// dense.h (k_ntd / k_nte), pq.h (k_pq), tn.h (k_tn, k_sum, k_rank_out).
 //
 // Kernel families (all hand-written MFMA, 64-wide waves):
 //
@@ -36,7 +38,6 @@
 //            | else k_sp_projsum (Q + G, T <= 4) / [k_sum] k_sp_proj / k_sp_projk / k_nt (Q), then k_ntd / k_ntl / k_nt (dX) [+ k_rank_out (dX_t)];
 //            k_sp_tn / k_tn + reduce for dA / dB.
 // DESIGN.md section 4.1 / 4.3 has the measurements and the experiments that were tried and dropped.
-#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <atomic>
@@ -45,34 +46,13 @@
 #include "common.h"
 #include "internal.h"
 #include "hid_params.h"
+#include "nt.h"
+#include "stream.h"
+#include "dense.h"
+#include "pq.h"
+#include "tn.h"
 
 namespace {
-
-constexpr int TILE = 128;    // rows per CTA tile, both operands
-constexpr int SUBT = 3;             // 64-byte MFMA sub-tiles per staged k-tile: K = 96 bf16 is ONE round trip
-constexpr int VPT = SUBT;           // 16-byte vectors per thread per tile row
-constexpr int ROWB = 64 * SUBT;     // payload bytes per row per k-tile (96 bf16 / 48 f32)
-constexpr int LDSB = ROWB + 16;     // padded LDS row stride (conflict-free ds_read_b128, 16-B aligned)
-constexpr int EPI_ROW = 64 * 2 + 8;                      // row stride of a wave's bf16 output image (epilogue)
-constexpr int EPI_BYTES = 4 * 64 * EPI_ROW;               // 4 waves x 64 rows = 8 waves x 32 rows
-constexpr int STAGE_BYTES = 2 * TILE * LDSB > EPI_BYTES ? 2 * TILE * LDSB : EPI_BYTES;  // staging / epilogue region
-constexpr int MAXO = MTLORA_MAX_TASKS + 1;
-// MTLORA_NT_DBG ablation toggles (tools/nt_ablate.sh) are compiled in only with -DMTL_NT_ABLATE=1 (MTLORA_ABLATE=1 for
-// csrc/build.py): the runtime tests cost the generic kernels ~10 SGPR spills each
-#ifndef MTL_NT_ABLATE
-#define MTL_NT_ABLATE 0
-#endif
-constexpr int NT_DBG_MASK = MTL_NT_ABLATE ? ~0 : 0;
-
-// ------------------------------------------------------------------------------------------------
-// segment table: output o (0 = shared, 1..T = tasks) owns columns [off, off + rp) of the rank axis
-// ------------------------------------------------------------------------------------------------
-struct Segs {
-    int n;  // 1 + T
-    int r[MAXO], rp[MAXO], off[MAXO];
-    int R;     // row stride of P / Q / the packed factors (columns), a multiple of 16
-    int used;  // columns that belong to a segment: [used, R) is padding nobody writes
-};
 
 static Segs make_segs(const mtlora_linear_desc* d) {
     Segs s;
@@ -96,11 +76,6 @@ static Segs make_segs(const mtlora_linear_desc* d) {
     return s;
 }
 
-// packed factors (offsets relative to the pack base: the head of the ctx buffer, or the caller's persistent d->packed buffer) and
-// P (offset relative to the ctx base)
-struct CtxLayout {
-    int64_t a_cat, b_cat, at_cat, bt_cat, alpha, a_proj, bt_proj, b_frag, at_frag, pack_total, p, total;
-};
 static CtxLayout ctx_layout(const mtlora_linear_desc* d, const Segs& s) {
     const int es = mtl_elem_size(d->dtype);
     CtxLayout L;
@@ -128,1313 +103,6 @@ static CtxLayout ctx_layout(const mtlora_linear_desc* d, const Segs& s) {
     L.p = take(d->M * s.R * es);
     L.total = o;
     return L;
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_pack
-// ------------------------------------------------------------------------------------------------
-struct PackParams {
-    const float* A[MAXO];
-    const float* B[MAXO];
-    float alpha[MAXO];
-    Segs s;
-    int K, N;
-};
-
-// The packing walks 64 x 64 TILES of the two concatenated factor matrices -- A_cat (R x K, rows = rank columns rr) and B_cat (N x R) -- one
-// tile per workgroup pass: the fp32 masters are read along their contiguous axis (K for A, the segment's rank for B), the same-orientation
-// copies (a_cat / a_proj, b_cat) are stored from registers, and the tile goes through LDS once for everything that is transposed or
-// permuted (at_cat, bt_cat / bt_proj, the fragment-major at_frag / b_frag): every global access of the launch is a coalesced row segment.
-// (Round 3's element-wise walk scattered 2-byte stores with a stride of R for the transposed copies and divided 64-bit indices per
-// element: 1.07 ms for the 72 layers of Swin-B at rank 128, 30 x the time of the bytes it moves.)
-constexpr int PK_T = 64;
-
-template <typename PP>
-__device__ __forceinline__ int pack_seg_of(const PP& p, int rr) {
-    int o = 0;
-#pragma unroll
-    for (int q = 1; q < MAXO; ++q)
-        if (q < p.s.n && rr >= p.s.off[q]) o = q;
-    return o;
-}
-
-template <typename T, typename PP>
-__device__ __forceinline__ void pack_body(const PP& p, T* a_cat, T* b_cat, T* at_cat, T* bt_cat, float* alpha, T* a_proj, T* bt_proj, T* b_frag,
-                                          T* at_frag, int bid, int nblk) {
-    __shared__ float tile[PK_T][PK_T + 1];
-    constexpr bool FRAG = sizeof(T) == 2;  // fragment-major expansion factors: 16-bit types only (the wave-streaming kernels)
-    const int R = p.s.R, K = p.K, N = p.N;
-    const int tr = (R + PK_T - 1) / PK_T, tk = (K + PK_T - 1) / PK_T, tn = (N + PK_T - 1) / PK_T;
-    const int na_t = tr * tk, nb_t = tn * tr;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int R16 = ((R + 31) >> 5) << 1, K32 = (K + 31) & ~31, N32 = (N + 31) & ~31;
-    for (int job = bid; job < na_t + nb_t; job += nblk) {
-        const bool isa = job < na_t;
-        const int jb = isa ? job : job - na_t;
-        // tile origin: rows r0 / cols c0 of A_cat (rr, k), or rows n0 / cols r0 of B_cat (n, rr)
-        const int row0 = isa ? (jb / tk) * PK_T : (jb / tr) * PK_T;
-        const int col0 = isa ? (jb % tk) * PK_T : (jb % tr) * PK_T;
-        float v[PK_T / 4];  // all 16 loads of the tile are in flight before the first store (the stores may alias for all the compiler knows)
-        if (isa) {
-            const int c = col0 + tx;
-            float al[PK_T / 4];
-#pragma unroll
-            for (int i = 0; i < PK_T / 4; ++i) {
-                const int rr = row0 + ty + 4 * i;  // (wave-uniform)
-                const int o = pack_seg_of(p, rr), lr = rr - p.s.off[o];
-                al[i] = p.alpha[o];
-                v[i] = (rr < R && lr < p.s.r[o] && c < K && p.A[o]) ? p.A[o][(int64_t)lr * K + c] : 0.f;
-            }
-#pragma unroll
-            for (int i = 0; i < PK_T / 4; ++i) {
-                const int row = ty + 4 * i, rr = row0 + row;
-                tile[row][tx] = v[i];
-                if (rr < R && c < K) {
-                    a_cat[(int64_t)rr * K + c] = mtl_from_f32<T>(v[i]);
-                    a_proj[(int64_t)rr * K + c] = mtl_from_f32<T>(v[i] * al[i]);
-                }
-            }
-            if (col0 == 0 && threadIdx.x < PK_T && row0 + tx < R) alpha[row0 + tx] = p.alpha[pack_seg_of(p, row0 + tx)];
-        } else {
-            const int rr = col0 + tx;
-            const int o = pack_seg_of(p, rr), lr = rr - p.s.off[o], ro = p.s.r[o];
-            const bool live = rr < R && lr < ro && p.B[o];
-            const float* __restrict__ Bo = p.B[o];
-#pragma unroll
-            for (int i = 0; i < PK_T / 4; ++i) {
-                const int n = row0 + ty + 4 * i;
-                v[i] = (live && n < N) ? Bo[(int64_t)n * ro + lr] : 0.f;
-            }
-#pragma unroll
-            for (int i = 0; i < PK_T / 4; ++i) {
-                const int row = ty + 4 * i, n = row0 + row;
-                tile[row][tx] = v[i];
-                if (rr < R && n < N) b_cat[(int64_t)n * R + rr] = mtl_from_f32<T>(v[i]);
-            }
-        }
-        __syncthreads();
-        if (isa) {  // at_cat[k][rr]: lanes along rr
-            const int rr = row0 + tx;
-#pragma unroll 4
-            for (int i = 0; i < PK_T / 4; ++i) {
-                const int cl = ty + 4 * i, c = col0 + cl;
-                if (rr < R && c < K) at_cat[(int64_t)c * R + rr] = mtl_from_f32<T>(tile[tx][cl]);
-            }
-        } else {    // bt_cat / bt_proj[rr][n]: lanes along n
-            const int n = row0 + tx;
-#pragma unroll 4
-            for (int i = 0; i < PK_T / 4; ++i) {
-                const int rl = ty + 4 * i, rr = col0 + rl;  // (wave-uniform)
-                if (rr < R && n < N) {
-                    const float v = tile[tx][rl];
-                    bt_cat[(int64_t)rr * N + n] = mtl_from_f32<T>(v);
-                    bt_proj[(int64_t)rr * N + n] = mtl_from_f32<T>(v * p.alpha[pack_seg_of(p, rr)]);
-                }
-            }
-        }
-        if constexpr (FRAG) {
-            // fragment (32-row block blk of k or n, 16-wide rank step t) = 512 elements: lane l = (row blk * 32 + (l & 31), h = l >> 5)
-            // holds rank columns 16 t + 8 (s >> 2) + 4 h + (s & 3), s = 0..7.  The tile holds 2 x 4 fragments; a thread writes two
-            // (fragment, lane) groups of 8 elements = one 16-byte store each.
-            T* __restrict__ dst = isa ? at_frag : b_frag;
-            const int blk0 = (isa ? col0 : row0) >> 5, t0 = (isa ? row0 : col0) >> 4, nblk32 = (isa ? K32 : N32) >> 5;
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                const int q = threadIdx.x + 256 * h2, fl = q >> 6, ln = q & 63;
-                const int bl = fl >> 2, tl = fl & 3, rl = bl * 32 + (ln & 31);
-                if (blk0 + bl < nblk32 && t0 + tl < R16) {
-                    T tmp[8];
-#pragma unroll
-                    for (int sidx = 0; sidx < 8; ++sidx) {
-                        const int kl = 16 * tl + 8 * (sidx >> 2) + 4 * (ln >> 5) + (sidx & 3);
-                        tmp[sidx] = mtl_from_f32<T>(isa ? tile[kl][rl] : tile[rl][kl]);
-                    }
-                    const int64_t f = (int64_t)(blk0 + bl) * R16 + (t0 + tl);
-                    *reinterpret_cast<uint4*>(dst + f * 512 + ln * 8) = *reinterpret_cast<const uint4*>(tmp);
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void k_pack(PackParams p, T* a_cat, T* b_cat, T* at_cat, T* bt_cat, float* alpha, T* a_proj,
-                                              T* bt_proj, T* b_frag, T* at_frag) {
-    pack_body<T>(p, a_cat, b_cat, at_cat, bt_cat, alpha, a_proj, bt_proj, b_frag, at_frag, (int)blockIdx.x, (int)gridDim.x);
-}
-
-// one launch for EVERY layer of a model (mtlora_linear_pack_table): blockIdx.y = table entry.  The factors change once per optimizer
-// step, so a trainer refreshes all the packed buffers here instead of paying one k_pack launch per layer and forward call
-// (48 launches per step at C2, 96 at C4).
-struct PackEntry {
-    PackParams pp;
-    unsigned char* dst;  // the layer's packed buffer (device)
-    int64_t off[9];      // a_cat, b_cat, at_cat, bt_cat, alpha, a_proj, bt_proj, b_frag, at_frag
-};
-template <typename T>
-__global__ __launch_bounds__(256) void k_pack_table(const PackEntry* __restrict__ table) {
-    const PackEntry& e = table[blockIdx.y];
-    unsigned char* d = e.dst;
-    pack_body<T>(e.pp, reinterpret_cast<T*>(d + e.off[0]), reinterpret_cast<T*>(d + e.off[1]), reinterpret_cast<T*>(d + e.off[2]),
-                 reinterpret_cast<T*>(d + e.off[3]), reinterpret_cast<float*>(d + e.off[4]), reinterpret_cast<T*>(d + e.off[5]),
-                 reinterpret_cast<T*>(d + e.off[6]), reinterpret_cast<T*>(d + e.off[7]), reinterpret_cast<T*>(d + e.off[8]), (int)blockIdx.x,
-                 (int)gridDim.x);
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_nt
-// ------------------------------------------------------------------------------------------------
-struct NtOut {
-    void* ptr;       // (M x ld_out) output, element type T
-    int seg_lo, seg_hi;  // rank-column range of L/R chained onto this output ([lo,hi) empty -> none)
-    int use_base;    // add the shared base accumulator
-    int mask_lr;     // multiply the low-rank part by the dropout keep mask of (m, n)
-    int fold;        // after storing: base += low-rank part ('matrixv2': tasks see the shared update)
-    const void* gate;  // GATE kernels: out *= gelu'(gate[m][n]) (same shape / dtype / row stride as the output), nullable
-    void* act;         // ACT kernels: second output gelu(out) (same shape / dtype / row stride), nullable
-};
-
-struct NtParams {
-    // base GEMM
-    const void* act[MAXO];  // (M x K) sources, summed while staging
-    int n_act;
-    int act_mask;           // dropout keep-mask applied to the staged activation
-    int64_t ld_act;
-    const void* wgt;        // (n_rows x K)
-    int64_t ld_wgt;
-    int64_t M;
-    int n_rows;             // rows of wgt == output columns
-    int K;                  // reduction length of the base GEMM (0 -> no base GEMM)
-    const float* bias;      // per output column, nullable
-    const float* alpha;     // per output column multiplier on the base GEMM, nullable
-    // low-rank epilogue
-    const void* L;          // (M x ldL)
-    const void* Rm;         // (n_rows x ldR)
-    int64_t ldL, ldR;
-    int n_out;
-    NtOut out[MAXO];
-    int64_t ld_out;
-    // batched form (gridDim.z = nz > 0): z selects activation / weight row slab / output column slab
-    int nz;
-    const void* zact[MAXO];
-    int zrow0[MAXO], zrows[MAXO], zmask[MAXO];
-    int dbg;               // MTLORA_NT_DBG ablation bits (tools only): 1 no global stores, 2 no global loads, 4 no MFMA, 8 no epilogue
-    DropoutCfg drop;
-};
-
-// kernel parameters are read straight from the kernarg segment (constant address space): dynamic indexing of a
-// by-value struct argument would make the compiler copy the whole struct to scratch
-typedef const __attribute__((address_space(4))) NtParams* NtPtr;
-
-// RI = tile rows per thread per operand: 2 with 256 threads (4 waves), 1 with 512 threads (8 waves)
-// A thread stages 3 * RI 16-byte vectors per operand per k-tile.  Which (row, vector) a thread owns is chosen for the LDS
-// STORE: ds_write_b128 is served 8 lanes (128 bytes = all 32 banks) at a time, so 8 consecutive lanes must write 8 pieces that
-// are distinct mod 128 bytes.  With the 208-byte row stride (13 pieces: odd, which is what keeps the ds_read_b128 fragment
-// reads conflict-free) the earlier 4-lanes-per-row map put (row r, piece 0) and (row r+1, piece 3) on the same banks in
-// every group -- a 2-way conflict on every staging store (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.25,
-// profiles/r01_pmc_sq.csv).  Now: slots 0 .. 2 RI - 1: 8 lanes x 16 B = the first 128 bytes of ONE row (also a 128-byte
-// global-load segment instead of two 64-byte ones); the last RI slots: the remaining 64 bytes of rows r and r + 4 (52 pieces
-// apart = 4 mod 8: the two halves interleave).
-// The 4-wave variants (RI = 2: MULTI / row-panel / f32, already at 256 VGPRs) keep the 4-lanes-per-row map: six distinct row
-// addresses per thread pushed their hot loop into scratch (8 -> 104 bytes per lane for the multi-output forward).
-template <int RI>
-__device__ __forceinline__ void nt_map(int tid, int slot, int& row, int& vec) {
-    constexpr int NT = 512 / RI;
-    if constexpr (RI == 2) {
-        row = (tid >> 2) + (slot & 1) * 64;
-        vec = (tid & 3) + 4 * (slot >> 1);
-    } else if (slot < 2 * RI) {
-        const int idx = tid + NT * slot;  // 0 .. 1023
-        row = idx >> 3;
-        vec = idx & 7;
-    } else {
-        const int idx = tid + NT * (slot - 2 * RI);  // 0 .. 511
-        const int g = idx >> 3, l = idx & 7;
-        row = (g >> 2) * 8 + (g & 3) + 4 * (l >> 2);
-        vec = 8 + (l & 3);
-    }
-}
-
-template <typename T, int RI>
-struct TileRegs {
-    u32x4 w[3 * RI], a[3 * RI];
-    int mask;  // dropout keep-mask still to be applied to a[] (done at LDS-store time: applying it at load time
-    int k0;    // would put an s_waitcnt vmcnt(0) behind every single load and serialise the tile's loads)
-};
-
-// stage one 128-row x ROWB-byte k-tile of the weight-like and activation-like operands into registers
-template <typename T, bool MS, int RI>
-__device__ __forceinline__ void nt_load(TileRegs<T, RI>& rg, int tid, const T* wgt, int64_t ld_w, int w_row0, int w_rows,
-                                        const void* act0, NtPtr P, int n_act, int64_t ld_a, int64_t a_row0,
-                                        int64_t a_rows, int k0, int k_hi, bool mask, int w_lo = 0) {
-    constexpr int VEC = ET<T>::VEC;
-    rg.mask = mask ? 1 : 0;
-    rg.k0 = k0;
-#pragma unroll
-    for (int sl = 0; sl < 3 * RI; ++sl) {
-        int r, v;
-        nt_map<RI>(tid, sl, r, v);
-        const int k = k0 + v * VEC;
-        const bool kin = k < k_hi;
-        const int wr = w_row0 + r;
-        const bool wok = wr < w_rows && wr >= w_lo;
-        rg.w[sl] = (kin && wok) ? *reinterpret_cast<const u32x4*>(wgt + (int64_t)wr * ld_w + k) : u32x4{0u, 0u, 0u, 0u};
-        const int64_t ar = a_row0 + r;
-        const bool aok = ar < a_rows && act0 != nullptr;
-        const int64_t aoff = ar * ld_a;
-        if (kin && aok) {
-            u32x4 x = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(act0) + aoff + k);
-            if (MS && n_act > 1) {
-                if constexpr (sizeof(T) == 4) {
-                    f32x4 fx = __builtin_bit_cast(f32x4, x);
-#pragma unroll
-                    for (int s = 1; s < MAXO; ++s) {
-                        if (s < n_act) fx += *reinterpret_cast<const f32x4*>(reinterpret_cast<const T*>(P->act[s]) + aoff + k);
-                    }
-                    x = __builtin_bit_cast(u32x4, fx);
-                } else {
-                    float f[8];
-                    VOps<T>::unpack(x, f);
-#pragma unroll
-                    for (int s = 1; s < MAXO; ++s) {
-                        if (s < n_act) {
-                            const u32x4 y = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(P->act[s]) + aoff + k);
-                            float g[8];
-                            VOps<T>::unpack(y, g);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) f[e] += g[e];
-                        }
-                    }
-                    x = VOps<T>::pack(f);
-                }
-            }
-            rg.a[sl] = x;
-        } else {
-            rg.a[sl] = u32x4{0u, 0u, 0u, 0u};
-        }
-    }
-}
-
-template <typename T, int RI>
-__device__ __forceinline__ void nt_store_lds(TileRegs<T, RI>& rg, int tid, unsigned char* sW, unsigned char* sA,
-                                             const DropoutCfg& dc, int64_t a_row0) {
-    constexpr int VEC = ET<T>::VEC;
-#pragma unroll
-    for (int sl = 0; sl < 3 * RI; ++sl) {
-        int r, v;
-        nt_map<RI>(tid, sl, r, v);
-        if (rg.mask) {  // wave-uniform
-            const uint32_t rh = mtl_dropout_rowhash(dc, 0u, (uint32_t)(a_row0 + r));
-            VOps<T>::drop(rg.a[sl], dc, rh, (uint32_t)(rg.k0 + v * VEC));
-        }
-        *reinterpret_cast<u32x4*>(sW + r * LDSB + v * 16) = rg.w[sl];
-        *reinterpret_cast<u32x4*>(sA + r * LDSB + v * 16) = rg.a[sl];
-    }
-}
-
-// multiply the staged tile; k_left = elements of the part's k range still ahead (sub-tiles past it are all zero
-// and skipped -- wave-uniform)
-// SM = 32-row m sub-blocks per wave: 2 (4 waves, wave tile 64 n x 64 m) or 1 (8 waves, wave tile 64 n x 32 m)
-template <typename T, int SM>
-__device__ __forceinline__ void nt_compute(f32x16 (&acc)[2][SM], const unsigned char* sW, const unsigned char* sA,
-                                           int lane, int wn, int wm, int k_left, int a_stride = LDSB) {
-    constexpr int KS = 64 / (int)sizeof(T);  // elements per 64-byte sub-tile
-    const int h = lane >> 5, rl = lane & 31;
-#pragma unroll
-    for (int t = 0; t < SUBT; ++t) {
-        if (t * KS >= k_left) break;
-        Frag<T> fw[2], fa[SM];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const unsigned char* pw = sW + (wn * 64 + s * 32 + rl) * LDSB + t * 64;
-            fw[s].v[0] = *reinterpret_cast<const u32x4*>(pw + h * 16);
-            fw[s].v[1] = *reinterpret_cast<const u32x4*>(pw + (2 + h) * 16);
-        }
-#pragma unroll
-        for (int s = 0; s < SM; ++s) {
-            const unsigned char* pa = sA + (wm * (32 * SM) + s * 32 + rl) * a_stride + t * 64;
-            fa[s].v[0] = *reinterpret_cast<const u32x4*>(pa + h * 16);
-            fa[s].v[1] = *reinterpret_cast<const u32x4*>(pa + (2 + h) * 16);
-        }
-#pragma unroll
-        for (int sn = 0; sn < 2; ++sn)
-#pragma unroll
-            for (int sm = 0; sm < SM; ++sm) mtl_mma(fw[sn], fa[sm], acc[sn][sm]);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_nt: one software-pipelined TILE STREAM per workgroup.
-// The k-tiles of the base GEMM and of every output's rank segment are consumed as ONE sequence: the register
-// prefetch of tile i+1 is issued before tile i is multiplied, ACROSS the boundaries between base / outputs, so a
-// workgroup pays the global->LDS latency once instead of once per output (with K = 96 a base GEMM is only
-// 3 k-tiles; cold starts per output were the dominant cost).
-//   MULTI  (forward with task outputs):  base | out0: base+lr0 | out1: base+lr1 ...   (base kept in registers)
-//   lean   (everything else):            per output: lr_o -> [mask] -> base -> store   (ONE accumulator set:
-//          the low-rank part is formed first so the dropout mask of dX = G W + keep.(Q A) applies to it alone)
-// ------------------------------------------------------------------------------------------------
-struct NtCursor {
-    int q;         // index in the part sequence
-    int k0;        // current k-tile origin
-    int k_hi;      // end of the part's k range
-    int lr;        // 1: rank-segment part (L x Rm), 0: base part (act x wgt)
-    int valid;
-    int bn;        // n-tile of the workgroup
-};
-
-__device__ __forceinline__ NtOut nt_out(NtPtr P, int o) {
-    NtOut O;
-    O.ptr = P->out[o].ptr;
-    O.seg_lo = P->out[o].seg_lo;
-    O.seg_hi = P->out[o].seg_hi;
-    O.use_base = P->out[o].use_base;
-    O.mask_lr = P->out[o].mask_lr;
-    O.fold = P->out[o].fold;
-    O.gate = P->out[o].gate;
-    O.act = P->out[o].act;
-    return O;
-}
-
-// k range of part q.  MULTI: q = 0 base, q = 1 + o rank segment of output o.
-// lean: q = 2 o rank segment of output o, q = 2 o + 1 base (if that output uses it).
-template <bool MULTI>
-__device__ __forceinline__ void nt_part(NtPtr P, int q, int& lr, int& k_lo, int& k_hi) {
-    if (MULTI) {
-        if (q == 0) {
-            lr = 0;
-            k_lo = 0;
-            k_hi = P->K;
-        } else {
-            const NtOut O = nt_out(P, q - 1);
-            lr = 1;
-            k_lo = O.seg_lo;
-            k_hi = O.seg_hi;
-        }
-    } else {
-        const NtOut O = nt_out(P, q >> 1);
-        if (q & 1) {
-            lr = 0;
-            k_lo = 0;
-            k_hi = O.use_base ? P->K : 0;
-        } else {
-            lr = 1;
-            k_lo = O.seg_lo;
-            k_hi = O.seg_hi;
-        }
-    }
-}
-
-template <bool MULTI>
-__device__ __forceinline__ NtCursor nt_seek(NtPtr P, int q, int nseq, int bn) {
-    NtCursor c;
-    c.valid = 0;
-    c.q = q;
-    c.k0 = c.k_hi = c.lr = 0;
-    c.bn = bn;
-    for (; q < nseq; ++q) {
-        int lr, lo, hi;
-        nt_part<MULTI>(P, q, lr, lo, hi);
-        if (hi > lo) {
-            c.q = q;
-            c.k0 = lo;
-            c.k_hi = hi;
-            c.lr = lr;
-            c.valid = 1;
-            return c;
-        }
-    }
-    return c;
-}
-
-// MLR: some output masks its low-rank part (dX = G W + keep .* (Q A)).  A template parameter, not a runtime test: the
-// keep-mask hashes depend only on (m, n), so the compiler hoists all 64 of them (+ their SGPR-pair results, spilled to
-// VGPR lanes) to the top of the kernel -- ~700 instructions per workgroup that the forward / P / Q launches never use.
-// NW = waves per workgroup.  The 128 x 128 tile is unchanged; with 8 waves a wave owns 64 n x 32 m (half the
-// accumulators, half the staging registers, half the loads / LDS traffic / MFMAs per step), fits 128 VGPRs and runs
-// 4 waves per SIMD instead of 2 -- the kernel is latency- and issue-bound, not bandwidth-bound.
-// d/dh of the exact (erf) GELU, the factor ATen's GeluBackward applies: Phi(h) + h * phi(h)
-// erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. fp32 rounding level) sharing its exp(-h^2/2) with the density:
-// ~16 VALU operations per element -- with ocml's erff + expf (~60) the epilogue of the hidden-width dX launches became
-// VALU-bound and gave back most of the saved pass.
-__device__ __forceinline__ float gelu_grad(float h) {
-    const float z = fabsf(h) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * z);
-    const float e = __expf(-z * z);  // exp(-h^2 / 2)
-    float p = 1.061405429f;
-    p = p * t - 1.453152027f;
-    p = p * t + 1.421413741f;
-    p = p * t - 0.284496736f;
-    p = p * t + 0.254829592f;
-    const float erf_abs = 1.f - p * t * e;  // erf(|h| / sqrt 2)
-    const float cdf = 0.5f + 0.5f * copysignf(erf_abs, h);
-    return cdf + h * e * 0.39894228040143268f;
-}
-
-// exact (erf) GELU with the same erf: h * Phi(h)
-__device__ __forceinline__ float gelu_fwd(float h) {
-    const float z = fabsf(h) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * z);
-    float p = 1.061405429f;
-    p = p * t - 1.453152027f;
-    p = p * t + 1.421413741f;
-    p = p * t - 0.284496736f;
-    p = p * t + 0.254829592f;
-    const float erf_abs = 1.f - p * t * __expf(-z * z);
-    return h * (0.5f + 0.5f * copysignf(erf_abs, h));
-}
-
-template <typename T, bool MULTI, bool MS, bool MLR, int NW, bool GATE = false, bool ACT = false>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_nt(const NtParams Pv) {
-    constexpr int SM = 8 / NW;       // 32-row m sub-blocks per wave
-    constexpr int MW = 32 * SM;      // m rows per wave
-    constexpr int NT = 64 * NW;      // threads
-    (void)Pv;
-    NtPtr P = (NtPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    constexpr int KE = ROWB / (int)sizeof(T);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // staging (2 x 128 x LDSB)
-    unsigned char* sW = smem;
-    unsigned char* sA = smem + TILE * LDSB;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wn = NW == 4 ? wave >> 1 : wave >> 2, wm = NW == 4 ? wave & 1 : wave & 3;
-
-    // batched form
-    const void* act0 = P->act[0];
-    int row_off = 0, n_rows = P->n_rows;
-    bool act_mask = P->act_mask != 0;
-    if (P->nz > 0) {
-        const int z = blockIdx.z;
-        act0 = P->zact[z];
-        row_off = P->zrow0[z];
-        n_rows = P->zrows[z];
-        act_mask = P->zmask[z] != 0;
-    }
-    if (n_rows <= 0) return;
-    if (P->dbg & NT_DBG_MASK & 16) return;
-    act_mask = act_mask && P->drop.thr16 != 0;
-
-    // XCD-aware tile order: hardware places block b on XCD b % 8; give every XCD a contiguous run of
-    // logical tiles so that the n-tiles sharing one activation row-block hit the same L2 (T1, bijective).
-    const int n_tiles = (n_rows + TILE - 1) / TILE;
-    const int64_t m_tiles = (P->M + TILE - 1) / TILE;
-    const int64_t nwg = m_tiles * n_tiles;
-    int64_t b = blockIdx.x;
-    if (b >= nwg) return;
-    {
-        const int64_t q = nwg / 8, r = nwg % 8, xcd = b % 8;
-        b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
-    }
-    const int64_t bm = b / n_tiles;
-    const int bn0 = (int)(b % n_tiles);
-    const int64_t m0 = bm * TILE;
-    const int n0 = bn0 * TILE;
-
-    const T* wgt = reinterpret_cast<const T*>(P->wgt) + (int64_t)row_off * P->ld_wgt;
-    DropoutCfg drop;
-    drop.seed_lo = P->drop.seed_lo;
-    drop.seed_hi = P->drop.seed_hi;
-    drop.thr16 = P->drop.thr16;
-    drop.off = P->drop.off;
-    mtl_dropout_resolve(drop);
-    const int nseq = MULTI ? 1 + P->n_out : 2 * P->n_out;
-
-    // ---- loader side of the stream (register prefetch, one wide tile ahead)
-    TileRegs<T, SM> rg;
-    NtCursor ld = nt_seek<MULTI>(P, 0, nseq, bn0);
-    auto issue = [&](const NtCursor& c) __attribute__((always_inline)) {
-        if (c.lr)  // rank segment: weights = Rm, activation = L
-            nt_load<T, false, SM>(rg, tid, reinterpret_cast<const T*>(P->Rm), P->ldR, c.bn * TILE, n_rows, P->L, P, 1, P->ldL, m0, P->M, c.k0,
-                                  c.k_hi, false);
-        else
-            nt_load<T, MS, SM>(rg, tid, wgt, P->ld_wgt, c.bn * TILE, n_rows, act0, P, P->n_act, P->ld_act, m0, P->M, c.k0, c.k_hi, act_mask);
-    };
-    const int dbg = P->dbg & NT_DBG_MASK;
-    if (ld.valid && !(dbg & 2)) issue(ld);
-    // consume one tile: registers -> LDS, prefetch the next tile of the stream, multiply
-    auto step = [&](f32x16(&acc)[2][SM], int k_left) __attribute__((always_inline)) {
-        if (!(dbg & 64)) nt_store_lds<T, SM>(rg, tid, sW, sA, drop, m0);
-        if (!(dbg & 128)) __syncthreads();
-        ld.k0 += KE;
-        if (ld.k0 >= ld.k_hi) ld = nt_seek<MULTI>(P, ld.q + 1, nseq, bn0);
-        if (ld.valid && !(dbg & 2)) issue(ld);
-        // a wave whose 64 output columns lie entirely past n_rows (P / Q passes: <= 64 of the tile's 128 columns exist)
-        // only helps staging: no LDS fragment reads, no MFMAs (wave-uniform test)
-        if (n0 + wn * 64 < n_rows && !(dbg & 4)) nt_compute<T, SM>(acc, sW, sA, lane, wn, wm, k_left);
-        if (!(dbg & 128)) __syncthreads();
-    };
-    auto run_part = [&](int q, f32x16(&acc)[2][SM]) __attribute__((always_inline)) {
-        int lr, lo, hi;
-        nt_part<MULTI>(P, q, lr, lo, hi);
-        for (int k0 = lo; k0 < hi; k0 += KE) step(acc, hi - k0);
-        return hi > lo;
-    };
-    auto zero = [](f32x16(&a)[2][SM]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < SM; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) a[i][j][r] = 0.f;
-    };
-    // acc = acc * alpha[n] + bias[n]
-    auto affine = [&](f32x16(&a)[2][SM]) __attribute__((always_inline)) {
-        if (!(P->alpha || P->bias) || (P->dbg & NT_DBG_MASK & 32)) return;
-#pragma unroll
-        for (int sn = 0; sn < 2; ++sn)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int n = n0 + wn * 64 + sn * 32 + 8 * q + 4 * (lane >> 5);
-                if (n < n_rows) {
-                    f32x4 al = {1.f, 1.f, 1.f, 1.f}, bi = {0.f, 0.f, 0.f, 0.f};
-                    if (P->alpha) al = *reinterpret_cast<const f32x4*>(P->alpha + row_off + n);
-                    if (P->bias) bi = *reinterpret_cast<const f32x4*>(P->bias + row_off + n);
-#pragma unroll
-                    for (int sm = 0; sm < SM; ++sm)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) a[sn][sm][q * 4 + e] = a[sn][sm][q * 4 + e] * al[e] + bi[e];
-                }
-            }
-    };
-    // acc *= keep(m, n)
-    auto apply_mask = [&](f32x16(&a)[2][SM]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int sm = 0; sm < SM; ++sm) {
-            const int64_t m = m0 + wm * MW + sm * 32 + (lane & 31);
-            const uint32_t rh = mtl_dropout_rowhash(drop, 0u, (uint32_t)m);
-#pragma unroll
-            for (int sn = 0; sn < 2; ++sn)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int n = n0 + wn * 64 + sn * 32 + 8 * q + 4 * (lane >> 5);
-                    const uint32_t h0 = mtl_dropout_pairbits(drop, rh, (uint32_t)n);
-                    const uint32_t h1 = mtl_dropout_pairbits(drop, rh, (uint32_t)(n + 2));
-                    if ((h0 & 0xFFFFu) < drop.thr16) a[sn][sm][q * 4 + 0] = 0.f;
-                    if ((h0 >> 16) < drop.thr16) a[sn][sm][q * 4 + 1] = 0.f;
-                    if ((h1 & 0xFFFFu) < drop.thr16) a[sn][sm][q * 4 + 2] = 0.f;
-                    if ((h1 >> 16) < drop.thr16) a[sn][sm][q * 4 + 3] = 0.f;
-                }
-        }
-    };
-    auto store = [&](const f32x16(&a)[2][SM], void* ptr, const void* gate_ptr, void* act_ptr) __attribute__((always_inline)) {
-        T* outp = reinterpret_cast<T*>(ptr);
-        const T* gate = reinterpret_cast<const T*>(gate_ptr);
-        T* actp = reinterpret_cast<T*>(act_ptr);
-        (void)gate;
-        (void)actp;
-        if (!outp || n0 + wn * 64 >= n_rows || (dbg & 8)) return;  // (the per-wave LDS image needs no workgroup barrier)
-        if constexpr (sizeof(T) == 2) {
-            // bf16: transpose the wave's 64(n) x 64(m) accumulator tile through LDS so that every store instruction
-            // writes whole 128-byte row segments (8 lanes x 16 B) instead of 16-byte pieces of 32 different rows.
-            // The staging buffers are idle here (the trailing barrier of the last tile has passed).
-            constexpr int ORS = EPI_ROW;  // row stride of the per-wave image (bytes): 2-way conflicts at most
-            unsigned char* img = smem + wave * (MW * ORS);
-#pragma unroll
-            for (int sm = 0; sm < SM; ++sm)
-#pragma unroll
-                for (int sn = 0; sn < 2; ++sn)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int ml = sm * 32 + (lane & 31), nl = sn * 32 + 8 * q + 4 * (lane >> 5);
-                        u32x2 pk = {mtl_pack2<T>(a[sn][sm][q * 4], a[sn][sm][q * 4 + 1]),
-                                    mtl_pack2<T>(a[sn][sm][q * 4 + 2], a[sn][sm][q * 4 + 3])};
-                        *reinterpret_cast<u32x2*>(img + ml * ORS + nl * 2) = pk;
-                    }
-            __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the image is private to this wave, no barrier needed
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int it = 0; it < 4 * SM; ++it) {
-                const int ml = it * 8 + (lane >> 3), c16 = lane & 7;
-                const int64_t m = m0 + wm * MW + ml;
-                const int n = n0 + wn * 64 + c16 * 8;
-                u32x4 v = *reinterpret_cast<const u32x4*>(img + ml * ORS + c16 * 16);
-                if (m < P->M && n < n_rows && !(dbg & 1)) {
-                    if constexpr (GATE) {
-                        if (gate) {  // the bf16-rounded gradient times gelu'(pre-activation), rounded once (as ATen does)
-                            const u32x4 hv = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gate + m * P->ld_out + row_off + n));
-                            v = mtl_gelu_gate_pk4<T, false>(v, hv);
-                        }
-                    }
-                    // non-temporal: the 77 - 308 MB outputs of a launch outlive L2 / MALL anyway (+1 % on the step; the same hint
-                    // on the glue kernels' stores costs 1.5 %: their consumers do hit in cache)
-                    __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(outp + m * P->ld_out + row_off + n));
-                    if constexpr (ACT) {
-                        if (actp) {  // second output: GELU of the bf16-rounded value, rounded once (ATen's gelu on the bf16 tensor)
-                            const u32x4 av = mtl_gelu_pk4<T, false>(v);
-                            __builtin_nontemporal_store(av, reinterpret_cast<u32x4*>(actp + m * P->ld_out + row_off + n));
-                        }
-                    }
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        } else {
-#pragma unroll
-            for (int sm = 0; sm < SM; ++sm) {
-                const int64_t m = m0 + wm * MW + sm * 32 + (lane & 31);
-#pragma unroll
-                for (int sn = 0; sn < 2; ++sn)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int n = n0 + wn * 64 + sn * 32 + 8 * q + 4 * (lane >> 5);
-                        if (m < P->M && n < n_rows) {
-                            T* dst = outp + m * P->ld_out + row_off + n;
-                            f32x4 o4 = {a[sn][sm][q * 4], a[sn][sm][q * 4 + 1], a[sn][sm][q * 4 + 2], a[sn][sm][q * 4 + 3]};
-                            if constexpr (GATE) {
-                                if (gate) {
-                                    const f32x4 hv = *reinterpret_cast<const f32x4*>(gate + m * P->ld_out + row_off + n);
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) o4[e] *= gelu_grad(hv[e]);
-                                }
-                            }
-                            *reinterpret_cast<f32x4*>(dst) = o4;
-                            if constexpr (ACT) {
-                                if (actp) {
-                                    f32x4 a4;
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) a4[e] = gelu_fwd(o4[e]);
-                                    *reinterpret_cast<f32x4*>(actp + m * P->ld_out + row_off + n) = a4;
-                                }
-                            }
-                        }
-                    }
-            }
-        }
-    };
-
-    if constexpr (MULTI) {
-        f32x16 base[2][SM], acc[2][SM];
-        zero(base);
-        run_part(0, base);
-        affine(base);
-        for (int o = 0; o < P->n_out; ++o) {
-            const NtOut O = nt_out(P, o);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < SM; ++j) acc[i][j] = base[i][j];
-            run_part(1 + o, acc);
-            if (O.fold) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < SM; ++j) base[i][j] = acc[i][j];
-            }
-            store(acc, O.ptr, O.gate, O.act);
-            __syncthreads();  // the output image lives in the staging buffers
-        }
-    } else {
-        f32x16 acc[2][SM];
-        for (int o = 0; o < P->n_out; ++o) {
-            const NtOut O = nt_out(P, o);
-            zero(acc);
-            const bool had_lr = run_part(2 * o, acc);
-            if constexpr (MLR) {
-                if (had_lr && O.mask_lr && drop.enabled()) apply_mask(acc);
-            } else {
-                (void)had_lr;
-            }
-            run_part(2 * o + 1, acc);
-            if (O.use_base) affine(acc);
-            store(acc, O.ptr, O.gate, O.act);
-            __syncthreads();  // the output image lives in the staging buffers
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_ntl : the lean bf16 launches of k_nt (ONE output, one activation source, no batched / row-panel form: every P / Q pass,
-// every T = 0 forward and dX) as straight-line code.
-// Why a second kernel: an ablation of k_nt (MTLORA_NT_DBG, tools/nt_ablate.sh; profiles/r02_nt_ablate.txt) showed that with
-// loads, MFMAs, stores and the epilogue all switched OFF the s0.qkv forward still took 100 of its 164 us -- the generic
-// kernel's bookkeeping.  Its prologue is a chain of ~15 DEPENDENT scalar loads from the 1 KB parameter block (each followed by
-// s_waitcnt lgkmcnt(0)), three software 64-bit divisions (~130 SALU instructions each) for the XCD map, a part-sequence cursor
-// that re-reads the output table per step, and every global load sits in its own exec-masked branch.  With only 2 - 4 k-steps
-// per workgroup nothing amortises that.  Here:
-//   * a compact parameter block (~200 B) read once; the XCD map and tile decomposition use 32-bit arithmetic and a host-side
-//     magic multiplier instead of divisions;
-//   * the step sequence is [rank-segment k-tiles | base k-tiles], both counts known up front: no cursor;
-//   * loads are unconditional: out-of-range rows are CLAMPED (their products land in rows / columns that are never stored)
-//     and out-of-range k vectors read a 16-byte zero page -- address selects, no branches;
-//   * the bias is the accumulator's initial value (its loads overlap the first tile's) instead of a dependent load + FMA pass
-//     after the last MFMA.
-// Tile geometry, LDS layout, fragment reads and the transposing epilogue are k_nt's 8-wave variant (128 x 128 x 96, wave tile
-// 64 n x 32 m), so results are bit-identical to k_nt's.
-// ------------------------------------------------------------------------------------------------
-__device__ __attribute__((aligned(16))) const uint32_t g_zero16[4] = {0u, 0u, 0u, 0u};
-
-struct NlParams {
-    const bf16* act;    // (M x K) activation-like operand of the base part
-    const bf16* wgt;    // (n_rows x K)
-    const bf16* L;      // (M x ldL) activation-like operand of the rank part
-    const bf16* Rm;     // (n_rows x ldR)
-    bf16* out;          // (M x ld_out)
-    bf16* act2;         // ACT: second output gelu(out)
-    const bf16* gate;   // GATE (k_ntd): out *= gelu'(gate[m][n]), same layout as out
-    const float* bias;  // per output column, nullable
-    const float* alpha; // per output column multiplier, nullable
-    int64_t ld_act, ld_wgt, ldL, ldR, ld_out;
-    int M, n_rows, K, seg_lo, seg_hi;
-    int n_tiles;
-    uint32_t nt_magic;  // floor(2^32 / n_tiles) + 1: b / n_tiles == umulhi(b, nt_magic) for b * n_tiles < 2^32 (n_tiles > 1)
-    uint32_t q8, r8;    // workgroups / 8, workgroups % 8 (XCD map)
-    int act_mask, use_base;
-    int dbg, pad_;
-    DropoutCfg drop;
-};
-
-// SN = 32-column sub-blocks per wave: 2 (128 x 128 tile) or 3 (128 rows x 192 columns).  The wide tile exists for the launches
-// whose 128 x 128 tile count lands just above a whole number of residency rounds (2 workgroups per CU = 512 slots): the
-// N = 384 outputs of stage 2 (196 x 3 = 588 tiles = 1.15 rounds -> 2 rounds, the second one 15 % full) run as 196 x 2 = 392
-// tiles of 1.5x the work in ONE round.  MLR: the low-rank part (rank tiles come first in the stream) is multiplied by the dropout
-// keep-mask of (m, n) before the base tiles are added -- the dX launches (dX = keep .* (Q A) + dY W).
-template <bool ACT, bool MLR, int SN>
-__global__ __launch_bounds__(512, 4) void k_ntl(const NlParams P) {
-    constexpr int KE = ROWB / 2;  // 96 elements per staged k-tile
-    constexpr int TN = 64 * SN;   // tile columns
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* sW = smem;
-    unsigned char* sA = smem + TN * LDSB;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wn = wave >> 2, wm = wave & 3;
-
-    // XCD-aware tile order (as k_nt): block b runs on XCD b % 8; every XCD gets a contiguous run of logical tiles
-    uint32_t b = blockIdx.x;
-    {
-        const uint32_t xcd = b & 7u, q = P.q8, r = P.r8;
-        b = (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + (b >> 3);
-    }
-    const uint32_t bm = P.n_tiles == 1 ? b : __umulhi(b, P.nt_magic);
-    const int bn = (int)(b - bm * (uint32_t)P.n_tiles);
-    const int m0 = (int)bm * TILE, n0 = bn * TN;
-    const int M = P.M, n_rows = P.n_rows;
-
-    DropoutCfg drop = P.drop;
-    mtl_dropout_resolve(drop);
-    const bool act_mask = P.act_mask != 0 && drop.thr16 != 0;
-    const int dbg = P.dbg & NT_DBG_MASK;
-
-    const int n1 = P.seg_hi > P.seg_lo ? (P.seg_hi - P.seg_lo + KE - 1) / KE : 0;
-    const int n2 = (P.use_base && P.K > 0) ? (P.K + KE - 1) / KE : 0;
-    const int total = n1 + n2;
-
-    f32x16 acc[SN];
-    // accumulator start: the bias (when nothing multiplies the sum afterwards and no mask is applied to the running sum)
-    const bool bias_first = !MLR && P.bias != nullptr && P.alpha == nullptr && P.use_base != 0;
-#pragma unroll
-    for (int sn = 0; sn < SN; ++sn)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            f32x4 bi = {0.f, 0.f, 0.f, 0.f};
-            if (bias_first) {
-                int n = n0 + wn * (32 * SN) + sn * 32 + 8 * q + 4 * (lane >> 5);
-                n = n < n_rows - 4 ? n : n_rows - 4;  // (columns >= n_rows are never stored)
-                bi = *reinterpret_cast<const f32x4*>(P.bias + n);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[sn][q * 4 + e] = bi[e];
-        }
-
-    u32x4 rw[3], rw2[SN == 3 ? 3 : 1], ra[3];  // staged k-tile: weight rows 0..127, weight rows 128..191 (SN = 3), activation rows
-    (void)rw2;
-    int cur_mask = 0, cur_k0 = 0;  // of the tile sitting in the registers
-    auto issue = [&](int i) __attribute__((always_inline)) {
-        const bool lr = i < n1;
-        const bf16* wp = lr ? P.Rm : P.wgt;
-        const bf16* ap = lr ? P.L : P.act;
-        const int64_t ldw = lr ? P.ldR : P.ld_wgt, lda = lr ? P.ldL : P.ld_act;
-        const int k0 = lr ? P.seg_lo + i * KE : (i - n1) * KE;
-        const int khi = lr ? P.seg_hi : P.K;
-        cur_mask = (!lr && act_mask) ? 1 : 0;
-        cur_k0 = k0;
-        const bf16* zp = reinterpret_cast<const bf16*>(g_zero16);
-#pragma unroll
-        for (int sl = 0; sl < 3; ++sl) {
-            int r, v;
-            nt_map<1>(tid, sl, r, v);
-            const int k = k0 + v * 8;
-            const bool kin = k < khi;
-            int wr = n0 + r, ar = m0 + r;
-            wr = wr < n_rows ? wr : n_rows - 1;
-            ar = ar < M ? ar : M - 1;
-            rw[sl] = *reinterpret_cast<const u32x4*>(kin ? wp + (int64_t)wr * ldw + k : zp);
-            ra[sl] = *reinterpret_cast<const u32x4*>(kin ? ap + (int64_t)ar * lda + k : zp);
-            if constexpr (SN == 3) {  // weight rows 128 .. 191: the same map on a second 128-row panel, upper half unused
-                int wr2 = n0 + 128 + r;
-                wr2 = wr2 < n_rows ? wr2 : n_rows - 1;
-                if (r < 64) rw2[sl] = *reinterpret_cast<const u32x4*>(kin ? wp + (int64_t)wr2 * ldw + k : zp);
-            }
-        }
-    };
-    auto stage = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int sl = 0; sl < 3; ++sl) {
-            int r, v;
-            nt_map<1>(tid, sl, r, v);
-            if (cur_mask) {  // uniform
-                const uint32_t rh = mtl_dropout_rowhash(drop, 0u, (uint32_t)(m0 + r));
-                VOps<bf16>::drop(ra[sl], drop, rh, (uint32_t)(cur_k0 + v * 8));
-            }
-            *reinterpret_cast<u32x4*>(sW + r * LDSB + v * 16) = rw[sl];
-            *reinterpret_cast<u32x4*>(sA + r * LDSB + v * 16) = ra[sl];
-            if constexpr (SN == 3) {
-                if (r < 64) *reinterpret_cast<u32x4*>(sW + (128 + r) * LDSB + v * 16) = rw2[sl];
-            }
-        }
-    };
-    auto compute = [&](int k_left) __attribute__((always_inline)) {
-        const int h = lane >> 5, rl = lane & 31;
-#pragma unroll
-        for (int t = 0; t < SUBT; ++t) {
-            if (t * 32 >= k_left) break;
-            Frag<bf16> fw[SN], fa;
-#pragma unroll
-            for (int sn = 0; sn < SN; ++sn) {
-                const unsigned char* pw = sW + (wn * (32 * SN) + sn * 32 + rl) * LDSB + t * 64;
-                fw[sn].v[0] = *reinterpret_cast<const u32x4*>(pw + h * 16);
-                fw[sn].v[1] = *reinterpret_cast<const u32x4*>(pw + (2 + h) * 16);
-            }
-            const unsigned char* pa = sA + (wm * 32 + rl) * LDSB + t * 64;
-            fa.v[0] = *reinterpret_cast<const u32x4*>(pa + h * 16);
-            fa.v[1] = *reinterpret_cast<const u32x4*>(pa + (2 + h) * 16);
-#pragma unroll
-            for (int sn = 0; sn < SN; ++sn) mtl_mma(fw[sn], fa, acc[sn]);
-        }
-    };
-    const bool wave_live = n0 + wn * (32 * SN) < n_rows;  // P / Q passes: a wave whose columns do not exist only helps staging
-    if (total > 0 && !(dbg & 2)) issue(0);
-    for (int i = 0; i < total; ++i) {
-        const bool lr = i < n1;
-        const int k_left = lr ? P.seg_hi - (P.seg_lo + i * KE) : P.K - (i - n1) * KE;
-        if (!(dbg & 64)) stage();
-        __syncthreads();
-        if (i + 1 < total && !(dbg & 2)) issue(i + 1);
-        if (wave_live && !(dbg & 4)) compute(k_left);
-        if constexpr (MLR) {
-            if (i + 1 == n1 && wave_live && drop.thr16 != 0) {  // the rank part is complete: acc *= keep(m, n)
-                const uint32_t rh = mtl_dropout_rowhash(drop, 0u, (uint32_t)(m0 + wm * 32 + (lane & 31)));
-#pragma unroll
-                for (int sn = 0; sn < SN; ++sn)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int n = n0 + wn * (32 * SN) + sn * 32 + 8 * q + 4 * (lane >> 5);
-                        const uint32_t h0 = mtl_dropout_pairbits(drop, rh, (uint32_t)n);
-                        const uint32_t h1 = mtl_dropout_pairbits(drop, rh, (uint32_t)(n + 2));
-                        if ((h0 & 0xFFFFu) < drop.thr16) acc[sn][q * 4 + 0] = 0.f;
-                        if ((h0 >> 16) < drop.thr16) acc[sn][q * 4 + 1] = 0.f;
-                        if ((h1 & 0xFFFFu) < drop.thr16) acc[sn][q * 4 + 2] = 0.f;
-                        if ((h1 >> 16) < drop.thr16) acc[sn][q * 4 + 3] = 0.f;
-                    }
-            }
-        }
-        __syncthreads();
-    }
-    if (!wave_live || (dbg & 8)) return;
-
-    if (!bias_first && (P.alpha || P.bias) && P.use_base) {  // acc = acc * alpha[n] + bias[n]
-#pragma unroll
-        for (int sn = 0; sn < SN; ++sn)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                int n = n0 + wn * (32 * SN) + sn * 32 + 8 * q + 4 * (lane >> 5);
-                n = n < n_rows - 4 ? n : n_rows - 4;
-                f32x4 al = {1.f, 1.f, 1.f, 1.f}, bi = {0.f, 0.f, 0.f, 0.f};
-                if (P.alpha) al = *reinterpret_cast<const f32x4*>(P.alpha + n);
-                if (P.bias) bi = *reinterpret_cast<const f32x4*>(P.bias + n);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[sn][q * 4 + e] = acc[sn][q * 4 + e] * al[e] + bi[e];
-            }
-    }
-
-    // epilogue: transpose the wave's (32 SN) (n) x 32 (m) tile through a private LDS image -> whole row-segment stores
-    {
-        constexpr int ORS = 64 * SN + 8;       // image row stride (bytes)
-        constexpr int CPRW = 4 * SN;           // 16-byte chunks per image row
-        unsigned char* img = smem + wave * (32 * ORS);
-#pragma unroll
-        for (int sn = 0; sn < SN; ++sn)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int ml = lane & 31, nl = sn * 32 + 8 * q + 4 * (lane >> 5);
-                u32x2 pk = {mtl_pack_bf16(acc[sn][q * 4], acc[sn][q * 4 + 1]), mtl_pack_bf16(acc[sn][q * 4 + 2], acc[sn][q * 4 + 3])};
-                *reinterpret_cast<u32x2*>(img + ml * ORS + nl * 2) = pk;
-            }
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the image is private to this wave
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int it = 0; it < 2 * SN; ++it) {
-            const int idx = it * 64 + lane;
-            const int ml = idx / CPRW, c16 = idx - ml * CPRW;
-            const int m = m0 + wm * 32 + ml;
-            const int n = n0 + wn * (32 * SN) + c16 * 8;
-            u32x4 v = *reinterpret_cast<const u32x4*>(img + ml * ORS + c16 * 16);
-            if (m < M && n < n_rows && !(dbg & 1)) {
-                const int64_t o = (int64_t)m * P.ld_out + n;
-                __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(P.out + o));
-                if constexpr (ACT) {
-                    if (P.act2) {
-                        const u32x4 av = mtl_gelu_pk4<bf16, false>(v);
-                        __builtin_nontemporal_store(av, reinterpret_cast<u32x4*>(P.act2 + o));
-                    }
-                }
-            }
-        }
-    }
-}
-
-#include "stream.h"
-#include "dense.h"
-#include "pq.h"
-
-// ------------------------------------------------------------------------------------------------
-// k_tn : Out[a][b] = sum_m SrcA[m][a0 + a] * SrcB[m][b0 + b], split over m.
-// SrcA is always the NARROW (rank-side) operand (Q or P, <= 64 columns per tile) and SrcB the WIDE one
-// (X or dY, 256 columns per tile), so a workgroup streams 64 + 256 columns per row and the wide matrix is
-// read ~once (x1.25 with the narrow slab) instead of twice with square tiles.  dB = dY^T P is computed as
-// its transpose P^T dY and written back transposed by k_tn_reduce.
-// ------------------------------------------------------------------------------------------------
-constexpr int TN_A = 64;
-constexpr int TN_B = 256;
-constexpr int TN_TILE = TN_A * TN_B;
-struct TnProblem {
-    const void* A;
-    const void* B;
-    int64_t lda, ldb;
-    int a0, Na, b0, Nb;  // column windows
-    int b_mask;          // dropout keep-mask on SrcB (keyed by (m, b0 + b))
-    int tiles_a, tiles_b;
-    float* part;         // [nsplit][tiles_a*tiles_b][64*256]
-    float* out;          // fp32; element (a, b) at out[a*ldo + b], or out[b*ldo + a] when transpose
-    int out_a, out_b, ldo, transpose;
-};
-struct TnParams {
-    TnProblem p[2 * MAXO];
-    int n_prob;
-    int64_t M;
-    int nsplit;
-    int64_t rows_per_split;
-    DropoutCfg drop;
-};
-
-template <typename T>
-struct TnCfg;
-template <>
-struct TnCfg<bf16> {
-    static constexpr int SUB = 32;  // rows (m) per MFMA k-tile
-};
-template <>
-struct TnCfg<f16> {
-    static constexpr int SUB = 32;
-};
-template <>
-struct TnCfg<float> {
-    static constexpr int SUB = 16;
-};
-
-// transposed fragment: lane (i = l & 31, h = l >> 5) gets Src[m = slot(h, e)][col0 + i]; ``lr`` = LDS row bytes
-template <typename H>  // any 16-bit element type (the transposing read moves bits)
-__device__ __forceinline__ Frag<H> tn_frag16(const unsigned char* s, int col0, int lane, int lr) {
-    // ds_read_b64_tr_b16: within each 16-lane group, lane i supplies the 8-byte address of row (i>>2),
-    // columns 4*(i&3)..+3 of a [4][16] block and receives column i of that block (4 rows).
-    const int g = lane >> 4, i = lane & 15, h = g >> 1;
-    const int col = col0 + 16 * (g & 1) + 4 * (i & 3);
-    Frag<H> f;
-    uint32_t w[8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {  // rows: {8h+0..3}, {8h+4..7}, {16+8h+0..3}, {16+8h+4..7}
-        const int row = ((j >> 1) * 16) + 8 * h + 4 * (j & 1) + (i >> 2);
-        const unsigned char* p = s + row * lr + col * 2;
-        s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) s16x4*)(p));
-        u32x2 u = __builtin_bit_cast(u32x2, v);
-        w[2 * j] = u[0];
-        w[2 * j + 1] = u[1];
-    }
-    f.v[0] = u32x4{w[0], w[1], w[2], w[3]};
-    f.v[1] = u32x4{w[4], w[5], w[6], w[7]};
-    return f;
-}
-__device__ __forceinline__ Frag<bf16> tn_frag(const unsigned char* s, int col0, int lane, int lr, bf16*) {
-    return tn_frag16<bf16>(s, col0, lane, lr);
-}
-__device__ __forceinline__ Frag<f16> tn_frag(const unsigned char* s, int col0, int lane, int lr, f16*) {
-    return tn_frag16<f16>(s, col0, lane, lr);
-}
-__device__ __forceinline__ Frag<float> tn_frag(const unsigned char* s, int col0, int lane, int lr, float*) {
-    const int h = lane >> 5, i = lane & 31;
-    Frag<float> f;
-    uint32_t w[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {  // rows {4h..4h+3} U {8+4h..8+4h+3}
-        const int row = (e >> 2) * 8 + 4 * h + (e & 3);
-        w[e] = *reinterpret_cast<const uint32_t*>(s + row * lr + (col0 + i) * 4);
-    }
-    f.v[0] = u32x4{w[0], w[1], w[2], w[3]};
-    f.v[1] = u32x4{w[4], w[5], w[6], w[7]};
-    return f;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256, 2) void k_tn(const TnParams P) {
-    constexpr int SUB = TnCfg<T>::SUB;
-    constexpr int KE = 2 * SUB;  // rows per staged chunk
-    constexpr int ES = (int)sizeof(T);
-    constexpr int VEC = ET<T>::VEC;
-    // padded LDS rows.  bf16: a ds_read_b64_tr_b16 cycle serves 32 lanes = 4 rows x 2 column halves of 32 B; the 8
-    // segments fall in distinct bank groups iff the row stride is 16 dwords (mod 64): 320 B / 576 B (strides of
-    // 144 B / 528 B cost 42 % of the LDS cycles in conflicts).  f32 (scalar 4-byte reads across 32 columns): +16 B.
-    constexpr int LRA = ES == 2 ? 320 : TN_A * ES + 16, LRB = ES == 2 ? 576 : TN_B * ES + 16;
-    constexpr int VPA = TN_A / VEC, VPB = TN_B / VEC;          // 16-byte vectors per tile row
-    constexpr int RSA = 256 / VPA, RSB = 256 / VPB;            // rows covered by one sweep of the workgroup
-    constexpr int NLA = KE / RSA, NLB = KE / RSB;              // loads per thread per chunk (2 and 8)
-    __shared__ __attribute__((aligned(16))) unsigned char smem[KE * (LRA + LRB)];
-    unsigned char* sA = smem;
-    unsigned char* sB = smem + KE * LRA;
-    const TnProblem& pr = P.p[blockIdx.z];
-    const int tile = blockIdx.y;
-    if (tile >= pr.tiles_a * pr.tiles_b) return;
-    const int ta = tile / pr.tiles_b, tb = tile % pr.tiles_b;
-    const int split = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-
-    const int64_t m_lo = (int64_t)split * P.rows_per_split;
-    int64_t m_hi = m_lo + P.rows_per_split;
-    if (m_hi > P.M) m_hi = P.M;
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int rowA = tid / VPA, vecA = tid % VPA, rowB = tid / VPB, vecB = tid % VPB;
-    const int ca = ta * TN_A + vecA * VEC;  // column inside the A window
-    const int cb = tb * TN_B + vecB * VEC;
-    const bool a_in = ca < pr.Na, b_in = cb < pr.Nb;
-    const bool wave_on = tb * TN_B + wave * 64 < pr.Nb;  // this wave's 64 wide columns hold data
-    const T* Ap = reinterpret_cast<const T*>(pr.A) + pr.a0 + ca;
-    const T* Bp = reinterpret_cast<const T*>(pr.B) + pr.b0 + cb;
-    DropoutCfg drop = P.drop;
-    mtl_dropout_resolve(drop);
-    const bool bmask = pr.b_mask && drop.enabled();
-
-    // two register sets = prefetch distance 2 chunks (the grid is sized to 2 workgroups per CU, i.e. 256 VGPRs per
-    // wave, and a workgroup's streaming rate is bounded by bytes in flight / load latency)
-    u32x4 ra0[NLA], rb0[NLB], ra1[NLA], rb1[NLB];
-    auto load = [&](u32x4* ra, u32x4* rb, int64_t mrow) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < NLA; ++j) {
-            const int64_t m = mrow + rowA + j * RSA;
-            ra[j] = (a_in && m < m_hi) ? *reinterpret_cast<const u32x4*>(Ap + m * pr.lda) : u32x4{0u, 0u, 0u, 0u};
-        }
-#pragma unroll
-        for (int j = 0; j < NLB; ++j) {
-            const int64_t m = mrow + rowB + j * RSB;
-            rb[j] = (b_in && m < m_hi) ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(Bp + m * pr.ldb)) : u32x4{0u, 0u, 0u, 0u};
-        }
-    };
-    auto stage = [&](u32x4* ra, u32x4* rb, int64_t mrow) __attribute__((always_inline)) {
-        if (bmask && b_in) {  // dropout keep-mask, applied just before the LDS store
-#pragma unroll
-            for (int j = 0; j < NLB; ++j) {
-                const uint32_t rh = mtl_dropout_rowhash(drop, 0u, (uint32_t)(mrow + rowB + j * RSB));
-                Vec16<T> x;
-                x.raw = rb[j];
-#pragma unroll
-                for (int e = 0; e < VEC; e += 2) {
-                    const uint32_t h = mtl_dropout_pairbits(drop, rh, (uint32_t)(pr.b0 + cb + e));
-                    if ((h & 0xFFFFu) < drop.thr16) x.e[e] = mtl_from_f32<T>(0.f);
-                    if ((h >> 16) < drop.thr16) x.e[e + 1] = mtl_from_f32<T>(0.f);
-                }
-                rb[j] = x.raw;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NLA; ++j) *reinterpret_cast<u32x4*>(sA + (rowA + j * RSA) * LRA + vecA * 16) = ra[j];
-#pragma unroll
-        for (int j = 0; j < NLB; ++j) *reinterpret_cast<u32x4*>(sB + (rowB + j * RSB) * LRB + vecB * 16) = rb[j];
-    };
-    auto compute = [&]() __attribute__((always_inline)) {
-        if (!wave_on) return;
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-            const unsigned char* a_s = sA + sub * SUB * LRA;
-            const unsigned char* b_s = sB + sub * SUB * LRB;
-            Frag<T> fa0 = tn_frag(a_s, 0, lane, LRA, (T*)nullptr);
-            Frag<T> fa1 = tn_frag(a_s, 32, lane, LRA, (T*)nullptr);
-            Frag<T> fb0 = tn_frag(b_s, wave * 64, lane, LRB, (T*)nullptr);
-            Frag<T> fb1 = tn_frag(b_s, wave * 64 + 32, lane, LRB, (T*)nullptr);
-            mtl_mma(fa0, fb0, acc[0][0]);
-            mtl_mma(fa0, fb1, acc[0][1]);
-            mtl_mma(fa1, fb0, acc[1][0]);
-            mtl_mma(fa1, fb1, acc[1][1]);
-        }
-    };
-
-    if (m_lo < m_hi) load(ra0, rb0, m_lo);
-    if (m_lo + KE < m_hi) load(ra1, rb1, m_lo + KE);
-    for (int64_t mrow = m_lo; mrow < m_hi; mrow += 2 * KE) {
-        stage(ra0, rb0, mrow);
-        __syncthreads();
-        if (mrow + 2 * KE < m_hi) load(ra0, rb0, mrow + 2 * KE);
-        compute();
-        __syncthreads();
-        if (mrow + KE < m_hi) {
-            stage(ra1, rb1, mrow + KE);
-            __syncthreads();
-            if (mrow + 3 * KE < m_hi) load(ra1, rb1, mrow + 3 * KE);
-            compute();
-            __syncthreads();
-        }
-    }
-
-    if (!wave_on) return;  // k_tn_reduce never reads columns outside the B window
-    float* dst = pr.part + ((int64_t)split * (pr.tiles_a * pr.tiles_b) + tile) * TN_TILE;
-#pragma unroll
-    for (int ia = 0; ia < 2; ++ia)
-#pragma unroll
-        for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = ia * 32 + mtl_d_row(lane, r), j = wave * 64 + jb * 32 + mtl_d_col(lane);
-                dst[i * TN_B + j] = acc[ia][jb][r];
-            }
-}
-
-constexpr int TN_RG = 4;  // thread groups that share the splits of a 1024-element block
-__global__ __launch_bounds__(256 * TN_RG) void k_tn_reduce(const TnParams P) {
-    // one workgroup per (problem, tile, 1024-element block): 4 outputs per thread (one 16-byte load per split, coalesced
-    // across the wave); the splits are dealt round-robin to TN_RG groups of 256 threads, each summing its share in a
-    // fixed order with 4 independent chains, then a fixed-order LDS combine (deterministic)
-    __shared__ f32x4 sm[TN_RG][256];
-    const TnProblem& pr = P.p[blockIdx.z];
-    const int ntile = pr.tiles_a * pr.tiles_b;
-    const int tile = blockIdx.y;
-    if (tile >= ntile) return;
-    const int t = threadIdx.x & 255, grp = threadIdx.x >> 8;
-    const int e0 = blockIdx.x * 1024 + t * 4;  // element inside the 64x256 tile
-    const int ta = tile / pr.tiles_b, tb = tile % pr.tiles_b;
-    const int a = ta * TN_A + e0 / TN_B, b0 = tb * TN_B + e0 % TN_B;
-    const bool live = a < pr.out_a && b0 < pr.out_b;
-    f32x4 acc[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (live) {
-        const float* src = pr.part + (int64_t)tile * TN_TILE + e0;
-        const int64_t stride = (int64_t)ntile * TN_TILE;
-        int sp = grp;
-        for (; sp + 3 * TN_RG < P.nsplit; sp += 4 * TN_RG) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[u] += *reinterpret_cast<const f32x4*>(src + (int64_t)(sp + u * TN_RG) * stride);
-        }
-        for (; sp < P.nsplit; sp += TN_RG) acc[0] += *reinterpret_cast<const f32x4*>(src + (int64_t)sp * stride);
-    }
-    sm[grp][t] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-    __syncthreads();
-    if (grp != 0 || !live) return;
-    f32x4 tsum = sm[0][t];
-#pragma unroll
-    for (int gI = 1; gI < TN_RG; ++gI) tsum += sm[gI][t];
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (b0 + e < pr.out_b) {
-            const int64_t at = pr.transpose ? (int64_t)(b0 + e) * pr.ldo + a : (int64_t)a * pr.ldo + b0 + e;
-            pr.out[at] = tsum[e];
-        }
-}
-
-// elementwise sum of up to MAXO tensors (matrixv2 backward: G for the shared factors)
-struct SumParams {
-    const void* src[MAXO];
-    int n;
-    int64_t nvec;
-};
-template <typename T>
-__global__ __launch_bounds__(256) void k_sum(SumParams P, T* out) {
-    constexpr int VEC = ET<T>::VEC;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < P.nvec; i += (int64_t)gridDim.x * 256) {
-        float f[VEC];
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) f[e] = 0.f;
-        for (int s = 0; s < P.n; ++s) {
-            Vec16<T> y = mtl_ld16<T>(reinterpret_cast<const T*>(P.src[s]) + i * VEC);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) f[e] += mtl_to_f32(y.e[e]);
-        }
-        Vec16<T> o;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) o.e[e] = mtl_from_f32<T>(f[e]);
-        *reinterpret_cast<u32x4*>(out + i * VEC) = o.raw;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_rank_out : the task outputs of a dX launch,  dX_t = Q_t A_t  [.* gelu'(h_t)],  for SMALL task ranks (rp <= 16).
-// They share nothing with the base GEMM (no dY W term), and with r_t = 4 the "GEMM" is 8 multiply-adds per element: in the tiled
-// multi-output kernel each of them costs a full tile pass (rank k-tile staging, MFMA on a mostly-zero k-tile, LDS transposition) --
-// the T = 4 fc2 dX spent ~180 us per task output at stage 0.  Here it is a streaming elementwise kernel: a thread owns ONE 16-byte
-// column chunk (its rp x 8 factor values live in registers) and walks the rows, 4 in flight; rounding as the tiled epilogue
-// (fp32 sum -> T, then T * gelu'(h) -> T).
-// ------------------------------------------------------------------------------------------------
-struct RankOutParams {
-    const void* Q;      // (M x ldq)
-    const void* Acat;   // (R x K) row-major, unscaled (Q carries alpha)
-    int64_t ldq, M;
-    int K, n_t;
-    int seg[MAXO], rp[MAXO];
-    void* out[MAXO];
-    const void* gate[MAXO];
-};
-template <typename T, bool GATE, int RP>
-__global__ __launch_bounds__(256) void k_rank_out(const RankOutParams P) {
-    constexpr int UNR = 4;
-    const int t = blockIdx.y;
-    const int nchunk = P.K >> 3;
-    const int rpb = 256 / nchunk;  // rows per block sweep (nchunk <= 256)
-    const int tid = threadIdx.x;
-    if (tid >= rpb * nchunk) return;
-    const int chunk = tid % nchunk, r0 = tid / nchunk;
-    const int seg = P.seg[t];
-    float a[RP][8];
-#pragma unroll
-    for (int j = 0; j < RP; ++j) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(P.Acat) + (int64_t)(seg + j) * P.K + chunk * 8);
-        VOps<T>::unpack(v, a[j]);
-    }
-    const T* q = reinterpret_cast<const T*>(P.Q) + seg;
-    T* out = reinterpret_cast<T*>(P.out[t]);
-    const T* gate = reinterpret_cast<const T*>(P.gate[t]);
-    const int64_t step = (int64_t)gridDim.x * rpb;
-    for (int64_t row = (int64_t)blockIdx.x * rpb + r0; row < P.M; row += UNR * step) {
-        u32x4 qv[UNR][RP / 8], hv[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            const int64_t m = row + u * step;
-            const int64_t mc = m < P.M ? m : P.M - 1;
-#pragma unroll
-            for (int w = 0; w < RP / 8; ++w) qv[u][w] = *reinterpret_cast<const u32x4*>(q + mc * P.ldq + w * 8);
-            if constexpr (GATE) hv[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gate + mc * P.K + chunk * 8));
-        }
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            const int64_t m = row + u * step;
-            float acc[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-#pragma unroll
-            for (int w = 0; w < RP / 8; ++w) {
-                float qf[8];
-                VOps<T>::unpack(qv[u][w], qf);
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc[e] += qf[j] * a[w * 8 + j][e];
-            }
-            u32x4 o = VOps<T>::pack(acc);
-            if constexpr (GATE) o = mtl_gelu_gate_pk4<T, false>(o, hv[u]);
-            if (m < P.M) __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(out + m * P.K + chunk * 8));
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1520,18 +188,6 @@ static bool raise_lds(std::atomic<unsigned long long>& done, const void* fn, int
         (void)raise_lds(done__, (const void*)(KERNEL), (int)(BYTES));       \
     } while (0)
 
-// developer ablation bits (tools/nt_ablate.sh, tools/sp_ablate.sh): read from the environment ONLY in a -DMTL_NT_ABLATE=1 build
-// (MTLORA_ABLATE=1 python -m mtlora_amd.csrc.build --force); the shipped library has neither the getenv nor the kernel branches
-static int ablate_bits(const char* name) {
-#if MTL_NT_ABLATE
-    const char* e = getenv(name);
-    return e ? atoi(e) : 0;
-#else
-    (void)name;
-    return 0;
-#endif
-}
-
 // k_nte (two 4-wave workgroups per CU) instead of k_ntd / k_ntl?  Measured per shape (tools/ntd_ab.sh, profiles/r04_ntd_ab.txt): it wins
 // where a tile spends a large share of its life outside the k loop -- short reductions (<= 12 k-steps of 64) with at least 1.5 tiles per
 // CU -- and where k_ntd's one-workgroup-per-CU rounds are badly filled (< 70 %) while every CU still gets a tile; it loses on long
@@ -1541,10 +197,60 @@ static bool nte_prefer(int64_t tiles, int ksteps, int64_t cus) {
     return (ksteps >= 4 && ksteps <= 12 && tiles * 2 >= 3 * cus) || (ksteps >= 6 && eff_d < 0.7 && tiles >= cus);
 }
 
+// the compact parameter block of the single-output bf16 kernels (k_ntd / k_nte: dense, k_ntl) from the generic one.  `nt` column tiles
+// per row of `mt` row tiles.  Only the dense kernels take a gate; they never see a masked activation (their eligibility excludes it).
+static NlParams make_nl(const NtParams& P, int64_t mt, int64_t nt, bool dense) {
+    NlParams q;
+    q.act = reinterpret_cast<const bf16*>(P.act[0]);
+    q.wgt = reinterpret_cast<const bf16*>(P.wgt);
+    q.L = reinterpret_cast<const bf16*>(P.L);
+    q.Rm = reinterpret_cast<const bf16*>(P.Rm);
+    q.out = reinterpret_cast<bf16*>(P.out[0].ptr);
+    q.act2 = reinterpret_cast<bf16*>(P.out[0].act);
+    q.gate = dense ? reinterpret_cast<const bf16*>(P.out[0].gate) : nullptr;
+    q.bias = P.bias;
+    q.alpha = P.alpha;
+    q.ld_act = P.ld_act;
+    q.ld_wgt = P.ld_wgt;
+    q.ldL = P.ldL;
+    q.ldR = P.ldR;
+    q.ld_out = P.ld_out;
+    q.M = (int)P.M;
+    q.n_rows = P.n_rows;
+    q.K = P.act[0] ? P.K : 0;
+    q.seg_lo = P.L ? P.out[0].seg_lo : 0;
+    q.seg_hi = P.L ? P.out[0].seg_hi : 0;
+    q.n_tiles = (int)nt;
+    q.nt_magic = (uint32_t)(((uint64_t)1 << 32) / (uint64_t)nt) + 1u;
+    const uint32_t nwg = (uint32_t)(mt * nt);
+    q.q8 = nwg / 8u;
+    q.r8 = nwg % 8u;
+    q.act_mask = dense ? 0 : P.act_mask;
+    q.use_base = P.out[0].use_base;
+    q.drop = P.drop;
+    return q;
+}
+
+// the <ACT, MLR, GATE> instance of a dense single-output kernel (k_ntd / k_nte): go(ACT, MLR, GATE) is called with the three as
+// std::bool_constant values.  The GELU second output excludes the other two.  (k_ntl's ladder is over (act2, wide, ml0): on its own below.)
+template <typename F>
+static void nl_dispatch(const NlParams& q, bool ml0, F&& go) {
+    using Y = std::true_type;
+    using N = std::false_type;
+    if (q.act2)
+        go(Y{}, N{}, N{});
+    else if (q.gate && ml0)
+        go(N{}, Y{}, Y{});
+    else if (q.gate)
+        go(N{}, N{}, Y{});
+    else if (ml0)
+        go(N{}, Y{}, N{});
+    else
+        go(N{}, N{}, N{});
+}
+
 template <typename T>
-static void launch_nt(const Tune& tu, const NtParams& P_in, hipStream_t s, int kind, double alg_bytes, double s8d_bytes = 0.0, double flops = 0.0) {
-    NtParams P = P_in;
-    P.dbg = ablate_bits("MTLORA_NT_DBG");
+static void launch_nt(const Tune& tu, const NtParams& P, hipStream_t s, int kind, double alg_bytes, double s8d_bytes = 0.0, double flops = 0.0) {
     mtl_prof_tag("M%lld K%d N%d ldL%lld no%d na%d nz%d", (long long)P.M, P.K, P.n_rows, (long long)P.ldL, P.n_out, P.n_act, P.nz);
     MtlProfScope prof(kind, alg_bytes, s, s8d_bytes, flops);
     int max_rows = P.n_rows;
@@ -1598,119 +304,36 @@ static void launch_nt(const Tune& tu, const NtParams& P_in, hipStream_t s, int k
                      (ksteps >= 6 && (eff >= 0.7 || (tiles <= slots && tiles >= slots / 2)) && (P.n_rows % ND_TN == 0 || P.n_rows > 2 * ND_TN)));
         }
         if (dense) {
-            NlParams q;
-            q.act = reinterpret_cast<const bf16*>(P.act[0]);
-            q.wgt = reinterpret_cast<const bf16*>(P.wgt);
-            q.L = reinterpret_cast<const bf16*>(P.L);
-            q.Rm = reinterpret_cast<const bf16*>(P.Rm);
-            q.out = reinterpret_cast<bf16*>(P.out[0].ptr);
-            q.act2 = reinterpret_cast<bf16*>(P.out[0].act);
-            q.gate = reinterpret_cast<const bf16*>(P.out[0].gate);
-            q.bias = P.bias;
-            q.alpha = P.alpha;
-            q.ld_act = P.ld_act;
-            q.ld_wgt = P.ld_wgt;
-            q.ldL = P.ldL;
-            q.ldR = P.ldR;
-            q.ld_out = P.ld_out;
-            q.M = (int)P.M;
-            q.n_rows = P.n_rows;
-            q.K = P.act[0] ? P.K : 0;
-            q.seg_lo = P.L ? P.out[0].seg_lo : 0;
-            q.seg_hi = P.L ? P.out[0].seg_hi : 0;
             const int64_t mt = mtl_ceil_div(P.M, ND_TM), nt = mtl_ceil_div(P.n_rows, ND_TN);
-            q.n_tiles = (int)nt;
-            q.nt_magic = (uint32_t)(((uint64_t)1 << 32) / (uint64_t)nt) + 1u;
-            const uint32_t nwg = (uint32_t)(mt * nt);
-            q.q8 = nwg / 8u;
-            q.r8 = nwg % 8u;
-            q.act_mask = 0;
-            q.use_base = P.out[0].use_base;
-            q.dbg = P.dbg;
-            q.pad_ = 0;
-            q.drop = P.drop;
+            const NlParams q = make_nl(P, mt, nt, true);
             const bool ml0 = P.out[0].mask_lr != 0 && P.drop.enabled() && q.seg_hi > q.seg_lo;
-            const uint32_t grid = nwg < (uint32_t)num_cu(tu) ? nwg : (uint32_t)num_cu(tu);
-#define MTL_NTD_GO(AC, ML, GA)                                                                \
-    do {                                                                                      \
-        MTL_RAISE_LDS((k_ntd<AC, ML, GA>), SP_LDS_MAX);                                       \
-        hipLaunchKernelGGL((k_ntd<AC, ML, GA>), dim3(grid), dim3(512), (size_t)ND_LDS, s, q); \
-    } while (0)
+            const uint32_t nwg = (uint32_t)(mt * nt), cus = (uint32_t)num_cu(tu);
             // k_nte: the same tile with two 4-wave workgroups per CU (dense.h); ntd_mode 3 forces it, 2 forces k_ntd
-            if (use_e) {
-                const uint32_t ge = nwg < 2u * (uint32_t)num_cu(tu) ? nwg : 2u * (uint32_t)num_cu(tu);
-#define MTL_NTE_GO(AC, ML, GA)                                                                \
-    do {                                                                                      \
-        MTL_RAISE_LDS((k_nte<AC, ML, GA>), SP_LDS_MAX);                                       \
-        hipLaunchKernelGGL((k_nte<AC, ML, GA>), dim3(ge), dim3(256), (size_t)NE_LDS, s, q);   \
-    } while (0)
-                if (q.act2)
-                    MTL_NTE_GO(true, false, false);
-                else if (q.gate && ml0)
-                    MTL_NTE_GO(false, true, true);
-                else if (q.gate)
-                    MTL_NTE_GO(false, false, true);
-                else if (ml0)
-                    MTL_NTE_GO(false, true, false);
-                else
-                    MTL_NTE_GO(false, false, false);
-#undef MTL_NTE_GO
-                return;
-            }
-            if (q.act2)
-                MTL_NTD_GO(true, false, false);
-            else if (q.gate && ml0)
-                MTL_NTD_GO(false, true, true);
-            else if (q.gate)
-                MTL_NTD_GO(false, false, true);
-            else if (ml0)
-                MTL_NTD_GO(false, true, false);
-            else
-                MTL_NTD_GO(false, false, false);
-#undef MTL_NTD_GO
+            nl_dispatch(q, ml0, [&](auto ac, auto ml, auto ga) {
+                constexpr bool AC = decltype(ac)::value, ML = decltype(ml)::value, GA = decltype(ga)::value;
+                if (use_e) {
+                    MTL_RAISE_LDS((k_nte<AC, ML, GA>), SP_LDS_MAX);
+                    hipLaunchKernelGGL((k_nte<AC, ML, GA>), dim3(nwg < 2u * cus ? nwg : 2u * cus), dim3(256), (size_t)NE_LDS, s, q);
+                } else {
+                    MTL_RAISE_LDS((k_ntd<AC, ML, GA>), SP_LDS_MAX);
+                    hipLaunchKernelGGL((k_ntd<AC, ML, GA>), dim3(nwg < cus ? nwg : cus), dim3(512), (size_t)ND_LDS, s, q);
+                }
+            });
             return;
         }
         if (variant == 2 && P.n_out == 1 && P.out[0].gate == nullptr && P.nz == 0 && P.M < (int64_t)0x7FFFFF00 &&
             m_tiles * n_tiles < ((int64_t)1 << 28) && P.n_rows >= 8 && P.n_rows % 8 == 0) {
-            NlParams q;
-            q.act = reinterpret_cast<const bf16*>(P.act[0]);
-            q.wgt = reinterpret_cast<const bf16*>(P.wgt);
-            q.L = reinterpret_cast<const bf16*>(P.L);
-            q.Rm = reinterpret_cast<const bf16*>(P.Rm);
-            q.out = reinterpret_cast<bf16*>(P.out[0].ptr);
-            q.act2 = reinterpret_cast<bf16*>(P.out[0].act);
-            q.gate = nullptr;
-            q.bias = P.bias;
-            q.alpha = P.alpha;
-            q.ld_act = P.ld_act;
-            q.ld_wgt = P.ld_wgt;
-            q.ldL = P.ldL;
-            q.ldR = P.ldR;
-            q.ld_out = P.ld_out;
-            q.M = (int)P.M;
-            q.n_rows = P.n_rows;
-            q.K = P.act[0] ? P.K : 0;
-            q.seg_lo = P.L ? P.out[0].seg_lo : 0;
-            q.seg_hi = P.L ? P.out[0].seg_hi : 0;
+            if (P.out[0].ptr == nullptr) return;
             // tile width: 128 columns, or 192 when that saves residency rounds (512 workgroup slots at 128 columns, 2 per CU either way;
             // a 192-wide tile is 1.5x the work)
             const int64_t t128 = m_tiles * mtl_ceil_div(P.n_rows, 128), t192 = m_tiles * mtl_ceil_div(P.n_rows, 192);
             const int64_t slots = 2 * (int64_t)dev_num_cu();
             const double c128 = (double)mtl_ceil_div(t128, slots), c192 = 1.5 * (double)mtl_ceil_div(t192, slots);
-            const bool wide = !q.act2 && P.n_rows >= 192 && c192 < c128 - 0.01;
+            const bool wide = !P.out[0].act && P.n_rows >= 192 && c192 < c128 - 0.01;
             const int64_t nt = wide ? mtl_ceil_div(P.n_rows, 192) : n_tiles;
-            q.n_tiles = (int)nt;
-            q.nt_magic = (uint32_t)(((uint64_t)1 << 32) / (uint64_t)nt) + 1u;
-            const uint32_t nwg = (uint32_t)(m_tiles * nt);
-            q.q8 = nwg / 8u;
-            q.r8 = nwg % 8u;
-            q.act_mask = P.act_mask;
-            q.use_base = P.out[0].use_base;
-            q.dbg = P.dbg;
-            q.pad_ = 0;
-            q.drop = P.drop;
-            if (q.out == nullptr) return;
+            const NlParams q = make_nl(P, m_tiles, nt, false);
             const bool ml0 = P.out[0].mask_lr != 0 && P.drop.enabled() && q.seg_hi > q.seg_lo;
+            const uint32_t nwg = (uint32_t)(m_tiles * nt);
             constexpr size_t LDS192 = (size_t)(192 + 128) * LDSB;
 #define MTL_NTL_GO(AC, ML, SNV, LDSV)                                                         \
     do {                                                                                      \
@@ -1972,14 +595,6 @@ static unsigned sp_lin_grid(const Tune& tu, int parts, int n_slabs, int& xsh) {
     if (g > by_slabs) g = by_slabs;
     return (unsigned)(parts * g);
 }
-static int sp_stg_mode() {  // developer switch (ablation builds only): MTLORA_SP_STG=0 direct row-per-lane stores, 1 staged stores whenever they fit
-#if MTL_NT_ABLATE
-    static const int m = [] { const char* e = getenv("MTLORA_SP_STG"); return e ? atoi(e) : -1; }();
-    return m;
-#else
-    return -1;
-#endif
-}
 template <typename T>
 static bool sp_xres_plan(const Tune& tu, SpLinParams& q, int K, SpXresPlan& pl) {
     if (sizeof(T) != 2 || tu.sp == 0 || q.M <= 0 || q.M >= ((int64_t)1 << 31) - 64) return false;
@@ -2019,17 +634,13 @@ static bool sp_xres_plan(const Tune& tu, SpLinParams& q, int K, SpXresPlan& pl) 
     int bpp_d = 0, bpp_s = 0;
     size_t lds_d = 0, lds_s = 0;
     const int np_d = fit(false, bpp_d, lds_d), np_s = fit(true, bpp_s, lds_s);
-    const int mode = sp_stg_mode();
-    bool stg = np_s > 0 && (np_d == 0 || np_s <= np_d + 1);
-    if (mode == 0 && np_d > 0) stg = false;
-    if (mode == 1 && np_s > 0) stg = true;
+    const bool stg = np_s > 0 && (np_d == 0 || np_s <= np_d + 1);
     const int parts = stg ? np_s : np_d;
     if (parts == 0) return false;
     pl.stg = stg;
     q.blk_per_part = stg ? bpp_s : bpp_d;
     pl.lds = stg ? lds_s : lds_d;
     q.n_parts = parts;
-    q.dbg = ablate_bits("MTLORA_SP_DBG");
     q.n_slabs = (int)mtl_ceil_div(q.M, 32);
     pl.grid = sp_lin_grid(tu, parts, q.n_slabs, q.xsh);
     return true;
@@ -2119,7 +730,6 @@ static bool sp_ares_plan(const Tune& tu, SpLinParams& q, int Kred, SpAresPlan& p
     pl.lds = (size_t)need;
     q.n_parts = parts;
     q.blk_per_part = pl.nob;
-    q.dbg = ablate_bits("MTLORA_SP_DBG");
     q.n_slabs = (int)mtl_ceil_div(q.M, 32);
     pl.grid = sp_lin_grid(tu, parts, q.n_slabs, q.xsh);
     return true;
@@ -2329,6 +939,150 @@ static void launch_pack(const mtlora_linear_desc* d, const Segs& sg, const CtxLa
                        reinterpret_cast<T*>(pk + L.bt_proj), reinterpret_cast<T*>(pk + L.b_frag), reinterpret_cast<T*>(pk + L.at_frag));
 }
 
+// ---- the P / Q passes: Out[:, columns of source i] = alpha * f_i(Act_i) Wp^T   (P = alpha D(X) A^T per input, Q = alpha dY_o B_o per
+// output).  One source list feeds every kernel that can run them.
+struct ProjSrc {
+    const void* act;     // (M x K) contiguous
+    int col_lo, col_hi;  // columns of Out (rows of the factor) this source owns
+    int mask;            // dropout keep-mask on the activation
+};
+static SpProjParams make_sp_proj(const ProjSrc* src, int n_src, const void* wproj, void* out, const Segs& sg, int64_t M, int K,
+                                 const DropoutCfg& dc) {
+    SpProjParams sp = {};
+    sp.wproj = wproj;
+    sp.out = out;
+    sp.ld_out = sg.R;
+    sp.M = M;
+    sp.K = K;
+    sp.Rw = sg.R;
+    sp.drop = dc;
+    for (int i = 0; i < n_src; ++i) {
+        SpSrc& ss = sp.src[sp.n_src++];
+        ss.act = src[i].act;
+        ss.col_lo = src[i].col_lo;
+        ss.col_hi = src[i].col_hi;
+        ss.blk_lo = ss.col_lo / 32;
+        ss.n_blk = (ss.col_hi - 1) / 32 - ss.blk_lo + 1;
+        ss.mask = src[i].mask;
+    }
+    return sp;
+}
+// the factor side, the output and the profiler figures of one P / Q pass
+template <typename T>
+struct ProjJob {
+    const void* wproj;   // (R x K) alpha-scaled factor rows (a_proj / bt_proj): the wave-streaming kernels and k_pq
+    const T* wcat;       // the same rows unscaled ...
+    const float* alpha;  // ... and their per-row alpha: k_nt
+    T* out;              // (M x R)
+    int64_t M;
+    int K;
+    bool one_panel;      // k_nt takes the single source as ONE (M x R) panel (pad columns included) instead of the batched form
+    int kind;            // profiler kind
+    double alg_bytes, s8d, flops;
+};
+template <typename T>
+static void launch_proj(const Tune& tu, const Segs& sg, const DropoutCfg& dc, hipStream_t s, const ProjSrc* src, int n_src, const ProjJob<T>& j) {
+    if (n_src == 0) return;
+    // wave-streaming form (stream.h) when the alpha-scaled factor rows fit in LDS next to the slab ring
+    SpProjParams sp = make_sp_proj(src, n_src, j.wproj, j.out, sg, j.M, j.K, dc);
+    int ch = 0;
+    const int ns = sp_proj_plan<T>(tu, sp, ch);
+    PqParams pq = {};
+    const int mb = pq_plan<T>(tu, sp, pq);
+    // k_pq first: forced (3: the "[pq]" test family), instead of a one-slot k_sp_proj ring (which cannot overlap its loads), and
+    // instead of k_sp_proj for launches of about one residency round (tools/pq_times.py: stage 2 of Swin-T 13 vs 16 us, Swin-B 14
+    // vs 21 us); where k_sp_proj does not fit at all, k_sp_projk's single-round rule comes first (stage 3: 15 vs 21 us)
+    if (mb > 0 && (tu.projk == 3 || ns == 1 || (ns > 1 && pq_one_round(tu, pq, mb)))) {
+        launch_pq<T>(pq, mb, s, j.kind, j.alg_bytes, j.s8d, j.flops);
+    } else if (ns > 0) {
+        launch_sp_proj<T>(tu, sp, ch, ns, s, j.kind, j.alg_bytes, j.s8d, j.flops);
+    } else if (sp_projk_plan<T>(tu, sp, ch)) {
+        launch_sp_projk<T>(tu, sp, ch, s, j.kind, j.alg_bytes, j.s8d, j.flops);
+    } else if (mb > 0) {
+        launch_pq<T>(pq, mb, s, j.kind, j.alg_bytes, j.s8d, j.flops);
+    } else {
+        NtParams q = {};
+        q.n_act = 1;
+        q.ld_act = j.K;
+        q.wgt = j.wcat;
+        q.ld_wgt = j.K;
+        q.M = j.M;
+        q.K = j.K;
+        q.alpha = j.alpha;
+        q.n_out = 1;
+        q.out[0].ptr = j.out;
+        q.out[0].use_base = 1;
+        q.ld_out = sg.R;
+        q.drop = dc;
+        if (j.one_panel) {
+            q.act[0] = src[0].act;
+            q.act_mask = src[0].mask;
+            q.n_rows = sg.R;
+        } else {
+            for (int i = 0; i < n_src; ++i) {
+                q.zact[i] = src[i].act;
+                q.zrow0[i] = src[i].col_lo;
+                q.zrows[i] = src[i].col_hi - src[i].col_lo;
+                q.zmask[i] = src[i].mask;
+            }
+            q.nz = n_src;
+        }
+        launch_nt<T>(tu, q, s, j.kind, j.alg_bytes, j.s8d, j.flops);
+    }
+}
+
+// sum of the un-padded ranks: of every output, or of the outputs o with a gradient (live[o] != null)
+static double rank_sum(const Segs& sg, const void* const* live = nullptr) {
+    double rsum = 0.0;
+    for (int o = 0; o < sg.n; ++o)
+        if (!live || (sg.rp[o] > 0 && live[o])) rsum += sg.r[o];
+    return rsum;
+}
+// a T = 0 layer in ONE launch, either direction: 8(d) bytes (input + output) and the flops of the base GEMM and both rank GEMMs
+static double fused_bytes(const mtlora_linear_desc* d, int es) { return (double)es * d->M * (d->K + (double)d->N); }
+static double fused_flops(const mtlora_linear_desc* d, const Segs& sg) {
+    return 2.0 * d->M * (double)d->K * d->N + 2.0 * d->M * (double)sg.r[0] * (d->K + d->N);
+}
+
+// T = 0 layers: ONE wave-streaming launch (projection kept in registers, stream.h) instead of the P pass + the output launch
+template <typename T>
+static bool fwd_one_pass(const mtlora_linear_desc* d, const Tune& tu, const Segs& sg, const CtxLayout& L, const unsigned char* pk, const void* x,
+                         const void* W, const float* bias, void* y_s, void* a_s, T* Pm, const DropoutCfg& dc, hipStream_t s) {
+    SpLinParams q = {};
+    q.act = x;
+    q.w = W;
+    q.proj = pk + L.a_proj;
+    q.expand = pk + L.b_frag;
+    q.bias = bias;
+    q.out = y_s;
+    q.out2 = a_s;
+    q.pout = Pm;
+    q.ld_out = d->N;
+    q.ldp = sg.R;
+    q.M = d->M;
+    q.n_cols = (int)d->N;
+    q.R = sg.R;
+    q.mask_act = 1;
+    q.mask_lr = 0;
+    q.drop = dc;
+    SpXresPlan pl;
+    const double b8d = fused_bytes(d, (int)sizeof(T)), fl = fused_flops(d, sg);
+    // a short reduction: the activation-resident form
+    if (sp_xres_plan<T>(tu, q, (int)d->K, pl)) {
+        launch_sp_xres<T>(q, pl, a_s != nullptr, s, PK_NT_FWD_MAIN, b8d + (a_s ? (double)sizeof(T) * d->M * d->N : 0.0), b8d, fl);
+        return true;
+    }
+    // a long reduction into few output columns (the Mlp's fc2 at stage 0: 384 -> 96): the accumulator-resident form, whose
+    // projection sees the dropout-masked activation -- the P pass and its re-read of X disappear here too
+    SpAresPlan pa;
+    q.estep = q.estep2 = 0;
+    if (a_s == nullptr && sp_ares_plan<T>(tu, q, (int)d->K, pa)) {
+        launch_sp_ares<T>(q, pa, s, PK_NT_FWD_MAIN, b8d, b8d, fl);
+        return true;
+    }
+    return false;
+}
+
 template <typename T>
 static int fwd_impl(const mtlora_linear_desc* d, const void* x, const void* const* x_t, const void* W,
                     const float* bias, const float* A_s, const float* B_s, const float* const* A_t,
@@ -2341,133 +1095,39 @@ static int fwd_impl(const mtlora_linear_desc* d, const void* x, const void* cons
     unsigned char* pk = d->packed ? const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(d->packed)) : c;
     T* a_cat = reinterpret_cast<T*>(pk + L.a_cat);
     T* b_cat = reinterpret_cast<T*>(pk + L.b_cat);
-    T* at_cat = reinterpret_cast<T*>(pk + L.at_cat);
-    T* bt_cat = reinterpret_cast<T*>(pk + L.bt_cat);
     float* alpha = reinterpret_cast<float*>(pk + L.alpha);
-    (void)at_cat;
-    (void)bt_cat;
     T* Pm = reinterpret_cast<T*>(c + L.p);
     const DropoutCfg dc = mtl_make_dropout(d->dropout_p, d->seed, d->seed_offset);
 
     if (sg.R > 0) {
         if (!d->packed) launch_pack<T>(d, sg, L, pk, A_s, B_s, A_t, B_t, s);
+        if (d->T == 0 && d->mode == 0 && fwd_one_pass<T>(d, tu, sg, L, pk, x, W, bias, y_s, a_s, Pm, dc, s)) return MTLORA_OK;
 
-        // T = 0 layers with a short reduction: ONE wave-streaming launch (projection in registers, stream.h)
-        if (d->T == 0 && d->mode == 0) {
-            SpLinParams q = {};
-            q.act = x;
-            q.w = W;
-            q.proj = pk + L.a_proj;
-            q.expand = pk + L.b_frag;
-            q.bias = bias;
-            q.out = y_s;
-            q.out2 = a_s;
-            q.pout = Pm;
-            q.ld_out = d->N;
-            q.ldp = sg.R;
-            q.M = d->M;
-            q.n_cols = (int)d->N;
-            q.R = sg.R;
-            q.mask_act = 1;
-            q.mask_lr = 0;
-            q.drop = dc;
-            SpXresPlan pl;
-            const double b8d = (double)sizeof(T) * d->M * (d->K + (double)d->N);
-            const double fl = 2.0 * d->M * (double)d->K * d->N + 2.0 * d->M * (double)sg.r[0] * (d->K + d->N);
-            if (sp_xres_plan<T>(tu, q, (int)d->K, pl)) {
-                launch_sp_xres<T>(q, pl, a_s != nullptr, s, PK_NT_FWD_MAIN, b8d + (a_s ? (double)sizeof(T) * d->M * d->N : 0.0), b8d, fl);
-                return MTLORA_OK;
-            }
-            // a long reduction into few output columns (the Mlp's fc2 at stage 0: 384 -> 96): the accumulator-resident form, whose
-            // projection sees the dropout-masked activation -- the P pass and its re-read of X disappear here too
-            SpAresPlan pa;
-            q.estep = q.estep2 = 0;
-            if (a_s == nullptr && sp_ares_plan<T>(tu, q, (int)d->K, pa)) {
-                launch_sp_ares<T>(q, pa, s, PK_NT_FWD_MAIN, b8d, b8d, fl);
-                return MTLORA_OK;
-            }
+        // P = alpha * D(X) A^T  (per source: x for every column, or x / the tasks' own inputs for their segments)
+        const bool own = d->T > 0 && d->has_x_tasks;
+        ProjSrc src[MAXO];
+        int n_src = 0;
+        if (!own) src[n_src++] = ProjSrc{x, 0, sg.used, 1};
+        for (int o = 0; own && o < sg.n; ++o) {
+            if (sg.rp[o] == 0) continue;
+            if (o > 0 && (d->hid & MTLORA_HID_P_GIVEN)) continue;  // (task columns of P: mtlora_mlp_hid_proj wrote them)
+            src[n_src++] = ProjSrc{o == 0 ? x : x_t[o - 1], sg.off[o], sg.off[o] + sg.rp[o], o == 0 ? 1 : 0};
         }
-        {
-            // P = alpha * D(X) A^T  (per source)
-            NtParams q = {};
-            q.n_act = 1;
-            q.ld_act = d->K;
-            q.wgt = a_cat;
-            q.ld_wgt = d->K;
-            q.M = d->M;
-            q.K = (int)d->K;
-            q.alpha = alpha;
-            q.n_out = 1;
-            q.out[0].ptr = Pm;
-            q.out[0].use_base = 1;
-            q.ld_out = sg.R;
-            q.drop = dc;
-            if (d->T > 0 && d->has_x_tasks) {
-                q.nz = 0;
-                for (int o = 0; o < sg.n; ++o) {
-                    if (sg.rp[o] == 0) continue;
-                    if (o > 0 && (d->hid & MTLORA_HID_P_GIVEN)) continue;  // (task columns of P: mtlora_mlp_hid_proj wrote them)
-                    q.zact[q.nz] = (o == 0) ? x : x_t[o - 1];
-                    q.zrow0[q.nz] = sg.off[o];
-                    q.zrows[q.nz] = sg.rp[o];
-                    q.zmask[q.nz] = (o == 0) ? 1 : 0;
-                    ++q.nz;
-                }
-                q.n_rows = 0;
-            } else {
-                q.act[0] = x;
-                q.act_mask = 1;
-                q.n_rows = sg.R;
-                q.nz = 0;
-            }
-            {
-                // (HID_P_GIVEN: the tasks' own inputs are read -- implicitly -- by k_hid_proj, which carries their 8(d) bytes)
-                const double xb = (double)sizeof(T) * ((d->has_x_tasks && !(d->hid & MTLORA_HID_P_GIVEN)) ? d->T : 0) * d->M * d->K;
-                double rsum = 0.0;  // un-padded ranks
-                for (int o = 0; o < sg.n; ++o) rsum += sg.r[o];
-                // wave-streaming form (stream.h) when the alpha-scaled factor rows fit in LDS next to the slab ring
-                SpProjParams sp = {};
-                sp.wproj = pk + L.a_proj;
-                sp.out = Pm;
-                sp.ld_out = sg.R;
-                sp.M = d->M;
-                sp.K = (int)d->K;
-                sp.Rw = sg.R;
-                sp.drop = dc;
-                for (int o = 0; o < sg.n; ++o) {
-                    const bool own = d->T > 0 && d->has_x_tasks;
-                    if (!own && o > 0) break;
-                    if (own && sg.rp[o] == 0) continue;
-                    if (own && o > 0 && (d->hid & MTLORA_HID_P_GIVEN)) continue;
-                    SpSrc& ss = sp.src[sp.n_src++];
-                    ss.act = (o == 0) ? x : x_t[o - 1];
-                    ss.col_lo = own ? sg.off[o] : 0;
-                    ss.col_hi = own ? sg.off[o] + sg.rp[o] : sg.used;
-                    ss.blk_lo = ss.col_lo / 32;
-                    ss.n_blk = (ss.col_hi - 1) / 32 - ss.blk_lo + 1;
-                    ss.mask = (o == 0) ? 1 : 0;
-                }
-                int ch = 0;
-                const int ns = sp_proj_plan<T>(tu, sp, ch);
-                PqParams pq = {};
-                const int mb = pq_plan<T>(tu, sp, pq);
-                // k_pq first: forced (3: the "[pq]" test family), instead of a one-slot k_sp_proj ring (which cannot overlap its loads), and
-                // instead of k_sp_proj for launches of about one residency round (tools/pq_times.py: stage 2 of Swin-T 13 vs 16 us, Swin-B 14
-                // vs 21 us); where k_sp_proj does not fit at all, k_sp_projk's single-round rule comes first (stage 3: 15 vs 21 us)
-                if (sp.n_src == 0)
-                    ;  // (no source left: r_s = 0 and the task columns are given)
-                else if (mb > 0 && (tu.projk == 3 || ns == 1 || (ns > 1 && pq_one_round(tu, pq, mb))))
-                    launch_pq<T>(pq, mb, s, PK_NT_FWD_P, xb, xb, 2.0 * d->M * d->K * rsum);
-                else if (ns > 0)
-                    launch_sp_proj<T>(tu, sp, ch, ns, s, PK_NT_FWD_P, xb, xb, 2.0 * d->M * d->K * rsum);
-                else if (sp_projk_plan<T>(tu, sp, ch))
-                    launch_sp_projk<T>(tu, sp, ch, s, PK_NT_FWD_P, xb, xb, 2.0 * d->M * d->K * rsum);
-                else if (mb > 0)
-                    launch_pq<T>(pq, mb, s, PK_NT_FWD_P, xb, xb, 2.0 * d->M * d->K * rsum);
-                else
-                    launch_nt<T>(tu, q, s, PK_NT_FWD_P, xb, xb, 2.0 * d->M * d->K * rsum);
-            }
-        }
+        // (HID_P_GIVEN: the tasks' own inputs are read -- implicitly -- by k_hid_proj, which carries their 8(d) bytes)
+        const double xb = (double)sizeof(T) * ((d->has_x_tasks && !(d->hid & MTLORA_HID_P_GIVEN)) ? d->T : 0) * d->M * d->K;
+        // (n_src == 0: r_s = 0 and the task columns are given -- nothing to launch)
+        ProjJob<T> j = {};
+        j.wproj = pk + L.a_proj;
+        j.wcat = a_cat;
+        j.alpha = alpha;
+        j.out = Pm;
+        j.M = d->M;
+        j.K = (int)d->K;
+        j.one_panel = !own;
+        j.kind = PK_NT_FWD_P;
+        j.alg_bytes = j.s8d = xb;
+        j.flops = 2.0 * d->M * d->K * rank_sum(sg);
+        launch_proj<T>(tu, sg, dc, s, src, n_src, j);
     }
 
     // all outputs
@@ -2510,15 +1170,11 @@ static int fwd_impl(const mtlora_linear_desc* d, const void* x, const void* cons
     }
     int n_actout = 0;  // GELU second outputs: one more M x N write each
     for (int o = 0; o < m.n_out; ++o) n_actout += m.out[o].act ? 1 : 0;
-    {
-        const double b8d = (double)sizeof(T) * d->M * (d->K + (double)(1 + d->T) * d->N);  // (SURVEY 8(d) counts every module output)
-        double rsum = 0.0;
-        for (int o = 0; o < sg.n; ++o) rsum += sg.r[o];
-        const double fl = 2.0 * d->M * d->K * d->N + 2.0 * d->M * d->N * rsum;
-        const bool plain = sg.R == 0;
-        launch_nt<T>(tu, m, s, plain ? PK_NT_PLAIN_FWD : PK_NT_FWD_MAIN, b8d + (double)sizeof(T) * d->M * (double)n_actout * d->N,
-                     plain ? 0.0 : b8d, fl);
-    }
+    const double b8d = (double)sizeof(T) * d->M * (d->K + (double)(1 + d->T) * d->N);  // (SURVEY 8(d) counts every module output)
+    const double fl = 2.0 * d->M * d->K * d->N + 2.0 * d->M * d->N * rank_sum(sg);
+    const bool plain = sg.R == 0;
+    launch_nt<T>(tu, m, s, plain ? PK_NT_PLAIN_FWD : PK_NT_FWD_MAIN, b8d + (double)sizeof(T) * d->M * (double)n_actout * d->N,
+                 plain ? 0.0 : b8d, fl);
     return MTLORA_OK;
 }
 
@@ -2567,457 +1223,456 @@ static BwdScratch bwd_scratch(const mtlora_linear_desc* d, const Segs& sg) {
     return S;
 }
 
+// ---- backward: the state shared by its stages
+template <typename T>
+struct Bwd {
+    const mtlora_linear_desc* d;
+    Segs sg;
+    Tune tu;
+    CtxLayout L;
+    BwdScratch S;
+    hipStream_t s;
+    DropoutCfg dc;
+    const unsigned char* pk;  // packed factors
+    const T *at_cat, *bt_cat, *Pm;
+    const float* alpha;
+    T *Qm, *Gm;
+    float* part;
+    const void* x;
+    const void* const* x_t;
+    const void* Wt;
+    void* dx;
+    void* const* dx_t;
+    float *dA_s, *dB_s;
+    float* const* dA_t;
+    float* const* dB_t;
+    const void* gate_s;
+    const void* const* gate_t;
+    const void* dy[MAXO];      // gradient of output o (null: none)
+    const void* dy_all[MAXO];  // the n_dy gradients that exist
+    int n_dy;
+    const void* dyo[MAXO];     // gradient feeding factor o (matrixv2: the shared factors see G)
+    bool do_dx;                // (bwd_phase 2 re-derives the same operand table without the dX launches)
+    bool hid_q;                // fc1 of an Mlp with implicit task hiddens (hid.hip): Q task columns given
+    bool presum;               // the dX launch reads G instead of re-summing the n_dy sources
+    bool have_g;               // G is (to be) materialised in Gm
+    bool q_done;               // Q came out of the k_sp_projsum pass
+};
+
+// G = sum of every output gradient, materialised when
+//  * matrixv2: the shared factors see G, or
+//  * the dX kernel would otherwise re-sum the n_dy sources once per output n-tile (it re-reads every dY panel for
+//    each of the ceil(K/128) n-tiles: 3..24x for fc2): one k_sum pass + the single-source kernel moves
+//    (n_dy + 1 + n_tiles) MN bytes instead of n_dy * n_tiles * MN.
+// Fills dyo.
+template <typename T>
+static void bwd_grad_sum(Bwd<T>& b) {
+    const mtlora_linear_desc* d = b.d;
+    const Segs& sg = b.sg;
+    const bool v2 = d->mode == 1 && d->T > 0;
+    b.presum = b.n_dy > 1 && b.dx && mtl_ceil_div(d->K, TILE) >= 3;
+    b.have_g = false;
+    // layers with task outputs ('matrix' mode, every output has a gradient): ONE wave-streaming pass over the 1 + T gradient
+    // tensors forms Q (all segments) AND G = sum_o dY_o (k_sp_projsum, stream.h); the dX launch then reads G alone
+    b.q_done = false;
+    if constexpr (sizeof(T) == 2) {
+        if (d->T >= 1 && d->mode == 0 && b.do_dx && b.dx && b.n_dy == 1 + d->T && sg.rp[0] > 0 && sg.rp[0] <= 64) {
+            ProjSrc src[MAXO];
+            bool ok = true;
+            for (int o = 0; o < sg.n; ++o) {
+                if (sg.rp[o] == 0 || (o > 0 && sg.rp[o] > 32)) ok = false;
+                src[o] = ProjSrc{b.dy[o], sg.off[o], sg.off[o] + sg.rp[o], 0};
+            }
+            SpProjParams sp = make_sp_proj(src, sg.n, b.pk + b.L.bt_proj, b.Qm, sg, d->M, (int)d->N, b.dc);
+            for (int o = 1; o < sg.n; ++o)
+                if (sp.src[o].n_blk != 1) ok = false;
+            if (ok && sp.src[sp.n_src - 1].blk_lo - sp.src[1].blk_lo + 1 > SP_PS_MAXT) ok = false;  // task segments span too many blocks
+            int ch = 0;
+            const int ns = ok ? sp_proj_plan<T>(b.tu, sp, ch) : 0;
+            if (ns > 0 && d->M * d->N * 2 < ((int64_t)1 << 32) - 64) {
+                launch_sp_projsum<T>(b.tu, sp, ch, ns, b.Gm, b.s, PK_NT_BWD_Q, 0.0, 0.0, 2.0 * d->M * d->N * rank_sum(sg));
+                b.q_done = true;
+                b.presum = true;
+                b.have_g = true;
+            }
+        }
+    }
+    if ((v2 || b.presum) && b.n_dy > 1) b.have_g = true;
+    if (b.have_g && b.do_dx && !b.q_done) {
+        SumParams sp;
+        sp.n = b.n_dy;
+        for (int i = 0; i < b.n_dy; ++i) sp.src[i] = b.dy_all[i];
+        sp.nvec = d->M * d->N / ET<T>::VEC;
+        int64_t blocks = mtl_ceil_div(sp.nvec, 256);
+        if (blocks > 4096) blocks = 4096;
+        if (blocks > 0) {
+            MtlProfScope prof(PK_SUM, (double)sizeof(T) * d->M * d->N * (b.n_dy + 1), b.s);
+            hipLaunchKernelGGL(k_sum<T>, dim3((unsigned)blocks), dim3(256), 0, b.s, sp, b.Gm);
+        }
+    }
+    const void* dy_shared = b.dy[0];
+    if (v2 && b.n_dy > 0) dy_shared = b.have_g ? (const void*)b.Gm : b.dy_all[0];
+    for (int o = 0; o < sg.n; ++o) b.dyo[o] = (o == 0) ? dy_shared : b.dy[o];
+}
+
+// T = 0 layers: Q, the masked rank part and dY W in ONE wave-streaming pass over dY (stream.h); false: not eligible
+template <typename T>
+static bool bwd_one_pass(Bwd<T>& b) {
+    const mtlora_linear_desc* d = b.d;
+    const Segs& sg = b.sg;
+    if (!(d->T == 0 && d->mode == 0 && b.do_dx && b.dx && b.dyo[0] && sg.R > 0)) return false;
+    SpLinParams q = {};
+    q.act = b.dyo[0];
+    q.w = b.Wt;
+    q.proj = b.pk + b.L.bt_proj;
+    q.expand = b.pk + b.L.at_frag;
+    q.out = b.dx;
+    q.pout = b.Qm;
+    q.ld_out = d->K;
+    q.ldp = sg.R;
+    q.M = d->M;
+    q.n_cols = (int)d->K;
+    q.R = sg.R;
+    q.mask_act = 0;
+    q.mask_lr = 1;
+    q.drop = b.dc;
+    const double b8d = fused_bytes(d, (int)sizeof(T)), fl = fused_flops(d, sg);
+    // narrow input: the accumulator-resident form
+    SpAresPlan pl;
+    if (!b.gate_s && sp_ares_plan<T>(b.tu, q, (int)d->N, pl)) {
+        launch_sp_ares<T>(q, pl, b.s, PK_NT_BWD_DX, b8d, b8d, fl);
+        return true;
+    }
+    // wide input, short reduction (the Mlp's fc2: dX has 4 C columns, the reduction C <= 192): the activation-resident form,
+    // with the GELU' gate of the fused Mlp in its epilogue
+    SpXresPlan px;
+    q.gate = b.gate_s;
+    if (sp_xres_plan<T>(b.tu, q, (int)d->N, px)) {
+        launch_sp_xres<T>(q, px, false, b.s, PK_NT_BWD_DX, b8d + (b.gate_s ? (double)sizeof(T) * d->M * d->K : 0.0), b8d, fl, b.gate_s != nullptr);
+        return true;
+    }
+    return false;
+}
+
+// Q[:, seg_o] = alpha_o * dY_o B_o   (zero where the output got no gradient)
+template <typename T>
+static void bwd_q(Bwd<T>& b) {
+    const mtlora_linear_desc* d = b.d;
+    const Segs& sg = b.sg;
+    if (!(sg.R > 0 && b.do_dx && !b.q_done)) return;
+    bool any_missing = false;
+    ProjSrc src[MAXO];
+    int n_src = 0;
+    for (int o = 0; o < sg.n; ++o) {
+        if (sg.rp[o] == 0) continue;
+        if (!b.dyo[o]) {
+            any_missing = true;
+            continue;
+        }
+        src[n_src++] = ProjSrc{b.dyo[o], sg.off[o], sg.off[o] + sg.rp[o], 0};
+    }
+    if (any_missing && !b.hid_q) mtl_zero_async(b.Qm, (size_t)(d->M * sg.R * sizeof(T)), b.s);  // (hid_q: the task columns are given)
+    if (n_src > 0) {
+        ProjJob<T> j = {};
+        j.wproj = b.pk + b.L.bt_proj;
+        j.wcat = b.bt_cat;
+        j.alpha = b.alpha;
+        j.out = b.Qm;
+        j.M = d->M;
+        j.K = (int)d->N;
+        j.kind = PK_NT_BWD_Q;
+        j.flops = 2.0 * d->M * d->N * rank_sum(sg, b.dyo);
+        launch_proj<T>(b.tu, sg, b.dc, b.s, src, n_src, j);
+    }
+}
+
+// dX = G W + keep .* (Q_s A_s [+ sum_t Q_t A_t]),  dX_t = Q_t A_t
+template <typename T>
+static void bwd_dx(Bwd<T>& b) {
+    const mtlora_linear_desc* d = b.d;
+    const Segs& sg = b.sg;
+    const Tune& tu = b.tu;
+    hipStream_t s = b.s;
+    void* const* dx_t = b.dx_t;
+    const void* const* gate_t = b.gate_t;
+    if (!b.do_dx) return;
+    NtParams m = {};
+    RankOutParams rank_out = {};
+    int rank_out_rp = 8;
+    bool rank_out_gated = false;
+    if (b.presum && b.have_g) {
+        m.n_act = 1;
+        m.act[0] = b.Gm;
+    } else {
+        m.n_act = b.n_dy;
+        for (int i = 0; i < b.n_dy; ++i) m.act[i] = b.dy_all[i];
+    }
+    if (b.hid_q && d->hid_ptr) {  // G = dH_s + sum_t dH_t was formed by k_hid_bwd
+        m.n_act = 1;
+        m.act[0] = d->hid_ptr;
+    }
+    m.ld_act = d->N;
+    m.wgt = b.Wt;
+    m.ld_wgt = d->N;
+    m.M = d->M;
+    m.n_rows = (int)d->K;
+    m.K = (b.n_dy > 0 || (b.hid_q && d->hid_ptr)) ? (int)d->N : 0;
+    m.L = b.Qm;
+    m.ldL = sg.R;
+    m.Rm = b.at_cat;
+    m.ldR = sg.R;
+    m.ld_out = d->K;
+    m.drop = b.dc;
+    m.n_out = 1;
+    NtOut& O = m.out[0];
+    O.ptr = b.dx;
+    O.use_base = 1;
+    O.mask_lr = 1;
+    O.gate = b.gate_s;
+    if (d->T > 0 && d->has_x_tasks) {
+        O.seg_lo = sg.off[0];
+        O.seg_hi = sg.off[0] + sg.rp[0];
+        // small task ranks: the task outputs are a streaming elementwise kernel of their own (k_rank_out), not tile passes
+        if constexpr (sizeof(T) == 2) {
+            bool ok = tu.sp != 0 && dx_t != nullptr && d->K % 8 == 0 && d->K / 8 <= 256 && d->M > 0;
+            int rpm = 0, gates = 0, outs = 0;
+            for (int t = 0; t < d->T; ++t) {
+                if (!dx_t || !dx_t[t]) continue;
+                ++outs;
+                rpm = sg.rp[t + 1] > rpm ? sg.rp[t + 1] : rpm;
+                gates += (gate_t && gate_t[t]) ? 1 : 0;
+                ok = ok && sg.rp[t + 1] > 0 && !misaligned(dx_t[t]) && !(gate_t && gate_t[t] && misaligned(gate_t[t]));
+            }
+            for (int t = 0; t < d->T; ++t)
+                if (dx_t && dx_t[t]) ok = ok && sg.rp[t + 1] == rpm;  // one register geometry per launch
+            ok = ok && outs > 0 && rpm <= 16 && (gates == 0 || gates == outs) && !misaligned(b.Qm) && (sg.R % 8) == 0;
+            if (ok) {
+                rank_out.Q = b.Qm;
+                rank_out.Acat = b.pk + b.L.a_cat;
+                rank_out.ldq = sg.R;
+                rank_out.M = d->M;
+                rank_out.K = (int)d->K;
+                for (int t = 0; t < d->T; ++t) {
+                    if (!dx_t[t]) continue;
+                    const int i = rank_out.n_t++;
+                    rank_out.seg[i] = sg.off[t + 1];
+                    rank_out.rp[i] = sg.rp[t + 1];
+                    rank_out.out[i] = dx_t[t];
+                    rank_out.gate[i] = gate_t ? gate_t[t] : nullptr;
+                }
+                rank_out_rp = rpm <= 8 ? 8 : 16;
+                rank_out_gated = gates > 0;
+            }
+        }
+        for (int t = 0; t < d->T && rank_out.n_t == 0; ++t) {
+            if (!dx_t || !dx_t[t]) continue;
+            NtOut& Ot = m.out[m.n_out++];
+            Ot.ptr = dx_t[t];
+            Ot.seg_lo = sg.off[t + 1];
+            Ot.seg_hi = sg.off[t + 1] + sg.rp[t + 1];
+            Ot.use_base = 0;
+            Ot.mask_lr = 0;
+            Ot.fold = 0;
+            Ot.gate = gate_t ? gate_t[t] : nullptr;
+        }
+    } else {
+        O.seg_lo = 0;
+        O.seg_hi = sg.used;  // (not R: the Q pass writes segments only, the pad columns of Q hold whatever the scratch held)
+    }
+    if (b.dx) {
+        int n_gate = 0;  // the fused GELU backward reads the pre-activation of every gated output (algorithmic: gelu'(h) needs h)
+        for (int o = 0; o < m.n_out; ++o) n_gate += m.out[o].gate ? 1 : 0;
+        const int n_xt = rank_out.n_t > 0 ? 0 : (d->has_x_tasks ? d->T : 0);  // task outputs written by THIS launch
+        const double b8d = (double)sizeof(T) * d->M * ((double)b.n_dy * d->N + (double)(1 + n_xt) * d->K);
+        const double fl = (b.n_dy > 0 ? 2.0 * d->M * d->N * d->K : 0.0) + 2.0 * d->M * d->K * rank_sum(sg, b.dyo);
+        const bool plain = sg.R == 0;
+        launch_nt<T>(tu, m, s, plain ? PK_NT_PLAIN_DX : PK_NT_BWD_DX, b8d + (double)sizeof(T) * d->M * (double)n_gate * d->K,
+                     plain ? 0.0 : b8d, fl);
+    }
+    if constexpr (sizeof(T) == 2) {
+        if (rank_out.n_t > 0) {
+            const double ob = (double)sizeof(T) * d->M * (double)rank_out.n_t * d->K;
+            mtl_prof_tag("rank_out M%lld K%lld nt%d rp%d gate%d", (long long)d->M, (long long)d->K, rank_out.n_t, rank_out_rp, rank_out_gated ? 1 : 0);
+            MtlProfScope prof(PK_NT_BWD_DX, ob * (rank_out_gated ? 2.0 : 1.0), s, ob, 0.0);
+            const int nchunk = (int)(d->K / 8), rpb = 256 / nchunk;
+            int64_t bx = mtl_ceil_div(d->M, (int64_t)rpb * 4);
+            const int64_t cap = (int64_t)num_cu(tu) * 8 / rank_out.n_t > 0 ? (int64_t)num_cu(tu) * 8 / rank_out.n_t : 1;
+            if (bx > cap) bx = cap;
+            const dim3 g((unsigned)bx, (unsigned)rank_out.n_t);
+            if (rank_out_gated && rank_out_rp == 8)
+                hipLaunchKernelGGL((k_rank_out<T, true, 8>), g, dim3(256), 0, s, rank_out);
+            else if (rank_out_gated)
+                hipLaunchKernelGGL((k_rank_out<T, true, 16>), g, dim3(256), 0, s, rank_out);
+            else if (rank_out_rp == 8)
+                hipLaunchKernelGGL((k_rank_out<T, false, 8>), g, dim3(256), 0, s, rank_out);
+            else
+                hipLaunchKernelGGL((k_rank_out<T, false, 16>), g, dim3(256), 0, s, rank_out);
+        }
+    }
+}
+
+// one factor-gradient problem  out (out_a x Nb) = A[:, a0 .. a0 + Na)^T B   (B is M x Nb, contiguous rows), stored transposed or not
+static void add_tn_problem(TnParams& tp, float*& part, int nsplit, const void* A, int64_t lda, int a0, int Na, const void* B, int Nb, int b_mask,
+                           float* out, int out_a, int ldo, int transpose) {
+    TnProblem& p = tp.p[tp.n_prob++];
+    p.A = A;
+    p.lda = lda;
+    p.a0 = a0;
+    p.Na = Na;
+    p.B = B;
+    p.ldb = Nb;
+    p.b0 = 0;
+    p.Nb = Nb;
+    p.b_mask = b_mask;
+    p.tiles_a = (int)mtl_ceil_div(p.Na, TN_A);
+    p.tiles_b = (int)mtl_ceil_div(p.Nb, TN_B);
+    p.part = part;
+    part += (int64_t)p.tiles_a * p.tiles_b * nsplit * TN_TILE;
+    p.out = out;
+    p.out_a = out_a;
+    p.out_b = Nb;
+    p.ldo = ldo;
+    p.transpose = transpose;
+}
+// the same problems as the wave-streaming kernel's table (k_sp_tn, nb 32-column blocks per part); false: a problem does not fit its rules
+static bool sp_tn_table(const TnParams& tp, int nb, SpTnParams& q) {
+    bool ok = nb != 0 && tp.n_prob > 0;
+    for (int i = 0; ok && i < tp.n_prob; ++i) {
+        const TnProblem& p = tp.p[i];
+        SpTnProb& r = q.p[i];
+        ok = ok && p.b0 == 0 && p.Nb == p.ldb && p.Nb % (32 * nb) == 0 && !misaligned(p.A) && !misaligned(p.B) && (p.lda % 8) == 0 &&
+             (p.a0 % 8) == 0;
+        r.A = p.A;
+        r.B = p.B;
+        r.lda = p.lda;
+        r.ldb = p.ldb;
+        r.a0 = p.a0;
+        r.Na = p.Na;
+        r.Nb = p.Nb;
+        r.b_mask = p.b_mask;
+        r.tiles_a = (int)mtl_ceil_div(p.Na, 64);
+        r.parts = p.Nb / (32 * nb);
+        r.pp_lo = q.n_pp;
+        r.transpose = p.transpose;
+        r.out = p.out;
+        r.out_a = p.out_a;
+        r.out_b = p.out_b;
+        r.ldo = p.ldo;
+        q.n_pp += r.tiles_a * r.parts;
+    }
+    return ok;
+}
+
+// dA_o = Q_o^T D(X_o),  dB_o = dY_o^T P_o
+template <typename T>
+static void bwd_factors(Bwd<T>& b) {
+    const mtlora_linear_desc* d = b.d;
+    const Segs& sg = b.sg;
+    const Tune& tu = b.tu;
+    const BwdScratch& S = b.S;
+    hipStream_t s = b.s;
+    if (sg.R == 0) return;
+    TnParams tp = {};
+    tp.M = d->M;
+    tp.nsplit = S.nsplit;
+    tp.rows_per_split = S.rows_per_split;
+    tp.drop = b.dc;
+    float* pp = b.part;
+    for (int o = 0; o < sg.n; ++o) {
+        const bool q_given = b.hid_q && o > 0;  // Q[:, seg_o] came from k_hid_bwd (which also returns dB_o): dA_o only
+        if (sg.rp[o] == 0 || (!b.dyo[o] && !q_given)) continue;
+        float* dAo = (o == 0) ? b.dA_s : (b.dA_t ? b.dA_t[o - 1] : nullptr);
+        float* dBo = (o == 0) ? b.dB_s : (b.dB_t ? b.dB_t[o - 1] : nullptr);
+        if (!b.dyo[o]) dBo = nullptr;
+        // (N x r_o) = dY_o^T P[:, seg_o], evaluated as its transpose P[:, seg_o]^T dY_o
+        if (dBo) add_tn_problem(tp, pp, S.nsplit, b.Pm, sg.R, sg.off[o], sg.rp[o], b.dyo[o], (int)d->N, 0, dBo, sg.r[o], sg.r[o], 1);
+        // (r_o x K) = Q[:, seg_o]^T . D(X_o)
+        const bool own_x = (o > 0 && d->has_x_tasks);
+        if (dAo) add_tn_problem(tp, pp, S.nsplit, b.Qm, sg.R, sg.off[o], sg.rp[o], own_x ? b.x_t[o - 1] : b.x, (int)d->K, own_x ? 0 : 1, dAo, sg.r[o], (int)d->K, 0);
+    }
+    int max_tiles = 0;
+    double fl = 0.0;
+    for (int i = 0; i < tp.n_prob; ++i) {
+        max_tiles = std::max(max_tiles, tp.p[i].tiles_a * tp.p[i].tiles_b);
+        fl += 2.0 * d->M * (double)tp.p[i].out_a * tp.p[i].out_b;
+    }
+    const double xb = (double)sizeof(T) * d->M * (double)(1 + (d->has_x_tasks ? d->T : 0)) * d->K;
+    if constexpr (sizeof(T) == 2) {
+        const int nb = (tu.sp != 0 && tu.tn != 0) ? sp_tn_nb(d) : 0;
+        SpTnParams q = {};
+        bool ok = sp_tn_table(tp, nb, q);
+        if (ok) {
+            const int mode = tu.tn;
+            q.n_prob = tp.n_prob;
+            q.G = sp_tn_groups(tu, q.n_pp, d->M);
+            ok = q.n_pp <= SP_TN_WGS && q.G < 65536 && (mode == 2 || (mode == 1 && mtl_ceil_div(d->M, 32) >= (int64_t)8 * q.G * SP_WAVES));
+            if (ok) {
+                SpTnParams probe = q;
+                ok = sp_tn_map(probe) != 0;
+                q.G = probe.G;
+            }
+        }
+        if (ok) {
+            q.M = d->M;
+            q.part = b.part;
+            q.drop = b.dc;
+            char tag[96];
+            snprintf(tag, sizeof(tag), "M%lld K%lld N%lld T%d", (long long)d->M, (long long)d->K, (long long)d->N, d->T);
+            launch_sp_tn<T>(q, nb, s, xb, fl, tag);
+            return;
+        }
+    }
+    if (tp.n_prob > 0 && d->M > 0) {
+        {
+            mtl_prof_tag("M%lld K%lld N%lld T%d np%d ns%d tiles%d", (long long)d->M, (long long)d->K, (long long)d->N, d->T, tp.n_prob,
+                         S.nsplit, max_tiles);
+            MtlProfScope prof(PK_TN, xb, s, xb, fl);
+            hipLaunchKernelGGL(k_tn<T>, dim3((unsigned)S.nsplit, (unsigned)max_tiles, (unsigned)tp.n_prob),
+                               dim3(256), 0, s, tp);
+        }
+        MtlProfScope prof(PK_REDUCE, 0.0, s);
+        hipLaunchKernelGGL(k_tn_reduce, dim3(TN_TILE / 1024, (unsigned)max_tiles, (unsigned)tp.n_prob), dim3(256 * TN_RG), 0, s, tp);
+    }
+}
+
 template <typename T>
 static int bwd_impl(const mtlora_linear_desc* d, const void* x, const void* const* x_t, const void* Wt,
                     const void* dy_s, const void* const* dy_t, const void* ctx, void* dx, void* const* dx_t,
                     float* dA_s, float* dB_s, float* const* dA_t, float* const* dB_t, void* scratch, hipStream_t s,
                     const void* gate_s = nullptr, const void* const* gate_t = nullptr) {
-    const Segs sg = make_segs(d);
-    const Tune tu = make_tune(d);
-    const CtxLayout L = ctx_layout(d, sg);
-    const BwdScratch S = bwd_scratch(d, sg);
+    Bwd<T> b = {};
+    b.d = d;
+    b.sg = make_segs(d);
+    b.tu = make_tune(d);
+    b.L = ctx_layout(d, b.sg);
+    b.S = bwd_scratch(d, b.sg);
+    b.s = s;
+    b.dc = mtl_make_dropout(d->dropout_p, d->seed, d->seed_offset);
     const unsigned char* c = reinterpret_cast<const unsigned char*>(ctx);
-    const unsigned char* pk = d->packed ? reinterpret_cast<const unsigned char*>(d->packed) : c;
-    const T* at_cat = reinterpret_cast<const T*>(pk + L.at_cat);
-    const T* bt_cat = reinterpret_cast<const T*>(pk + L.bt_cat);
-    const float* alpha = reinterpret_cast<const float*>(pk + L.alpha);
-    const T* Pm = reinterpret_cast<const T*>(c + L.p);
     unsigned char* sc = reinterpret_cast<unsigned char*>(scratch);
-    T* Qm = reinterpret_cast<T*>(sc + S.q);
-    T* Gm = reinterpret_cast<T*>(sc + S.g);
-    float* part = reinterpret_cast<float*>(sc + S.part);
-    const DropoutCfg dc = mtl_make_dropout(d->dropout_p, d->seed, d->seed_offset);
-    const bool v2 = d->mode == 1 && d->T > 0;
-    const bool hid_q = (d->hid & MTLORA_HID_Q_GIVEN) != 0;  // fc1 of an Mlp with implicit task hiddens (hid.hip): Q task columns given
+    b.pk = d->packed ? reinterpret_cast<const unsigned char*>(d->packed) : c;
+    b.at_cat = reinterpret_cast<const T*>(b.pk + b.L.at_cat), b.bt_cat = reinterpret_cast<const T*>(b.pk + b.L.bt_cat);
+    b.alpha = reinterpret_cast<const float*>(b.pk + b.L.alpha);
+    b.Pm = reinterpret_cast<const T*>(c + b.L.p);
+    b.Qm = reinterpret_cast<T*>(sc + b.S.q), b.Gm = reinterpret_cast<T*>(sc + b.S.g);
+    b.part = reinterpret_cast<float*>(sc + b.S.part);
+    b.x = x, b.x_t = x_t, b.Wt = Wt;
+    b.dx = dx, b.dx_t = dx_t;
+    b.dA_s = dA_s, b.dB_s = dB_s, b.dA_t = dA_t, b.dB_t = dB_t;
+    b.gate_s = gate_s, b.gate_t = gate_t;
+    b.do_dx = d->bwd_phase != 2;
+    b.hid_q = (d->hid & MTLORA_HID_Q_GIVEN) != 0;
+    b.dy[0] = dy_s;
+    for (int t = 0; t < d->T; ++t) b.dy[t + 1] = dy_t ? dy_t[t] : nullptr;
+    for (int o = 0; o < b.sg.n; ++o)
+        if (b.dy[o]) b.dy_all[b.n_dy++] = b.dy[o];
 
-    // gradient sources per output
-    const void* dy[MAXO];
-    dy[0] = dy_s;
-    for (int t = 0; t < d->T; ++t) dy[t + 1] = dy_t ? dy_t[t] : nullptr;
-    int n_dy = 0;
-    const void* dy_all[MAXO];
-    for (int o = 0; o < sg.n; ++o)
-        if (dy[o]) dy_all[n_dy++] = dy[o];
-
-    // G = sum of every output gradient, materialised when
-    //  * matrixv2: the shared factors see G, or
-    //  * the dX kernel would otherwise re-sum the n_dy sources once per output n-tile (it re-reads every dY panel for
-    //    each of the ceil(K/128) n-tiles: 3..24x for fc2): one k_sum pass + the single-source kernel moves
-    //    (n_dy + 1 + n_tiles) MN bytes instead of n_dy * n_tiles * MN.
-    const void* dy_shared = dy[0];
-    const bool do_dx = d->bwd_phase != 2, do_factors = d->bwd_phase != 1;  // (phase 2 re-derives the same operand table)
-    bool presum = n_dy > 1 && dx && mtl_ceil_div(d->K, TILE) >= 3;
-    bool have_g = false;
-    // layers with task outputs ('matrix' mode, every output has a gradient): ONE wave-streaming pass over the 1 + T gradient
-    // tensors forms Q (all segments) AND G = sum_o dY_o (k_sp_projsum, stream.h); the dX launch then reads G alone
-    bool q_done = false;
-    if constexpr (sizeof(T) == 2) {
-        if (d->T >= 1 && d->mode == 0 && do_dx && dx && n_dy == 1 + d->T && sg.rp[0] > 0 && sg.rp[0] <= 64) {
-            SpProjParams sp = {};
-            sp.wproj = pk + L.bt_proj;
-            sp.out = Qm;
-            sp.ld_out = sg.R;
-            sp.M = d->M;
-            sp.K = (int)d->N;
-            sp.Rw = sg.R;
-            sp.drop = dc;
-            bool ok = true;
-            for (int o = 0; o < sg.n; ++o) {
-                if (sg.rp[o] == 0 || (o > 0 && sg.rp[o] > 32)) ok = false;
-                SpSrc& ss = sp.src[sp.n_src++];
-                ss.act = dy[o];
-                ss.col_lo = sg.off[o];
-                ss.col_hi = sg.off[o] + sg.rp[o];
-                ss.blk_lo = ss.col_lo / 32;
-                ss.n_blk = (ss.col_hi - 1) / 32 - ss.blk_lo + 1;
-                ss.mask = 0;
-                if (o > 0 && ss.n_blk != 1) ok = false;
-            }
-            if (ok && sp.src[sp.n_src - 1].blk_lo - sp.src[1].blk_lo + 1 > SP_PS_MAXT) ok = false;  // task segments span too many blocks
-            int ch = 0;
-            const int ns = ok ? sp_proj_plan<T>(tu, sp, ch) : 0;
-            if (ns > 0 && d->M * d->N * 2 < ((int64_t)1 << 32) - 64) {
-                double rsum = 0.0;
-                for (int o = 0; o < sg.n; ++o) rsum += sg.r[o];
-                launch_sp_projsum<T>(tu, sp, ch, ns, Gm, s, PK_NT_BWD_Q, 0.0, 0.0, 2.0 * d->M * d->N * rsum);
-                q_done = true;
-                presum = true;
-                have_g = true;
-            }
-        }
+    bwd_grad_sum(b);
+    if (!bwd_one_pass(b)) {
+        bwd_q(b);
+        bwd_dx(b);
     }
-    if ((v2 || presum) && n_dy > 1) {
-        have_g = true;
-    }
-    if (have_g && do_dx && !q_done) {
-        SumParams sp;
-        sp.n = n_dy;
-        for (int i = 0; i < n_dy; ++i) sp.src[i] = dy_all[i];
-        sp.nvec = d->M * d->N / ET<T>::VEC;
-        int64_t blocks = mtl_ceil_div(sp.nvec, 256);
-        if (blocks > 4096) blocks = 4096;
-        if (blocks > 0) {
-            MtlProfScope prof(PK_SUM, (double)sizeof(T) * d->M * d->N * (n_dy + 1), s);
-            hipLaunchKernelGGL(k_sum<T>, dim3((unsigned)blocks), dim3(256), 0, s, sp, Gm);
-        }
-    }
-    if (v2 && n_dy > 0) dy_shared = have_g ? (const void*)Gm : dy_all[0];
-    const void* dyo[MAXO];  // gradient feeding factor o
-    for (int o = 0; o < sg.n; ++o) dyo[o] = (o == 0) ? dy_shared : dy[o];
-
-    // T = 0 layers whose input is narrow: Q, the masked rank part and dY W in ONE wave-streaming pass over dY (stream.h)
-    bool sp_dx_done = false;
-    if (d->T == 0 && d->mode == 0 && do_dx && dx && dyo[0] && sg.R > 0) {
-        SpLinParams q = {};
-        q.act = dyo[0];
-        q.w = Wt;
-        q.proj = pk + L.bt_proj;
-        q.expand = pk + L.at_frag;
-        q.out = dx;
-        q.pout = Qm;
-        q.ld_out = d->K;
-        q.ldp = sg.R;
-        q.M = d->M;
-        q.n_cols = (int)d->K;
-        q.R = sg.R;
-        q.mask_act = 0;
-        q.mask_lr = 1;
-        q.drop = dc;
-        const double b8d = (double)sizeof(T) * d->M * ((double)d->N + d->K);
-        const double fl = 2.0 * d->M * (double)d->N * d->K + 2.0 * d->M * (double)sg.r[0] * (d->K + d->N);
-        SpAresPlan pl;
-        SpXresPlan px;
-        if (!gate_s && sp_ares_plan<T>(tu, q, (int)d->N, pl)) {
-            launch_sp_ares<T>(q, pl, s, PK_NT_BWD_DX, b8d, b8d, fl);
-            sp_dx_done = true;
-        } else {
-            // wide input, short reduction (the Mlp's fc2: dX has 4 C columns, the reduction C <= 192): the activation-resident form,
-            // with the GELU' gate of the fused Mlp in its epilogue
-            q.gate = gate_s;
-            if (sp_xres_plan<T>(tu, q, (int)d->N, px)) {
-                launch_sp_xres<T>(q, px, false, s, PK_NT_BWD_DX, b8d + (gate_s ? (double)sizeof(T) * d->M * d->K : 0.0), b8d, fl, gate_s != nullptr);
-                sp_dx_done = true;
-            }
-            q.gate = nullptr;
-        }
-    }
-
-    // Q[:, seg_o] = alpha_o * dY_o B_o   (zero where the output got no gradient)
-    if (sg.R > 0 && do_dx && !sp_dx_done && !q_done) {
-        bool any_missing = false;
-        for (int o = 0; o < sg.n; ++o)
-            if (sg.rp[o] > 0 && !dyo[o]) any_missing = true;
-        if (any_missing && !hid_q) mtl_zero_async(Qm, (size_t)(d->M * sg.R * sizeof(T)), s);  // (hid_q: the task columns are given)
-        NtParams q = {};
-        q.n_act = 1;
-        q.ld_act = d->N;
-        q.wgt = bt_cat;
-        q.ld_wgt = d->N;
-        q.M = d->M;
-        q.K = (int)d->N;
-        q.alpha = alpha;
-        q.n_out = 1;
-        q.out[0].ptr = Qm;
-        q.out[0].use_base = 1;
-        q.ld_out = sg.R;
-        q.drop = dc;
-        q.nz = 0;
-        for (int o = 0; o < sg.n; ++o) {
-            if (sg.rp[o] == 0 || !dyo[o]) continue;
-            q.zact[q.nz] = dyo[o];
-            q.zrow0[q.nz] = sg.off[o];
-            q.zrows[q.nz] = sg.rp[o];
-            q.zmask[q.nz] = 0;
-            ++q.nz;
-        }
-        if (q.nz > 0) {
-            double rsum = 0.0;
-            for (int o = 0; o < sg.n; ++o)
-                if (sg.rp[o] > 0 && dyo[o]) rsum += sg.r[o];
-            SpProjParams sp = {};
-            sp.wproj = pk + L.bt_proj;
-            sp.out = Qm;
-            sp.ld_out = sg.R;
-            sp.M = d->M;
-            sp.K = (int)d->N;
-            sp.Rw = sg.R;
-            sp.drop = dc;
-            for (int o = 0; o < sg.n; ++o) {
-                if (sg.rp[o] == 0 || !dyo[o]) continue;
-                SpSrc& ss = sp.src[sp.n_src++];
-                ss.act = dyo[o];
-                ss.col_lo = sg.off[o];
-                ss.col_hi = sg.off[o] + sg.rp[o];
-                ss.blk_lo = ss.col_lo / 32;
-                ss.n_blk = (ss.col_hi - 1) / 32 - ss.blk_lo + 1;
-                ss.mask = 0;
-            }
-            int ch = 0;
-            const int ns = sp_proj_plan<T>(tu, sp, ch);
-            PqParams pq = {};
-            const int mb = pq_plan<T>(tu, sp, pq);
-            if (mb > 0 && (tu.projk == 3 || ns == 1 || (ns > 1 && pq_one_round(tu, pq, mb))))
-                launch_pq<T>(pq, mb, s, PK_NT_BWD_Q, 0.0, 0.0, 2.0 * d->M * d->N * rsum);
-            else if (ns > 0)
-                launch_sp_proj<T>(tu, sp, ch, ns, s, PK_NT_BWD_Q, 0.0, 0.0, 2.0 * d->M * d->N * rsum);
-            else if (sp_projk_plan<T>(tu, sp, ch))
-                launch_sp_projk<T>(tu, sp, ch, s, PK_NT_BWD_Q, 0.0, 0.0, 2.0 * d->M * d->N * rsum);
-            else if (mb > 0)
-                launch_pq<T>(pq, mb, s, PK_NT_BWD_Q, 0.0, 0.0, 2.0 * d->M * d->N * rsum);
-            else
-                launch_nt<T>(tu, q, s, PK_NT_BWD_Q, 0.0, 0.0, 2.0 * d->M * d->N * rsum);
-        }
-    }
-
-    // dX = G W + keep .* (Q_s A_s [+ sum_t Q_t A_t]),  dX_t = Q_t A_t
-    if (do_dx && !sp_dx_done) {
-        NtParams m = {};
-        RankOutParams rank_out = {};
-        int rank_out_rp = 8;
-        bool rank_out_gated = false;
-        if (presum && have_g) {
-            m.n_act = 1;
-            m.act[0] = Gm;
-        } else {
-            m.n_act = n_dy;
-            for (int i = 0; i < n_dy; ++i) m.act[i] = dy_all[i];
-        }
-        if (hid_q && d->hid_ptr) {  // G = dH_s + sum_t dH_t was formed by k_hid_bwd
-            m.n_act = 1;
-            m.act[0] = d->hid_ptr;
-        }
-        m.ld_act = d->N;
-        m.wgt = Wt;
-        m.ld_wgt = d->N;
-        m.M = d->M;
-        m.n_rows = (int)d->K;
-        m.K = (n_dy > 0 || (hid_q && d->hid_ptr)) ? (int)d->N : 0;
-        m.L = Qm;
-        m.ldL = sg.R;
-        m.Rm = at_cat;
-        m.ldR = sg.R;
-        m.ld_out = d->K;
-        m.drop = dc;
-        m.n_out = 1;
-        NtOut& O = m.out[0];
-        O.ptr = dx;
-        O.use_base = 1;
-        O.mask_lr = 1;
-        O.gate = gate_s;
-        if (d->T > 0 && d->has_x_tasks) {
-            O.seg_lo = sg.off[0];
-            O.seg_hi = sg.off[0] + sg.rp[0];
-            // small task ranks: the task outputs are a streaming elementwise kernel of their own (k_rank_out), not tile passes
-            if constexpr (sizeof(T) == 2) {
-                bool ok = tu.sp != 0 && dx_t != nullptr && d->K % 8 == 0 && d->K / 8 <= 256 && d->M > 0;
-                int rpm = 0, gates = 0, outs = 0;
-                for (int t = 0; t < d->T; ++t) {
-                    if (!dx_t || !dx_t[t]) continue;
-                    ++outs;
-                    rpm = sg.rp[t + 1] > rpm ? sg.rp[t + 1] : rpm;
-                    gates += (gate_t && gate_t[t]) ? 1 : 0;
-                    ok = ok && sg.rp[t + 1] > 0 && !misaligned(dx_t[t]) && !(gate_t && gate_t[t] && misaligned(gate_t[t]));
-                }
-                for (int t = 0; t < d->T; ++t)
-                    if (dx_t && dx_t[t]) ok = ok && sg.rp[t + 1] == rpm;  // one register geometry per launch
-                ok = ok && outs > 0 && rpm <= 16 && (gates == 0 || gates == outs) && !misaligned(Qm) && (sg.R % 8) == 0;
-                if (ok) {
-                    rank_out.Q = Qm;
-                    rank_out.Acat = pk + L.a_cat;
-                    rank_out.ldq = sg.R;
-                    rank_out.M = d->M;
-                    rank_out.K = (int)d->K;
-                    for (int t = 0; t < d->T; ++t) {
-                        if (!dx_t[t]) continue;
-                        const int i = rank_out.n_t++;
-                        rank_out.seg[i] = sg.off[t + 1];
-                        rank_out.rp[i] = sg.rp[t + 1];
-                        rank_out.out[i] = dx_t[t];
-                        rank_out.gate[i] = gate_t ? gate_t[t] : nullptr;
-                    }
-                    rank_out_rp = rpm <= 8 ? 8 : 16;
-                    rank_out_gated = gates > 0;
-                }
-            }
-            for (int t = 0; t < d->T && rank_out.n_t == 0; ++t) {
-                if (!dx_t || !dx_t[t]) continue;
-                NtOut& Ot = m.out[m.n_out++];
-                Ot.ptr = dx_t[t];
-                Ot.seg_lo = sg.off[t + 1];
-                Ot.seg_hi = sg.off[t + 1] + sg.rp[t + 1];
-                Ot.use_base = 0;
-                Ot.mask_lr = 0;
-                Ot.fold = 0;
-                Ot.gate = gate_t ? gate_t[t] : nullptr;
-            }
-        } else {
-            O.seg_lo = 0;
-            O.seg_hi = sg.used;  // (not R: the Q pass writes segments only, the pad columns of Q hold whatever the scratch held)
-        }
-        if (dx) {
-            int n_gate = 0;  // the fused GELU backward reads the pre-activation of every gated output (algorithmic: gelu'(h) needs h)
-            for (int o = 0; o < m.n_out; ++o) n_gate += m.out[o].gate ? 1 : 0;
-            const int n_xt = rank_out.n_t > 0 ? 0 : (d->has_x_tasks ? d->T : 0);  // task outputs written by THIS launch
-            const double b8d = (double)sizeof(T) * d->M * ((double)n_dy * d->N + (double)(1 + n_xt) * d->K);
-            double rsum = 0.0;
-            for (int o = 0; o < sg.n; ++o)
-                if (sg.rp[o] > 0 && dyo[o]) rsum += sg.r[o];
-            const double fl = (n_dy > 0 ? 2.0 * d->M * d->N * d->K : 0.0) + 2.0 * d->M * d->K * rsum;
-            const bool plain = sg.R == 0;
-            launch_nt<T>(tu, m, s, plain ? PK_NT_PLAIN_DX : PK_NT_BWD_DX, b8d + (double)sizeof(T) * d->M * (double)n_gate * d->K,
-                         plain ? 0.0 : b8d, fl);
-        }
-        if constexpr (sizeof(T) == 2) {
-            if (rank_out.n_t > 0) {
-                const double ob = (double)sizeof(T) * d->M * (double)rank_out.n_t * d->K;
-                mtl_prof_tag("rank_out M%lld K%lld nt%d rp%d gate%d", (long long)d->M, (long long)d->K, rank_out.n_t, rank_out_rp, rank_out_gated ? 1 : 0);
-                MtlProfScope prof(PK_NT_BWD_DX, ob * (rank_out_gated ? 2.0 : 1.0), s, ob, 0.0);
-                const int nchunk = (int)(d->K / 8), rpb = 256 / nchunk;
-                int64_t bx = mtl_ceil_div(d->M, (int64_t)rpb * 4);
-                const int64_t cap = (int64_t)num_cu(tu) * 8 / rank_out.n_t > 0 ? (int64_t)num_cu(tu) * 8 / rank_out.n_t : 1;
-                if (bx > cap) bx = cap;
-                const dim3 g((unsigned)bx, (unsigned)rank_out.n_t);
-                if (rank_out_gated && rank_out_rp == 8)
-                    hipLaunchKernelGGL((k_rank_out<T, true, 8>), g, dim3(256), 0, s, rank_out);
-                else if (rank_out_gated)
-                    hipLaunchKernelGGL((k_rank_out<T, true, 16>), g, dim3(256), 0, s, rank_out);
-                else if (rank_out_rp == 8)
-                    hipLaunchKernelGGL((k_rank_out<T, false, 8>), g, dim3(256), 0, s, rank_out);
-                else
-                    hipLaunchKernelGGL((k_rank_out<T, false, 16>), g, dim3(256), 0, s, rank_out);
-            }
-        }
-    }
-
-    // dA_o = Q_o^T D(X_o),  dB_o = dY_o^T P_o
-    if (sg.R > 0 && do_factors) {
-        TnParams tp = {};
-        tp.M = d->M;
-        tp.nsplit = S.nsplit;
-        tp.rows_per_split = S.rows_per_split;
-        tp.drop = dc;
-        float* pp = part;
-        int max_tiles = 0;
-        for (int o = 0; o < sg.n; ++o) {
-            const bool q_given = hid_q && o > 0;  // Q[:, seg_o] came from k_hid_bwd (which also returns dB_o): dA_o only
-            if (sg.rp[o] == 0 || (!dyo[o] && !q_given)) continue;
-            float* dAo = (o == 0) ? dA_s : (dA_t ? dA_t[o - 1] : nullptr);
-            float* dBo = (o == 0) ? dB_s : (dB_t ? dB_t[o - 1] : nullptr);
-            if (!dyo[o]) dBo = nullptr;
-            if (dBo) {  // (N x r_o) = dY_o^T P[:, seg_o], evaluated as its transpose P[:, seg_o]^T dY_o
-                TnProblem& p = tp.p[tp.n_prob++];
-                p.A = Pm;
-                p.lda = sg.R;
-                p.a0 = sg.off[o];
-                p.Na = sg.rp[o];
-                p.B = dyo[o];
-                p.ldb = d->N;
-                p.b0 = 0;
-                p.Nb = (int)d->N;
-                p.b_mask = 0;
-                p.tiles_a = (int)mtl_ceil_div(p.Na, TN_A);
-                p.tiles_b = (int)mtl_ceil_div(p.Nb, TN_B);
-                p.part = pp;
-                pp += (int64_t)p.tiles_a * p.tiles_b * S.nsplit * TN_TILE;
-                p.out = dBo;
-                p.out_a = sg.r[o];
-                p.out_b = (int)d->N;
-                p.ldo = sg.r[o];
-                p.transpose = 1;
-                if (p.tiles_a * p.tiles_b > max_tiles) max_tiles = p.tiles_a * p.tiles_b;
-            }
-            if (dAo) {  // (r_o x K) = Q[:, seg_o]^T . D(X_o)
-                TnProblem& p = tp.p[tp.n_prob++];
-                p.A = Qm;
-                p.lda = sg.R;
-                p.a0 = sg.off[o];
-                p.Na = sg.rp[o];
-                const bool own_x = (o > 0 && d->has_x_tasks);
-                p.B = own_x ? x_t[o - 1] : x;
-                p.ldb = d->K;
-                p.b0 = 0;
-                p.Nb = (int)d->K;
-                p.b_mask = own_x ? 0 : 1;
-                p.tiles_a = (int)mtl_ceil_div(p.Na, TN_A);
-                p.tiles_b = (int)mtl_ceil_div(p.Nb, TN_B);
-                p.part = pp;
-                pp += (int64_t)p.tiles_a * p.tiles_b * S.nsplit * TN_TILE;
-                p.out = dAo;
-                p.out_a = sg.r[o];
-                p.out_b = (int)d->K;
-                p.ldo = (int)d->K;
-                p.transpose = 0;
-                if (p.tiles_a * p.tiles_b > max_tiles) max_tiles = p.tiles_a * p.tiles_b;
-            }
-        }
-        bool tn_done = false;
-        if constexpr (sizeof(T) == 2) {
-            const int nb = (tu.sp != 0 && tu.tn != 0) ? sp_tn_nb(d) : 0;
-            bool ok = nb != 0 && tp.n_prob > 0;
-            SpTnParams q = {};
-            for (int i = 0; ok && i < tp.n_prob; ++i) {
-                const TnProblem& p = tp.p[i];
-                SpTnProb& r = q.p[i];
-                ok = ok && p.b0 == 0 && p.Nb == p.ldb && p.Nb % (32 * nb) == 0 && !misaligned(p.A) && !misaligned(p.B) && (p.lda % 8) == 0 &&
-                     (p.a0 % 8) == 0;
-                r.A = p.A;
-                r.B = p.B;
-                r.lda = p.lda;
-                r.ldb = p.ldb;
-                r.a0 = p.a0;
-                r.Na = p.Na;
-                r.Nb = p.Nb;
-                r.b_mask = p.b_mask;
-                r.tiles_a = (int)mtl_ceil_div(p.Na, 64);
-                r.parts = p.Nb / (32 * nb);
-                r.pp_lo = q.n_pp;
-                r.transpose = p.transpose;
-                r.out = p.out;
-                r.out_a = p.out_a;
-                r.out_b = p.out_b;
-                r.ldo = p.ldo;
-                q.n_pp += r.tiles_a * r.parts;
-            }
-            if (ok) {
-                const int mode = tu.tn;
-                q.n_prob = tp.n_prob;
-                q.G = sp_tn_groups(tu, q.n_pp, d->M);
-                ok = q.n_pp <= SP_TN_WGS && q.G < 65536 && (mode == 2 || (mode == 1 && mtl_ceil_div(d->M, 32) >= (int64_t)8 * q.G * SP_WAVES));
-                if (ok) {
-                    SpTnParams probe = q;
-                    ok = sp_tn_map(probe) != 0;
-                    q.G = probe.G;
-                }
-            }
-            if (ok) {
-                q.n_prob = tp.n_prob;
-                q.M = d->M;
-                q.part = part;
-                q.drop = dc;
-                const double xb = (double)sizeof(T) * d->M * (double)(1 + (d->has_x_tasks ? d->T : 0)) * d->K;
-                double fl = 0.0;
-                for (int i = 0; i < tp.n_prob; ++i) fl += 2.0 * d->M * (double)tp.p[i].out_a * tp.p[i].out_b;
-                char tag[96];
-                snprintf(tag, sizeof(tag), "M%lld K%lld N%lld T%d", (long long)d->M, (long long)d->K, (long long)d->N, d->T);
-                launch_sp_tn<T>(q, nb, s, xb, fl, tag);
-                tn_done = true;
-            }
-        }
-        if (!tn_done && tp.n_prob > 0 && d->M > 0) {
-            {
-                mtl_prof_tag("M%lld K%lld N%lld T%d np%d ns%d tiles%d", (long long)d->M, (long long)d->K, (long long)d->N, d->T, tp.n_prob,
-                             S.nsplit, max_tiles);
-                const double xb = (double)sizeof(T) * d->M * (double)(1 + (d->has_x_tasks ? d->T : 0)) * d->K;
-                double fl = 0.0;
-                for (int i = 0; i < tp.n_prob; ++i) fl += 2.0 * d->M * (double)tp.p[i].out_a * tp.p[i].out_b;
-                MtlProfScope prof(PK_TN, xb, s, xb, fl);
-                hipLaunchKernelGGL(k_tn<T>, dim3((unsigned)S.nsplit, (unsigned)max_tiles, (unsigned)tp.n_prob),
-                                   dim3(256), 0, s, tp);
-            }
-            MtlProfScope prof(PK_REDUCE, 0.0, s);
-            hipLaunchKernelGGL(k_tn_reduce, dim3(TN_TILE / 1024, (unsigned)max_tiles, (unsigned)tp.n_prob), dim3(256 * TN_RG), 0, s, tp);
-        }
-    }
+    if (d->bwd_phase != 1) bwd_factors(b);
     return MTLORA_OK;
 }
 

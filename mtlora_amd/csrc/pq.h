@@ -13,6 +13,11 @@
 // (layers without task inputs; the Q pass of layers without task outputs).
 #pragma once
 
+#include "nt.h"
+#include "stream.h"
+
+namespace {
+
 struct PqSrc {
     const void* act;     // (M x K) contiguous rows
     int col_lo, col_hi;  // columns of Out (= rows of wproj) this source owns (multiples of 8)
@@ -185,3 +190,5 @@ __global__ __launch_bounds__(256) void k_pq(const PqParams P) {
         sp_bstore(v, orsrc, (m < M && n < c_hi) ? (uint32_t)m * ldo2 + (uint32_t)n * 2u : 0xFFFFFFFFu);
     }
 }
+
+}  // namespace

@@ -1,5 +1,5 @@
 // stream.h -- k_sp*: wave-streaming kernels for the HBM-side MTLoRALinear launches (16-bit types).  Included by linear.hip
-// inside its anonymous namespace (after Segs / CtxLayout / g_zero16 / gelu_* / MtlProfScope are visible).
+// after nt.h (Segs / CtxLayout / g_zero16 / gelu_*); everything lives in the translation unit's anonymous namespace.
 //
 // Why another family: the tiled kernels (k_nt / k_ntl) run a workgroup as ONE serial chain
 //     global -> registers -> LDS -> barrier -> MFMA -> barrier -> ... -> epilogue -> exit
@@ -26,6 +26,10 @@
 // vmcnt(#DMA instructions of the YOUNGER chunks only): whatever the stores do, the count can only be reached once every
 // older load has landed (it may additionally wait for store acknowledgements -- the other waves of the CU cover that).
 #pragma once
+
+#include "nt.h"
+
+namespace {
 
 #ifndef MTL_SP_WAVES
 #define MTL_SP_WAVES 8
@@ -281,7 +285,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_proj(const S
 // one slab group sit on the same XCD (blockIdx b -> XCD b % 8) so that the slab is re-read from that L2.
 // STG: the epilogue goes through a per-wave LDS image (32 rows x 64 columns) so that a store instruction writes 8 rows x
 // 128 contiguous bytes: a row-per-lane store (32 rows x 32 bytes) costs the texture-addresser ~80 cycles per instruction --
-// with 20 of them per slab the store ISSUE alone is 45 us of a 57 us launch (tools/sp_ablate.sh).
+// with 20 of them per slab the store ISSUE alone is 45 us of a 57 us launch (ablation quoted in profiles/DESIGN_history_r01_r05.md 4.1d).
 // ------------------------------------------------------------------------------------------------
 struct SpLinParams {
     const void* act;     // (M x K) contiguous
@@ -295,9 +299,9 @@ struct SpLinParams {
     void* pout;          // (M x ldp) projection image for the factor gradients, nullable
     int64_t ld_out, ldp, M;
     int n_cols, R, n_parts, blk_per_part;
-    int n_slabs, mask_act, mask_lr, dbg;  // dbg: developer ablation bits (MTLORA_SP_DBG, -DMTL_NT_ABLATE=1 builds only): 1 no output stores, 2 no slab loads, 4 no block MFMAs, 8 no P store
+    int n_slabs, mask_act, mask_lr;
     int estep, estep2;   // rank steps per block in `expand` (2 * ceil(R / 32)); k_sp_ares: the reduction length K
-    int xsh, pad_;       // blockIdx -> (part, slab group): part = (b >> xsh) % n_parts, group = (b & (2^xsh - 1)) + ((b / (n_parts << xsh)) << xsh);
+    int xsh;             // blockIdx -> (part, slab group): part = (b >> xsh) % n_parts, group = (b & (2^xsh - 1)) + ((b / (n_parts << xsh)) << xsh);
                          // xsh = 3: the parts of a group share an XCD (b % 8); xsh = 0: grids smaller than 8 * n_parts (desc.max_cu)
     DropoutCfg drop;
 };
@@ -362,7 +366,6 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_xres(const S
     drop.off = P->drop.off;
     mtl_dropout_resolve(drop);
     const bool mask_act = P->mask_act != 0 && drop.thr16 != 0, mask_lr = P->mask_lr != 0 && drop.thr16 != 0;
-    const int dbg = P->dbg & NT_DBG_MASK;  // (0 at compile time unless -DMTL_NT_ABLATE=1)
 
     {   // stationary operands
         const T* wp = reinterpret_cast<const T*>(P->w);
@@ -408,8 +411,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_xres(const S
     auto issue = [&]() __attribute__((always_inline)) -> bool {
         if (l_slab >= n_slabs) return false;
         const T* base = reinterpret_cast<const T*>(P->act) + (int64_t)l_slab * 32 * K + l_ch * CH;
-        if (dbg & 2) {
-        } else if ((int64_t)l_slab * 32 + 32 <= M) {
+        if ((int64_t)l_slab * 32 + 32 <= M) {
 #pragma unroll
             for (int j = 0; j < G::NDMA; ++j) sp_dma16(base + goff[j], slots + j * 1024);
         } else {
@@ -475,7 +477,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_xres(const S
             for (int t = 0; t < 2; ++t)
                 pf[2 * rb + t] = u32x4{mtl_pk2<T>(accP[rb][8 * t + 0], accP[rb][8 * t + 1]), mtl_pk2<T>(accP[rb][8 * t + 2], accP[rb][8 * t + 3]),
                                        mtl_pk2<T>(accP[rb][8 * t + 4], accP[rb][8 * t + 5]), mtl_pk2<T>(accP[rb][8 * t + 6], accP[rb][8 * t + 7])};
-        if (P->pout && part == 0 && !(dbg & 8)) {
+        if (P->pout && part == 0) {
             const uint32_t prow = (uint32_t)m * (uint32_t)(P->ldp * 2);
 #pragma unroll
             for (int rb = 0; rb < NRB; ++rb)
@@ -548,10 +550,8 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_xres(const S
                     if ((h1 >> 16) < drop.thr16) acc[4 * q + 3] = 0.f;
                 }
             }
-            if (!(dbg & 4)) {
 #pragma unroll
-                for (int ks = 0; ks < KST; ++ks) sp_mma1<T>(wf[ks], xf[ks], acc);
-            }
+            for (int ks = 0; ks < KST; ++ks) sp_mma1<T>(wf[ks], xf[ks], acc);
             if constexpr (PF) {
                 if (nb + 1 < nbn) load_blk(nb + 1);  // lands while this block is converted and stored
             }
@@ -574,7 +574,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_xres(const S
                     const uint32_t o0 = ((uint32_t)slab * 32u + (uint32_t)(lane >> 3)) * ldo2 + (uint32_t)col * 2u;
 #pragma unroll
                     for (int it = 0; it < 4; ++it) {
-                        const uint32_t off = (colok && !(dbg & 1)) ? o0 + (uint32_t)(it * 8) * ldo2 : 0xFFFFFFFFu;
+                        const uint32_t off = colok ? o0 + (uint32_t)(it * 8) * ldo2 : 0xFFFFFFFFu;
                         if constexpr (GATE) {  // the rounded gradient times gelu'(pre-activation), rounded once (as ATen does)
                             v[it] = mtl_gelu_gate_pk4<T, true>(v[it], hv[it]);
                         }
@@ -594,7 +594,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_xres(const S
                     u32x4 v;
                     sp_pack_pair<T>(acc, q, h, v);
                     const int col = col0 + 8 * q + 8 * h;
-                    const uint32_t off = (col < n_cols && !(dbg & 1)) ? rowoff + (uint32_t)col * 2u : 0xFFFFFFFFu;
+                    const uint32_t off = (col < n_cols) ? rowoff + (uint32_t)col * 2u : 0xFFFFFFFFu;
                     if constexpr (GATE) {
                         v = mtl_gelu_gate_pk4<T, true>(v, hv[q >> 1]);
                     }
@@ -658,7 +658,6 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_ares(const S
     drop.off = P->drop.off;
     mtl_dropout_resolve(drop);
     const bool mask_act = P->mask_act != 0 && drop.thr16 != 0, mask_lr = P->mask_lr != 0 && drop.thr16 != 0;
-    const int dbg = P->dbg & NT_DBG_MASK;  // (0 at compile time unless -DMTL_NT_ABLATE=1)
 
     {   // stationary operands
         const T* wp = reinterpret_cast<const T*>(P->w);
@@ -703,8 +702,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_ares(const S
     auto issue = [&]() __attribute__((always_inline)) -> bool {
         if (l_slab >= n_slabs) return false;
         const T* base = reinterpret_cast<const T*>(P->act) + (int64_t)l_slab * 32 * K + l_ch * CH;
-        if (dbg & 2) {
-        } else if ((int64_t)l_slab * 32 + 32 <= M) {
+        if ((int64_t)l_slab * 32 + 32 <= M) {
 #pragma unroll
             for (int j = 0; j < G::NDMA; ++j) sp_dma16(base + goff[j], slots + j * 1024);
         } else {
@@ -766,11 +764,9 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_ares(const S
 #pragma unroll
                 for (int rb = 0; rb < NRB; ++rb) pfr[rb] = *reinterpret_cast<const u32x4*>(pb + ((size_t)rb * KST + ks) * 1024);
                 u32x4 a = xf[ks];
-                if (!(dbg & 4)) {
 #pragma unroll
-                    for (int ob = 0; ob < NOB; ++ob)
-                        sp_mma1<T>(wfr[ob], a, acc[ob]);
-                }
+                for (int ob = 0; ob < NOB; ++ob)
+                    sp_mma1<T>(wfr[ob], a, acc[ob]);
                 if (mask_act) VOps<T>::drop(a, drop, rh, (uint32_t)(ch * CH + ks * 16 + 8 * h));
 #pragma unroll
                 for (int rb = 0; rb < NRB; ++rb) sp_mma1<T>(pfr[rb], a, accP[rb]);
@@ -783,7 +779,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_ares(const S
             for (int t = 0; t < 2; ++t)
                 pf[2 * rb + t] = u32x4{mtl_pk2<T>(accP[rb][8 * t + 0], accP[rb][8 * t + 1]), mtl_pk2<T>(accP[rb][8 * t + 2], accP[rb][8 * t + 3]),
                                        mtl_pk2<T>(accP[rb][8 * t + 4], accP[rb][8 * t + 5]), mtl_pk2<T>(accP[rb][8 * t + 6], accP[rb][8 * t + 7])};
-        if (P->pout && part == 0 && !(dbg & 8)) {
+        if (P->pout && part == 0) {
             const uint32_t prow = (uint32_t)m * (uint32_t)(P->ldp * 2);
 #pragma unroll
             for (int rb = 0; rb < NRB; ++rb)
@@ -856,7 +852,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_ares(const S
                     u32x4 v;
                     sp_pack_pair<T>(acc[ob], q, h, v);
                     const int col = col0 + 8 * q + 8 * h;
-                    sp_bstore(v, orsrc, (col < n_cols && !(dbg & 1)) ? rowoff + (uint32_t)col * 2u : 0xFFFFFFFFu);
+                    sp_bstore(v, orsrc, (col < n_cols) ? rowoff + (uint32_t)col * 2u : 0xFFFFFFFFu);
                 }
                 st_since += 2;
             }
@@ -1491,3 +1487,5 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_projk(const 
         __syncthreads();  // the image is read: the next item's loads may overwrite it
     }
 }
+
+}  // namespace

@@ -125,6 +125,53 @@ def test_descriptor_selection_fields_are_validated(built_lib):
         assert name not in blob, name
 
 
+def _linear_plan_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden_linear_plan", os.path.join(ROOT, "tests", "golden", "make_golden_linear_plan.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_linear_workspace_sizes_match_fixture(built_lib):
+    """ctx bytes, backward scratch bytes, mtlora_mlp_hid_supported and the hid scratch sizes of every descriptor of
+    make_golden_linear_plan.size_table() equal tests/golden/linear_sizes.json (recorded from the library before the host dispatch of
+    csrc/linear.hip was split into launchers and stages): a host-side refactor must not move a workspace size."""
+    import json
+    from mtlora_amd import _lib
+    G = _linear_plan_module()
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "linear_sizes.json")))
+    L = _lib.lib()
+    keys = []
+    for i, (key, kw) in enumerate(G.size_table()):
+        keys.append(key)
+        assert G.sizes_of(L, kw) == want["values"][want["index"][i]], key
+    assert len(keys) == len(set(keys)) == len(want["index"]) and len(keys) > 6000
+
+
+def test_linear_sources_have_no_ablation_build():
+    """no source file of the project (package, kernels, header, tools, oracle, entry points; documents and recorded profiles
+    aside) carries an ablation switch, and the kernel sources read no environment variable outside the profiler (selftest.hip)"""
+    exts = (".hip", ".h", ".py", ".sh", ".c", ".cpp", ".cu", ".cmake", ".toml", ".cfg")
+    seen = 0
+    for top in ("mtlora_amd", "include", "tools", "oracle", "bench.py", "__graft_entry__.py"):
+        path = os.path.join(ROOT, top)
+        walk = os.walk(path) if os.path.isdir(path) else [(ROOT, [], [top])]
+        for base, dirs, files in walk:
+            dirs[:] = [x for x in dirs if x not in ("_ref", "__pycache__")]
+            for f in sorted(files):
+                if not f.endswith(exts):
+                    continue
+                seen += 1
+                text = open(os.path.join(base, f), errors="replace").read()
+                for name in ("MTLORA_NT_DBG", "MTLORA_SP_DBG", "MTLORA_SP_STG", "MTL_NT_ABLATE", "MTLORA_ABLATE", "NT_DBG_MASK",
+                             "ablate_bits"):
+                    assert name not in text, (f, name)
+                if base.endswith(os.path.join("mtlora_amd", "csrc")) and f != "selftest.hip":
+                    assert "getenv" not in text, f
+    assert seen > 60
+
+
 def test_partial_state_dict_into_merged_layer_unmerges_first():
     """loading a LoRA-only (strict=False) dict into a MERGED layer must not leave W + s B_old A_old behind with the
     merged flag cleared (the shared update would be added twice; a later unmerge would subtract the wrong delta)."""
