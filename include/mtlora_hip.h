@@ -248,7 +248,8 @@ int mtlora_gemm_tn(const void* a, const void* b, float* out, int64_t M, int Na, 
  *                     rows/cols ((wy*ws+ty+shift) mod H, (wx*ws+tx+shift) mod W).
  * out has the same token order as qkv, (.., C).  bias: dense (num_heads, N, N) fp32
  * (table[index] gathered by the host, :202-206).  mask: (nW_per_image, N, N) fp32 or NULL (:209-213).
- * N = ws*ws <= 64, head_dim == 32 (every Swin variant).
+ * N = ws*ws <= 144 (window sizes up to 12; N <= 64 runs one wave per (window, head), larger windows one workgroup),
+ * head_dim == 32 (every Swin variant).  Larger windows return MTLORA_ERR_UNSUPPORTED.
  * ------------------------------------------------------------------------------------------ */
 typedef struct mtlora_attn_desc {
     int64_t B;            /* images */

@@ -21,6 +21,8 @@
 // selects) so that their LDS reads are issued back to back; the dense-mask path is a separate template variant.
 // The k-slot <-> key assignment of every register-fed operand follows the accumulator layout
 // (row = (r&3) + 8(r>>2) + 4(lane>>5)); the LDS-fed partner operand is gathered in the same order.
+#include <atomic>
+
 #include "common.h"
 
 namespace {
@@ -857,11 +859,13 @@ __global__ __launch_bounds__(256) void k_dbias_reduce(const float* part, float* 
     }
 }
 
+constexpr int WIDE_MAX_N = 144;  // 64 < N <= 144 (ws 9..12): the multi-wave kernels of attention_wide.h
+
 int check(const mtlora_attn_desc* d) {
     if (!d) return MTLORA_ERR_NULL;
     if (d->dtype != MTLORA_F32 && d->dtype != MTLORA_BF16 && d->dtype != MTLORA_F16) return MTLORA_ERR_DTYPE;
     if (d->head_dim != HD) return MTLORA_ERR_UNSUPPORTED;
-    if (d->window_size <= 0 || d->window_size * d->window_size > AN) return MTLORA_ERR_UNSUPPORTED;
+    if (d->window_size <= 0 || d->window_size * d->window_size > WIDE_MAX_N) return MTLORA_ERR_UNSUPPORTED;
     if (d->B < 0 || d->H <= 0 || d->W <= 0 || d->num_heads <= 0) return MTLORA_ERR_SHAPE;
     if (d->H % d->window_size || d->W % d->window_size) return MTLORA_ERR_SHAPE;
     if (d->shift < 0 || d->shift >= d->window_size) return MTLORA_ERR_SHAPE;
@@ -913,6 +917,8 @@ AttnParams make_params(const mtlora_attn_desc* d) {
     return p;
 }
 
+#include "attention_wide.h"
+
 }  // namespace
 
 extern "C" {
@@ -920,6 +926,7 @@ extern "C" {
 int64_t mtlora_window_attn_bwd_scratch_bytes(const mtlora_attn_desc* d) {
     if (check(d) != MTLORA_OK) return -1;
     const int N = d->window_size * d->window_size;
+    if (N > AN) return (int64_t)wide_groups(d) * d->num_heads * N * N * 4 + 256;
     return (int64_t)bwd_groups(d) * d->num_heads * N * N * 4 + 256;
 }
 
@@ -937,6 +944,15 @@ int mtlora_window_attn_fwd(const mtlora_attn_desc* d, const void* qkv, const flo
     p.mask_ids = mask_ids;
     p.mask_value = d->mask_value;
     p.out = out;
+    if (p.N > AN) {
+        hipStream_t ws = (hipStream_t)stream;
+        const double wab = 4.0 * mtl_elem_size(d->dtype) * (double)p.n_windows * p.N * p.C;
+        MtlProfScope prof(PK_ATTN_FWD, wab, ws, wab, 4.0 * (double)p.n_windows * p.N * p.N * p.C);
+        const int wst = wide_fwd(d, p, ws);
+        if (wst != MTLORA_OK) return wst;
+        MTL_CHECK_LAUNCH();
+        return MTLORA_OK;
+    }
     const int rs = d->dtype == MTLORA_F32 ? AC<float>::RS : AC<bf16>::RS;
     const size_t ib = (size_t)((img_rows_h(p.N) * rs + 15) / 16) * 16;
     const size_t lds = 3 * ib + 2 * AN * 4 + (d->dtype == MTLORA_F32 ? STG<float>::BYTES : STG<bf16>::BYTES) + (d->dtype == MTLORA_F32 ? (size_t)p.N * bias_stride_c(p.N) * 4 : 0);  // (fp32: bias image)
@@ -988,6 +1004,19 @@ int mtlora_window_attn_bwd(const mtlora_attn_desc* d, const void* qkv, const flo
     p.dout = dout;
     p.dqkv = dqkv;
     p.dbias_part = reinterpret_cast<float*>(scratch);
+    if (p.N > AN) {
+        {
+            const double wab = 7.0 * mtl_elem_size(d->dtype) * (double)p.n_windows * p.N * p.C;
+            MtlProfScope prof(PK_ATTN_BWD, wab, s, wab, 8.0 * (double)p.n_windows * p.N * p.N * p.C);
+            const int wst = wide_bwd(d, p, s);
+            if (wst != MTLORA_OK) return wst;
+        }
+        const int wtotal = p.nH * p.N * p.N;
+        hipLaunchKernelGGL(k_dbias_reduce, dim3((unsigned)((wtotal + 63) / 64)), dim3(256), 0, s, (const float*)p.dbias_part, dbias,
+                           p.G, p.nH, p.N);
+        MTL_CHECK_LAUNCH();
+        return MTLORA_OK;
+    }
     p.G = bwd_groups(d);
     const unsigned grid = (unsigned)(p.G * p.nH);
     const size_t lds = bwd_lds_bytes(d);

@@ -29,6 +29,7 @@ import torch.nn as nn
 from torch import Tensor
 
 import os
+import weakref
 
 from . import functional as Fn
 from .lora import MTLoRALinear
@@ -199,6 +200,30 @@ def _relative_position_index(wh: int, ww: int) -> Tensor:
     return (rel[0] + wh - 1) * (2 * ww - 1) + (rel[1] + ww - 1)
 
 
+# gather constants of ``WindowAttention.dense_bias``, ONE per (window size, device) for all modules: the matrix depends on the window
+# size alone, and at 12 x 12 it is 529 x 20736 fp32 = 44 MB (a private copy per attention module of a 24-block model: over 1 GB).
+# Weak values: the modules that use a matrix keep it alive (``_rpi_onehot``), and it is freed with the last of them.
+_RPI_ONEHOT = weakref.WeakValueDictionary()
+
+
+def _shared_rpi_onehot(index: Tensor, wh: int, ww: int, rows: int, device) -> Tensor:
+    """the one-hot matrix of ``index`` on ``device``, shared when ``index`` is the standard one of a (wh, ww) window (checked once per
+    module, on its first call: one device-to-host copy of the index buffer); a module whose buffer was edited gets a private matrix"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:  # 'cuda' and 'cuda:<current>' are one device
+        device = torch.device("cuda", torch.cuda.current_device())
+    standard = torch.equal(index.detach().cpu(), _relative_position_index(wh, ww))
+    key = (wh, ww, device.type, device.index)
+    oh = _RPI_ONEHOT.get(key) if standard else None
+    if oh is None:
+        n = wh * ww
+        oh = torch.zeros(rows, n * n, dtype=torch.float32, device=device)
+        oh[index.view(-1).to(device), torch.arange(n * n, device=device)] = 1.0
+        if standard:
+            _RPI_ONEHOT[key] = oh
+    return oh
+
+
 class WindowAttention(nn.Module):
     """W-MSA / SW-MSA with relative position bias; qkv and proj are MTLoRALinear (reference :119-243)."""
 
@@ -236,9 +261,7 @@ class WindowAttention(nn.Module):
             return b.view(n, n, -1).permute(2, 0, 1).float()
         oh = getattr(self, "_rpi_onehot", None)
         if oh is None or oh.device != table.device:
-            idx = self.relative_position_index.view(-1).to(table.device)
-            oh = torch.zeros(table.shape[0], n * n, dtype=torch.float32, device=table.device)
-            oh[idx, torch.arange(n * n, device=table.device)] = 1.0
+            oh = _shared_rpi_onehot(self.relative_position_index, self.window_size[0], self.window_size[1], table.shape[0], table.device)
             self._rpi_onehot = oh  # plain attribute: a constant derived from relative_position_index, not module state
         with torch.autocast("cuda", enabled=False):
             return (table.float().t() @ oh).view(-1, n, n)
@@ -354,7 +377,7 @@ class SwinTransformerBlock(nn.Module):
                 and type(self.mlp.act) is nn.GELU and getattr(self.mlp.act, "approximate", "none") == "none"
                 and all(isinstance(d, nn.Dropout) for d in (self.mlp.drop, self.attn.proj_drop, self.attn.attn_drop))
                 and C % 8 == 0 and self.mlp.fc1.linear.out_features % 8 == 0
-                and C // self.num_heads == 32 and self.window_size * self.window_size <= 64)
+                and C // self.num_heads == 32 and self.window_size * self.window_size <= 144)
 
     def _block_call(self, has_norm1: bool, next_norm, cdtype, x):
         """(BlockCall, flat tensor list) of this block for a ``SwinBlockRunFn`` call, or None when the block cannot run fused NOW.
