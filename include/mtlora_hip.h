@@ -35,7 +35,8 @@ typedef enum mtlora_dtype {
     MTLORA_BF16 = 1, /* bf16 in/out, fp32 accumulate (v_mfma_f32_32x32x16_bf16) */
     MTLORA_F16 = 2,  /* fp16 in/out, fp32 accumulate (v_mfma_f32_32x32x16_f16): MTLoRALinear, window attention, gemm_tn, the
                         window_process copies and the block glue (LayerNorm family, residual + DropPath, BatchNorm + ReLU) -- the
-                        reference's default autocast dtype (main.py:341); upsample / loss / column-sum entries take fp32 / bf16 */
+                        reference's default autocast dtype (main.py:341), and mtlora_upsample_cl_fwd / _bwd; loss / column-sum entries take
+                        fp32 / bf16 */
     MTLORA_U8 = 3    /* OUTPUT dtype of mtlora_upsample_predict (ABI v11): class ids and [0, 255] images; SOURCE dtype of the
                         image and class-map jobs of mtlora_ingest_batch (ABI v12) */
 } mtlora_dtype;
@@ -472,7 +473,8 @@ int mtlora_label_stat(const float* label, int64_t n, int kind, float ignore_inde
  * (models/seg_hrnet.py:498-526: F.interpolate of the coarse maps + torch.cat).  coarse (B,h,w,C) contiguous; the fine
  * tensor (B, scale*h, scale*w, .) is addressed with `ld_fine` elements per pixel, its pointer already offset to the
  * first channel of this map -- i.e. a channel slice of the concatenated matrix.  C and ld_fine multiples of 4,
- * pointers 8-byte (bf16) / 16-byte (fp32) aligned.  bwd = exact transpose (gather form, deterministic).
+ * pointers 8-byte (bf16, fp16) / 16-byte (fp32) aligned.  bwd = exact transpose (gather form, deterministic: ATen's
+ * bilinear backward adds with atomics, which in fp16 with scaled gradients differs from run to run).
  * ------------------------------------------------------------------------------------------ */
 int mtlora_upsample_cl_fwd(const void* coarse, void* fine, int64_t B, int h, int w, int C, int scale, int64_t ld_fine,
                            int dtype, void* stream);
@@ -582,11 +584,28 @@ int mtlora_block_bwd(const mtlora_block_desc* d, const mtlora_block_params* p, c
  *                        and t stay bitwise unchanged; with a scaler the scale backs off) -- with or without a scaler.
  *                        Otherwise, per element: g' = g [3]; p *= 1 - lr wd; m = b1 m + (1 - b1) g';
  *                        v = b2 v + (1 - b2) g'^2; p -= lr / (1 - b1^t) m / (sqrt(v) / sqrt(1 - b2^t) + eps).
+ *   mtlora_adamw_update_dev  the same step with the hyper-parameters read from DEVICE memory, for a step captured in a HIP
+ *                        graph (additive, ABI stays 12): launch arguments are frozen at capture, so a replay of
+ *                        mtlora_adamw_update would use the capture step's lr forever; here only pointers are baked in.
+ *                        `groups_dev`: DEVICE buffer of MTLORA_ADAMW_GROUPS_DEV_BYTES, 8-byte aligned.  The caller writes
+ *                        the n_groups records at its start (an ordinary copy on `stream` before the step / the replay,
+ *                        whenever a value changes) and never touches the rest: the tail behind
+ *                        MTLORA_ADAMW_MAX_GROUPS records is the library's, it holds what the kernels derive from the
+ *                        records each step -- (float)lr, (float)(1 - lr wd), (float)beta, (float)(1 - beta), (float)eps,
+ *                        formed in double exactly as the host forms them for mtlora_adamw_update, so with equal
+ *                        hyper-parameters the two entries give bit-identical results.  growth_factor / backoff_factor are
+ *                        doubles here and are rounded to fp32 once.  Pointer and count checks are made on the host before
+ *                        any launch, as above.  The VALUES of the records cannot be checked on the host: a record that
+ *                        mtlora_adamw_update rejects with MTLORA_ERR_SHAPE (lr, eps or weight_decay negative, a beta outside
+ *                        [0, 1), any nan) sets found_inf on the device instead -- the step is skipped exactly like one with
+ *                        an inf gradient (parameters, state and t bitwise unchanged; with a scaler the scale backs off)
+ *                        and the norm in ctrl[0] / norm_out is nan.
  * Deterministic: no float atomics; the norm is summed in a fixed order (per-chunk fp32 partials, combined in double).
  * ------------------------------------------------------------------------------------------ */
 #define MTLORA_ADAMW_CHUNK 4096
 #define MTLORA_ADAMW_MAX_GROUPS 16
 #define MTLORA_ADAMW_CTRL_WORDS 64
+#define MTLORA_ADAMW_GROUPS_DEV_BYTES 1152 /* MAX_GROUPS 40-byte records, then 512 bytes for what is derived from them */
 typedef struct mtlora_adamw_group {
     double lr, beta1, beta2, eps, weight_decay; /* doubles, as torch holds them: 1 - beta, 1 - lr wd and the powers are formed in
                                                    double and rounded once */
@@ -599,6 +618,11 @@ int mtlora_adamw_update(const void* table, const void* grads, int64_t n_tensors,
                         const mtlora_adamw_group* groups, int n_groups, float max_norm, float* ctrl, float* norm_out,
                         float* scale, int32_t* growth_tracker, float growth_factor, float backoff_factor,
                         int growth_interval, void* scratch, int64_t scratch_bytes, void* stream);
+int mtlora_adamw_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks,
+                            const mtlora_adamw_group* groups_dev, int n_groups, float max_norm, float* ctrl,
+                            float* norm_out, float* scale, int32_t* growth_tracker, double growth_factor,
+                            double backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Batch ingest (ABI v12): the tail of the reference's loader pipelines on the device -- RandomHorizontalFlip,

@@ -84,6 +84,7 @@ AUGMENT_GEOM_BITS, AUGMENT_FLAG_NO_RENORM = 24, 1
 INGEST_IMAGE, INGEST_CLASS, INGEST_CLASS_ALLZERO_IGNORE, INGEST_NORMALS, INGEST_DEPTH = 0, 1, 2, 3, 4
 
 ADAMW_CHUNK, ADAMW_MAX_GROUPS, ADAMW_CTRL_WORDS = 4096, 16, 64
+ADAMW_GROUPS_DEV_BYTES = 1152  # device buffer of mtlora_adamw_update_dev: MAX_GROUPS records, then the library's derived values
 
 PROF_KINDS = 24
 
@@ -204,6 +205,8 @@ _SIGS = {
                                    c_void_p, c_int64]),
     "mtlora_adamw_update": (c_int, [c_void_p, c_void_p, c_int64, c_int64, POINTER(AdamwGroup), c_int, c_float, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_float, c_float, c_int, c_void_p, c_int64, c_void_p]),
+    "mtlora_adamw_update_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_float, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_int64, c_void_p]),
     "mtlora_ingest_scratch_bytes": (c_int64, [c_int, c_int64]),
     "mtlora_ingest_batch": (c_int, [POINTER(IngestJob), c_int, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                     c_void_p]),

@@ -24,6 +24,13 @@
 //                       p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)
 //                   lr, wd, betas, eps per parameter group, BY VALUE in the launch arguments (lr moves every step under a
 //                   scheduler; nothing to upload).
+//
+// mtlora_adamw_update_dev is the same three launches with the hyper-parameters in DEVICE memory, for a step that is captured in a
+// HIP graph: launch arguments are frozen at capture, device memory is read at replay.  The group records (doubles) sit in a buffer
+// of MTLORA_ADAMW_GROUPS_DEV_BYTES; k_optim_finish's one-thread-per-group part derives from them, in double, what the host derives
+// for the by-value entry ((float)lr, (float)(1 - lr wd), (float)b, (float)(1 - b), (float)eps -- the same IEEE operations, no
+// contraction, so the two entries are bit-identical) and stores it in that buffer's tail, where k_optim_step reads it.  A record
+// the host entry would reject (negative lr, beta >= 1, nan) raises found_inf: the step is skipped and the norm is nan.
 #include "common.h"
 
 namespace {
@@ -49,12 +56,51 @@ struct OptChunk {
 };
 static_assert(sizeof(OptTensor) == 40 && sizeof(OptChunk) == 8, "table layout");
 
+struct OptHyperArr {  // what k_optim_step needs of the groups: 448 bytes
+    float lr[OPT_MAXG], decay[OPT_MAXG], b1[OPT_MAXG], omb1[OPT_MAXG], b2[OPT_MAXG], omb2[OPT_MAXG], eps[OPT_MAXG];
+};
 struct OptGroups {  // kernel argument.  The hyper-parameters arrive as doubles (as torch holds them); what is derived from them is
     // formed in double on the host and rounded once: 1 - 0.999f is 1.3e-5 away from 1 - 0.999
-    float lr[OPT_MAXG], decay[OPT_MAXG], b1[OPT_MAXG], omb1[OPT_MAXG], b2[OPT_MAXG], omb2[OPT_MAXG], eps[OPT_MAXG];
+    OptHyperArr h;
     double b1d[OPT_MAXG], b2d[OPT_MAXG];
     int n;
 };
+struct OptGroupsDev {  // kernel argument of the _dev entry: [OPT_MAXG] records the caller uploads; behind them the OptHyperArr that
+    const mtlora_adamw_group* rec;  // k_optim_finish derives from them -- the same arrays, indexed the same way, as the by-value
+    OptHyperArr* hyp;               // argument holds, so that k_optim_step is the same code on both paths
+    int n;
+};
+struct OptHyper {  // one group's derived values
+    float lr, decay, b1, omb1, b2, omb2, eps;
+};
+static_assert(sizeof(mtlora_adamw_group) == 40 && sizeof(OptHyperArr) == 28 * OPT_MAXG, "group buffer layout");
+static_assert(OPT_MAXG * sizeof(mtlora_adamw_group) + sizeof(OptHyperArr) <= MTLORA_ADAMW_GROUPS_DEV_BYTES, "group buffer size");
+
+__device__ __forceinline__ const OptHyperArr& opt_hyper(const OptGroups& g) { return g.h; }
+__device__ __forceinline__ const OptHyperArr& opt_hyper(const OptGroupsDev& g) { return *g.hyp; }
+__host__ __device__ inline void opt_put(OptHyperArr& a, int i, const OptHyper& h) {
+    a.lr[i] = h.lr;
+    a.decay[i] = h.decay;
+    a.b1[i] = h.b1;
+    a.omb1[i] = h.omb1;
+    a.b2[i] = h.b2;
+    a.omb2[i] = h.omb2;
+    a.eps[i] = h.eps;
+}
+
+// host and device form the derived values with the same expression; on the device the product and the difference must stay two
+// roundings (the host has no fused multiply-add to contract them into)
+__host__ __device__ inline bool opt_derive(const mtlora_adamw_group& s, OptHyper& h) {
+#pragma clang fp contract(off)
+    h.lr = (float)s.lr;
+    h.decay = (float)(1.0 - s.lr * s.weight_decay);
+    h.b1 = (float)s.beta1;
+    h.omb1 = (float)(1.0 - s.beta1);
+    h.b2 = (float)s.beta2;
+    h.omb2 = (float)(1.0 - s.beta2);
+    h.eps = (float)s.eps;
+    return s.lr >= 0.0 && s.eps >= 0.0 && s.weight_decay >= 0.0 && s.beta1 >= 0.0 && s.beta1 < 1.0 && s.beta2 >= 0.0 && s.beta2 < 1.0;
+}
 
 // control block words (floats), MTLORA_ADAMW_CTRL_WORDS of them
 enum { OC_NORM = 0, OC_FOUND_INF = 1, OC_COEF = 2, OC_GMUL = 3, OC_STEP = 4, OC_BC = 8 };  // OC_BC + 2 g: bc1, sqrt(bc2) of group g
@@ -130,8 +176,9 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_norm(const OptTensor* __r
     }
 }
 
+template <class G>  // OptGroups (by value) or OptGroupsDev
 __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __restrict__ partials, const uint32_t* __restrict__ flags,
-                                                              int n_chunks, const OptGroups grp, float max_norm, float* __restrict__ ctrl,
+                                                              int n_chunks, const G grp, float max_norm, float* __restrict__ ctrl,
                                                               float* __restrict__ norm_out, float* __restrict__ scale,
                                                               int32_t* __restrict__ tracker, float growth, float backoff, int interval) {
     __shared__ double red[OPT_THREADS];
@@ -140,12 +187,27 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __res
     const int tid = threadIdx.x;
     double s = 0.0;
     uint32_t f = 0u;
+    double b1d = 0.0, b2d = 0.0;
+    if (tid < grp.n) {
+        if constexpr (__is_same(G, OptGroupsDev)) {
+            const mtlora_adamw_group r = grp.rec[tid];
+            OptHyper h;
+            if (!opt_derive(r, h)) f = 1u;  // what the host entry rejects: found_inf, a skipped step
+            opt_put(*grp.hyp, tid, h);
+            b1d = r.beta1;
+            b2d = r.beta2;
+        } else {
+            b1d = grp.b1d[tid];
+            b2d = grp.b2d[tid];
+        }
+    }
+    const uint32_t bad_hyper = f;
     for (int i = tid; i < n_chunks; i += OPT_THREADS) {
         s += (double)partials[i];
         f |= flags[i];
     }
     red[tid] = s;
-    fl[tid] = f;
+    fl[tid] = f | (bad_hyper << 1);
     __syncthreads();
     for (int w = OPT_THREADS / 2; w > 0; w >>= 1) {
         if (tid < w) {
@@ -158,7 +220,7 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __res
         const bool found = fl[0] != 0u;
         const float sc = scale ? *scale : 1.f;
         const float inv = (float)(1.0 / (double)sc);  // GradScaler.unscale_: the reciprocal in double, applied in fp32
-        const float norm = (float)(sqrt(red[0]) * (double)inv);
+        const float norm = (fl[0] & 2u) ? __builtin_nanf("") : (float)(sqrt(red[0]) * (double)inv);
         const float coef = max_norm > 0.f ? fminf(1.f, max_norm / (norm + 1e-6f)) : 1.f;  // clip_grad_norm_
         const float st = ctrl[OC_STEP] + (found ? 0.f : 1.f);
         ctrl[OC_NORM] = norm;
@@ -187,8 +249,8 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __res
     __syncthreads();
     if (tid < grp.n) {
         const double t = (double)step_new;
-        ctrl[OC_BC + 2 * tid] = (float)(1.0 - pow(grp.b1d[tid], t));
-        ctrl[OC_BC + 2 * tid + 1] = (float)sqrt(1.0 - pow(grp.b2d[tid], t));
+        ctrl[OC_BC + 2 * tid] = (float)(1.0 - pow(b1d, t));
+        ctrl[OC_BC + 2 * tid + 1] = (float)sqrt(1.0 - pow(b2d, t));
     }
 }
 
@@ -204,9 +266,10 @@ __device__ __forceinline__ void opt_adamw(float& p, float g, float& m, float& v,
     p -= c.step_size * (m / (sqrtf(v) * c.inv_bc2s + c.eps));
 }
 
+template <class G>
 __global__ __launch_bounds__(OPT_THREADS) void k_optim_step(const OptTensor* __restrict__ tens, const OptChunk* __restrict__ chunks,
                                                             const float* const* __restrict__ grads, const float* __restrict__ ctrl,
-                                                            const OptGroups grp) {
+                                                            const G grp) {
     if (ctrl[OC_FOUND_INF] != 0.f) return;  // skipped step: nothing is written
     const int tid = threadIdx.x;
     const OptChunk ck = chunks[blockIdx.x];
@@ -221,16 +284,17 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_step(const OptTensor* __r
     float* m = t.m + off;
     float* v = t.v + off;
     const int gi = t.group;
+    const OptHyperArr& h = opt_hyper(grp);
     OptCoef c;
     c.gmul = ctrl[OC_GMUL];
-    c.decay = grp.decay[gi];
-    c.b1 = grp.b1[gi];
-    c.omb1 = grp.omb1[gi];
-    c.b2 = grp.b2[gi];
-    c.omb2 = grp.omb2[gi];
-    c.step_size = grp.lr[gi] / ctrl[OC_BC + 2 * gi];
+    c.decay = h.decay[gi];
+    c.b1 = h.b1[gi];
+    c.omb1 = h.omb1[gi];
+    c.b2 = h.b2[gi];
+    c.omb2 = h.omb2[gi];
+    c.step_size = h.lr[gi] / ctrl[OC_BC + 2 * gi];
     c.inv_bc2s = 1.f / ctrl[OC_BC + 2 * gi + 1];
-    c.eps = grp.eps[gi];
+    c.eps = h.eps[gi];
     if ((((uintptr_t)g | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15u) == 0) {
         const int nv = n >> 2;
         f32x4 xg[OPT_VPT], xp[OPT_VPT], xm[OPT_VPT], xv[OPT_VPT];
@@ -293,6 +357,39 @@ static int opt_count(int64_t n_tensors, const int64_t* numel, int64_t* n_chunks)
     return MTLORA_OK;
 }
 
+// argument checks shared by the two entries, before any launch
+static int opt_check(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const void* groups, int n_groups,
+                     const float* ctrl, const float* norm_out, const float* scale, const int32_t* growth_tracker, float growth_factor,
+                     float backoff_factor, int growth_interval, const void* scratch, int64_t scratch_bytes) {
+    if (n_tensors <= 0 || n_tensors >= ((int64_t)1 << 31) || n_chunks < 0 || n_chunks >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
+    if (n_groups < 1 || n_groups > OPT_MAXG) return MTLORA_ERR_UNSUPPORTED;
+    if (!table || !grads || !groups || !ctrl || !scratch) return MTLORA_ERR_NULL;
+    if ((scale == nullptr) != (growth_tracker == nullptr)) return MTLORA_ERR_NULL;
+    if (((uintptr_t)table | (uintptr_t)grads | (uintptr_t)scratch) & 7u) return MTLORA_ERR_ALIGN;
+    if (((uintptr_t)ctrl | (uintptr_t)norm_out | (uintptr_t)scale | (uintptr_t)growth_tracker) & 3u) return MTLORA_ERR_ALIGN;
+    if (scratch_bytes < n_chunks * 8) return MTLORA_ERR_WORKSPACE;
+    if (scale && (growth_interval < 1 || !(growth_factor > 1.f) || !(backoff_factor > 0.f && backoff_factor < 1.f))) return MTLORA_ERR_SHAPE;
+    return MTLORA_OK;
+}
+
+template <class G>
+static int opt_launch(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const G& g, float max_norm, float* ctrl,
+                      float* norm_out, float* scale, int32_t* growth_tracker, float growth_factor, float backoff_factor,
+                      int growth_interval, void* scratch, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const OptTensor* te = reinterpret_cast<const OptTensor*>(table);
+    const OptChunk* ce = reinterpret_cast<const OptChunk*>(te + n_tensors);
+    const float* const* gp = reinterpret_cast<const float* const*>(grads);
+    float* partials = reinterpret_cast<float*>(scratch);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(partials + n_chunks);
+    if (n_chunks > 0) hipLaunchKernelGGL(k_optim_norm, dim3((unsigned)n_chunks), dim3(OPT_THREADS), 0, s, te, ce, gp, partials, flags);
+    hipLaunchKernelGGL(k_optim_finish<G>, dim3(1), dim3(OPT_THREADS), 0, s, partials, flags, (int)n_chunks, g, max_norm, ctrl, norm_out,
+                       scale, growth_tracker, growth_factor, backoff_factor, growth_interval);
+    if (n_chunks > 0) hipLaunchKernelGGL(k_optim_step<G>, dim3((unsigned)n_chunks), dim3(OPT_THREADS), 0, s, te, ce, gp, ctrl, g);
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -341,43 +438,37 @@ int mtlora_adamw_update(const void* table, const void* grads, int64_t n_tensors,
                         int n_groups, float max_norm, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker,
                         float growth_factor, float backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes,
                         void* stream) {
-    if (n_tensors <= 0 || n_tensors >= ((int64_t)1 << 31) || n_chunks < 0 || n_chunks >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
-    if (n_groups < 1 || n_groups > OPT_MAXG) return MTLORA_ERR_UNSUPPORTED;
-    if (!table || !grads || !groups || !ctrl || !scratch) return MTLORA_ERR_NULL;
-    if ((scale == nullptr) != (growth_tracker == nullptr)) return MTLORA_ERR_NULL;
-    if (((uintptr_t)table | (uintptr_t)grads | (uintptr_t)scratch) & 7u) return MTLORA_ERR_ALIGN;
-    if (((uintptr_t)ctrl | (uintptr_t)norm_out | (uintptr_t)scale | (uintptr_t)growth_tracker) & 3u) return MTLORA_ERR_ALIGN;
-    if (scratch_bytes < n_chunks * 8) return MTLORA_ERR_WORKSPACE;
-    if (scale && (growth_interval < 1 || !(growth_factor > 1.f) || !(backoff_factor > 0.f && backoff_factor < 1.f))) return MTLORA_ERR_SHAPE;
+    const int rc = opt_check(table, grads, n_tensors, n_chunks, groups, n_groups, ctrl, norm_out, scale, growth_tracker, growth_factor,
+                             backoff_factor, growth_interval, scratch, scratch_bytes);
+    if (rc != MTLORA_OK) return rc;
     OptGroups g = {};
     g.n = n_groups;
     for (int i = 0; i < n_groups; ++i) {
-        const mtlora_adamw_group& s = groups[i];
-        if (!(s.lr >= 0.0) || !(s.eps >= 0.0) || !(s.weight_decay >= 0.0) || !(s.beta1 >= 0.0 && s.beta1 < 1.0) ||
-            !(s.beta2 >= 0.0 && s.beta2 < 1.0))
-            return MTLORA_ERR_SHAPE;
-        g.lr[i] = (float)s.lr;
-        g.decay[i] = (float)(1.0 - s.lr * s.weight_decay);
-        g.b1[i] = (float)s.beta1;
-        g.omb1[i] = (float)(1.0 - s.beta1);
-        g.b2[i] = (float)s.beta2;
-        g.omb2[i] = (float)(1.0 - s.beta2);
-        g.eps[i] = (float)s.eps;
-        g.b1d[i] = s.beta1;
-        g.b2d[i] = s.beta2;
+        OptHyper h;
+        if (!opt_derive(groups[i], h)) return MTLORA_ERR_SHAPE;
+        opt_put(g.h, i, h);
+        g.b1d[i] = groups[i].beta1;
+        g.b2d[i] = groups[i].beta2;
     }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const OptTensor* te = reinterpret_cast<const OptTensor*>(table);
-    const OptChunk* ce = reinterpret_cast<const OptChunk*>(te + n_tensors);
-    const float* const* gp = reinterpret_cast<const float* const*>(grads);
-    float* partials = reinterpret_cast<float*>(scratch);
-    uint32_t* flags = reinterpret_cast<uint32_t*>(partials + n_chunks);
-    if (n_chunks > 0) hipLaunchKernelGGL(k_optim_norm, dim3((unsigned)n_chunks), dim3(OPT_THREADS), 0, s, te, ce, gp, partials, flags);
-    hipLaunchKernelGGL(k_optim_finish, dim3(1), dim3(OPT_THREADS), 0, s, partials, flags, (int)n_chunks, g, max_norm, ctrl, norm_out, scale,
-                       growth_tracker, growth_factor, backoff_factor, growth_interval);
-    if (n_chunks > 0) hipLaunchKernelGGL(k_optim_step, dim3((unsigned)n_chunks), dim3(OPT_THREADS), 0, s, te, ce, gp, ctrl, g);
-    MTL_CHECK_LAUNCH();
-    return MTLORA_OK;
+    return opt_launch(table, grads, n_tensors, n_chunks, g, max_norm, ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor,
+                      growth_interval, scratch, stream);
+}
+
+int mtlora_adamw_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks,
+                            const mtlora_adamw_group* groups_dev, int n_groups, float max_norm, float* ctrl, float* norm_out, float* scale,
+                            int32_t* growth_tracker, double growth_factor, double backoff_factor, int growth_interval, void* scratch,
+                            int64_t scratch_bytes, void* stream) {
+    const float growth = (float)growth_factor, backoff = (float)backoff_factor;
+    const int rc = opt_check(table, grads, n_tensors, n_chunks, groups_dev, n_groups, ctrl, norm_out, scale, growth_tracker, growth, backoff,
+                             growth_interval, scratch, scratch_bytes);
+    if (rc != MTLORA_OK) return rc;
+    if ((uintptr_t)groups_dev & 7u) return MTLORA_ERR_ALIGN;
+    OptGroupsDev g;
+    g.rec = groups_dev;  // the records are only read; the tail behind them is the library's
+    g.hyp = reinterpret_cast<OptHyperArr*>(const_cast<mtlora_adamw_group*>(groups_dev) + OPT_MAXG);
+    g.n = n_groups;
+    return opt_launch(table, grads, n_tensors, n_chunks, g, max_norm, ctrl, norm_out, scale, growth_tracker, growth, backoff,
+                      growth_interval, scratch, stream);
 }
 
 }  // extern "C"

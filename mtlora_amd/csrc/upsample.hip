@@ -36,6 +36,17 @@ struct V4<bf16> {
     }
 };
 
+template <>
+struct V4<f16> {  // the fp16 step's heads: ATen's bilinear backward adds with atomics, so its gradients differ from run to run
+    static __device__ __forceinline__ f32x4 ld(const f16* p) {
+        const f16x4 v = *reinterpret_cast<const f16x4*>(p);
+        return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+    }
+    static __device__ __forceinline__ void st(f16* p, f32x4 v) {
+        *reinterpret_cast<f16x4*>(p) = f16x4{(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
+    }
+};
+
 __device__ __forceinline__ void src_index(int o, float rs, int n_in, int& i0, int& i1, float& f) {
     float s = ((float)o + 0.5f) * rs - 0.5f;
     s = s < 0.f ? 0.f : s;
@@ -133,7 +144,7 @@ __global__ __launch_bounds__(256) void k_up_bwd(const UpParams p) {
 
 static int check_up(const void* a, const void* b, int64_t B, int h, int w, int C, int S, int64_t ld, int dtype) {
     if (B < 0 || h <= 0 || w <= 0 || C <= 0 || S <= 0 || ld < C) return MTLORA_ERR_SHAPE;
-    if (dtype != MTLORA_F32 && dtype != MTLORA_BF16) return MTLORA_ERR_DTYPE;
+    if (dtype != MTLORA_F32 && dtype != MTLORA_BF16 && dtype != MTLORA_F16) return MTLORA_ERR_DTYPE;
     if (C % 4 || ld % 4) return MTLORA_ERR_ALIGN;
     if (B > 0 && (!a || !b)) return MTLORA_ERR_NULL;
     const size_t al = dtype == MTLORA_F32 ? 16 : 8;
@@ -158,6 +169,8 @@ int mtlora_upsample_cl_fwd(const void* coarse, void* fine, int64_t B, int h, int
     MtlProfScope prof(PK_UPSAMPLE, (double)mtl_elem_size(dtype) * B * h * w * C * (1.0 + (double)scale * scale), s);
     if (dtype == MTLORA_F32)
         hipLaunchKernelGGL(k_up_fwd<float>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    else if (dtype == MTLORA_F16)
+        hipLaunchKernelGGL(k_up_fwd<f16>, dim3((unsigned)blocks), dim3(256), 0, s, p);
     else
         hipLaunchKernelGGL(k_up_fwd<bf16>, dim3((unsigned)blocks), dim3(256), 0, s, p);
     MTL_CHECK_LAUNCH();
@@ -176,6 +189,8 @@ int mtlora_upsample_cl_bwd(const void* grad_fine, void* grad_coarse, int64_t B, 
     MtlProfScope prof(PK_UPSAMPLE, (double)mtl_elem_size(dtype) * B * h * w * C * (1.0 + (double)scale * scale), s);
     if (dtype == MTLORA_F32)
         hipLaunchKernelGGL(k_up_bwd<float>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    else if (dtype == MTLORA_F16)
+        hipLaunchKernelGGL(k_up_bwd<f16>, dim3((unsigned)blocks), dim3(256), 0, s, p);
     else
         hipLaunchKernelGGL(k_up_bwd<bf16>, dim3((unsigned)blocks), dim3(256), 0, s, p);
     MTL_CHECK_LAUNCH();

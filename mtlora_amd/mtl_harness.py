@@ -165,7 +165,7 @@ class HighResolutionHead(nn.Module):
         xc = [m.permute(0, 2, 3, 1) for m in x]  # the Downsampler's maps are channels-last views
         chans = [t.shape[3] for t in xc]
         if (x[0].is_cuda and all(t.is_contiguous() for t in xc) and all(c % 4 == 0 for c in chans[1:])
-                and len({t.dtype for t in xc}) == 1 and xc[0].dtype in (torch.float32, torch.bfloat16)
+                and len({t.dtype for t in xc}) == 1 and xc[0].dtype in (torch.float32, torch.bfloat16, torch.float16)
                 and all(Hh % t.shape[1] == 0 and Ww % t.shape[2] == 0 and Hh // t.shape[1] == Ww // t.shape[2] for t in xc)):
             # upsample kernels write straight into the channel slices of the concatenated pixel matrix (padded so that
             # every slice starts at a multiple of 4 channels and rows are 16-byte aligned); the 1x1 conv weight gets the
@@ -376,7 +376,8 @@ def build_optimizer(model: nn.Module, lr=5e-4, weight_decay=0.05, fused: Optiona
     """AdamW(betas .9/.999, eps 1e-8, wd .05) with the no-decay set of optimizer.py:71-85 (1-D tensors, biases,
     relative_position_bias_table); only trainable tensors are handed over (frozen ones never get a grad in the
     reference either).  ``impl="hip"``: the same two groups under ``optim.FusedAdamW`` (clip + unscale + AdamW as
-    three launches, csrc/optim.hip; ``fused`` / ``capturable`` do not apply)."""
+    three launches, csrc/optim.hip; ``fused`` does not apply; ``capturable=True``: the form ``GraphedTrainStep`` can capture,
+    hyper-parameters read from device memory at replay)."""
     if impl not in ("torch", "hip"):
         raise ValueError(f"build_optimizer: impl must be 'torch' or 'hip', got {impl!r}")
     decay, no_decay = [], []
@@ -389,7 +390,7 @@ def build_optimizer(model: nn.Module, lr=5e-4, weight_decay=0.05, fused: Optiona
             decay.append(p)
     groups = [{"params": decay}, {"params": no_decay, "weight_decay": 0.0}]
     if impl == "hip":
-        return FusedAdamW(groups, lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay)
+        return FusedAdamW(groups, lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay, capturable=bool(capturable))
     if fused is None:
         fused = all(p.is_cuda for p in decay + no_decay)
     return torch.optim.AdamW(groups, lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay, fused=fused,
@@ -616,7 +617,12 @@ class GraphedTrainStep:
       by a captured add at the start of every replay and added to the seeds by the kernels at run time; DropPath
       uses torch's graph-safe generator;
     * data: ``images`` / ``targets`` are static buffers -- ``copy_`` the next batch into them before calling;
-    * optimizer: must be ``capturable`` (``build_optimizer(..., capturable=True)``).
+    * optimizer: must be ``capturable`` (``build_optimizer(..., capturable=True)``).  With ``impl="hip"`` the update is
+      ``FusedAdamW.clip_and_step``'s three launches inside the graph, ``loss_scaler`` (an ``optim.LossScaler``: the fp16 recipe)
+      is allowed, the learning rate follows ``optimizer.param_groups`` from replay to replay (the values are pushed to the
+      device before each replay; nothing of them is baked in) and ``self.grad_norm`` is the unscaled gradient norm of the last
+      step, a 0-d device tensor.  A non-capturable ``FusedAdamW`` is a ``TypeError``, not a fallback.  With a torch optimizer the
+      hyper-parameters of the capture step are what every replay uses.
     Falls back to the eager step (``self.graphed = False``, reason in ``self.why``) if capture fails.
 
     Not bench.py's default (``--graph``): at C2 the eager step with its side streams is faster (34.8 ms vs 36.5 ms for the
@@ -629,10 +635,20 @@ class GraphedTrainStep:
     SEED_STEP = 0x1E3779B97F4A7C15  # odd: a full-period walk of the 64-bit seed offset
 
     def __init__(self, model, criterion, optimizer, images, targets, clip_grad: float = 5.0, reducer=None,
-                 amp_dtype: Optional[torch.dtype] = torch.bfloat16, fused_loss: bool = True, warmup: int = 3):
+                 amp_dtype: Optional[torch.dtype] = torch.bfloat16, fused_loss: bool = True, warmup: int = 3, loss_scaler=None):
+        self.fused_opt = isinstance(optimizer, FusedAdamW)
+        if self.fused_opt and not optimizer._capturable:
+            raise TypeError("GraphedTrainStep: a FusedAdamW inside the graph must be built with capturable=True "
+                            "(build_optimizer(impl='hip', capturable=True)): its hyper-parameters travel in the launch arguments, "
+                            "which a replay cannot follow")
+        if loss_scaler is not None and not self.fused_opt:
+            raise TypeError("GraphedTrainStep: loss_scaler needs the HIP optimizer (build_optimizer(impl='hip', capturable=True))")
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
         self.images, self.targets = images, targets
         self.clip_grad, self.reducer, self.amp_dtype, self.fused_loss = clip_grad, reducer, amp_dtype, fused_loss
+        self.loss_scaler, self.grad_norm = loss_scaler, None
+        if loss_scaler is not None:
+            loss_scaler._lazy_init(images.device)  # its two device words exist before the capture begins
         self.graphed, self.why = False, ""
         self.seed = torch.zeros(1, dtype=torch.int64, device=images.device)
         Fn.set_seed_offset(self.seed)
@@ -649,6 +665,8 @@ class GraphedTrainStep:
             self.why = f"{type(e).__name__}: {e}"
             torch.cuda.synchronize()
             self.g_bwd = self.g_opt = None
+            if self.fused_opt:
+                optimizer.reset_capture()  # the graphs are gone: their gradient addresses with them
             optimizer.zero_grad(set_to_none=True)
             Fn.set_seed_offset(None)  # the eager fallback draws its dropout seeds on the host again
 
@@ -660,11 +678,17 @@ class GraphedTrainStep:
         params = [p for g in self.optimizer.param_groups for p in g["params"]]
         bufs = [b for b in self.model.buffers() if b.is_floating_point()]
 
+        # what the torch path never had: FusedAdamW's control block (step counter) and flat state buffers, the scaler's two words
+        extra = [self.optimizer._ctrl, self.optimizer._exp_avg, self.optimizer._exp_avg_sq] if self.fused_opt else []
+        if self.loss_scaler is not None:
+            extra += [self.loss_scaler._scale, self.loss_scaler._growth_tracker]
+
         def snap():
-            st = {id(p): {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.optimizer.state.get(p, {}).items()}
-                  for p in params}
+            st = {} if self.fused_opt else {
+                id(p): {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.optimizer.state.get(p, {}).items()}
+                for p in params}  # (FusedAdamW's state entries are views of the buffers in `extra`)
             return ([p.detach().clone() for p in params], [b.clone() for b in bufs], st, torch.cuda.get_rng_state(),
-                    self.seed.clone())
+                    self.seed.clone(), [t.clone() for t in extra])
 
         def restore(s):
             with torch.no_grad():
@@ -672,12 +696,16 @@ class GraphedTrainStep:
                 if bufs:
                     torch._foreach_copy_(bufs, s[1])
                 for p in params:
-                    for k, v in s[2][id(p)].items():
+                    for k, v in s[2].get(id(p), {}).items():
                         if torch.is_tensor(v):
                             self.optimizer.state[p][k].copy_(v)
                 self.seed.copy_(s[4])
+                for t, v in zip(extra, s[5]):
+                    t.copy_(v)
             torch.cuda.set_rng_state(s[3])
 
+        if self.fused_opt:
+            self.optimizer.push_hyperparameters()  # (also sends the captured gradient addresses, in front of the first replay)
         torch.cuda.synchronize()
         s0 = snap()
         seen = []
@@ -690,10 +718,15 @@ class GraphedTrainStep:
             torch.cuda.synchronize()
             seen.append((self.loss.clone(), torch.stack([p.detach().double().sum() for p in params]).sum()))
         restore(s0)
+        if self.fused_opt:
+            self.optimizer.bump_versions()  # the parameters were rewritten: copies made from them are stale
         for l, c in seen[1:]:
             if not (torch.equal(l, seen[0][0]) and torch.equal(c, seen[0][1]) and torch.isfinite(l).all()):
-                return False, ("graph replays from identical state differ (loss %r vs %r): captured small memsets do not replay "
-                               "on this ROCm stack; running eagerly" % (seen[0][0].item(), l.item()))
+                return False, ("graph replays from identical state differ (loss %r vs %r, parameter sums %r); running eagerly.  A "
+                               "loss that differs from the second replay on points at a captured small memset (an ATen reduction), "
+                               "which does not replay on this ROCm stack; an equal loss with differing parameters at a gradient "
+                               "that is summed with atomics (an ATen backward such as bilinear interpolation)"
+                               % (seen[0][0].item(), l.item(), [c.item() for _, c in seen]))
         return True, ""
 
     # -- pieces of the step (shared by the eager fallback and the capture)
@@ -718,7 +751,7 @@ class GraphedTrainStep:
             self.reducer.prepare(defer=True)
         Fn.set_factor_stream(side)
         try:
-            loss.backward()
+            (loss if self.loss_scaler is None else self.loss_scaler.scale(loss)).backward()
         finally:
             Fn.set_factor_stream(None)
         if side is not None:  # joins the side stream back (inside a capture: closes the graph's second branch)
@@ -731,6 +764,10 @@ class GraphedTrainStep:
     def _optimize(self):
         if self.reducer is not None:
             self.reducer.unpack()
+        if self.fused_opt:  # clip + unscale + AdamW + scaler update: three launches (optim.FusedAdamW)
+            self.grad_norm = self.optimizer.clip_and_step(self.clip_grad or None, self.loss_scaler)
+            self.optimizer.zero_grad(set_to_none=True)
+            return
         params = [p for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
         if self.clip_grad:
             torch.nn.utils.clip_grad_norm_(params, self.clip_grad, foreach=True)
@@ -769,8 +806,12 @@ class GraphedTrainStep:
     def __call__(self):
         if not self.graphed:
             return self._eager()
+        if self.fused_opt:
+            self.optimizer.push_hyperparameters()  # a non-captured copy in front of the replay, only when param_groups changed
         self.g_bwd.replay()
         if self.g_opt is not None:
             self.reducer.all_reduce_packed()
             self.g_opt.replay()
+        if self.fused_opt:
+            self.optimizer.bump_versions()  # host code inside clip_and_step does not replay
         return self.loss

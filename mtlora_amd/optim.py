@@ -22,6 +22,8 @@ from . import _lib
 __all__ = ["FusedAdamW", "LossScaler", "uniform_step"]
 
 _STATE_ALIGN = 4  # elements: every tensor's slice of the flat state buffers starts 16-byte aligned
+_HYPER_SLOTS = 4  # pinned staging slots of a capturable optimizer's hyper-parameter uploads
+_GROUP_WORDS = 5  # doubles per mtlora_adamw_group record
 
 
 def uniform_step(state: Dict[Any, Dict[str, Any]]) -> float:
@@ -46,19 +48,31 @@ class FusedAdamW(torch.optim.Optimizer):
     * Every parameter that had a gradient gets its ``_version`` bumped after each call -- the kernels write through raw pointers,
       and ``MTLoRALinear`` / ``FactorPacker`` judge freshness by ``_version``.  This includes skipped steps (the skip is decided
       on the device; the host cannot know).
+    * ``capturable=True``: ``clip_and_step`` may be captured in a HIP graph (``torch.cuda.graph``,
+      ``mtl_harness.GraphedTrainStep``) and replayed.  The hyper-parameters then live in a device buffer the kernels read at run
+      time (``mtlora_adamw_update_dev``; bit-identical to the by-value path), so a replay follows ``param_groups``: set them,
+      call ``push_hyperparameters()`` (an ordinary copy on the current stream, only if something changed), replay.  After a
+      replay call ``bump_versions()`` -- the version bump above is host code and is not replayed.  Hyper-parameters are NOT
+      validated on this path: a value the by-value path rejects (negative lr, beta >= 1, nan) makes the device skip the step and
+      return a nan norm.  Inside a capture the scaler must already be initialised and the hyper-parameters pushed; the gradient
+      addresses of the capture go into a device array of their own, uploaded once by the first ``push_hyperparameters()`` after
+      the capture (so that call is needed before the first replay even if no value changed), and ONE set of gradient addresses
+      can be captured per optimizer (eager calls between replays use buffers of their own).
     """
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 amsgrad: bool = False, maximize: bool = False):
+                 amsgrad: bool = False, maximize: bool = False, capturable: bool = False):
         if amsgrad or maximize:
             raise ValueError("mtlora_amd: FusedAdamW supports neither amsgrad nor maximize")
         if isinstance(lr, torch.Tensor):
-            raise ValueError("mtlora_amd: FusedAdamW takes lr as a Python number (it travels in the launch arguments)")
+            raise ValueError("mtlora_amd: FusedAdamW takes lr as a Python number (it travels in the launch arguments, or with "
+                             "capturable=True through push_hyperparameters())")
+        self._capturable = bool(capturable)
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"mtlora_amd: invalid AdamW hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
         # torch AdamW's group keys, so that the two state_dict formats interchange
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
-                        capturable=False, differentiable=False, fused=None, decoupled_weight_decay=True)
+                        capturable=self._capturable, differentiable=False, fused=None, decoupled_weight_decay=True)
         super().__init__(params, defaults)
         if len(self.param_groups) > _lib.ADAMW_MAX_GROUPS:
             raise ValueError(f"mtlora_amd: FusedAdamW supports up to {_lib.ADAMW_MAX_GROUPS} parameter groups")
@@ -107,6 +121,22 @@ class FusedAdamW(torch.optim.Optimizer):
         self._grad_ptrs = torch.zeros(nt, dtype=torch.int64, device=dev)
         self._scratch = torch.empty(max(self._scratch_bytes // 4, 1), dtype=torch.float32, device=dev)
         self._groups = (_lib.AdamwGroup * len(self.param_groups))()
+        if self._capturable:
+            # the records the kernels read (and, behind them, what the library derives from them): never re-allocated
+            self._hyper_dev = torch.zeros(_lib.ADAMW_GROUPS_DEV_BYTES // 8, dtype=torch.float64, device=dev)
+            self._hyper_pushed = None  # the values last uploaded
+            # a ring of persistent pinned slots, each guarded by the event of the copy that last read it (as data.DeviceLoader's)
+            self._hyper_ring = [torch.zeros(_GROUP_WORDS * _lib.ADAMW_MAX_GROUPS, dtype=torch.float64, pin_memory=True)
+                                for _ in range(_HYPER_SLOTS)]
+            self._hyper_done: List[Optional[torch.cuda.Event]] = [None] * _HYPER_SLOTS
+            self._hyper_slot = 0
+            # the captured call's gradient pointers: a pinned buffer and a device array of their own, both written ONCE (at
+            # capture / in front of the first replay) and alive as long as the optimizer; eager calls never touch them
+            self._graph_ptr_host = torch.zeros(nt, dtype=torch.int64, pin_memory=True)
+            self._graph_grad_ptrs = torch.zeros(nt, dtype=torch.int64, device=dev)
+            self._graph_ptrs: Optional[List[int]] = None
+            self._graph_ptrs_sent = True  # (nothing to send yet)
+            self._graph_live: List[torch.Tensor] = []
 
     def _slot(self, i: int, buf: torch.Tensor) -> torch.Tensor:
         p = self._params[i]
@@ -116,6 +146,61 @@ class FusedAdamW(torch.optim.Optimizer):
         self.state[self._params[i]] = {"step": self._ctrl[4], "exp_avg": self._slot(i, self._exp_avg),
                                        "exp_avg_sq": self._slot(i, self._exp_avg_sq)}
         self._has_state[i] = True
+
+    # ---- capturable: hyper-parameters on the device ------------------------------------------------------------------------
+    def _hyper_values(self) -> List[float]:
+        vals: List[float] = []
+        for g in self.param_groups:
+            vals += [float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"])]
+        return vals
+
+    def push_hyperparameters(self) -> bool:
+        """upload ``param_groups``' lr / betas / eps / weight_decay to the device records if they differ from what was pushed
+        last (capturable only): one small non-captured copy on the current stream, so call it on the stream that replays, before
+        ``replay()``.  The first call after a capture also uploads the captured gradient addresses.  Returns whether
+        hyper-parameters were uploaded."""
+        if not self._capturable:
+            raise RuntimeError("mtlora_amd: push_hyperparameters() needs FusedAdamW(capturable=True); without it the "
+                               "hyper-parameters travel in the launch arguments")
+        if not self._graph_ptrs_sent and not torch.cuda.is_current_stream_capturing():
+            self._graph_grad_ptrs.copy_(self._graph_ptr_host, non_blocking=True)  # the captured gradient addresses, once
+            self._graph_ptrs_sent = True
+        vals = self._hyper_values()
+        if vals == self._hyper_pushed:
+            return False
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("mtlora_amd: the hyper-parameters changed inside a graph capture; the upload would be baked into "
+                               "the graph -- call push_hyperparameters() before capturing")
+        _lib.require_gpu(self._params[0])
+        k = self._hyper_slot
+        if self._hyper_done[k] is not None:
+            self._hyper_done[k].synchronize()  # the copy that last read this slot has finished
+        slot = self._hyper_ring[k][:len(vals)]
+        slot.copy_(torch.tensor(vals, dtype=torch.float64))
+        self._hyper_dev[:len(vals)].copy_(slot, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._hyper_done[k] = ev
+        self._hyper_slot = (k + 1) % _HYPER_SLOTS
+        self._hyper_pushed = vals
+        return True
+
+    def bump_versions(self) -> None:
+        """bump ``_version`` of the parameters the captured ``clip_and_step`` updates -- call it after every replay, so that
+        ``MTLoRALinear`` / ``FactorPacker`` copies made from them are seen as stale (the bump inside ``clip_and_step`` is host
+        code: it ran at capture, not at replay)"""
+        if self._capturable and self._graph_live:
+            if not self._graph_ptrs_sent:  # the replay that just ran read an all-null pointer table: it did nothing but count a step
+                raise RuntimeError("mtlora_amd: the captured update was replayed before push_hyperparameters() sent its gradient "
+                                   "addresses; call push_hyperparameters() before every replay()")
+            torch.autograd.graph.increment_version(self._graph_live)
+
+    def reset_capture(self) -> None:
+        """forget the captured gradient addresses, so that ``clip_and_step`` can be captured again (after a capture that was
+        aborted, or once the old graph is destroyed).  Replaying a graph captured before this call is an error the optimizer
+        cannot detect."""
+        if self._capturable:
+            self._graph_ptrs, self._graph_live, self._graph_ptrs_sent = None, [], True
 
     # ---- the update --------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -138,13 +223,26 @@ class FusedAdamW(torch.optim.Optimizer):
             ptrs.append(g.data_ptr())
             live.append(p)
         dev = params[0].device
-        # pinned staging from torch's caching host allocator: the block is not reused before this copy has run
-        host = torch.empty(len(ptrs), dtype=torch.int64, pin_memory=True)
-        host.copy_(torch.tensor(ptrs, dtype=torch.int64))
-        self._grad_ptrs.copy_(host, non_blocking=True)
-        for gi, g in enumerate(self.param_groups):
-            s = self._groups[gi]
-            s.lr, (s.beta1, s.beta2), s.eps, s.weight_decay = g["lr"], g["betas"], g["eps"], g["weight_decay"]
+        capturing = self._capturable and torch.cuda.is_current_stream_capturing()
+        if capturing:
+            if scaler is not None and scaler._scale is None:
+                raise RuntimeError("mtlora_amd: the LossScaler must be initialised before a graph capture (one eager step, or "
+                                   "what GraphedTrainStep does on construction)")
+            if self._graph_ptrs is None:
+                self._graph_ptr_host.copy_(torch.tensor(ptrs, dtype=torch.int64))
+                self._graph_ptrs, self._graph_live, self._graph_ptrs_sent = ptrs, live, False
+            elif ptrs != self._graph_ptrs:  # the device array the earlier graph reads would have to change under it
+                raise RuntimeError("mtlora_amd: this FusedAdamW was already captured with other gradient addresses; one capture "
+                                   "per optimizer (reset_capture() once the old graph is gone, or build a new optimizer)")
+            # no copy node in the graph: the addresses cannot change from replay to replay, so the array is uploaded ONCE, by an
+            # ordinary copy in front of the first replay (push_hyperparameters)
+            grad_ptrs = self._graph_grad_ptrs
+        else:
+            grad_ptrs = self._grad_ptrs
+            # pinned staging from torch's caching host allocator: the block is not reused before this copy has run
+            host = torch.empty(len(ptrs), dtype=torch.int64, pin_memory=True)
+            host.copy_(torch.tensor(ptrs, dtype=torch.int64))
+            grad_ptrs.copy_(host, non_blocking=True)
         norm = torch.empty((), dtype=torch.float32, device=dev)
         if scaler is not None:
             scaler._lazy_init(dev)
@@ -152,10 +250,20 @@ class FusedAdamW(torch.optim.Optimizer):
             gf, bf, gint = scaler._growth_factor, scaler._backoff_factor, scaler._growth_interval
         else:
             sc, tr, gf, bf, gint = 0, 0, 2.0, 0.5, 1
-        _lib.check(_lib.lib().mtlora_adamw_update(
-            self._table.data_ptr(), self._grad_ptrs.data_ptr(), len(params), self._n_chunks, self._groups, len(self.param_groups),
-            float(max_norm) if max_norm else 0.0, self._ctrl.data_ptr(), norm.data_ptr(), sc, tr, gf, bf, gint,
-            self._scratch.data_ptr(), self._scratch_bytes, _lib.stream_ptr()), "adamw_update")
+        if self._capturable:
+            self.push_hyperparameters()  # (uploads only on change; raises if that happens inside a capture)
+            _lib.check(_lib.lib().mtlora_adamw_update_dev(
+                self._table.data_ptr(), grad_ptrs.data_ptr(), len(params), self._n_chunks, self._hyper_dev.data_ptr(),
+                len(self.param_groups), float(max_norm) if max_norm else 0.0, self._ctrl.data_ptr(), norm.data_ptr(), sc, tr, gf,
+                bf, gint, self._scratch.data_ptr(), self._scratch_bytes, _lib.stream_ptr()), "adamw_update_dev")
+        else:
+            for gi, g in enumerate(self.param_groups):
+                s = self._groups[gi]
+                s.lr, (s.beta1, s.beta2), s.eps, s.weight_decay = g["lr"], g["betas"], g["eps"], g["weight_decay"]
+            _lib.check(_lib.lib().mtlora_adamw_update(
+                self._table.data_ptr(), grad_ptrs.data_ptr(), len(params), self._n_chunks, self._groups, len(self.param_groups),
+                float(max_norm) if max_norm else 0.0, self._ctrl.data_ptr(), norm.data_ptr(), sc, tr, gf, bf, gint,
+                self._scratch.data_ptr(), self._scratch_bytes, _lib.stream_ptr()), "adamw_update")
         if live:
             torch.autograd.graph.increment_version(live)
         self._opt_called = True  # (what torch's LR schedulers look at to order scheduler.step() after optimizer.step())
@@ -199,6 +307,12 @@ class FusedAdamW(torch.optim.Optimizer):
             self._init_state(i)
         self._ctrl.zero_()
         self._ctrl[4] = step
+        for g in self.param_groups:
+            g["capturable"] = self._capturable  # (a property of this object's buffers, not of the checkpoint)
+        if self._capturable:
+            for p in self._graph_live:  # the captured update keeps writing these slices: they keep their (now zero) state entries
+                if not self._has_state[index[id(p)]]:
+                    self._init_state(index[id(p)])
 
 
 class LossScaler:

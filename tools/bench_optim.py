@@ -2,16 +2,26 @@
 -- what train_step runs with build_optimizer(impl="torch") -- against FusedAdamW.clip_and_step (impl="hip", csrc/optim.hip).
 
     python tools/bench_optim.py [--config c2] [--iters 50] [--rounds 5] [--out profiles/optim_ab.txt]
+    python tools/bench_optim.py --graph [--config c2] [--iters 200] [--runs 3] [--out profiles/optim_graph_ab.txt]
 
 Per call and implementation: HOST time (perf_counter around the call, no synchronisation inside: what the update adds to the
 step's issue time) and DEVICE time (HIP events around the call on the launch stream; where the host issues slower than the GPU
 executes this is the issue-bound span, not the kernels' sum).  The two implementations alternate in rounds inside one process;
 the medians over all timed calls are reported.  The gradients alternate between two sets of buffers, so the gradient pointers
 change from call to call as they do after zero_grad(set_to_none=True).  Needs a GPU: there is no CPU fallback to time.
+
+``--graph``: the update as it runs inside ``GraphedTrainStep`` -- captured once in a HIP graph and REPLAYED: clip_grad_norm_(foreach)
++ torch AdamW(fused, capturable=True), what the graph held before, against FusedAdamW(capturable=True).clip_and_step, whose
+learning rate is set anew and pushed to the device before every replay (the torch graph cannot follow it).  Gradients in static
+buffers.  Each leg runs in a process of its own, ``--runs`` times, alternating; per leg the median over its replays of the DEVICE
+time (HIP events around the replay) and of the HOST time of one replay (with push_hyperparameters() and bump_versions() for the
+fused leg), then the median and the spread (max - min) over the runs.
 """
 import argparse
+import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -22,16 +32,125 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 HBM_COPY_TBS = 6.29  # the copy ceiling the project quotes for the MI355X
 
 
+def graph_leg(a):
+    """one leg of --graph in this process: capture the update once, replay it; prints one GRAPH_LEG json line"""
+    from mtlora_amd import mtl_harness as H
+    impl, dev = a.graph_leg, torch.device("cuda:0")
+    model = H.build_config_model(a.config, seed=0).to(dev).train()
+    opt = H.build_optimizer(model, lr=5e-4, impl=impl, capturable=True)
+    ps = [p for g in opt.param_groups for p in g["params"]]
+    gen = torch.Generator(device=dev).manual_seed(1)
+    for p in ps:
+        p.grad = torch.randn(p.shape, device=dev, generator=gen) * 1e-2  # static buffers: the graph holds their addresses
+
+    def update():
+        if impl == "torch":
+            torch.nn.utils.clip_grad_norm_(ps, 5.0, foreach=True)
+            opt.step()
+        else:
+            opt.clip_and_step(5.0)
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            update()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        update()
+
+    def replay(k):
+        if impl == "hip":  # a moving learning rate: set, pushed (one small copy in front of the replay), replayed
+            for g in opt.param_groups:
+                g["lr"] = 5e-4 * (1.0 - 1e-4 * k)
+            opt.push_hyperparameters()
+        graph.replay()
+        if impl == "hip":
+            opt.bump_versions()
+
+    for k in range(a.warmup):
+        replay(k)
+    torch.cuda.synchronize()
+    host, events = [], []
+    w0 = time.perf_counter()
+    for k in range(a.iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        replay(a.warmup + k)
+        e1.record()
+        host.append((time.perf_counter() - t0) * 1e3)
+        events.append((e0, e1))
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - w0) * 1e3 / a.iters
+    devms = [e0.elapsed_time(e1) for e0, e1 in events]
+    finite = all(bool(torch.isfinite(p).all()) for p in ps)
+    print("GRAPH_LEG " + json.dumps({"impl": impl, "device_ms": statistics.median(devms), "host_ms": statistics.median(host),
+                                     "wall_ms": wall, "finite": finite, "tensors": len(ps), "elements": sum(p.numel() for p in ps),
+                                     "gpu": torch.cuda.get_device_name(0)}), flush=True)
+
+
+def graph_ab(a):
+    """--graph: the two legs alternate, each in a fresh child process (this process never opens the GPU)"""
+    rows = {"torch": [], "hip": []}
+    for _ in range(a.runs):
+        for impl in ("torch", "hip"):
+            cmd = [sys.executable, os.path.abspath(__file__), "--graph-leg", impl, "--config", a.config, "--iters", str(a.iters),
+                   "--warmup", str(a.warmup)]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            line = [l for l in r.stdout.splitlines() if l.startswith("GRAPH_LEG ")]
+            if r.returncode != 0 or not line:
+                raise SystemExit(f"bench_optim: the {impl} leg failed (exit {r.returncode}):\n{r.stderr[-2000:]}")
+            rows[impl].append(json.loads(line[-1][len("GRAPH_LEG "):]))
+            print(f"  run {len(rows[impl])} {impl}: device {rows[impl][-1]['device_ms']:.4f} ms per replay", flush=True)
+            if not rows[impl][-1]["finite"]:
+                raise SystemExit(f"bench_optim: the {impl} leg left non-finite parameters")
+    one = rows["hip"][0]
+    lines = [f"bench_optim --graph: clip + AdamW REPLAYED from a HIP graph on the trainable set of {a.config}: {one['tensors']} tensors, "
+             f"{one['elements']} elements",
+             f"box: {one['gpu']}, torch {torch.__version__}, HIP {torch.version.hip}; each leg in its own process, {a.runs} runs each, "
+             f"alternating; {a.iters} timed replays after {a.warmup} warm-up replays",
+             "per replay                                        device ms            host ms              wall ms (iters / sync)",
+             "                                                  median  spread       median  spread       median  spread"]
+    med = {}
+    for impl, what in (("torch", "torch: clip_grad_norm_ + AdamW(capturable)    "), ("hip", "hip:   FusedAdamW(capturable).clip_and_step   ")):
+        cols = []
+        for key in ("device_ms", "host_ms", "wall_ms"):
+            v = [r[key] for r in rows[impl]]
+            med[impl, key] = statistics.median(v)
+            cols.append(f"{med[impl, key]:8.4f} {max(v) - min(v):7.4f}")
+        lines.append(f"{what}   " + "     ".join(cols) + "    runs (device): " + " ".join(f"{r['device_ms']:.4f}" for r in rows[impl]))
+    lines.append(f"hip / torch: device {med['hip', 'device_ms'] / med['torch', 'device_ms']:.3f}, host "
+                 f"{med['hip', 'host_ms'] / med['torch', 'host_ms']:.3f}, wall {med['hip', 'wall_ms'] / med['torch', 'wall_ms']:.3f} "
+                 "(the fused leg's host time includes setting and pushing a new learning rate before every replay)")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2")
-    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--iters", type=int, default=0, help="timed calls per round (default 50), or timed replays per --graph leg (200)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join("profiles", "optim_ab.txt"))
+    ap.add_argument("--graph", action="store_true", help="A/B of the update replayed from a HIP graph, each leg in its own process")
+    ap.add_argument("--runs", type=int, default=3, help="--graph: runs per leg")
+    ap.add_argument("--graph-leg", choices=("torch", "hip"), default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.iters = a.iters or (200 if (a.graph or a.graph_leg) else 50)
+    a.out = a.out or os.path.join("profiles", "optim_graph_ab.txt" if a.graph else "optim_ab.txt")
+    if a.graph:
+        return graph_ab(a)
     if not torch.cuda.is_available():
         raise SystemExit("bench_optim: needs a GPU")
+    if a.graph_leg:
+        return graph_leg(a)
     from mtlora_amd import mtl_harness as H
     dev = torch.device("cuda:0")
     side = {}
