@@ -884,6 +884,53 @@ def window_merge_and_roll_backward(grad_in, B, H, W, C, shift_size, window_size)
 # ----------------------------------------------------------------------------------------------
 # LayerNorm (block glue): reads x once, writes y directly in the dtype the next linear consumes
 # ----------------------------------------------------------------------------------------------
+def _ln_module_ok(mod: torch.nn.Module, last_dim_only: bool = False) -> bool:
+    """an affine ``nn.LayerNorm`` with a bias, nothing derived from it (``last_dim_only``: normalised over one dim; the merge
+    forms do not ask)"""
+    return (type(mod) is torch.nn.LayerNorm and mod.elementwise_affine and mod.bias is not None
+            and (not last_dim_only or len(mod.normalized_shape) == 1))
+
+
+def _ln_width_ok(x: torch.Tensor, multiple: int, width: int, cap=(2048, 4096)) -> bool:
+    """x on the GPU in a kernel dtype, its last dim a multiple of ``multiple``, and the normalised ``width`` within
+    ``cap`` = (fp32 limit, 16-bit limit)"""
+    return (x.is_cuda and x.dtype in _GLUE_DTYPES and x.shape[-1] % multiple == 0
+            and width <= cap[0 if x.dtype == torch.float32 else 1])
+
+
+def _ln_vec(x: torch.Tensor) -> int:
+    """elements per 16-byte vector: what the token width of the merge forms must be a multiple of"""
+    return 4 if x.dtype == torch.float32 else 8
+
+
+def _ln_affine(weight, bias):
+    """(gamma, beta) as the kernels read them: fp32, contiguous"""
+    return weight.detach().float().contiguous(), bias.detach().float().contiguous()
+
+
+def _ln_row_stats(M: int, device):
+    return torch.empty(M, dtype=torch.float32, device=device), torch.empty(M, dtype=torch.float32, device=device)
+
+
+def _ln_stream_stats(n: int, M: int, device=None, stats=None):
+    """(stats, means, rstds): one (2n, M) fp32 tensor (saved for the backward, which passes it back in) and its per-stream rows"""
+    if stats is None:
+        stats = torch.empty((2 * n, M), dtype=torch.float32, device=device)
+    return stats, [stats[k] for k in range(n)], [stats[n + k] for k in range(n)]
+
+
+def _ln_bwd_buffers(M: int, C: int, x: torch.Tensor, n=None):
+    """(scratch, scratch bytes, dgamma, dbeta) of a backward call; ``n``: streams of the multi_x forms (their partials are per
+    stream)"""
+    lib, code = L.lib(), L.dtype_code(x)
+    sb = (lib.mtlora_layernorm_bwd_scratch_bytes(M, C, code) if n is None
+          else lib.mtlora_layernorm_multi_bwd_scratch_bytes(n, M, C, code))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=x.device)
+    dg = torch.empty(C, dtype=torch.float32, device=x.device)
+    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    return scratch, sb, dg, db
+
+
 def _ln_forward(ctx, x, weight, bias, eps, out_dtype, merge=None):
     """merge=(H, W): x is a (B, H*W, C) token tensor and the normalised rows are its 2x2 neighbourhoods (PatchMerging):
     output (B, H*W/4, 4C), gathered by the kernel."""
@@ -899,10 +946,9 @@ def _ln_forward(ctx, x, weight, bias, eps, out_dtype, merge=None):
         C, M = 4 * Ct, B * Lt // 4
         x2 = x.contiguous()
         out_shape = (B, Lt // 4, C)
-    w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
+    w, b = _ln_affine(weight, bias)
     y = torch.empty((M, C), dtype=out_dtype, device=x.device)
-    mean = torch.empty(M, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
+    mean, rstd = _ln_row_stats(M, x.device)
     st = L.lib().mtlora_layernorm_fwd(L.ptr(x2), L.ptr(w), L.ptr(b), L.ptr(y), L.ptr(mean), L.ptr(rstd), M, C,
                                       float(eps), L.dtype_code(x2), L.dtype_code(y), mh, mw, L.stream_ptr())
     L.check(st, "mtlora_layernorm_fwd")
@@ -922,13 +968,9 @@ def _ln_backward(ctx, dy, addend=None):
     add2 = None
     if addend is not None:
         add2 = addend.reshape(x2.shape).to(x2.dtype).contiguous()
-    lib = L.lib()
-    sb = lib.mtlora_layernorm_bwd_scratch_bytes(M, C, L.dtype_code(x2))
-    scratch = torch.empty(sb, dtype=torch.uint8, device=x2.device)
+    scratch, sb, dg, db = _ln_bwd_buffers(M, C, x2)
     dx = torch.empty_like(x2)
-    dg = torch.empty(C, dtype=torch.float32, device=x2.device)
-    db = torch.empty(C, dtype=torch.float32, device=x2.device)
-    st = lib.mtlora_layernorm_bwd(L.ptr(dy2), L.ptr(x2), L.ptr(w), L.ptr(mean), L.ptr(rstd), L.ptr(dx), L.ptr(dg),
+    st = L.lib().mtlora_layernorm_bwd(L.ptr(dy2), L.ptr(x2), L.ptr(w), L.ptr(mean), L.ptr(rstd), L.ptr(dx), L.ptr(dg),
                                   L.ptr(db), M, C, L.dtype_code(x2), L.dtype_code(dy2), L.ptr(scratch), sb, L.ptr(add2),
                                   mh, mw, L.stream_ptr())
     L.check(st, "mtlora_layernorm_bwd")
@@ -978,11 +1020,10 @@ class ResidualLayerNormFn(torch.autograd.Function):
         s2 = shortcut.reshape(-1, C).contiguous()
         b2 = branch.reshape(-1, C).contiguous()
         M = s2.shape[0]
-        w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
+        w, b = _ln_affine(weight, bias)
         x_new = torch.empty_like(s2)
         y = torch.empty((M, C), dtype=out_dtype, device=s2.device)
-        mean = torch.empty(M, dtype=torch.float32, device=s2.device)
-        rstd = torch.empty(M, dtype=torch.float32, device=s2.device)
+        mean, rstd = _ln_row_stats(M, s2.device)
         st = L.lib().mtlora_residual_layernorm_fwd(L.ptr(s2), L.ptr(b2), L.ptr(scale), B, L.ptr(w), L.ptr(b), L.ptr(x_new),
                                                    L.ptr(y), L.ptr(mean), L.ptr(rstd), M, C, float(eps), L.dtype_code(s2),
                                                    L.dtype_code(y), L.stream_ptr())
@@ -1006,14 +1047,10 @@ class ResidualLayerNormFn(torch.autograd.Function):
         if dy2.dtype != ctx.bdtype:
             dy2 = dy2.to(ctx.bdtype)
         add2 = None if g_skip is None else g_skip.reshape(M, C).to(x_new.dtype).contiguous()
-        lib = L.lib()
-        sb = lib.mtlora_layernorm_bwd_scratch_bytes(M, C, L.dtype_code(x_new))
-        scratch = torch.empty(sb, dtype=torch.uint8, device=x_new.device)
+        scratch, sb, dg, db = _ln_bwd_buffers(M, C, x_new)
         dx = torch.empty_like(x_new)
         dbr = torch.empty((M, C), dtype=ctx.bdtype, device=x_new.device)
-        dg = torch.empty(C, dtype=torch.float32, device=x_new.device)
-        db = torch.empty(C, dtype=torch.float32, device=x_new.device)
-        st = lib.mtlora_residual_layernorm_bwd(L.ptr(dy2), L.ptr(x_new), L.ptr(w), L.ptr(mean), L.ptr(rstd), L.ptr(dx),
+        st = L.lib().mtlora_residual_layernorm_bwd(L.ptr(dy2), L.ptr(x_new), L.ptr(w), L.ptr(mean), L.ptr(rstd), L.ptr(dx),
                                                L.ptr(dbr), L.ptr(dg), L.ptr(db), L.ptr(scale), ctx.B, M, C,
                                                L.dtype_code(x_new), L.dtype_code(dy2), L.ptr(scratch), sb, L.ptr(add2),
                                                L.stream_ptr())
@@ -1034,11 +1071,10 @@ class ResidualLayerNormMultiFn(torch.autograd.Function):
         s2 = shortcut.reshape(-1, C).contiguous()
         bs = [b.reshape(-1, C).contiguous() for b in branches]
         M = s2.shape[0]
-        w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
+        w, b = _ln_affine(weight, bias)
         xs = [torch.empty_like(s2) for _ in range(n)]
         ys = [torch.empty((M, C), dtype=out_dtype, device=s2.device) for _ in range(n)]
-        stats = torch.empty((2 * n, M), dtype=torch.float32, device=s2.device)
-        means, rstds = [stats[k] for k in range(n)], [stats[n + k] for k in range(n)]
+        stats, means, rstds = _ln_stream_stats(n, M, s2.device)
         st = L.lib().mtlora_residual_layernorm_multi_fwd(n, L.ptr(s2), L.ptr_array9(bs), L.ptr(scale), B, L.ptr(w), L.ptr(b),
                                                          L.ptr_array9(xs), L.ptr_array9(ys), L.ptr_array9(means),
                                                          L.ptr_array9(rstds), M, C, float(eps), L.dtype_code(s2),
@@ -1056,15 +1092,11 @@ class ResidualLayerNormMultiFn(torch.autograd.Function):
         dev = xs[0].device
         dys = [g.reshape(M, C).to(ctx.bdtype).contiguous() for g in g_y]             # (materialised: zeros if unused)
         adds = [g.reshape(M, C).to(xs[0].dtype).contiguous() for g in g_skip]
-        lib = L.lib()
-        sb = lib.mtlora_layernorm_bwd_scratch_bytes(M, C, L.dtype_code(xs[0]))
-        scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
+        scratch, sb, dg, db = _ln_bwd_buffers(M, C, xs[0])
         dsh = torch.empty_like(xs[0])
         dbr = [torch.empty((M, C), dtype=ctx.bdtype, device=dev) for _ in range(n)]
-        dg = torch.empty(C, dtype=torch.float32, device=dev)
-        db = torch.empty(C, dtype=torch.float32, device=dev)
-        means, rstds = [stats[k] for k in range(n)], [stats[n + k] for k in range(n)]
-        st = lib.mtlora_residual_layernorm_multi_bwd(n, L.ptr_array9(dys), L.ptr_array9(xs), L.ptr(w), L.ptr_array9(means),
+        _, means, rstds = _ln_stream_stats(n, M, stats=stats)
+        st = L.lib().mtlora_residual_layernorm_multi_bwd(n, L.ptr_array9(dys), L.ptr_array9(xs), L.ptr(w), L.ptr_array9(means),
                                                      L.ptr_array9(rstds), L.ptr_array9(adds), L.ptr(dsh), L.ptr_array9(dbr),
                                                      L.ptr(dg), L.ptr(db), L.ptr(scale), ctx.B, M, C, L.dtype_code(xs[0]),
                                                      L.dtype_code(dys[0]), L.ptr(scratch), sb, L.stream_ptr())
@@ -1076,10 +1108,8 @@ def residual_layer_norm_multi(mod: torch.nn.Module, shortcut: torch.Tensor, bran
     """([x_new_k], [mod(x_new_k)]) with x_new_k = shortcut + DropPath_k(branches[k]) (an independent per-sample mask per k):
     the fused multi-stream kernels when they apply, else residual_droppath + layer_norm_fork per stream."""
     C, n = shortcut.shape[-1], len(branches)
-    ok = (type(mod) is torch.nn.LayerNorm and mod.elementwise_affine and mod.bias is not None
-          and len(mod.normalized_shape) == 1 and shortcut.is_cuda and shortcut.dtype in _GLUE_DTYPES
-          and C % 8 == 0 and C <= (1024 if shortcut.dtype == torch.float32 else 1536) and shortcut.dim() == 3
-          and 1 <= n <= L.MAX_TASKS + 1 and all(b.shape == shortcut.shape for b in branches) and torch.is_grad_enabled()
+    ok = (_ln_module_ok(mod, last_dim_only=True) and _ln_width_ok(shortcut, multiple=8, width=C, cap=(1024, 1536))
+          and shortcut.dim() == 3 and 1 <= n <= L.MAX_TASKS + 1 and all(b.shape == shortcut.shape for b in branches) and torch.is_grad_enabled()
           and (shortcut.requires_grad or any(b.requires_grad for b in branches)))
     if ok:
         out_dtype = glue_dtype(shortcut)
@@ -1100,10 +1130,8 @@ def residual_layer_norm(mod: torch.nn.Module, shortcut: torch.Tensor, branch: to
     """(x_new, mod(x_new)) with x_new = shortcut + DropPath(branch): the fused kernel when it applies (nn.LayerNorm over
     the last dim, branch already in the dtype the LayerNorm output takes), else residual_droppath + layer_norm_fork."""
     C = shortcut.shape[-1]
-    ok = (type(mod) is torch.nn.LayerNorm and mod.elementwise_affine and mod.bias is not None
-          and len(mod.normalized_shape) == 1 and shortcut.is_cuda and shortcut.dtype in _GLUE_DTYPES
-          and C % 8 == 0 and C <= (2048 if shortcut.dtype == torch.float32 else 4096) and branch.shape == shortcut.shape
-          and shortcut.dim() == 3 and torch.is_grad_enabled() and (shortcut.requires_grad or branch.requires_grad))
+    ok = (_ln_module_ok(mod, last_dim_only=True) and _ln_width_ok(shortcut, multiple=8, width=C)
+          and branch.shape == shortcut.shape and shortcut.dim() == 3 and torch.is_grad_enabled() and (shortcut.requires_grad or branch.requires_grad))
     if ok:
         out_dtype = glue_dtype(shortcut)
         ok = branch.dtype == out_dtype
@@ -1129,10 +1157,8 @@ def layer_norm_merge(mod: torch.nn.Module, x: torch.Tensor, H: int, W: int) -> t
     done by the LayerNorm kernels' addressing (forward reads, backward scatters), not by a strided copy.  Falls back to
     the explicit gather when the kernel does not apply."""
     B, Lt, C = x.shape
-    ve = 4 if x.dtype == torch.float32 else 8
-    ok = (type(mod) is torch.nn.LayerNorm and mod.elementwise_affine and mod.bias is not None and x.is_cuda
-          and x.dtype in _GLUE_DTYPES and C % ve == 0 and Lt == H * W and H % 2 == 0 and W % 2 == 0
-          and 4 * C <= (2048 if x.dtype == torch.float32 else 4096))
+    ok = (_ln_module_ok(mod) and _ln_width_ok(x, multiple=_ln_vec(x), width=4 * C)
+          and Lt == H * W and H % 2 == 0 and W % 2 == 0)
     if not ok:
         g = x.view(B, H // 2, 2, W // 2, 2, C).permute(0, 1, 3, 4, 2, 5).reshape(B, (H // 2) * (W // 2), 4 * C)
         return layer_norm(mod, g)
@@ -1150,10 +1176,9 @@ class LayerNormMergeMultiFn(torch.autograd.Function):
         B, Lt, Ct = xs[0].shape
         C, M = 4 * Ct, B * Lt // 4
         x2 = [x.contiguous() for x in xs]
-        w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
+        w, b = _ln_affine(weight, bias)
         y = torch.empty((n, M, C), dtype=out_dtype, device=x2[0].device)
-        stats = torch.empty((2 * n, M), dtype=torch.float32, device=x2[0].device)
-        means, rstds = [stats[k] for k in range(n)], [stats[n + k] for k in range(n)]
+        stats, means, rstds = _ln_stream_stats(n, M, x2[0].device)
         st = L.lib().mtlora_layernorm_multi_fwd(n, L.ptr_array9(x2), L.ptr(w), L.ptr(b), L.ptr_array9([y[k] for k in range(n)]),
                                                 L.ptr_array9(means), L.ptr_array9(rstds), M, C, float(eps), L.dtype_code(x2[0]),
                                                 L.dtype_code(y), H, W, L.stream_ptr())
@@ -1170,15 +1195,10 @@ class LayerNormMergeMultiFn(torch.autograd.Function):
         if g3.dtype not in _GLUE_DTYPES:
             g3 = g3.float()
         g3 = g3.contiguous()
-        dev = x2[0].device
-        lib = L.lib()
-        sb = lib.mtlora_layernorm_multi_bwd_scratch_bytes(n, M, C, L.dtype_code(x2[0]))
-        scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
+        scratch, sb, dg, db = _ln_bwd_buffers(M, C, x2[0], n)
         dxs = [torch.empty_like(x) for x in x2]
-        dg = torch.empty(C, dtype=torch.float32, device=dev)
-        db = torch.empty(C, dtype=torch.float32, device=dev)
-        means, rstds = [stats[k] for k in range(n)], [stats[n + k] for k in range(n)]
-        st = lib.mtlora_layernorm_multi_bwd(n, L.ptr_array9([g3[k] for k in range(n)]), L.ptr_array9(x2), L.ptr(w),
+        _, means, rstds = _ln_stream_stats(n, M, stats=stats)
+        st = L.lib().mtlora_layernorm_multi_bwd(n, L.ptr_array9([g3[k] for k in range(n)]), L.ptr_array9(x2), L.ptr(w),
                                             L.ptr_array9(means), L.ptr_array9(rstds), L.ptr_array9(dxs), L.ptr(dg), L.ptr(db), M, C,
                                             L.dtype_code(x2[0]), L.dtype_code(g3), L.ptr(scratch), sb, L.ptr_array9(None), H, W,
                                             L.stream_ptr())
@@ -1201,11 +1221,10 @@ class ResidualMergeNormStreamsFn(torch.autograd.Function):
         C, M = 4 * Ct, B * Lt // 4
         r2 = [x.contiguous() for x in res]
         b2 = [x.contiguous() for x in brs]
-        w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
+        w, b = _ln_affine(weight, bias)
         xs = [torch.empty_like(x) for x in r2]
         y = torch.empty((n, M, C), dtype=out_dtype, device=r2[0].device)
-        stats = torch.empty((2 * n, M), dtype=torch.float32, device=r2[0].device)
-        means, rstds = [stats[k] for k in range(n)], [stats[n + k] for k in range(n)]
+        stats, means, rstds = _ln_stream_stats(n, M, r2[0].device)
         st = L.lib().mtlora_residual_layernorm_streams_fwd(n, L.ptr_array9(r2), L.ptr_array9(b2), L.ptr(scale), B, L.ptr(w), L.ptr(b),
                                                            L.ptr_array9(xs), L.ptr_array9([y[k] for k in range(n)]),
                                                            L.ptr_array9(means), L.ptr_array9(rstds), M, C, float(eps),
@@ -1224,15 +1243,11 @@ class ResidualMergeNormStreamsFn(torch.autograd.Function):
             g3 = g3.to(bdt)
         g3 = g3.contiguous()
         dev = xs[0].device
-        lib = L.lib()
-        sb = lib.mtlora_layernorm_multi_bwd_scratch_bytes(n, M, C, L.dtype_code(xs[0]))
-        scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
+        scratch, sb, dg, db = _ln_bwd_buffers(M, C, xs[0], n)
         dres = [torch.empty_like(x) for x in xs]
         dbr = [torch.empty(shape, dtype=bdt, device=dev) for _ in range(n)]
-        dg = torch.empty(C, dtype=torch.float32, device=dev)
-        db = torch.empty(C, dtype=torch.float32, device=dev)
-        means, rstds = [stats[k] for k in range(n)], [stats[n + k] for k in range(n)]
-        st = lib.mtlora_residual_layernorm_streams_bwd(n, L.ptr_array9([g3[k] for k in range(n)]), L.ptr_array9(xs), L.ptr(w),
+        _, means, rstds = _ln_stream_stats(n, M, stats=stats)
+        st = L.lib().mtlora_residual_layernorm_streams_bwd(n, L.ptr_array9([g3[k] for k in range(n)]), L.ptr_array9(xs), L.ptr(w),
                                                        L.ptr_array9(means), L.ptr_array9(rstds), L.ptr_array9(dres),
                                                        L.ptr_array9(dbr), L.ptr(dg), L.ptr(db), L.ptr(scale), B, M, C,
                                                        L.dtype_code(xs[0]), L.dtype_code(g3), L.ptr(scratch), sb, L.ptr_array9(None),
@@ -1246,12 +1261,11 @@ def residual_merge_norm_streams(mod: torch.nn.Module, res, branches, H: int, W: 
     apply (the caller then forms the residuals and calls ``layer_norm_merge_multi`` / per-stream code)."""
     n = len(res)
     B, Lt, C = res[0].shape
-    ve = 4 if res[0].dtype == torch.float32 else 8
-    ok = (type(mod) is torch.nn.LayerNorm and mod.elementwise_affine and mod.bias is not None and 2 <= n <= L.MAX_TASKS + 1
+    ok = (_ln_module_ok(mod) and 2 <= n <= L.MAX_TASKS + 1
           and len(branches) == n and all(x.is_cuda and x.dtype == res[0].dtype and x.shape == res[0].shape for x in res)
           and all(x.shape == res[0].shape and x.dtype == branches[0].dtype for x in branches)
-          and res[0].dtype in _GLUE_DTYPES and C % ve == 0 and Lt == H * W and H % 2 == 0 and W % 2 == 0
-          and 4 * C <= (2048 if res[0].dtype == torch.float32 else 4096) and torch.is_grad_enabled())
+          and _ln_width_ok(res[0], multiple=_ln_vec(res[0]), width=4 * C) and Lt == H * W and H % 2 == 0 and W % 2 == 0
+          and torch.is_grad_enabled())
     if ok:
         out_dtype = glue_dtype(res[0])
         ok = branches[0].dtype == out_dtype
@@ -1267,11 +1281,9 @@ def residual_merge_norm_streams(mod: torch.nn.Module, res, branches, H: int, W: 
 def layer_norm_merge_multi(mod: torch.nn.Module, xs, H: int, W: int):
     """stacked (n*B, H*W/4, 4C) = cat_k PatchMerging-norm(xs[k]) (stream-major), or None when the fused kernel does not apply."""
     B, Lt, C = xs[0].shape
-    ve = 4 if xs[0].dtype == torch.float32 else 8
-    ok = (type(mod) is torch.nn.LayerNorm and mod.elementwise_affine and mod.bias is not None and 2 <= len(xs) <= L.MAX_TASKS + 1
+    ok = (_ln_module_ok(mod) and 2 <= len(xs) <= L.MAX_TASKS + 1
           and all(x.is_cuda and x.dtype == xs[0].dtype and x.shape == xs[0].shape for x in xs)
-          and xs[0].dtype in _GLUE_DTYPES and C % ve == 0 and Lt == H * W and H % 2 == 0 and W % 2 == 0
-          and 4 * C <= (2048 if xs[0].dtype == torch.float32 else 4096))
+          and _ln_width_ok(xs[0], multiple=_ln_vec(xs[0]), width=4 * C) and Lt == H * W and H % 2 == 0 and W % 2 == 0)
     if not ok:
         return None
     return LayerNormMergeMultiFn.apply(mod.weight, mod.bias, mod.eps, glue_dtype(xs[0]), H, W, len(xs), *xs)
@@ -1283,9 +1295,7 @@ def layer_norm(mod: torch.nn.Module, x: torch.Tensor, feeds_linear: bool = True,
     -- no fp32 intermediate + cast pass).  Otherwise (patch_embed.norm, whose output IS the residual stream) the
     output dtype is what the reference produces: fp32 under autocast (autocast runs layer_norm in fp32), else the
     input dtype.  Anything else (custom norm layers, no affine, exotic dtypes) goes to the module itself."""
-    ok = (type(mod) is torch.nn.LayerNorm and mod.elementwise_affine and mod.bias is not None
-          and len(mod.normalized_shape) == 1 and x.is_cuda and x.dtype in _GLUE_DTYPES
-          and x.shape[-1] % 8 == 0 and x.shape[-1] <= (2048 if x.dtype == torch.float32 else 4096))
+    ok = _ln_module_ok(mod, last_dim_only=True) and _ln_width_ok(x, multiple=8, width=x.shape[-1])
     if not ok:
         return mod(x)
     if feeds_linear:

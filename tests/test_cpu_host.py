@@ -149,6 +149,35 @@ def test_linear_workspace_sizes_match_fixture(built_lib):
     assert len(keys) == len(set(keys)) == len(want["index"]) and len(keys) > 6000
 
 
+def test_layernorm_host_matches_fixture(built_lib):
+    """both LayerNorm scratch-size queries over make_golden_layernorm_host.scratch_table(), and the return code of every exported
+    LayerNorm entry for every call of reject_table() (one defect per call, rejected on the host; forward entries with M == 0
+    return OK without a launch), equal tests/golden/layernorm_host.json, recorded from the library before the LayerNorm host
+    dispatch moved to csrc/layernorm.hip: the refactor moves no workspace size and no return code."""
+    import importlib.util
+    import json
+    from mtlora_amd import _lib
+    spec = importlib.util.spec_from_file_location("make_golden_layernorm_host",
+                                                  os.path.join(ROOT, "tests", "golden", "make_golden_layernorm_host.py"))
+    G = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(G)
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "layernorm_host.json")))
+    L = _lib.lib()
+    keys = []
+    for key, args in G.scratch_table():
+        keys.append(key)
+        assert G.scratch_of(L, *args) == want["scratch"][key], key
+    assert len(keys) == len(set(keys)) == len(want["scratch"]) and len(keys) > 500
+    keys = []
+    for key, entry, edits in G.reject_table():
+        keys.append(key)
+        # (checked BEFORE the call: a row the fixture has as accepted must be a forward entry without rows -- nothing may launch)
+        assert want["reject"][key] < 0 or (edits.get("M") == 0 and entry.endswith("_fwd")), key
+        assert G.call(L, entry, edits) == want["reject"][key], key
+    assert len(keys) == len(set(keys)) == len(want["reject"]) and len(keys) > 400
+    assert {k.split(":")[0] for k in keys} == {e for e in _lib.EXPORTS if "layernorm" in e and not e.endswith("_bytes")}
+
+
 def test_linear_sources_have_no_ablation_build():
     """no source file of the project (package, kernels, header, tools, oracle, entry points; documents and recorded profiles
     aside) carries an ablation switch, and the kernel sources read no environment variable outside the profiler (selftest.hip)"""
