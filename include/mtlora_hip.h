@@ -600,6 +600,35 @@ int mtlora_block_bwd(const mtlora_block_desc* d, const mtlora_block_params* p, c
  *                        [0, 1), any nan) sets found_inf on the device instead -- the step is skipped exactly like one with
  *                        an inf gradient (parameters, state and t bitwise unchanged; with a scaler the scale backs off)
  *                        and the norm in ctrl[0] / norm_out is nan.
+ *   mtlora_adamw_accum_update_dev  ONE MICRO-STEP of gradient accumulation over k = accum_steps calls (the reference's
+ *                        TRAIN.ACCUMULATION_STEPS, main.py:347-353; additive, ABI stays 12), for a graph that is replayed
+ *                        once per micro-step.  Arguments as mtlora_adamw_update_dev, plus:
+ *                        `acc`: persistent fp32 DEVICE accumulator the caller owns, 16-byte aligned, of the `acc_elems`
+ *                        elements mtlora_adamw_accum_layout returns; never memset, by anyone (its first use overwrites it).
+ *                        `acc_offsets`: DEVICE copy of the n_tensors int64 element offsets that call fills (tensor i's slice
+ *                        is acc + acc_offsets[i], numel[i] elements, every slice 16-byte aligned); uploaded once.
+ *                        `accum_steps`: 1 .. MTLORA_ADAMW_MAX_ACCUM_STEPS.  It is a LAUNCH ARGUMENT: a captured graph keeps
+ *                        the k of its capture.
+ *                        Two more words of `ctrl` (zero before first use, like the rest):
+ *                            [MTLORA_ADAMW_CTRL_MICRO]    c, the micro-step counter, 0 <= c < k
+ *                            [MTLORA_ADAMW_CTRL_UPDATED]  1 if the last call was an update micro-step, else 0
+ *                        Every decision is taken on the device from c; nothing is read back.  Per call, still three launches:
+ *                          accumulate   for every tensor with a non-null gradient entry: acc = g if c == 0 (what acc held is
+ *                                       not read: a cycle poisoned by inf / nan cannot leak into the next), else
+ *                                       acc = acc + g -- one fp32 add per element, in micro-step order, the bits autograd
+ *                                       gives when it accumulates into .grad.  Fused into the norm pass: the value stored is
+ *                                       the value squared.  A tensor's entry must be null or non-null for a WHOLE cycle.
+ *                          c < k - 1    c = c + 1, [UPDATED] = 0.  Parameters, state, t, the bias corrections, ctrl[0..4],
+ *                                       *scale, *growth_tracker and *norm_out stay bitwise unchanged: the update launch is
+ *                                       still issued, and every workgroup leaves on [UPDATED] == 0 before it writes.
+ *                          c == k - 1   the step of mtlora_adamw_update_dev with acc's slices as the gradients (norm,
+ *                                       found_inf, clip, unscale, AdamW, scaler update, bad records -> skip and nan norm),
+ *                                       then c = 0, [UPDATED] = 1 -- also when the step was skipped.
+ *                        The loss is NOT divided by k (main.py:341-349): acc is the plain sum.  accum_steps == 1: every
+ *                        call updates straight from `grads` (acc and acc_offsets are checked but not dereferenced), p, m, v
+ *                        and ctrl[0..4] have the bits mtlora_adamw_update_dev gives, and [UPDATED] = 1.
+ *   mtlora_adamw_accum_layout  pure host call: the accumulator's layout for n_tensors element counts -- `host_offsets`
+ *                        (n_tensors int64, HOST memory, may be null) and the total `acc_elems`; slices are rounded up to 4.
  * Deterministic: no float atomics; the norm is summed in a fixed order (per-chunk fp32 partials, combined in double).
  * ------------------------------------------------------------------------------------------ */
 #define MTLORA_ADAMW_CHUNK 4096
@@ -623,6 +652,15 @@ int mtlora_adamw_update_dev(const void* table, const void* grads, int64_t n_tens
                             float* norm_out, float* scale, int32_t* growth_tracker, double growth_factor,
                             double backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes,
                             void* stream);
+#define MTLORA_ADAMW_CTRL_MICRO 5
+#define MTLORA_ADAMW_CTRL_UPDATED 6
+#define MTLORA_ADAMW_MAX_ACCUM_STEPS (1 << 24) /* c lives in an fp32 word */
+int mtlora_adamw_accum_layout(int64_t n_tensors, const int64_t* numel, int64_t* host_offsets, int64_t* acc_elems);
+int mtlora_adamw_accum_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks,
+                                  const mtlora_adamw_group* groups_dev, int n_groups, float max_norm, float* ctrl,
+                                  float* norm_out, float* scale, int32_t* growth_tracker, double growth_factor,
+                                  double backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes,
+                                  float* acc, const int64_t* acc_offsets, int accum_steps, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Batch ingest (ABI v12): the tail of the reference's loader pipelines on the device -- RandomHorizontalFlip,

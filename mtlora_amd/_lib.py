@@ -85,6 +85,8 @@ INGEST_IMAGE, INGEST_CLASS, INGEST_CLASS_ALLZERO_IGNORE, INGEST_NORMALS, INGEST_
 
 ADAMW_CHUNK, ADAMW_MAX_GROUPS, ADAMW_CTRL_WORDS = 4096, 16, 64
 ADAMW_GROUPS_DEV_BYTES = 1152  # device buffer of mtlora_adamw_update_dev: MAX_GROUPS records, then the library's derived values
+ADAMW_CTRL_MICRO, ADAMW_CTRL_UPDATED = 5, 6  # mtlora_adamw_accum_update_dev: the micro-step counter, "the last call updated"
+ADAMW_MAX_ACCUM_STEPS = 1 << 24
 
 PROF_KINDS = 24
 
@@ -207,6 +209,10 @@ _SIGS = {
                                     c_void_p, c_void_p, c_float, c_float, c_int, c_void_p, c_int64, c_void_p]),
     "mtlora_adamw_update_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_float, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_int64, c_void_p]),
+    "mtlora_adamw_accum_layout": (c_int, [c_int64, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "mtlora_adamw_accum_update_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_float, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                              c_int, c_void_p]),
     "mtlora_ingest_scratch_bytes": (c_int64, [c_int, c_int64]),
     "mtlora_ingest_batch": (c_int, [POINTER(IngestJob), c_int, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                     c_void_p]),

@@ -31,6 +31,16 @@
 // for the by-value entry ((float)lr, (float)(1 - lr wd), (float)b, (float)(1 - b), (float)eps -- the same IEEE operations, no
 // contraction, so the two entries are bit-identical) and stores it in that buffer's tail, where k_optim_step reads it.  A record
 // the host entry would reject (negative lr, beta >= 1, nan) raises found_inf: the step is skipped and the norm is nan.
+//
+// mtlora_adamw_accum_update_dev is one MICRO-step of gradient accumulation (main.py:347-353 with ACCUMULATION_STEPS = k), still three
+// launches, for a graph that is replayed once per micro-step.  Two more control words: c, the micro-step counter, and `updated`.
+//   k_optim_norm<true>    the accumulate pass and the norm pass are ONE kernel: acc = g (c == 0) or acc + g (one fp32 add, in micro-step
+//                         order: the bits autograd's accumulation into .grad gives), stored, and the partial / flag formed from the
+//                         value just stored.  acc is read once and written once per micro-step and not read again for the norm.
+//   k_optim_finish<G, true>  c < k - 1: c = c + 1, updated = 0, and nothing else is written.  c == k - 1: the finish above, then
+//                         c = 0, updated = 1.
+//   k_optim_step<G, OptGradAcc>  the same launch every micro-step (a graph replays a fixed launch list); every workgroup leaves on
+//                         updated == 0 before it reads or writes anything else; otherwise the step above with acc's slices as gradients.
 #include "common.h"
 
 namespace {
@@ -104,7 +114,23 @@ __host__ __device__ inline bool opt_derive(const mtlora_adamw_group& s, OptHyper
 
 // control block words (floats), MTLORA_ADAMW_CTRL_WORDS of them
 enum { OC_NORM = 0, OC_FOUND_INF = 1, OC_COEF = 2, OC_GMUL = 3, OC_STEP = 4, OC_BC = 8 };  // OC_BC + 2 g: bc1, sqrt(bc2) of group g
+enum { OC_MICRO = MTLORA_ADAMW_CTRL_MICRO, OC_UPDATED = MTLORA_ADAMW_CTRL_UPDATED };  // gradient accumulation only
+static_assert(OC_MICRO > OC_STEP && OC_UPDATED > OC_MICRO && OC_UPDATED < OC_BC, "control block");
 static_assert(OC_BC + 2 * OPT_MAXG <= MTLORA_ADAMW_CTRL_WORDS, "control block");
+
+// where k_optim_step finds a tensor's gradient, and whether this launch may write at all
+struct OptGradPtrs {  // the caller's gradient pointers
+    const float* const* grads;
+    __device__ __forceinline__ bool live(const float*) const { return true; }
+    __device__ __forceinline__ const float* at(int t) const { return grads[t]; }
+};
+struct OptGradAcc {  // the accumulator's slices; a null gradient pointer still switches the tensor off
+    const float* const* grads;
+    const float* acc;
+    const int64_t* off;
+    __device__ __forceinline__ bool live(const float* ctrl) const { return ctrl[OC_UPDATED] != 0.f; }
+    __device__ __forceinline__ const float* at(int t) const { return grads[t] ? acc + off[t] : nullptr; }
+};
 
 __device__ __forceinline__ bool opt_nonfinite(float x) { return (__builtin_bit_cast(uint32_t, x) & 0x7F800000u) == 0x7F800000u; }
 
@@ -117,9 +143,13 @@ __device__ __forceinline__ float opt_block_sum(float s, float* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
+// ACC: gradient accumulation -- the chunk of acc (at acc + acc_off[tensor]) becomes g (ctrl[OC_MICRO] == 0: whatever acc held is
+// overwritten, never read) or acc + g, and the partial / flag are those of the value stored.  Each element of acc has one writer.
+template <bool ACC>
 __global__ __launch_bounds__(OPT_THREADS) void k_optim_norm(const OptTensor* __restrict__ tens, const OptChunk* __restrict__ chunks,
                                                             const float* const* __restrict__ grads, float* __restrict__ partials,
-                                                            uint32_t* __restrict__ flags) {
+                                                            uint32_t* __restrict__ flags, float* __restrict__ acc,
+                                                            const int64_t* __restrict__ acc_off, const float* __restrict__ ctrl) {
     __shared__ float red[4];
     __shared__ int bad_any;
     const int tid = threadIdx.x;
@@ -136,16 +166,36 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_norm(const OptTensor* __r
     const int64_t left = tens[ck.tensor].n - off;
     const int n = left < OPT_CHUNK ? (int)left : OPT_CHUNK;
     g += off;
+    float* a = nullptr;
+    bool first = true;
+    if constexpr (ACC) {
+        a = acc + acc_off[ck.tensor] + off;
+        first = ctrl[OC_MICRO] == 0.f;  // (workgroup-uniform; k_optim_finish, the next launch, is the one that moves it)
+    }
     if (tid == 0) bad_any = 0;
     float s = 0.f;
     bool bad = false;
-    if (((uintptr_t)g & 15u) == 0) {
+    if ((((uintptr_t)g | (uintptr_t)a) & 15u) == 0) {
         const int nv = n >> 2;
         f32x4 x[OPT_VPT];
 #pragma unroll
         for (int k = 0; k < OPT_VPT; ++k) {
             const int i = k * OPT_THREADS + tid;
             x[k] = i < nv ? *reinterpret_cast<const f32x4*>(g + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        if constexpr (ACC) {
+#pragma unroll
+            for (int k = 0; k < OPT_VPT; ++k) {
+                const int i = k * OPT_THREADS + tid;
+                if (i < nv) {
+                    if (!first) {
+                        const f32x4 y = *reinterpret_cast<const f32x4*>(a + 4 * i);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) x[k][e] = y[e] + x[k][e];
+                    }
+                    *reinterpret_cast<f32x4*>(a + 4 * i) = x[k];
+                }
+            }
         }
 #pragma unroll
         for (int k = 0; k < OPT_VPT; ++k)
@@ -156,13 +206,21 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_norm(const OptTensor* __r
             }
         const int i = 4 * nv + tid;  // the last n % 4 elements
         if (tid < 4 && i < n) {
-            const float t = g[i];
+            float t = g[i];
+            if constexpr (ACC) {
+                if (!first) t = a[i] + t;
+                a[i] = t;
+            }
             s += t * t;
             bad |= opt_nonfinite(t);
         }
     } else {
         for (int i = tid; i < n; i += OPT_THREADS) {
-            const float t = g[i];
+            float t = g[i];
+            if constexpr (ACC) {
+                if (!first) t = a[i] + t;
+                a[i] = t;
+            }
             s += t * t;
             bad |= opt_nonfinite(t);
         }
@@ -176,15 +234,29 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_norm(const OptTensor* __r
     }
 }
 
-template <class G>  // OptGroups (by value) or OptGroupsDev
+// G: OptGroups (by value) or OptGroupsDev.  ACC: gradient accumulation over accum_steps micro-steps -- ctrl[OC_MICRO] decides, on
+// the device, whether this call is the cycle's last; if it is not, the counter moves and NOTHING else is written.
+template <class G, bool ACC>
 __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __restrict__ partials, const uint32_t* __restrict__ flags,
                                                               int n_chunks, const G grp, float max_norm, float* __restrict__ ctrl,
                                                               float* __restrict__ norm_out, float* __restrict__ scale,
-                                                              int32_t* __restrict__ tracker, float growth, float backoff, int interval) {
+                                                              int32_t* __restrict__ tracker, float growth, float backoff, int interval,
+                                                              int accum_steps) {
     __shared__ double red[OPT_THREADS];
     __shared__ uint32_t fl[OPT_THREADS];
     __shared__ float step_new;
     const int tid = threadIdx.x;
+    if constexpr (ACC) {
+        const float c = ctrl[OC_MICRO];
+        __syncthreads();  // every thread has read c before thread 0 moves it
+        if (c + 1.f < (float)accum_steps) {  // (workgroup-uniform; accum_steps <= 2^24, so the floats are exact)
+            if (tid == 0) {
+                ctrl[OC_MICRO] = c + 1.f;
+                ctrl[OC_UPDATED] = 0.f;
+            }
+            return;
+        }
+    }
     double s = 0.0;
     uint32_t f = 0u;
     double b1d = 0.0, b2d = 0.0;
@@ -228,6 +300,10 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __res
         ctrl[OC_COEF] = coef;
         ctrl[OC_GMUL] = coef * inv;
         ctrl[OC_STEP] = st;
+        if constexpr (ACC) {  // the cycle ends here, whether the step was taken or skipped
+            ctrl[OC_MICRO] = 0.f;
+            ctrl[OC_UPDATED] = 1.f;
+        }
         step_new = st;
         if (norm_out) *norm_out = norm;
         if (scale) {  // GradScaler.update (ATen amp_update_scale)
@@ -266,14 +342,14 @@ __device__ __forceinline__ void opt_adamw(float& p, float g, float& m, float& v,
     p -= c.step_size * (m / (sqrtf(v) * c.inv_bc2s + c.eps));
 }
 
-template <class G>
+template <class G, class S>  // S: OptGradPtrs or OptGradAcc
 __global__ __launch_bounds__(OPT_THREADS) void k_optim_step(const OptTensor* __restrict__ tens, const OptChunk* __restrict__ chunks,
-                                                            const float* const* __restrict__ grads, const float* __restrict__ ctrl,
-                                                            const G grp) {
+                                                            const S src, const float* __restrict__ ctrl, const G grp) {
+    if (!src.live(ctrl)) return;            // an accumulating micro-step: nothing is written (ctrl[OC_FOUND_INF] is the last update's)
     if (ctrl[OC_FOUND_INF] != 0.f) return;  // skipped step: nothing is written
     const int tid = threadIdx.x;
     const OptChunk ck = chunks[blockIdx.x];
-    const float* g = grads[ck.tensor];
+    const float* g = src.at(ck.tensor);
     if (!g) return;
     const OptTensor t = tens[ck.tensor];
     const int64_t off = (int64_t)ck.index * OPT_CHUNK;
@@ -372,20 +448,64 @@ static int opt_check(const void* table, const void* grads, int64_t n_tensors, in
     return MTLORA_OK;
 }
 
+struct OptLaunch {  // what the three launches share
+    hipStream_t s;
+    const OptTensor* te;
+    const OptChunk* ce;
+    const float* const* gp;
+    float* partials;
+    uint32_t* flags;
+    dim3 grid;
+    OptLaunch(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, void* scratch, void* stream)
+        : s(reinterpret_cast<hipStream_t>(stream)), te(reinterpret_cast<const OptTensor*>(table)),
+          ce(reinterpret_cast<const OptChunk*>(te + n_tensors)), gp(reinterpret_cast<const float* const*>(grads)),
+          partials(reinterpret_cast<float*>(scratch)), flags(reinterpret_cast<uint32_t*>(partials + n_chunks)),
+          grid((unsigned)n_chunks) {}
+};
+
 template <class G>
 static int opt_launch(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const G& g, float max_norm, float* ctrl,
                       float* norm_out, float* scale, int32_t* growth_tracker, float growth_factor, float backoff_factor,
                       int growth_interval, void* scratch, void* stream) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const OptTensor* te = reinterpret_cast<const OptTensor*>(table);
-    const OptChunk* ce = reinterpret_cast<const OptChunk*>(te + n_tensors);
-    const float* const* gp = reinterpret_cast<const float* const*>(grads);
-    float* partials = reinterpret_cast<float*>(scratch);
-    uint32_t* flags = reinterpret_cast<uint32_t*>(partials + n_chunks);
-    if (n_chunks > 0) hipLaunchKernelGGL(k_optim_norm, dim3((unsigned)n_chunks), dim3(OPT_THREADS), 0, s, te, ce, gp, partials, flags);
-    hipLaunchKernelGGL(k_optim_finish<G>, dim3(1), dim3(OPT_THREADS), 0, s, partials, flags, (int)n_chunks, g, max_norm, ctrl, norm_out,
-                       scale, growth_tracker, growth_factor, backoff_factor, growth_interval);
-    if (n_chunks > 0) hipLaunchKernelGGL(k_optim_step<G>, dim3((unsigned)n_chunks), dim3(OPT_THREADS), 0, s, te, ce, gp, ctrl, g);
+    const OptLaunch l(table, grads, n_tensors, n_chunks, scratch, stream);
+    const dim3 block(OPT_THREADS);
+    if (n_chunks > 0)
+        hipLaunchKernelGGL(k_optim_norm<false>, l.grid, block, 0, l.s, l.te, l.ce, l.gp, l.partials, l.flags, (float*)nullptr,
+                           (const int64_t*)nullptr, (const float*)nullptr);
+    hipLaunchKernelGGL((k_optim_finish<G, false>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g, max_norm, ctrl, norm_out,
+                       scale, growth_tracker, growth_factor, backoff_factor, growth_interval, 0);
+    if (n_chunks > 0) hipLaunchKernelGGL((k_optim_step<G, OptGradPtrs>), l.grid, block, 0, l.s, l.te, l.ce, OptGradPtrs{l.gp}, ctrl, g);
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
+// one micro-step of a cycle of accum_steps.  With accum_steps == 1 every call is the cycle's last and updates straight from the
+// caller's gradients: acc is not touched, and the bits are opt_launch's.
+static int opt_launch_accum(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const OptGroupsDev& g,
+                            float max_norm, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker, float growth_factor,
+                            float backoff_factor, int growth_interval, void* scratch, void* stream, float* acc, const int64_t* acc_off,
+                            int accum_steps) {
+    const OptLaunch l(table, grads, n_tensors, n_chunks, scratch, stream);
+    const dim3 block(OPT_THREADS);
+    const bool sum = accum_steps > 1;
+    if (n_chunks > 0) {
+        if (sum)
+            hipLaunchKernelGGL(k_optim_norm<true>, l.grid, block, 0, l.s, l.te, l.ce, l.gp, l.partials, l.flags, acc, acc_off,
+                               (const float*)ctrl);
+        else
+            hipLaunchKernelGGL(k_optim_norm<false>, l.grid, block, 0, l.s, l.te, l.ce, l.gp, l.partials, l.flags, (float*)nullptr,
+                               (const int64_t*)nullptr, (const float*)nullptr);
+    }
+    hipLaunchKernelGGL((k_optim_finish<OptGroupsDev, true>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g, max_norm, ctrl,
+                       norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, accum_steps);
+    if (n_chunks > 0) {
+        if (sum)
+            hipLaunchKernelGGL((k_optim_step<OptGroupsDev, OptGradAcc>), l.grid, block, 0, l.s, l.te, l.ce, OptGradAcc{l.gp, acc, acc_off},
+                               (const float*)ctrl, g);
+        else
+            hipLaunchKernelGGL((k_optim_step<OptGroupsDev, OptGradPtrs>), l.grid, block, 0, l.s, l.te, l.ce, OptGradPtrs{l.gp},
+                               (const float*)ctrl, g);
+    }
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }
@@ -469,6 +589,41 @@ int mtlora_adamw_update_dev(const void* table, const void* grads, int64_t n_tens
     g.n = n_groups;
     return opt_launch(table, grads, n_tensors, n_chunks, g, max_norm, ctrl, norm_out, scale, growth_tracker, growth, backoff,
                       growth_interval, scratch, stream);
+}
+
+int mtlora_adamw_accum_layout(int64_t n_tensors, const int64_t* numel, int64_t* host_offsets, int64_t* acc_elems) {
+    if (!acc_elems) return MTLORA_ERR_NULL;
+    int64_t nc = 0;
+    const int rc = opt_count(n_tensors, numel, &nc);
+    if (rc != MTLORA_OK) return rc;
+    int64_t total = 0;
+    for (int64_t i = 0; i < n_tensors; ++i) {
+        if (host_offsets) host_offsets[i] = total;
+        total += mtl_ceil_div(numel[i], (int64_t)4) * 4;  // every slice starts 16-byte aligned
+    }
+    *acc_elems = total;
+    return MTLORA_OK;
+}
+
+int mtlora_adamw_accum_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks,
+                                  const mtlora_adamw_group* groups_dev, int n_groups, float max_norm, float* ctrl, float* norm_out,
+                                  float* scale, int32_t* growth_tracker, double growth_factor, double backoff_factor, int growth_interval,
+                                  void* scratch, int64_t scratch_bytes, float* acc, const int64_t* acc_offsets, int accum_steps,
+                                  void* stream) {
+    const float growth = (float)growth_factor, backoff = (float)backoff_factor;
+    const int rc = opt_check(table, grads, n_tensors, n_chunks, groups_dev, n_groups, ctrl, norm_out, scale, growth_tracker, growth, backoff,
+                             growth_interval, scratch, scratch_bytes);
+    if (rc != MTLORA_OK) return rc;
+    if (!acc || !acc_offsets) return MTLORA_ERR_NULL;
+    if (accum_steps < 1 || accum_steps > MTLORA_ADAMW_MAX_ACCUM_STEPS) return MTLORA_ERR_SHAPE;
+    if (((uintptr_t)groups_dev | (uintptr_t)acc_offsets) & 7u) return MTLORA_ERR_ALIGN;
+    if ((uintptr_t)acc & 15u) return MTLORA_ERR_ALIGN;
+    OptGroupsDev g;
+    g.rec = groups_dev;
+    g.hyp = reinterpret_cast<OptHyperArr*>(const_cast<mtlora_adamw_group*>(groups_dev) + OPT_MAXG);
+    g.n = n_groups;
+    return opt_launch_accum(table, grads, n_tensors, n_chunks, g, max_norm, ctrl, norm_out, scale, growth_tracker, growth, backoff,
+                            growth_interval, scratch, stream, acc, acc_offsets, accum_steps);
 }
 
 }  // extern "C"

@@ -25,7 +25,7 @@ import torch.nn.functional as F
 from . import functional as Fn
 from .functional import BatchNormReluFn, UpsampleLossFn
 from .lora import MTLoRALinear, mark_only_lora_as_trainable
-from .optim import FusedAdamW
+from .optim import FusedAdamW, accumulation_steps_of
 from .swin_transformer_mtlora import SwinTransformerMTLoRA
 
 NUM_OUTPUT = {"semseg": 21, "normals": 3, "sal": 1, "human_parts": 7, "depth": 1, "edge": 1}  # data/mtl_ds.py:749-780
@@ -623,6 +623,12 @@ class GraphedTrainStep:
       device before each replay; nothing of them is baked in) and ``self.grad_norm`` is the unscaled gradient norm of the last
       step, a 0-d device tensor.  A non-capturable ``FusedAdamW`` is a ``TypeError``, not a fallback.  With a torch optimizer the
       hyper-parameters of the capture step are what every replay uses.
+    * gradient accumulation (``accumulation_steps`` k > 1, the reference's ``TRAIN.ACCUMULATION_STEPS``; ``FusedAdamW`` only, no
+      reducer): still ONE graph, and each call is one MICRO-step -- forward, losses, backward, then
+      ``clip_and_step(accumulation_steps=k)``, which adds the gradients into the optimizer's accumulator and, on the device, steps
+      only at every k-th call, then zero_grad.  ``self.updated`` says whether the call just made was such an update (a host count
+      of the calls: nothing is read back), i.e. when to call ``lr_scheduler.step_update``; ``self.grad_norm`` keeps the last
+      update's norm in between.  The loss is not divided by k (main.py:341-349).  With the default 1 the capture is what it was.
     Falls back to the eager step (``self.graphed = False``, reason in ``self.why``) if capture fails.
 
     Not bench.py's default (``--graph``): at C2 the eager step with its side streams is faster (34.8 ms vs 36.5 ms for the
@@ -635,8 +641,16 @@ class GraphedTrainStep:
     SEED_STEP = 0x1E3779B97F4A7C15  # odd: a full-period walk of the 64-bit seed offset
 
     def __init__(self, model, criterion, optimizer, images, targets, clip_grad: float = 5.0, reducer=None,
-                 amp_dtype: Optional[torch.dtype] = torch.bfloat16, fused_loss: bool = True, warmup: int = 3, loss_scaler=None):
+                 amp_dtype: Optional[torch.dtype] = torch.bfloat16, fused_loss: bool = True, warmup: int = 3, loss_scaler=None,
+                 accumulation_steps: int = 1):
+        self.accumulation_steps = accumulation_steps_of(accumulation_steps)
+        if self.accumulation_steps > 1 and reducer is not None:
+            raise ValueError("GraphedTrainStep: accumulation_steps > 1 with a reducer is not supported (the all-reduce would have to "
+                             "sit between two graphs on every k-th call only); use train_step(..., reducer=, update_grad=)")
         self.fused_opt = isinstance(optimizer, FusedAdamW)
+        if self.accumulation_steps > 1 and not self.fused_opt:
+            raise TypeError("GraphedTrainStep: accumulation_steps > 1 needs the HIP optimizer (build_optimizer(impl='hip', "
+                            "capturable=True)): the decision to step is taken on the device by its kernels")
         if self.fused_opt and not optimizer._capturable:
             raise TypeError("GraphedTrainStep: a FusedAdamW inside the graph must be built with capturable=True "
                             "(build_optimizer(impl='hip', capturable=True)): its hyper-parameters travel in the launch arguments, "
@@ -647,6 +661,9 @@ class GraphedTrainStep:
         self.images, self.targets = images, targets
         self.clip_grad, self.reducer, self.amp_dtype, self.fused_loss = clip_grad, reducer, amp_dtype, fused_loss
         self.loss_scaler, self.grad_norm = loss_scaler, None
+        self._calls, self.updated = 0, False  # micro-steps made so far; whether the last one updated the parameters
+        if self.accumulation_steps > 1:
+            optimizer.prepare_accumulation()  # the accumulator exists before the capture begins
         if loss_scaler is not None:
             loss_scaler._lazy_init(images.device)  # its two device words exist before the capture begins
         self.graphed, self.why = False, ""
@@ -668,12 +685,15 @@ class GraphedTrainStep:
             if self.fused_opt:
                 optimizer.reset_capture()  # the graphs are gone: their gradient addresses with them
             optimizer.zero_grad(set_to_none=True)
+            self._calls = 0  # (reset_capture returned the device counter to 0 as well)
             Fn.set_seed_offset(None)  # the eager fallback draws its dropout seeds on the host again
 
     def _replays_reproduce(self):
         """Replay the captured step three times FROM THE SAME STATE (parameters, optimizer state, RNG, dropout seed offset
-        restored in between) and require bit-identical loss and parameters.  On this ROCm stack a captured small memset
-        stops taking effect from the second replay on, so a whole-step graph (ATen's reductions issue such memsets) computes
+        restored in between) and require bit-identical loss and parameters (with ``accumulation_steps`` > 1 a replay from c = 0 is an
+        accumulating micro-step that writes no parameter: the accumulator, which then holds the gradients, is compared as well;
+        it and the counter are part of what is restored, so the check begins and ends at c = 0).
+        On this ROCm stack a captured small memset stops taking effect from the second replay on, so a whole-step graph (ATen's reductions issue such memsets) computes
         from stale memory after the first replay -- exactly what this catches.  The state is restored afterwards."""
         params = [p for g in self.optimizer.param_groups for p in g["params"]]
         bufs = [b for b in self.model.buffers() if b.is_floating_point()]
@@ -682,6 +702,9 @@ class GraphedTrainStep:
         extra = [self.optimizer._ctrl, self.optimizer._exp_avg, self.optimizer._exp_avg_sq] if self.fused_opt else []
         if self.loss_scaler is not None:
             extra += [self.loss_scaler._scale, self.loss_scaler._growth_tracker]
+        acc = self.optimizer._acc if self.accumulation_steps > 1 else None
+        if acc is not None:
+            extra += [acc, self.optimizer._accum_norm]  # (the counter and the "updated" word are in _ctrl)
 
         def snap():
             st = {} if self.fused_opt else {
@@ -708,7 +731,7 @@ class GraphedTrainStep:
             self.optimizer.push_hyperparameters()  # (also sends the captured gradient addresses, in front of the first replay)
         torch.cuda.synchronize()
         s0 = snap()
-        seen = []
+        seen, acc_seen = [], []
         for _ in range(3):
             restore(s0)
             self.g_bwd.replay()
@@ -717,6 +740,8 @@ class GraphedTrainStep:
                 self.g_opt.replay()
             torch.cuda.synchronize()
             seen.append((self.loss.clone(), torch.stack([p.detach().double().sum() for p in params]).sum()))
+            if acc is not None:  # its bit patterns, summed as integers (slices of parameters without a gradient are never written)
+                acc_seen.append(acc.view(torch.int32).sum())
         restore(s0)
         if self.fused_opt:
             self.optimizer.bump_versions()  # the parameters were rewritten: copies made from them are stale
@@ -727,6 +752,9 @@ class GraphedTrainStep:
                                "which does not replay on this ROCm stack; an equal loss with differing parameters at a gradient "
                                "that is summed with atomics (an ATen backward such as bilinear interpolation)"
                                % (seen[0][0].item(), l.item(), [c.item() for _, c in seen]))
+        if any(not torch.equal(a, acc_seen[0]) for a in acc_seen[1:]):
+            return False, ("graph replays from identical state accumulate different gradients (checksums %r); running eagerly"
+                           % [a.item() for a in acc_seen])
         return True, ""
 
     # -- pieces of the step (shared by the eager fallback and the capture)
@@ -761,11 +789,11 @@ class GraphedTrainStep:
             self.reducer.flush_packs()
         return loss.detach()
 
-    def _optimize(self):
+    def _optimize(self, accumulation_steps: int = 1):
         if self.reducer is not None:
             self.reducer.unpack()
         if self.fused_opt:  # clip + unscale + AdamW + scaler update: three launches (optim.FusedAdamW)
-            self.grad_norm = self.optimizer.clip_and_step(self.clip_grad or None, self.loss_scaler)
+            self.grad_norm = self.optimizer.clip_and_step(self.clip_grad or None, self.loss_scaler, accumulation_steps)
             self.optimizer.zero_grad(set_to_none=True)
             return
         params = [p for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
@@ -774,17 +802,27 @@ class GraphedTrainStep:
         self.optimizer.step()
         self.optimizer.zero_grad(set_to_none=True)
 
-    def _eager(self):
+    def _eager(self, update_grad: bool = True):
+        """the step without a graph; ``update_grad=False`` is an accumulating micro-step as ``train_step``'s: the gradients stay
+        in ``.grad``, where autograd adds the next micro-step's, and the plain (k = 1) update consumes them at the k-th"""
         loss = self._forward_backward()
         if self.reducer is not None:
             self.reducer.all_reduce_packed()
-        self._optimize()
+        if update_grad:
+            self._optimize()
         return loss
+
+    def _count(self) -> bool:
+        self._calls += 1
+        self.updated = self._calls % self.accumulation_steps == 0
+        return self.updated
 
     def _capture(self, warmup: int):
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):  # allocator / autotune / lazy-init warm-up off the capture stream
+            # every warm-up step takes the plain k = 1 update, whatever accumulation_steps is: the step counter and the scaler end
+            # where a k = 1 warm-up leaves them, and the accumulator's counter is never touched (c == 0 when the capture begins)
             for _ in range(max(2, warmup)):  # (two: the FactorPacker builds its table -- a host-to-device copy -- at the SECOND step)
                 self._eager()
         torch.cuda.current_stream().wait_stream(side)
@@ -794,7 +832,7 @@ class GraphedTrainStep:
         if self.reducer is None:
             with torch.cuda.graph(self.g_bwd):
                 self.loss = self._forward_backward()
-                self._optimize()
+                self._optimize(self.accumulation_steps)
         else:
             with torch.cuda.graph(self.g_bwd):
                 self.loss = self._forward_backward()
@@ -804,8 +842,9 @@ class GraphedTrainStep:
         torch.cuda.synchronize()
 
     def __call__(self):
+        updated = self._count()
         if not self.graphed:
-            return self._eager()
+            return self._eager(updated)
         if self.fused_opt:
             self.optimizer.push_hyperparameters()  # a non-captured copy in front of the replay, only when param_groups changed
         self.g_bwd.replay()
@@ -813,5 +852,5 @@ class GraphedTrainStep:
             self.reducer.all_reduce_packed()
             self.g_opt.replay()
         if self.fused_opt:
-            self.optimizer.bump_versions()  # host code inside clip_and_step does not replay
+            self.optimizer.bump_versions(updated)  # host code inside clip_and_step does not replay
         return self.loss

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["FusedAdamW", "LossScaler", "uniform_step"]
+__all__ = ["FusedAdamW", "LossScaler", "uniform_step", "accumulation_steps_of"]
 
 _STATE_ALIGN = 4  # elements: every tensor's slice of the flat state buffers starts 16-byte aligned
 _HYPER_SLOTS = 4  # pinned staging slots of a capturable optimizer's hyper-parameter uploads
@@ -33,6 +33,13 @@ def uniform_step(state: Dict[Any, Dict[str, Any]]) -> float:
     if len(steps) > 1:
         raise ValueError(f"mtlora_amd: FusedAdamW keeps one step counter for all parameters; this state has steps {sorted(steps)}")
     return steps.pop() if steps else 0.0
+
+
+def accumulation_steps_of(k: Any) -> int:
+    """``k`` as a gradient-accumulation step count (the reference's ``TRAIN.ACCUMULATION_STEPS``): an integer >= 1, else ValueError"""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.ADAMW_MAX_ACCUM_STEPS:
+        raise ValueError(f"mtlora_amd: accumulation_steps must be an integer in [1, {_lib.ADAMW_MAX_ACCUM_STEPS}], got {k!r}")
+    return k
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -58,6 +65,14 @@ class FusedAdamW(torch.optim.Optimizer):
       addresses of the capture go into a device array of their own, uploaded once by the first ``push_hyperparameters()`` after
       the capture (so that call is needed before the first replay even if no value changed), and ONE set of gradient addresses
       can be captured per optimizer (eager calls between replays use buffers of their own).
+    * ``clip_and_step(..., accumulation_steps=k)`` with k > 1 (capturable only) is ONE MICRO-STEP of gradient accumulation
+      (``mtlora_adamw_accum_update_dev``; main.py:347-353): the gradients are added into a persistent fp32 accumulator the size of
+      all parameters (allocated at the first such call, or by ``prepare_accumulation()``; never zeroed: a cycle's first micro-step
+      overwrites it) and a device counter decides whether this call is the cycle's k-th, the only one that clips, steps and
+      updates the scaler.  The caller zeroes the gradients after EVERY call (they have been consumed), does not divide the loss by
+      k, and a parameter has a gradient in all of a cycle's micro-steps or in none.  The returned norm is a persistent 0-d tensor
+      that keeps the last update's value.  The accumulator and the counter are not part of ``state_dict()`` (the reference does
+      not checkpoint ``.grad`` either); ``load_state_dict()`` and ``reset_capture()`` return the counter to 0.
     """
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
@@ -137,6 +152,26 @@ class FusedAdamW(torch.optim.Optimizer):
             self._graph_ptrs: Optional[List[int]] = None
             self._graph_ptrs_sent = True  # (nothing to send yet)
             self._graph_live: List[torch.Tensor] = []
+        self._acc: Optional[torch.Tensor] = None  # gradient accumulation (capturable only): allocated on first use
+
+    def prepare_accumulation(self) -> None:
+        """allocate what ``clip_and_step(accumulation_steps > 1)`` needs -- the fp32 accumulator (as many elements as all parameters
+        together; NOT zeroed), its offset table and the persistent norm word -- so that a graph capture finds them in place"""
+        if not self._capturable:
+            raise TypeError("mtlora_amd: gradient accumulation inside the fused update needs FusedAdamW(capturable=True); with the "
+                            "by-value optimizer let autograd accumulate and call clip_and_step() every k-th micro-step")
+        if self._acc is not None:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("mtlora_amd: the accumulator must exist before a graph capture; call prepare_accumulation() first")
+        nt, dev = len(self._params), self._params[0].device
+        numel = (ctypes.c_int64 * nt)(*[p.numel() for p in self._params])
+        offs, total = torch.zeros(nt, dtype=torch.int64), ctypes.c_int64()
+        _lib.check(_lib.lib().mtlora_adamw_accum_layout(nt, numel, ctypes.cast(offs.data_ptr(), ctypes.POINTER(ctypes.c_int64)),
+                                                        ctypes.byref(total)), "adamw_accum_layout")
+        self._acc_offsets = offs.to(dev)
+        self._accum_norm = torch.zeros((), dtype=torch.float32, device=dev)
+        self._acc = torch.empty(max(total.value, 4), dtype=torch.float32, device=dev)
 
     def _slot(self, i: int, buf: torch.Tensor) -> torch.Tensor:
         p = self._params[i]
@@ -185,15 +220,17 @@ class FusedAdamW(torch.optim.Optimizer):
         self._hyper_pushed = vals
         return True
 
-    def bump_versions(self) -> None:
+    def bump_versions(self, updated: bool = True) -> None:
         """bump ``_version`` of the parameters the captured ``clip_and_step`` updates -- call it after every replay, so that
         ``MTLoRALinear`` / ``FactorPacker`` copies made from them are seen as stale (the bump inside ``clip_and_step`` is host
-        code: it ran at capture, not at replay)"""
+        code: it ran at capture, not at replay).  ``updated=False`` after the replay of an accumulating micro-step, which wrote no
+        parameter: only the order of calls is checked, no version moves and no cache is invalidated."""
         if self._capturable and self._graph_live:
             if not self._graph_ptrs_sent:  # the replay that just ran read an all-null pointer table: it did nothing but count a step
                 raise RuntimeError("mtlora_amd: the captured update was replayed before push_hyperparameters() sent its gradient "
                                    "addresses; call push_hyperparameters() before every replay()")
-            torch.autograd.graph.increment_version(self._graph_live)
+            if updated:
+                torch.autograd.graph.increment_version(self._graph_live)
 
     def reset_capture(self) -> None:
         """forget the captured gradient addresses, so that ``clip_and_step`` can be captured again (after a capture that was
@@ -201,12 +238,18 @@ class FusedAdamW(torch.optim.Optimizer):
         cannot detect."""
         if self._capturable:
             self._graph_ptrs, self._graph_live, self._graph_ptrs_sent = None, [], True
+            self._ctrl[_lib.ADAMW_CTRL_MICRO:_lib.ADAMW_CTRL_UPDATED + 1].zero_()  # an accumulation cycle starts over
 
     # ---- the update --------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def clip_and_step(self, max_norm: Optional[float] = None, scaler: Optional["LossScaler"] = None) -> torch.Tensor:
+    def clip_and_step(self, max_norm: Optional[float] = None, scaler: Optional["LossScaler"] = None,
+                      accumulation_steps: int = 1) -> torch.Tensor:
         """unscale (``scaler``) + clip_grad_norm_(``max_norm``) + AdamW + scaler update; returns the total norm of the unscaled
-        gradients before clipping as a 0-d device tensor (no ``.item()``, no synchronisation)."""
+        gradients before clipping as a 0-d device tensor (no ``.item()``, no synchronisation).  ``accumulation_steps`` k > 1: one
+        micro-step of gradient accumulation (see the class); the norm returned is that of the last update."""
+        k = accumulation_steps_of(accumulation_steps)
+        if k > 1:
+            self.prepare_accumulation()  # (TypeError for a by-value optimizer)
         params, ptrs, live, has = self._params, [], [], self._has_state
         _lib.require_gpu(params[0])
         for i, p in enumerate(params):
@@ -243,14 +286,21 @@ class FusedAdamW(torch.optim.Optimizer):
             host = torch.empty(len(ptrs), dtype=torch.int64, pin_memory=True)
             host.copy_(torch.tensor(ptrs, dtype=torch.int64))
             grad_ptrs.copy_(host, non_blocking=True)
-        norm = torch.empty((), dtype=torch.float32, device=dev)
+        norm = self._accum_norm if k > 1 else torch.empty((), dtype=torch.float32, device=dev)
         if scaler is not None:
             scaler._lazy_init(dev)
             sc, tr = scaler._scale.data_ptr(), scaler._growth_tracker.data_ptr()
             gf, bf, gint = scaler._growth_factor, scaler._backoff_factor, scaler._growth_interval
         else:
             sc, tr, gf, bf, gint = 0, 0, 2.0, 0.5, 1
-        if self._capturable:
+        if k > 1:
+            self.push_hyperparameters()
+            _lib.check(_lib.lib().mtlora_adamw_accum_update_dev(
+                self._table.data_ptr(), grad_ptrs.data_ptr(), len(params), self._n_chunks, self._hyper_dev.data_ptr(),
+                len(self.param_groups), float(max_norm) if max_norm else 0.0, self._ctrl.data_ptr(), norm.data_ptr(), sc, tr, gf,
+                bf, gint, self._scratch.data_ptr(), self._scratch_bytes, self._acc.data_ptr(), self._acc_offsets.data_ptr(), k,
+                _lib.stream_ptr()), "adamw_accum_update_dev")
+        elif self._capturable:
             self.push_hyperparameters()  # (uploads only on change; raises if that happens inside a capture)
             _lib.check(_lib.lib().mtlora_adamw_update_dev(
                 self._table.data_ptr(), grad_ptrs.data_ptr(), len(params), self._n_chunks, self._hyper_dev.data_ptr(),
