@@ -662,6 +662,67 @@ int mtlora_adamw_accum_update_dev(const void* table, const void* grads, int64_t 
                                   double backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes,
                                   float* acc, const int64_t* acc_offsets, int accum_steps, void* stream);
 
+/* The learning-rate schedule INSIDE the fused update (additive, ABI stays 12): the reference's last per-step host action,
+ * lr_scheduler.step_update((epoch * num_steps + idx) // ACCUMULATION_STEPS) (main.py:350-353, lr_scheduler.py), done by
+ * k_optim_finish from a call counter in device memory, so that a replayed train step needs nothing from the host but the next batch.
+ *   mtlora_lr_schedule   a plain record the host fills once: the four schedules of the reference's build_scheduler, counted in
+ *                        update calls (t_in_epochs = False).  For group g with base value v = base_lr[g], at count t, in double,
+ *                        without contraction, in exactly this order of operations (the order of the Python classes):
+ *                          t < warmup_t (all kinds)   warmup_lr_init + t * ((v - warmup_lr_init) / warmup_t)
+ *                          MTLORA_LR_COSINE     t -= warmup_t if warmup_prefix; i = t / t_initial; t_curr = t - t_initial * i;
+ *                                               i < 1: lr_min + 0.5 * (v - lr_min) * (1 + cos(pi * t_curr / t_initial)), else lr_min
+ *                          MTLORA_LR_STEP       v * pow(decay_rate, t / decay_t)                     (integer quotient)
+ *                          MTLORA_LR_LINEAR     t -= warmup_t; v - (v - v * lr_min_rate) * (t / (t_initial - warmup_t))
+ *                          MTLORA_LR_MULTISTEP  v * pow(gamma, the number of milestones <= t)        (milestones ascending)
+ *                        Warm-up, the linear kind and the lr_min plateau use + - * / only and equal the host's Python floats bit
+ *                        for bit; cos and pow are the device math library's.
+ *   the schedule buffer  MTLORA_ADAMW_SCHED_DEV_BYTES of DEVICE memory the optimizer owns, 8-byte aligned: the record, then
+ *                        at byte MTLORA_ADAMW_SCHED_COUNT_OFFSET an int64 u, the number of UPDATE CALLS made so far (a real
+ *                        integer: a schedule counts past 2^24, which the fp32 control words cannot), then at byte
+ *                        MTLORA_ADAMW_SCHED_LR_OFFSET double lr_used[MTLORA_ADAMW_MAX_GROUPS], the values the last update used.
+ *                        The caller uploads record and u with an ordinary copy; the kernels own them from then on.
+ *   mtlora_adamw_sched_update_dev  mtlora_adamw_accum_update_dev (same parameters, same three launches on every call) plus
+ *                        `sched_dev`, that buffer.  accum_steps == 1: every call is an update call, acc and acc_offsets may be
+ *                        null.  On an update call (c == k - 1) the per-group threads of k_optim_finish read u, form
+ *                        lr = L_g(max(u - 1, 0)), store it to lr_used[g] and use it IN PLACE OF the group record's lr (betas,
+ *                        eps and weight decay still come from `groups_dev`); u + 1 is written.  On an accumulating micro-step
+ *                        u and lr_used stay bitwise unchanged.  u follows CALLS, not Adam steps: a call that found_inf skips
+ *                        advances u (as the reference's idx advances) and not ctrl[4].  Why u - 1: the reference steps its
+ *                        scheduler AFTER the optimizer, so update 0 runs at the constructor's value, which is L(0) for all four
+ *                        kinds (milestones >= 1), and update n >= 1 at L(n - 1).  This reproduces the reference whenever
+ *                        num_steps % ACCUMULATION_STEPS == 0 (otherwise its (epoch * num_steps + idx) // k repeats or skips a
+ *                        count at an epoch boundary).  A record mtlora_lr_schedule_check rejects, a negative u or a value that
+ *                        comes out negative or nan sets found_inf on the device, exactly as a bad hyper-parameter record does:
+ *                        the step is skipped, the norm is nan, lr_used is nan.
+ *   mtlora_lr_schedule_check  pure host call: MTLORA_OK if the kernels accept the record for n_groups groups, else
+ *                        MTLORA_ERR_SHAPE -- unknown kind, n_milestones outside 0 .. MTLORA_LR_MAX_MILESTONES, milestones < 1 or
+ *                        not ascending or in front of warmup_t, warmup_t < 0, a nan or negative warmup_lr_init / base_lr /
+ *                        lr_min / lr_min_rate / decay_rate / gamma, t_initial <= 0 (cosine), t_initial <= warmup_t
+ *                        (linear), decay_t <= 0 (step).  The kernels run the same function on the device record.
+ *   mtlora_lr_schedule_value  pure host call: *lr = L_group(t) by the very function the kernel runs (the host compiler's cos
+ *                        and pow), for checks without a device; MTLORA_ERR_SHAPE if the record is rejected or t < 0. */
+#define MTLORA_LR_MAX_MILESTONES 16
+#define MTLORA_LR_COSINE 1
+#define MTLORA_LR_STEP 2
+#define MTLORA_LR_LINEAR 3
+#define MTLORA_LR_MULTISTEP 4
+typedef struct mtlora_lr_schedule {
+    int64_t kind, warmup_t, warmup_prefix, t_initial, decay_t, n_milestones; /* counts are int64, values are doubles */
+    int64_t milestones[MTLORA_LR_MAX_MILESTONES];
+    double warmup_lr_init, lr_min, lr_min_rate, decay_rate, gamma;
+    double base_lr[MTLORA_ADAMW_MAX_GROUPS];
+} mtlora_lr_schedule;
+#define MTLORA_ADAMW_SCHED_COUNT_OFFSET 344 /* sizeof(mtlora_lr_schedule) */
+#define MTLORA_ADAMW_SCHED_LR_OFFSET 352
+#define MTLORA_ADAMW_SCHED_DEV_BYTES 480
+int mtlora_lr_schedule_check(const mtlora_lr_schedule* host_record, int n_groups);
+int mtlora_lr_schedule_value(const mtlora_lr_schedule* host_record, int n_groups, int group, int64_t t, double* lr);
+int mtlora_adamw_sched_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks,
+                                  const mtlora_adamw_group* groups_dev, int n_groups, float max_norm, float* ctrl,
+                                  float* norm_out, float* scale, int32_t* growth_tracker, double growth_factor,
+                                  double backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes,
+                                  float* acc, const int64_t* acc_offsets, int accum_steps, void* sched_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Batch ingest (ABI v12): the tail of the reference's loader pipelines on the device -- RandomHorizontalFlip,
  * AddIgnoreRegions, ToTensor and Normalize of data/custom_transforms.py:192-209 and :266-341 -- for one batch in the

@@ -67,6 +67,14 @@ class AdamwGroup(Structure):
     _fields_ = [("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double)]
 
 
+class LrSchedule(Structure):
+    """mtlora_lr_schedule: the record of a device-side learning-rate schedule (mtlora_adamw_sched_update_dev); counts are int64,
+    values doubles"""
+    _fields_ = [("kind", c_int64), ("warmup_t", c_int64), ("warmup_prefix", c_int64), ("t_initial", c_int64), ("decay_t", c_int64),
+                ("n_milestones", c_int64), ("milestones", c_int64 * 16), ("warmup_lr_init", c_double), ("lr_min", c_double),
+                ("lr_min_rate", c_double), ("decay_rate", c_double), ("gamma", c_double), ("base_lr", c_double * 16)]
+
+
 class IngestJob(Structure):
     """mtlora_ingest_job (ABI v12): one tensor of a host batch in wire format, passed by value"""
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("kind", c_int32), ("src_dtype", c_int32), ("C", c_int32),
@@ -87,6 +95,10 @@ ADAMW_CHUNK, ADAMW_MAX_GROUPS, ADAMW_CTRL_WORDS = 4096, 16, 64
 ADAMW_GROUPS_DEV_BYTES = 1152  # device buffer of mtlora_adamw_update_dev: MAX_GROUPS records, then the library's derived values
 ADAMW_CTRL_MICRO, ADAMW_CTRL_UPDATED = 5, 6  # mtlora_adamw_accum_update_dev: the micro-step counter, "the last call updated"
 ADAMW_MAX_ACCUM_STEPS = 1 << 24
+LR_MAX_MILESTONES = 16
+LR_COSINE, LR_STEP, LR_LINEAR, LR_MULTISTEP = 1, 2, 3, 4
+# the schedule buffer of mtlora_adamw_sched_update_dev: the record, the int64 count of update calls, lr_used[MAX_GROUPS]
+ADAMW_SCHED_COUNT_OFFSET, ADAMW_SCHED_LR_OFFSET, ADAMW_SCHED_DEV_BYTES = 344, 352, 480
 
 PROF_KINDS = 24
 
@@ -213,6 +225,11 @@ _SIGS = {
     "mtlora_adamw_accum_update_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_float, c_void_p, c_void_p,
                                               c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_int64, c_void_p, c_void_p,
                                               c_int, c_void_p]),
+    "mtlora_lr_schedule_check": (c_int, [POINTER(LrSchedule), c_int]),
+    "mtlora_lr_schedule_value": (c_int, [POINTER(LrSchedule), c_int, c_int, c_int64, POINTER(c_double)]),
+    "mtlora_adamw_sched_update_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_float, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                              c_int, c_void_p, c_void_p]),
     "mtlora_ingest_scratch_bytes": (c_int64, [c_int, c_int64]),
     "mtlora_ingest_batch": (c_int, [POINTER(IngestJob), c_int, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                     c_void_p]),

@@ -41,6 +41,18 @@
 //                         c = 0, updated = 1.
 //   k_optim_step<G, OptGradAcc>  the same launch every micro-step (a graph replays a fixed launch list); every workgroup leaves on
 //                         updated == 0 before it reads or writes anything else; otherwise the step above with acc's slices as gradients.
+//
+// mtlora_adamw_sched_update_dev is that micro-step (k >= 1) with the learning-rate schedule of the reference's lr_scheduler.py on the
+// device: the last thing the host did between two replays (lr_scheduler.step_update, main.py:350-353).  A buffer of
+// MTLORA_ADAMW_SCHED_DEV_BYTES holds the mtlora_lr_schedule record, an int64 count u of UPDATE CALLS (not of Adam steps: a skipped
+// call counts, as the reference's idx does; and a real integer, a schedule runs past the 2^24 an fp32 word counts to) and the
+// doubles lr_used[g].
+//   k_optim_finish<OptGroupsDev, true, true>  on an update call the one-thread-per-group part reads u, forms lr = L_g(max(u - 1, 0))
+//                         (opt_sched_lr: double, no contraction, the Python classes' order of operations, so warm-up, the linear
+//                         kind and the lr_min plateau are the host's bits), stores it to lr_used[g] and hands it to opt_derive in
+//                         place of the record's lr; thread 0 writes u + 1.  A record opt_sched_ok rejects raises found_inf like a
+//                         bad hyper-parameter record.  An accumulating micro-step leaves before any of this.
+//   k_optim_norm, k_optim_step  the instantiations above, unchanged: what they read of the schedule is h.lr[g] in the groups' tail.
 #include "common.h"
 
 namespace {
@@ -110,6 +122,64 @@ __host__ __device__ inline bool opt_derive(const mtlora_adamw_group& s, OptHyper
     h.omb2 = (float)(1.0 - s.beta2);
     h.eps = (float)s.eps;
     return s.lr >= 0.0 && s.eps >= 0.0 && s.weight_decay >= 0.0 && s.beta1 >= 0.0 && s.beta1 < 1.0 && s.beta2 >= 0.0 && s.beta2 < 1.0;
+}
+
+// the schedule buffer of mtlora_adamw_sched_update_dev
+struct OptSched {
+    mtlora_lr_schedule rec;
+    int64_t u;  // update calls made so far
+    double lr_used[OPT_MAXG];
+};
+static_assert(sizeof(mtlora_lr_schedule) == MTLORA_ADAMW_SCHED_COUNT_OFFSET && __builtin_offsetof(OptSched, u) == MTLORA_ADAMW_SCHED_COUNT_OFFSET &&
+                  __builtin_offsetof(OptSched, lr_used) == MTLORA_ADAMW_SCHED_LR_OFFSET && sizeof(OptSched) == MTLORA_ADAMW_SCHED_DEV_BYTES,
+              "schedule buffer layout");
+
+// what the host checks before it uploads a record and the kernel checks again on the record it finds (fields are read in place:
+// the record is never copied into registers, so the milestone loop indexes memory, not a private array)
+__host__ __device__ inline bool opt_sched_ok(const mtlora_lr_schedule& s, int n_groups) {
+    bool ok = s.warmup_t >= 0 && s.warmup_lr_init >= 0.0;  // (a comparison with nan is false)
+    for (int g = 0; g < n_groups; ++g) ok = ok && s.base_lr[g] >= 0.0;
+    switch (s.kind) {
+        case MTLORA_LR_COSINE: return ok && s.t_initial > 0 && s.lr_min >= 0.0;
+        case MTLORA_LR_STEP: return ok && s.decay_t > 0 && s.decay_rate >= 0.0;
+        case MTLORA_LR_LINEAR: return ok && s.t_initial > s.warmup_t && s.lr_min_rate >= 0.0;
+        case MTLORA_LR_MULTISTEP: {
+            if (!(ok && s.gamma >= 0.0 && s.n_milestones >= 0 && s.n_milestones <= MTLORA_LR_MAX_MILESTONES)) return false;
+            int64_t prev = s.warmup_t > 1 ? s.warmup_t : 1;  // milestones >= 1 (L(0) is the constructor's value) and >= warmup_t
+            for (int64_t i = 0; i < s.n_milestones; ++i) {
+                if (s.milestones[i] < prev) return false;
+                prev = s.milestones[i];
+            }
+            return true;
+        }
+        default: return false;
+    }
+}
+
+// L_g(t), t >= 0, of a record opt_sched_ok accepts.  Every expression is the Python class's, operation for operation
+// (mtlora_amd/lr_scheduler.py); integer counts become doubles exactly (< 2^53)
+__host__ __device__ inline double opt_sched_lr(const mtlora_lr_schedule& s, int g, int64_t t) {
+#pragma clang fp contract(off)
+    const double v = s.base_lr[g];
+    if (t < s.warmup_t) return s.warmup_lr_init + (double)t * ((v - s.warmup_lr_init) / (double)s.warmup_t);
+    switch (s.kind) {
+        case MTLORA_LR_COSINE: {
+            if (s.warmup_prefix) t -= s.warmup_t;
+            const int64_t i = t / s.t_initial, t_curr = t - s.t_initial * i;
+            if (i >= 1) return s.lr_min;
+            return s.lr_min + 0.5 * (v - s.lr_min) * (1.0 + cos(3.141592653589793 * (double)t_curr / (double)s.t_initial));
+        }
+        case MTLORA_LR_STEP: return v * pow(s.decay_rate, (double)(t / s.decay_t));
+        case MTLORA_LR_LINEAR: {
+            t -= s.warmup_t;
+            return v - ((v - v * s.lr_min_rate) * ((double)t / (double)(s.t_initial - s.warmup_t)));
+        }
+        default: {  // MTLORA_LR_MULTISTEP
+            int passed = 0;
+            for (int64_t i = 0; i < s.n_milestones; ++i) passed += s.milestones[i] <= t ? 1 : 0;
+            return v * pow(s.gamma, (double)passed);
+        }
+    }
 }
 
 // control block words (floats), MTLORA_ADAMW_CTRL_WORDS of them
@@ -235,13 +305,15 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_norm(const OptTensor* __r
 }
 
 // G: OptGroups (by value) or OptGroupsDev.  ACC: gradient accumulation over accum_steps micro-steps -- ctrl[OC_MICRO] decides, on
-// the device, whether this call is the cycle's last; if it is not, the counter moves and NOTHING else is written.
-template <class G, bool ACC>
+// the device, whether this call is the cycle's last; if it is not, the counter moves and NOTHING else is written.  SCHED (with
+// OptGroupsDev and ACC): an update call takes each group's lr from the schedule in `sch` and counts itself there.
+template <class G, bool ACC, bool SCHED = false>
 __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __restrict__ partials, const uint32_t* __restrict__ flags,
                                                               int n_chunks, const G grp, float max_norm, float* __restrict__ ctrl,
                                                               float* __restrict__ norm_out, float* __restrict__ scale,
                                                               int32_t* __restrict__ tracker, float growth, float backoff, int interval,
-                                                              int accum_steps) {
+                                                              int accum_steps, OptSched* __restrict__ sch) {
+    static_assert(!SCHED || (ACC && __is_same(G, OptGroupsDev)), "the schedule rides on the accumulating device-record entry");
     __shared__ double red[OPT_THREADS];
     __shared__ uint32_t fl[OPT_THREADS];
     __shared__ float step_new;
@@ -260,9 +332,16 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __res
     double s = 0.0;
     uint32_t f = 0u;
     double b1d = 0.0, b2d = 0.0;
+    int64_t u = 0;
     if (tid < grp.n) {
         if constexpr (__is_same(G, OptGroupsDev)) {
-            const mtlora_adamw_group r = grp.rec[tid];
+            mtlora_adamw_group r = grp.rec[tid];
+            if constexpr (SCHED) {  // the reference steps its scheduler AFTER the optimizer: update n >= 1 runs at L(n - 1), update 0 at L(0)
+                u = sch->u;  // (thread 0 moves it behind the barrier below)
+                const bool ok = u >= 0 && opt_sched_ok(sch->rec, grp.n);
+                r.lr = ok ? opt_sched_lr(sch->rec, tid, u > 0 ? u - 1 : 0) : (double)__builtin_nanf("");  // nan: opt_derive rejects it
+                sch->lr_used[tid] = r.lr;
+            }
             OptHyper h;
             if (!opt_derive(r, h)) f = 1u;  // what the host entry rejects: found_inf, a skipped step
             opt_put(*grp.hyp, tid, h);
@@ -304,6 +383,7 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __res
             ctrl[OC_MICRO] = 0.f;
             ctrl[OC_UPDATED] = 1.f;
         }
+        if constexpr (SCHED) sch->u = u + 1;  // an update CALL, taken or skipped
         step_new = st;
         if (norm_out) *norm_out = norm;
         if (scale) {  // GradScaler.update (ATen amp_update_scale)
@@ -473,18 +553,19 @@ static int opt_launch(const void* table, const void* grads, int64_t n_tensors, i
         hipLaunchKernelGGL(k_optim_norm<false>, l.grid, block, 0, l.s, l.te, l.ce, l.gp, l.partials, l.flags, (float*)nullptr,
                            (const int64_t*)nullptr, (const float*)nullptr);
     hipLaunchKernelGGL((k_optim_finish<G, false>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g, max_norm, ctrl, norm_out,
-                       scale, growth_tracker, growth_factor, backoff_factor, growth_interval, 0);
+                       scale, growth_tracker, growth_factor, backoff_factor, growth_interval, 0, (OptSched*)nullptr);
     if (n_chunks > 0) hipLaunchKernelGGL((k_optim_step<G, OptGradPtrs>), l.grid, block, 0, l.s, l.te, l.ce, OptGradPtrs{l.gp}, ctrl, g);
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }
 
 // one micro-step of a cycle of accum_steps.  With accum_steps == 1 every call is the cycle's last and updates straight from the
-// caller's gradients: acc is not touched, and the bits are opt_launch's.
+// caller's gradients: acc is not touched, and the bits are opt_launch's.  sch: the schedule buffer, or null -- the same launches
+// either way, only k_optim_finish differs.
 static int opt_launch_accum(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const OptGroupsDev& g,
                             float max_norm, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker, float growth_factor,
                             float backoff_factor, int growth_interval, void* scratch, void* stream, float* acc, const int64_t* acc_off,
-                            int accum_steps) {
+                            int accum_steps, OptSched* sch) {
     const OptLaunch l(table, grads, n_tensors, n_chunks, scratch, stream);
     const dim3 block(OPT_THREADS);
     const bool sum = accum_steps > 1;
@@ -496,8 +577,13 @@ static int opt_launch_accum(const void* table, const void* grads, int64_t n_tens
             hipLaunchKernelGGL(k_optim_norm<false>, l.grid, block, 0, l.s, l.te, l.ce, l.gp, l.partials, l.flags, (float*)nullptr,
                                (const int64_t*)nullptr, (const float*)nullptr);
     }
-    hipLaunchKernelGGL((k_optim_finish<OptGroupsDev, true>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g, max_norm, ctrl,
-                       norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, accum_steps);
+    if (sch)
+        hipLaunchKernelGGL((k_optim_finish<OptGroupsDev, true, true>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g,
+                           max_norm, ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, accum_steps, sch);
+    else
+        hipLaunchKernelGGL((k_optim_finish<OptGroupsDev, true>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g, max_norm,
+                           ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, accum_steps,
+                           (OptSched*)nullptr);
     if (n_chunks > 0) {
         if (sum)
             hipLaunchKernelGGL((k_optim_step<OptGroupsDev, OptGradAcc>), l.grid, block, 0, l.s, l.te, l.ce, OptGradAcc{l.gp, acc, acc_off},
@@ -623,7 +709,44 @@ int mtlora_adamw_accum_update_dev(const void* table, const void* grads, int64_t 
     g.hyp = reinterpret_cast<OptHyperArr*>(const_cast<mtlora_adamw_group*>(groups_dev) + OPT_MAXG);
     g.n = n_groups;
     return opt_launch_accum(table, grads, n_tensors, n_chunks, g, max_norm, ctrl, norm_out, scale, growth_tracker, growth, backoff,
-                            growth_interval, scratch, stream, acc, acc_offsets, accum_steps);
+                            growth_interval, scratch, stream, acc, acc_offsets, accum_steps, nullptr);
+}
+
+int mtlora_lr_schedule_check(const mtlora_lr_schedule* host_record, int n_groups) {
+    if (!host_record) return MTLORA_ERR_NULL;
+    if (n_groups < 1 || n_groups > OPT_MAXG) return MTLORA_ERR_UNSUPPORTED;
+    return opt_sched_ok(*host_record, n_groups) ? MTLORA_OK : MTLORA_ERR_SHAPE;
+}
+
+int mtlora_lr_schedule_value(const mtlora_lr_schedule* host_record, int n_groups, int group, int64_t t, double* lr) {
+    if (!lr) return MTLORA_ERR_NULL;
+    const int rc = mtlora_lr_schedule_check(host_record, n_groups);
+    if (rc != MTLORA_OK) return rc;
+    if (group < 0 || group >= n_groups || t < 0) return MTLORA_ERR_SHAPE;
+    *lr = opt_sched_lr(*host_record, group, t);
+    return MTLORA_OK;
+}
+
+int mtlora_adamw_sched_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks,
+                                  const mtlora_adamw_group* groups_dev, int n_groups, float max_norm, float* ctrl, float* norm_out,
+                                  float* scale, int32_t* growth_tracker, double growth_factor, double backoff_factor, int growth_interval,
+                                  void* scratch, int64_t scratch_bytes, float* acc, const int64_t* acc_offsets, int accum_steps,
+                                  void* sched_dev, void* stream) {
+    const float growth = (float)growth_factor, backoff = (float)backoff_factor;
+    const int rc = opt_check(table, grads, n_tensors, n_chunks, groups_dev, n_groups, ctrl, norm_out, scale, growth_tracker, growth, backoff,
+                             growth_interval, scratch, scratch_bytes);
+    if (rc != MTLORA_OK) return rc;
+    if (!sched_dev) return MTLORA_ERR_NULL;
+    if (accum_steps < 1 || accum_steps > MTLORA_ADAMW_MAX_ACCUM_STEPS) return MTLORA_ERR_SHAPE;
+    if (accum_steps > 1 && (!acc || !acc_offsets)) return MTLORA_ERR_NULL;  // (k = 1 updates straight from `grads`)
+    if (((uintptr_t)groups_dev | (uintptr_t)acc_offsets | (uintptr_t)sched_dev) & 7u) return MTLORA_ERR_ALIGN;
+    if ((uintptr_t)acc & 15u) return MTLORA_ERR_ALIGN;
+    OptGroupsDev g;
+    g.rec = groups_dev;
+    g.hyp = reinterpret_cast<OptHyperArr*>(const_cast<mtlora_adamw_group*>(groups_dev) + OPT_MAXG);
+    g.n = n_groups;
+    return opt_launch_accum(table, grads, n_tensors, n_chunks, g, max_norm, ctrl, norm_out, scale, growth_tracker, growth, backoff,
+                            growth_interval, scratch, stream, acc, acc_offsets, accum_steps, reinterpret_cast<OptSched*>(sched_dev));
 }
 
 }  // extern "C"

@@ -629,6 +629,12 @@ class GraphedTrainStep:
       only at every k-th call, then zero_grad.  ``self.updated`` says whether the call just made was such an update (a host count
       of the calls: nothing is read back), i.e. when to call ``lr_scheduler.step_update``; ``self.grad_norm`` keeps the last
       update's norm in between.  The loss is not divided by k (main.py:341-349).  With the default 1 the capture is what it was.
+    * ``lr_scheduler`` (one of ``mtlora_amd.lr_scheduler``'s, built with ``t_in_epochs=False``; ``FusedAdamW`` only): the schedule is
+      attached to the optimizer before the capture (``FusedAdamW.attach_schedule``), so the captured update -- the optimizer graph
+      with a reducer -- computes each update call's learning rate on the device and counts the calls itself; the warm-up steps
+      of the capture are update calls like any other.  The loop then hands over batches and nothing else: no ``step_update``, no
+      upload in front of a replay.  Calling ``lr_scheduler.step_update`` anyway is harmless, it moves ``param_groups["lr"]`` for
+      logging only (``optimizer.lr_used()`` is what the kernels used).
     Falls back to the eager step (``self.graphed = False``, reason in ``self.why``) if capture fails.
 
     Not bench.py's default (``--graph``): at C2 the eager step with its side streams is faster (34.8 ms vs 36.5 ms for the
@@ -642,7 +648,7 @@ class GraphedTrainStep:
 
     def __init__(self, model, criterion, optimizer, images, targets, clip_grad: float = 5.0, reducer=None,
                  amp_dtype: Optional[torch.dtype] = torch.bfloat16, fused_loss: bool = True, warmup: int = 3, loss_scaler=None,
-                 accumulation_steps: int = 1):
+                 accumulation_steps: int = 1, lr_scheduler=None):
         self.accumulation_steps = accumulation_steps_of(accumulation_steps)
         if self.accumulation_steps > 1 and reducer is not None:
             raise ValueError("GraphedTrainStep: accumulation_steps > 1 with a reducer is not supported (the all-reduce would have to "
@@ -657,7 +663,13 @@ class GraphedTrainStep:
                             "which a replay cannot follow")
         if loss_scaler is not None and not self.fused_opt:
             raise TypeError("GraphedTrainStep: loss_scaler needs the HIP optimizer (build_optimizer(impl='hip', capturable=True))")
+        if lr_scheduler is not None and not self.fused_opt:
+            raise TypeError("GraphedTrainStep: lr_scheduler needs the HIP optimizer (build_optimizer(impl='hip', capturable=True)): the "
+                            "schedule runs inside its kernels; with a torch optimizer the capture step's lr is what every replay uses")
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
+        self.lr_scheduler = lr_scheduler
+        if lr_scheduler is not None:
+            optimizer.attach_schedule(lr_scheduler)  # before the warm-up and the capture: the captured update contains the schedule
         self.images, self.targets = images, targets
         self.clip_grad, self.reducer, self.amp_dtype, self.fused_loss = clip_grad, reducer, amp_dtype, fused_loss
         self.loss_scaler, self.grad_norm = loss_scaler, None
@@ -700,6 +712,8 @@ class GraphedTrainStep:
 
         # what the torch path never had: FusedAdamW's control block (step counter) and flat state buffers, the scaler's two words
         extra = [self.optimizer._ctrl, self.optimizer._exp_avg, self.optimizer._exp_avg_sq] if self.fused_opt else []
+        if self.fused_opt:
+            extra.append(self.optimizer._sched_dev)  # the schedule's count of update calls and lr_used (zeros without a schedule)
         if self.loss_scaler is not None:
             extra += [self.loss_scaler._scale, self.loss_scaler._growth_tracker]
         acc = self.optimizer._acc if self.accumulation_steps > 1 else None

@@ -73,6 +73,15 @@ class FusedAdamW(torch.optim.Optimizer):
       k, and a parameter has a gradient in all of a cycle's micro-steps or in none.  The returned norm is a persistent 0-d tensor
       that keeps the last update's value.  The accumulator and the counter are not part of ``state_dict()`` (the reference does
       not checkpoint ``.grad`` either); ``load_state_dict()`` and ``reset_capture()`` return the counter to 0.
+    * ``attach_schedule(scheduler)`` (capturable only) moves the learning-rate schedule onto the device
+      (``mtlora_adamw_sched_update_dev``): every update call then takes each group's lr from the schedule, at a count ``u`` of
+      update calls the kernels keep themselves, and ``lr_scheduler.step_update`` has nothing left to do -- a replayed step needs
+      no ``push_hyperparameters()`` upload for the lr.  Update call n uses ``scheduler._get_lr(max(n - 1, 0))``: the reference
+      steps its scheduler AFTER the optimizer (main.py:350-353), so update 0 runs at the constructor's value, which is
+      ``_get_lr(0)``, and update n at what ``step_update(n - 1)`` set.  This reproduces the reference whenever ``num_steps %
+      ACCUMULATION_STEPS == 0`` (otherwise its ``(epoch * num_steps + idx) // k`` repeats a count at an epoch boundary).  ``u``
+      counts CALLS: a call skipped for inf / nan advances it and not the Adam step.  ``lr_used()`` / ``num_updates()`` are device
+      views for logging; ``state_dict()`` carries ``u`` under ``"lr_schedule_updates"`` while a schedule is attached.
     """
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
@@ -152,6 +161,10 @@ class FusedAdamW(torch.optim.Optimizer):
             self._graph_ptrs: Optional[List[int]] = None
             self._graph_ptrs_sent = True  # (nothing to send yet)
             self._graph_live: List[torch.Tensor] = []
+            # the schedule buffer (record, update-call count, lr_used): in place from the start, so that a capture finds it
+            self._sched_dev = torch.zeros(_lib.ADAMW_SCHED_DEV_BYTES // 8, dtype=torch.int64, device=dev)
+        self._sched = None  # the attached scheduler (capturable only)
+        self._sched_loaded: Optional[int] = None  # an update-call count load_state_dict() found and attach_schedule() has yet to use
         self._acc: Optional[torch.Tensor] = None  # gradient accumulation (capturable only): allocated on first use
 
     def prepare_accumulation(self) -> None:
@@ -172,6 +185,102 @@ class FusedAdamW(torch.optim.Optimizer):
         self._acc_offsets = offs.to(dev)
         self._accum_norm = torch.zeros((), dtype=torch.float32, device=dev)
         self._acc = torch.empty(max(total.value, 4), dtype=torch.float32, device=dev)
+
+    # ---- capturable: the learning-rate schedule on the device ---------------------------------------------------------------
+    def _schedule_record(self, scheduler) -> "_lib.LrSchedule":
+        """``scheduler`` (one of lr_scheduler's four classes, counted in updates) as the record the kernels read; ValueError for
+        what they would reject"""
+        from . import lr_scheduler as S
+        kinds = ((S.CosineLRScheduler, _lib.LR_COSINE), (S.StepLRScheduler, _lib.LR_STEP), (S.LinearLRScheduler, _lib.LR_LINEAR),
+                 (S.MultiStepLRScheduler, _lib.LR_MULTISTEP))
+        kind = next((k for c, k in kinds if isinstance(scheduler, c)), None)
+        if kind is None:
+            raise TypeError("mtlora_amd: attach_schedule() takes a scheduler of mtlora_amd.lr_scheduler (cosine, step, linear or "
+                            f"multistep), got {type(scheduler).__name__}")
+        if scheduler.t_in_epochs:
+            raise ValueError("mtlora_amd: the device-side schedule counts update calls; build the scheduler with t_in_epochs=False")
+        n = len(self.param_groups)
+        if len(scheduler.base_values) != n:
+            raise ValueError(f"mtlora_amd: the scheduler has {len(scheduler.base_values)} base values, the optimizer {n} groups")
+        r = _lib.LrSchedule()
+        r.kind, r.warmup_t, r.warmup_lr_init = kind, int(scheduler.warmup_t), float(scheduler.warmup_lr_init)
+        for g, v in enumerate(scheduler.base_values):
+            r.base_lr[g] = float(v)
+        if kind == _lib.LR_COSINE:
+            if (scheduler.cycle_mul, scheduler.cycle_decay, scheduler.cycle_limit, scheduler.k_decay) != (1, 1, 1, 1):
+                raise ValueError("mtlora_amd: the device-side cosine schedule is one cycle without decay")
+            r.t_initial, r.lr_min, r.warmup_prefix = int(scheduler.t_initial), float(scheduler.lr_min), int(bool(scheduler.warmup_prefix))
+        elif kind == _lib.LR_STEP:
+            r.decay_t, r.decay_rate = int(scheduler.decay_t), float(scheduler.decay_rate)
+        elif kind == _lib.LR_LINEAR:
+            r.t_initial, r.lr_min_rate = int(scheduler.t_initial), float(scheduler.lr_min_rate)
+        else:
+            ms = [int(m) for m in scheduler.milestones]
+            if len(ms) > _lib.LR_MAX_MILESTONES:
+                raise ValueError(f"mtlora_amd: the device-side multistep schedule holds up to {_lib.LR_MAX_MILESTONES} milestones, got {len(ms)}")
+            r.gamma, r.n_milestones = float(scheduler.gamma), len(ms)
+            for i, m in enumerate(ms):
+                r.milestones[i] = m
+        for name in ("warmup_t", "t_initial", "decay_t"):  # counts the kernels hold as integers
+            if hasattr(scheduler, name) and int(getattr(scheduler, name)) != getattr(scheduler, name):
+                raise ValueError(f"mtlora_amd: the device-side schedule needs an integer {name}, got {getattr(scheduler, name)!r}")
+        if _lib.lib().mtlora_lr_schedule_check(ctypes.byref(r), n) != 0:
+            raise ValueError("mtlora_amd: this schedule cannot run on the device (a nan or negative value, t_initial <= 0 where it "
+                             "divides, milestones that are not ascending, below 1 or inside the warm-up): "
+                             f"{ {k: v for k, v in scheduler.state_dict().items() if not k.startswith('_')} }")
+        return r
+
+    def attach_schedule(self, scheduler, num_updates: Optional[int] = None) -> None:
+        """run ``scheduler`` on the device from now on (see the class): the record is validated, uploaded with an ordinary copy,
+        and the count of update calls set to ``num_updates`` -- by default the count ``load_state_dict()`` found in the checkpoint
+        if there was one, else what the scheduler last saw (0 for a fresh one, n + 1 after ``step_update(n)`` or after its
+        ``load_state_dict`` of such a state).  Attach BEFORE capturing ``clip_and_step``: a graph keeps the entry point of its capture."""
+        if not self._capturable:
+            raise TypeError("mtlora_amd: attach_schedule() needs FusedAdamW(capturable=True); a by-value optimizer takes its lr "
+                            "from param_groups at every call (lr_scheduler.step_update)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("mtlora_amd: attach_schedule() inside a graph capture: the upload would be baked into the graph -- "
+                               "attach the schedule before capturing")
+        if self._graph_ptrs is not None:
+            raise RuntimeError("mtlora_amd: clip_and_step was already captured without this schedule; attach it before the capture "
+                               "(or reset_capture() once the old graph is gone)")
+        rec = self._schedule_record(scheduler)
+        if num_updates is None:
+            num_updates = self._sched_loaded if self._sched_loaded is not None else int(getattr(scheduler, "num_updates_seen", 0))
+        if isinstance(num_updates, bool) or int(num_updates) != num_updates or num_updates < 0:
+            raise ValueError(f"mtlora_amd: num_updates must be an integer >= 0, got {num_updates!r}")
+        _lib.require_gpu(self._params[0])
+        host = torch.zeros(_lib.ADAMW_SCHED_DEV_BYTES // 8, dtype=torch.int64)
+        ctypes.memmove(host.data_ptr(), ctypes.byref(rec), ctypes.sizeof(rec))
+        host[_lib.ADAMW_SCHED_COUNT_OFFSET // 8] = int(num_updates)
+        self._sched_dev.copy_(host)  # (lr_used starts at 0.0; the first update call writes it)
+        self._sched, self._sched_loaded = scheduler, None
+
+    def detach_schedule(self) -> None:
+        """back to the group records' lr (``param_groups`` through ``push_hyperparameters()``) from the next call on; the count
+        and ``lr_used`` keep their last values.  As ``attach_schedule``: not under a capture, not after one."""
+        if self._sched is None:
+            return
+        if torch.cuda.is_current_stream_capturing() or self._graph_ptrs is not None:
+            raise RuntimeError("mtlora_amd: detach_schedule() cannot change a captured clip_and_step; reset_capture() first, once "
+                               "the graph is gone")
+        self._sched = None
+        self._hyper_pushed = None  # the lr in the device records is whatever was pushed before the schedule took over: push again
+
+    def _need_schedule(self) -> None:
+        if not self._capturable or self._sched is None:
+            raise RuntimeError("mtlora_amd: no schedule is attached (FusedAdamW(capturable=True).attach_schedule(scheduler))")
+
+    def lr_used(self) -> torch.Tensor:
+        """the learning rates the last update call used, one double per param group: a view of device memory, no synchronisation"""
+        self._need_schedule()
+        at = _lib.ADAMW_SCHED_LR_OFFSET // 8
+        return self._sched_dev.view(torch.float64)[at:at + len(self.param_groups)]
+
+    def num_updates(self) -> torch.Tensor:
+        """the number of update calls made so far (skipped ones included), a 0-d int64 view of device memory"""
+        self._need_schedule()
+        return self._sched_dev[_lib.ADAMW_SCHED_COUNT_OFFSET // 8]
 
     def _slot(self, i: int, buf: torch.Tensor) -> torch.Tensor:
         p = self._params[i]
@@ -201,6 +310,9 @@ class FusedAdamW(torch.optim.Optimizer):
             self._graph_grad_ptrs.copy_(self._graph_ptr_host, non_blocking=True)  # the captured gradient addresses, once
             self._graph_ptrs_sent = True
         vals = self._hyper_values()
+        if self._sched is not None and self._hyper_pushed is not None:
+            # the kernels take lr from the schedule: a host-side step_update() that moves param_groups["lr"] (for logging) uploads nothing
+            vals[0::_GROUP_WORDS] = self._hyper_pushed[0::_GROUP_WORDS]
         if vals == self._hyper_pushed:
             return False
         if torch.cuda.is_current_stream_capturing():
@@ -293,7 +405,15 @@ class FusedAdamW(torch.optim.Optimizer):
             gf, bf, gint = scaler._growth_factor, scaler._backoff_factor, scaler._growth_interval
         else:
             sc, tr, gf, bf, gint = 0, 0, 2.0, 0.5, 1
-        if k > 1:
+        if self._capturable and self._sched is not None:  # the lr comes from the schedule buffer, for any k
+            self.push_hyperparameters()  # (betas / eps / weight decay, on change)
+            acc, off = (self._acc.data_ptr(), self._acc_offsets.data_ptr()) if k > 1 else (0, 0)
+            _lib.check(_lib.lib().mtlora_adamw_sched_update_dev(
+                self._table.data_ptr(), grad_ptrs.data_ptr(), len(params), self._n_chunks, self._hyper_dev.data_ptr(),
+                len(self.param_groups), float(max_norm) if max_norm else 0.0, self._ctrl.data_ptr(), norm.data_ptr(), sc, tr, gf,
+                bf, gint, self._scratch.data_ptr(), self._scratch_bytes, acc, off, k, self._sched_dev.data_ptr(),
+                _lib.stream_ptr()), "adamw_sched_update_dev")
+        elif k > 1:
             self.push_hyperparameters()
             _lib.check(_lib.lib().mtlora_adamw_accum_update_dev(
                 self._table.data_ptr(), grad_ptrs.data_ptr(), len(params), self._n_chunks, self._hyper_dev.data_ptr(),
@@ -335,6 +455,8 @@ class FusedAdamW(torch.optim.Optimizer):
         sd = super().state_dict()
         sd["state"] = {k: {n: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for n, v in s.items()}
                        for k, s in sd["state"].items()}
+        if self._capturable and self._sched is not None:  # the schedule's position, next to the step counter (torch ignores the key)
+            sd["lr_schedule_updates"] = int(self.num_updates().item())
         return sd
 
     @torch.no_grad()
@@ -357,6 +479,12 @@ class FusedAdamW(torch.optim.Optimizer):
             self._init_state(i)
         self._ctrl.zero_()
         self._ctrl[4] = step
+        if self._capturable and "lr_schedule_updates" in state_dict:  # (a state without the key loads as it always did)
+            n = int(state_dict["lr_schedule_updates"])
+            if self._sched is not None:
+                self._sched_dev[_lib.ADAMW_SCHED_COUNT_OFFSET // 8] = n
+            else:
+                self._sched_loaded = n  # the next attach_schedule() starts from it
         for g in self.param_groups:
             g["capturable"] = self._capturable  # (a property of this object's buffers, not of the checkpoint)
         if self._capturable:

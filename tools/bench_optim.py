@@ -16,6 +16,10 @@ learning rate is set anew and pushed to the device before every replay (the torc
 buffers.  Each leg runs in a process of its own, ``--runs`` times, alternating; per leg the median over its replays of the DEVICE
 time (HIP events around the replay) and of the HOST time of one replay (with push_hyperparameters() and bump_versions() for the
 fused leg), then the median and the spread (max - min) over the runs.
+
+``--graph --schedule``: what the device-side LR schedule takes off the host.  Two FusedAdamW legs under the same cosine schedule
+(mtlora_amd.lr_scheduler): ``hip`` steps the host scheduler and pushes the new lr in front of every replay, ``hipsched`` has the
+schedule attached (FusedAdamW.attach_schedule) and only replays.  Same columns; written to profiles/optim_graph_schedule.txt.
 """
 import argparse
 import json
@@ -35,9 +39,16 @@ HBM_COPY_TBS = 6.29  # the copy ceiling the project quotes for the MI355X (BASEL
 def graph_leg(a):
     """one leg of --graph in this process: capture the update once, replay it; prints one GRAPH_LEG json line"""
     from mtlora_amd import mtl_harness as H
-    impl, dev = a.graph_leg, torch.device("cuda:0")
+    from mtlora_amd.lr_scheduler import CosineLRScheduler
+    leg, dev = a.graph_leg, torch.device("cuda:0")
+    impl = "hip" if leg == "hipsched" else leg
     model = H.build_config_model(a.config, seed=0).to(dev).train()
     opt = H.build_optimizer(model, lr=5e-4, impl=impl, capturable=True)
+    sched = None
+    if a.schedule and impl == "hip":  # (long enough that the timed replays stay on the cosine segment)
+        sched = CosineLRScheduler(opt, t_initial=100 * (a.iters + a.warmup), lr_min=1e-6, warmup_t=5, warmup_lr_init=1e-7, t_in_epochs=False)
+        if leg == "hipsched":
+            opt.attach_schedule(sched)
     ps = [p for g in opt.param_groups for p in g["params"]]
     gen = torch.Generator(device=dev).manual_seed(1)
     for p in ps:
@@ -62,7 +73,12 @@ def graph_leg(a):
         update()
 
     def replay(k):
-        if impl == "hip":  # a moving learning rate: set, pushed (one small copy in front of the replay), replayed
+        if leg == "hipsched":  # the schedule is in the graph: nothing to do on the host
+            pass
+        elif sched is not None:  # the host scheduler steps, the new lr is pushed
+            sched.step_update(k)
+            opt.push_hyperparameters()
+        elif impl == "hip":  # a moving learning rate: set, pushed (one small copy in front of the replay), replayed
             for g in opt.param_groups:
                 g["lr"] = 5e-4 * (1.0 - 1e-4 * k)
             opt.push_hyperparameters()
@@ -87,13 +103,15 @@ def graph_leg(a):
     wall = (time.perf_counter() - w0) * 1e3 / a.iters
     devms = [e0.elapsed_time(e1) for e0, e1 in events]
     finite = all(bool(torch.isfinite(p).all()) for p in ps)
-    print("GRAPH_LEG " + json.dumps({"impl": impl, "device_ms": statistics.median(devms), "host_ms": statistics.median(host),
+    print("GRAPH_LEG " + json.dumps({"impl": leg, "device_ms": statistics.median(devms), "host_ms": statistics.median(host),
                                      "wall_ms": wall, "finite": finite, "tensors": len(ps), "elements": sum(p.numel() for p in ps),
                                      "gpu": torch.cuda.get_device_name(0)}), flush=True)
 
 
 def graph_ab(a):
     """--graph: the two legs alternate, each in a fresh child process (this process never opens the GPU)"""
+    if a.schedule:
+        return schedule_ab(a)
     rows = {"torch": [], "hip": []}
     for _ in range(a.runs):
         for impl in ("torch", "hip"):
@@ -132,6 +150,44 @@ def graph_ab(a):
         f.write(text)
 
 
+def schedule_ab(a):
+    """--graph --schedule: per-step push against the schedule inside the graph; each leg in a fresh child process, alternating"""
+    rows = {"hip": [], "hipsched": []}
+    for _ in range(a.runs):
+        for leg in rows:
+            cmd = [sys.executable, os.path.abspath(__file__), "--graph-leg", leg, "--schedule", "--config", a.config, "--iters",
+                   str(a.iters), "--warmup", str(a.warmup)]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            line = [l for l in r.stdout.splitlines() if l.startswith("GRAPH_LEG ")]
+            if r.returncode != 0 or not line:
+                raise SystemExit(f"bench_optim: the {leg} leg failed (exit {r.returncode}):\n{r.stderr[-2000:]}")
+            rows[leg].append(json.loads(line[-1][len("GRAPH_LEG "):]))
+            if not rows[leg][-1]["finite"]:
+                raise SystemExit(f"bench_optim: the {leg} leg left non-finite parameters")
+    one = rows["hip"][0]
+    lines = [f"bench_optim --graph --schedule: FusedAdamW.clip_and_step REPLAYED under a cosine schedule on the trainable set of "
+             f"{a.config}: {one['tensors']} tensors, {one['elements']} elements",
+             f"box: {one['gpu']}, torch {torch.__version__}, HIP {torch.version.hip}; each leg in its own process, {a.runs} runs each, "
+             f"alternating; {a.iters} timed replays after {a.warmup} warm-up replays",
+             "per replay                                               device ms            host ms              wall ms (iters / sync)",
+             "                                                         median  spread       median  spread       median  spread"]
+    med = {}
+    for leg, what in (("hip", "host: step_update + push_hyperparameters + replay     "),
+                      ("hipsched", "device: attach_schedule, replay only                  ")):
+        cols = []
+        for key in ("device_ms", "host_ms", "wall_ms"):
+            v = [r[key] for r in rows[leg]]
+            med[leg, key] = statistics.median(v)
+            cols.append(f"{med[leg, key]:8.4f} {max(v) - min(v):7.4f}")
+        lines.append(f"{what}   " + "     ".join(cols))
+    lines.append(f"host time saved per replay: {(med['hip', 'host_ms'] - med['hipsched', 'host_ms']) * 1e3:.1f} us")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2")
@@ -140,11 +196,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--graph", action="store_true", help="A/B of the update replayed from a HIP graph, each leg in its own process")
     ap.add_argument("--runs", type=int, default=3, help="--graph: runs per leg")
-    ap.add_argument("--graph-leg", choices=("torch", "hip"), default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--schedule", action="store_true", help="--graph: host scheduler + per-step push against the device-side schedule")
+    ap.add_argument("--graph-leg", choices=("torch", "hip", "hipsched"), default=None, help=argparse.SUPPRESS)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     a.iters = a.iters or (200 if (a.graph or a.graph_leg) else 50)
-    a.out = a.out or os.path.join("profiles", "optim_graph_ab.txt" if a.graph else "optim_ab.txt")
+    a.out = a.out or os.path.join("profiles", ("optim_graph_schedule.txt" if a.schedule else "optim_graph_ab.txt") if a.graph else "optim_ab.txt")
     if a.graph:
         return graph_ab(a)
     if not torch.cuda.is_available():
