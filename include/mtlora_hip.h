@@ -822,6 +822,40 @@ int mtlora_augment_batch(const mtlora_augment_job* jobs, int n_jobs, int64_t B, 
                          const float* cubic_f32, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training meters (added under ABI v12, additive): replaces timm's AverageMeter.update as the reference's train loop uses it
+ * (main.py:318-321 the meters, :354-365 loss scale, loss, gradient norm, :384-386 the per-task losses) -- there one .item() /
+ * state_dict() read-back per value and step, here ONE launch at the end of the step that reads every value where it already
+ * sits in device memory.
+ *
+ * `bank`     n_slots x {val, sum, count, skipped}, doubles, 16-byte aligned.  avg = sum / count is the reader's division.
+ * `table`    n_slots records in device memory: `src` a device address holding one fp32 (MTLORA_METER_F32) or fp64
+ *            (MTLORA_METER_F64) value, aligned to it; `weight` AverageMeter's n; `period` k >= 1 (a smaller value counts as 1).
+ *            A record whose src is null is never served.
+ * `counter`  one device int64, owned by the bank: the number of update calls so far.
+ * A call that finds the counter at c serves slot i iff (c + 1) % period == 0 (an untouched slot is not written): v = *src;
+ * v finite: val = v, sum += v * weight, count += weight (product and sum rounded separately); v inf or nan: val = v,
+ * skipped += 1, sum and count stay -- unlike AverageMeter, where one overflowed fp16 step would turn the epoch's average into
+ * inf / nan.  Then counter = c + 1.
+ * One launch of one 64-lane workgroup on `stream`, lane i serving slot i; plain loads and vector stores, no atomics, no
+ * memset, nothing allocated, retained or synchronised: every pointer is a launch argument, so a captured launch replays as is.
+ * The reset is a zero-fill kernel over the bank (a captured memset does not replay reliably, see the train-step notes);
+ * keep_phase == 0 zeroes the counter as well, keep_phase != 0 keeps the position inside the periods.
+ * Rejected before any launch: n_slots outside 1 .. MTLORA_METER_MAX_SLOTS (MTLORA_ERR_SHAPE, before any pointer is looked at);
+ * a null bank, table or counter (MTLORA_ERR_NULL); a bank off 16 bytes, a table or counter off 8 (MTLORA_ERR_ALIGN).
+ * ------------------------------------------------------------------------------------------ */
+#define MTLORA_METER_MAX_SLOTS 64
+#define MTLORA_METER_F32 0
+#define MTLORA_METER_F64 1
+typedef struct mtlora_meter_source {
+    const void* src;
+    int32_t dtype, reserved;
+    double weight;
+    int64_t period;
+} mtlora_meter_source;
+int mtlora_meter_update(double* bank, const mtlora_meter_source* table, int n_slots, int64_t* counter, void* stream);
+int mtlora_meter_reset(double* bank, int n_slots, int64_t* counter, int keep_phase, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hardware self-test: writes the lane->element maps of the MFMA / LDS-transpose primitives the
  * kernels rely on into `out` (int32[4096]) so a GPU test can assert them (tests/test_gpu_layouts.py).
  * ------------------------------------------------------------------------------------------ */

@@ -86,6 +86,12 @@ class AugmentJob(Structure):
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("kind", c_int32), ("flags", c_int32)]
 
 
+class MeterSource(Structure):
+    """mtlora_meter_source: where one slot of a meter bank reads its value, AverageMeter's n and the slot's period"""
+    _fields_ = [("src", c_void_p), ("dtype", c_int32), ("reserved", c_int32), ("weight", c_double), ("period", c_int64)]
+
+
+METER_MAX_SLOTS, METER_F32, METER_F64 = 64, 0, 1
 INGEST_MAX_JOBS = 8
 AUGMENT_IMAGE_CUBIC_U8, AUGMENT_CLASS_NEAREST_U8, AUGMENT_NORMALS_CUBIC_F32, AUGMENT_DEPTH_NEAREST_F32 = 0, 1, 2, 3
 AUGMENT_GEOM_BITS, AUGMENT_FLAG_NO_RENORM = 24, 1
@@ -235,6 +241,8 @@ _SIGS = {
                                     c_void_p]),
     "mtlora_augment_batch": (c_int, [POINTER(AugmentJob), c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mtlora_meter_update": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "mtlora_meter_reset": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "mtlora_selftest_layouts": (c_int, [c_void_p, c_void_p]),
     "mtlora_prof_begin": (c_int, [c_int]),
     "mtlora_prof_end": (c_int, [POINTER(ProfSummary)]),

@@ -460,13 +460,16 @@ def _factor_packer(model):
 
 def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 5.0, reducer=None,
                amp_dtype: Optional[torch.dtype] = torch.bfloat16, fused_loss: bool = True, loss_scaler=None,
-               update_grad: bool = True):
+               update_grad: bool = True, meters=None):
     """one reference train step (main.py:329-354): autocast fwd + weighted multi-task loss, backward,
     [gradient all-reduce], clip_grad_norm_(5.0), AdamW, zero_grad.  bf16 autocast needs no GradScaler
     (the reference's scaler exists for its fp16 default: ``loss_scaler``, an ``optim.LossScaler``, scales the loss before
     backward and is unscaled / updated inside the ``optim.FusedAdamW`` update).  ``update_grad=False`` is a gradient-accumulation
     micro-step (main.py:349): forward and backward only, the gradients stay and ``(loss, None)`` is returned.  With a
-    ``FusedAdamW`` the clip, the step and the scaler update are ``clip_and_step``'s three launches."""
+    ``FusedAdamW`` the clip, the step and the scaler update are ``clip_and_step``'s three launches.  ``meters`` (a
+    ``meters.TrainMeters.for_train_step``): after the update, or after the backward of an accumulating micro-step, the loss, the
+    per-task losses and -- on an update step -- the norm are written into the meters' device sources by one small kernel and
+    ``meters.update()`` is launched; nothing is read back, and the step computes what it computes without them."""
     fused_opt = isinstance(optimizer, FusedAdamW)
     if loss_scaler is not None and not fused_opt:
         raise TypeError("train_step: loss_scaler needs the HIP optimizer (build_optimizer(impl='hip'))")
@@ -505,15 +508,19 @@ def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 
     if reducer is not None:
         reducer.finish()
     if not update_grad:
+        if meters is not None:
+            meters.stage_train_step(loss, per, None)
         return loss.detach(), None
     if fused_opt:
         norm = optimizer.clip_and_step(clip_grad or None, loss_scaler)
         optimizer.zero_grad(set_to_none=True)
-        return loss.detach(), norm
-    params = [p for g in optimizer.param_groups for p in g["params"] if p.grad is not None]
-    norm = torch.nn.utils.clip_grad_norm_(params, clip_grad, foreach=True) if clip_grad else None
-    optimizer.step()
-    optimizer.zero_grad(set_to_none=True)
+    else:
+        params = [p for g in optimizer.param_groups for p in g["params"] if p.grad is not None]
+        norm = torch.nn.utils.clip_grad_norm_(params, clip_grad, foreach=True) if clip_grad else None
+        optimizer.step()
+        optimizer.zero_grad(set_to_none=True)
+    if meters is not None:
+        meters.stage_train_step(loss, per, norm)
     return loss.detach(), norm
 
 
@@ -635,6 +642,12 @@ class GraphedTrainStep:
       of the capture are update calls like any other.  The loop then hands over batches and nothing else: no ``step_update``, no
       upload in front of a replay.  Calling ``lr_scheduler.step_update`` anyway is harmless, it moves ``param_groups["lr"]`` for
       logging only (``optimizer.lr_used()`` is what the kernels used).
+    * ``meters`` (a ``meters.TrainMeters.for_train_step``; with ``lr_scheduler``, attach the schedule to the optimizer before building
+      them so that they hold the ``lr`` slot): the loss, the per-task losses and the norm are written into the meters' device sources
+      and ``meters.update()`` is launched as the LAST nodes of the graph (of the optimizer graph with a reducer), so a replay meters
+      itself and the loop logs from ``meters.snapshot()`` / ``meters.latest()`` without a ``.item()``.  The constructor ends with
+      ``meters.reset(keep_phase=False)`` -- the warm-up steps and the replays of ``_replays_reproduce`` do not count -- and the
+      bank's call counter then moves in lockstep with the calls made here.
     Falls back to the eager step (``self.graphed = False``, reason in ``self.why``) if capture fails.
 
     Not bench.py's default (``--graph``): at C2 the eager step with its side streams is faster (34.8 ms vs 36.5 ms for the
@@ -648,7 +661,7 @@ class GraphedTrainStep:
 
     def __init__(self, model, criterion, optimizer, images, targets, clip_grad: float = 5.0, reducer=None,
                  amp_dtype: Optional[torch.dtype] = torch.bfloat16, fused_loss: bool = True, warmup: int = 3, loss_scaler=None,
-                 accumulation_steps: int = 1, lr_scheduler=None):
+                 accumulation_steps: int = 1, lr_scheduler=None, meters=None):
         self.accumulation_steps = accumulation_steps_of(accumulation_steps)
         if self.accumulation_steps > 1 and reducer is not None:
             raise ValueError("GraphedTrainStep: accumulation_steps > 1 with a reducer is not supported (the all-reduce would have to "
@@ -673,6 +686,7 @@ class GraphedTrainStep:
         self.images, self.targets = images, targets
         self.clip_grad, self.reducer, self.amp_dtype, self.fused_loss = clip_grad, reducer, amp_dtype, fused_loss
         self.loss_scaler, self.grad_norm = loss_scaler, None
+        self.meters, self._per = meters, None  # (the per-task losses of the last forward: what the meters read)
         self._calls, self.updated = 0, False  # micro-steps made so far; whether the last one updated the parameters
         if self.accumulation_steps > 1:
             optimizer.prepare_accumulation()  # the accumulator exists before the capture begins
@@ -699,6 +713,10 @@ class GraphedTrainStep:
             optimizer.zero_grad(set_to_none=True)
             self._calls = 0  # (reset_capture returned the device counter to 0 as well)
             Fn.set_seed_offset(None)  # the eager fallback draws its dropout seeds on the host again
+        if meters is not None:
+            # the warm-up steps and the replays of _replays_reproduce were metered like any other: the epoch starts empty, and the
+            # bank's call counter starts at 0 with _calls (they stay in lockstep: both count every call from here on)
+            meters.reset(keep_phase=False)
 
     def _replays_reproduce(self):
         """Replay the captured step three times FROM THE SAME STATE (parameters, optimizer state, RNG, dropout seed offset
@@ -780,12 +798,14 @@ class GraphedTrainStep:
                else contextlib.nullcontext())
         with ctx:
             if self.fused_loss and isinstance(self.model, MultiTaskSwin):  # as train_step: each loss inside its task's stream
-                loss, _ = self.criterion.combine(self.model(
+                loss, per = self.criterion.combine(self.model(
                     self.images, upsample=False, per_task_fn=lambda t, lo: self.criterion.task_low(t, lo, self.targets[t])))
             elif self.fused_loss:
-                loss, _ = self.criterion.forward_low(self.model(self.images, upsample=False), self.targets)
+                loss, per = self.criterion.forward_low(self.model(self.images, upsample=False), self.targets)
             else:
-                loss, _ = self.criterion(self.model(self.images), self.targets)
+                loss, per = self.criterion(self.model(self.images), self.targets)
+        if self.meters is not None:  # (detached: what is kept is the values' memory, not the autograd graph)
+            self._per = (loss.detach(), {t: per[t].detach() for t in self.meters.tasks})
         side = _factor_side_stream(self.images.device) if self.images.is_cuda else None
         if self.reducer is not None:
             extra = list(self.model._streams) if (isinstance(self.model, MultiTaskSwin) and getattr(self.model, "_streams", None)) else []
@@ -809,12 +829,21 @@ class GraphedTrainStep:
         if self.fused_opt:  # clip + unscale + AdamW + scaler update: three launches (optim.FusedAdamW)
             self.grad_norm = self.optimizer.clip_and_step(self.clip_grad or None, self.loss_scaler, accumulation_steps)
             self.optimizer.zero_grad(set_to_none=True)
+            if self.meters is not None:
+                self._meter(self.grad_norm)
             return
         params = [p for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
-        if self.clip_grad:
-            torch.nn.utils.clip_grad_norm_(params, self.clip_grad, foreach=True)
+        norm = torch.nn.utils.clip_grad_norm_(params, self.clip_grad, foreach=True) if self.clip_grad else None
         self.optimizer.step()
         self.optimizer.zero_grad(set_to_none=True)
+        if self.meters is not None:
+            self._meter(norm)
+
+    def _meter(self, norm):
+        """the step's last launches (inside a capture: the last nodes of the graph that holds the update): loss, per-task losses and
+        norm into the meters' device sources, then the meters' update.  With accumulation inside the graph the norm is the last
+        update's on every call, and the meters' own period picks the update calls."""
+        self.meters.stage_train_step(self._per[0], self._per[1], norm)
 
     def _eager(self, update_grad: bool = True):
         """the step without a graph; ``update_grad=False`` is an accumulating micro-step as ``train_step``'s: the gradients stay
@@ -824,6 +853,8 @@ class GraphedTrainStep:
             self.reducer.all_reduce_packed()
         if update_grad:
             self._optimize()
+        elif self.meters is not None:
+            self._meter(None)
         return loss
 
     def _count(self) -> bool:
