@@ -856,6 +856,50 @@ int mtlora_meter_update(double* bank, const mtlora_meter_source* table, int n_sl
 int mtlora_meter_reset(double* bank, int n_slots, int64_t* counter, int keep_phase, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training-state snapshot (added under ABI v12, additive): the device half of the reference's save_checkpoint and
+ * auto_resume_helper (utils.py:280-321).  There the checkpoint is model.state_dict() / optimizer.state_dict() /
+ * loss_scaler.state_dict(): one device-to-host copy per tensor and a host synchronisation.  Here every tensor a train step mutates
+ * is gathered into one contiguous `packed` buffer by ONE launch between two replays of the step, and scattered back by one.
+ *
+ * `table`   n entries of mtlora_snapshot_entry_bytes each: a device address, a byte count (0 is legal) and the entry's offset in
+ *           `packed`.  Entries ascend in `packed`, every offset a multiple of 16, none reaching into the next; the bytes between
+ *           entries are never written.  Tensors are opaque bytes at ANY address alignment: 16-byte vector accesses where the
+ *           address is 16-byte aligned, dwords where it is 4-byte aligned, bytes otherwise; nothing outside
+ *           [address, address + bytes) is read or written.  The caller builds the table once on the host, uploads it and keeps
+ *           it (8-byte aligned); it holds raw addresses, valid while the tensors live and are only updated in place.
+ * Work is cut into chunks of MTLORA_SNAPSHOT_CHUNK bytes of `packed`; one workgroup owns one chunk.
+ *
+ *   mtlora_snapshot_entry_bytes   utils.py:280-321 has no counterpart: size of one table entry.
+ *   mtlora_snapshot_entry         fills one entry of a HOST table (what utils.py:280-321 names by state_dict key).  MTLORA_ERR_NULL
+ *                                 for a null entry or a null address with bytes > 0, MTLORA_ERR_SHAPE for a negative size or
+ *                                 offset, MTLORA_ERR_ALIGN for an offset that is no multiple of 16.
+ *   mtlora_snapshot_chunks        the number of chunks a HOST table of n entries needs (ceil(extent / MTLORA_SNAPSHOT_CHUNK), the
+ *                                 extent being the end of the last entry; 0 for an empty table), or a negative status: what
+ *                                 mtlora_snapshot_entry rejects, found per entry, MTLORA_ERR_NULL for a null table with n > 0 and
+ *                                 MTLORA_ERR_SHAPE for an entry that begins before the previous one ends.  Pure host call, for the
+ *                                 save of utils.py:280-321.
+ *   mtlora_snapshot_check         the same validation plus MTLORA_ERR_WORKSPACE if packed_bytes is smaller than the extent; pure
+ *                                 host call, made once when the table is built (utils.py:280-321: before the first save).
+ *   mtlora_snapshot_pack          tensors -> packed: the copy behind save_checkpoint (utils.py:280-321), one launch on `stream`.
+ *   mtlora_snapshot_unpack        packed -> tensors through the same table: the copy behind a resume (auto_resume_helper and
+ *                                 load_checkpoint, utils.py:280-321 and :41-176), one launch on `stream`.
+ * Both launches reject, before anything runs: negative n, n_chunks or packed_bytes (MTLORA_ERR_SHAPE); a null table with n > 0
+ * or a null `packed` with n_chunks > 0 (MTLORA_ERR_NULL); a table off 8 bytes or a `packed` off 16 (MTLORA_ERR_ALIGN); a
+ * packed_bytes that n_chunks chunks cannot fit in, packed_bytes <= (n_chunks - 1) * MTLORA_SNAPSHOT_CHUNK (MTLORA_ERR_WORKSPACE; the
+ * table is device memory at this point, the exact comparison is mtlora_snapshot_check's).  The kernel touches no byte of `packed`
+ * at or behind packed_bytes whatever the table says.  n == 0 or n_chunks == 0 launches nothing.  Plain vector loads and stores,
+ * no atomics, no scratch, no memset; nothing is allocated, retained or synchronised and every pointer is a launch argument or
+ * sits in the table, so a captured launch replays as it is.
+ * ------------------------------------------------------------------------------------------ */
+#define MTLORA_SNAPSHOT_CHUNK 32768
+int64_t mtlora_snapshot_entry_bytes(void);
+int mtlora_snapshot_entry(void* host_entry, const void* ptr, int64_t bytes, int64_t packed_offset);
+int64_t mtlora_snapshot_chunks(const void* host_table, int64_t n);
+int mtlora_snapshot_check(const void* host_table, int64_t n, int64_t packed_bytes);
+int mtlora_snapshot_pack(const void* dev_table, int64_t n, int64_t n_chunks, void* packed, int64_t packed_bytes, void* stream);
+int mtlora_snapshot_unpack(const void* dev_table, int64_t n, int64_t n_chunks, const void* packed, int64_t packed_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hardware self-test: writes the lane->element maps of the MFMA / LDS-transpose primitives the
  * kernels rely on into `out` (int32[4096]) so a GPU test can assert them (tests/test_gpu_layouts.py).
  * ------------------------------------------------------------------------------------------ */

@@ -105,6 +105,7 @@ LR_MAX_MILESTONES = 16
 LR_COSINE, LR_STEP, LR_LINEAR, LR_MULTISTEP = 1, 2, 3, 4
 # the schedule buffer of mtlora_adamw_sched_update_dev: the record, the int64 count of update calls, lr_used[MAX_GROUPS]
 ADAMW_SCHED_COUNT_OFFSET, ADAMW_SCHED_LR_OFFSET, ADAMW_SCHED_DEV_BYTES = 344, 352, 480
+SNAPSHOT_CHUNK = 32768  # bytes of the packed buffer one workgroup of mtlora_snapshot_pack / _unpack owns
 
 PROF_KINDS = 24
 
@@ -243,6 +244,12 @@ _SIGS = {
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "mtlora_meter_update": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "mtlora_meter_reset": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "mtlora_snapshot_entry_bytes": (c_int64, []),
+    "mtlora_snapshot_entry": (c_int, [c_void_p, c_void_p, c_int64, c_int64]),
+    "mtlora_snapshot_chunks": (c_int64, [c_void_p, c_int64]),
+    "mtlora_snapshot_check": (c_int, [c_void_p, c_int64, c_int64]),
+    "mtlora_snapshot_pack": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "mtlora_snapshot_unpack": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "mtlora_selftest_layouts": (c_int, [c_void_p, c_void_p]),
     "mtlora_prof_begin": (c_int, [c_int]),
     "mtlora_prof_end": (c_int, [POINTER(ProfSummary)]),

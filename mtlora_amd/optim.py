@@ -459,6 +459,35 @@ class FusedAdamW(torch.optim.Optimizer):
             sd["lr_schedule_updates"] = int(self.num_updates().item())
         return sd
 
+    # ---- snapshots (checkpoint.TrainState): the same format from copies of the device buffers, without a synchronisation ------
+    def state_tensors(self) -> Dict[str, torch.Tensor]:
+        """the device buffers an update call writes, by name: the two flat moment buffers, the control block (``[4]`` the step
+        count, ``[5]`` the accumulation counter) and, capturable, the schedule buffer (record, count of update calls, lr_used).
+        The tensors themselves, not copies; they are never re-allocated."""
+        t = {"exp_avg": self._exp_avg, "exp_avg_sq": self._exp_avg_sq, "ctrl": self._ctrl}
+        if self._capturable:
+            t["schedule"] = self._sched_dev
+        return t
+
+    def state_meta(self) -> Dict[str, Any]:
+        """the host half of ``state_dict()`` as of now: ``param_groups`` in torch's packed form, which parameters have a state
+        entry (in ``state``'s order) and whether a schedule is attached.  Reads no device memory."""
+        index = {id(p): i for i, p in enumerate(self._params)}
+        return {"param_groups": torch.optim.Optimizer.state_dict(self)["param_groups"],
+                "order": [index[id(p)] for p in self.state], "scheduled": bool(self._capturable and self._sched is not None)}
+
+    def state_dict_from(self, tensors: Dict[str, torch.Tensor], meta: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """``state_dict()`` as it would read if the device buffers held ``tensors`` -- copies of ``state_tensors()`` on any device,
+        for instance views of a pinned snapshot -- and the host half were ``meta`` (``state_meta()``; default: now).  The state
+        tensors are VIEWS of ``tensors``; ``"lr_schedule_updates"`` is read from ``tensors["schedule"]``."""
+        meta = self.state_meta() if meta is None else meta
+        ea, es, step = tensors["exp_avg"], tensors["exp_avg_sq"], tensors["ctrl"][4]
+        sd = {"state": {i: {"step": step, "exp_avg": self._slot(i, ea), "exp_avg_sq": self._slot(i, es)} for i in meta["order"]},
+              "param_groups": meta["param_groups"]}
+        if meta["scheduled"]:
+            sd["lr_schedule_updates"] = int(tensors["schedule"][_lib.ADAMW_SCHED_COUNT_OFFSET // 8].item())
+        return sd
+
     @torch.no_grad()
     def load_state_dict(self, state_dict: Dict[str, Any]) -> None:
         step = uniform_step(state_dict["state"])  # before anything is touched
@@ -534,6 +563,18 @@ class LossScaler:
     def state_dict(self) -> Dict[str, Any]:
         tracker = self._init_growth_tracker if self._growth_tracker is None else int(self._growth_tracker.item())
         return {"scale": self.get_scale(), "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
+                "growth_interval": self._growth_interval, "_growth_tracker": tracker}
+
+    def device_words(self) -> Optional[Dict[str, torch.Tensor]]:
+        """the two device words the optimizer's kernels update (the tensors themselves), or None before the first use"""
+        return None if self._scale is None else {"scale": self._scale, "growth_tracker": self._growth_tracker}
+
+    def state_dict_from(self, words: Optional[Dict[str, torch.Tensor]]) -> Dict[str, Any]:
+        """``state_dict()`` as it would read if the device words held ``words`` (copies of ``device_words()`` on any device; None:
+        the scaler was not initialised when they were taken)"""
+        scale = self._init_scale if words is None else float(words["scale"].item())
+        tracker = self._init_growth_tracker if words is None else int(words["growth_tracker"].item())
+        return {"scale": scale, "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
                 "growth_interval": self._growth_interval, "_growth_tracker": tracker}
 
     def load_state_dict(self, state_dict: Dict[str, Any]) -> None:
