@@ -278,6 +278,28 @@ int mtlora_window_attn_bwd(const mtlora_attn_desc* d, const void* qkv, const flo
                            const int32_t* mask_ids, const void* dout, void* dqkv, float* dbias, void* scratch,
                            int64_t scratch_bytes, void* stream);
 
+/* Attention dropout (swin_transformer_mtlora.py:216, `attn_drop` on the softmax output):  P' = keep . P / (1 - p),  out = P' V.
+ * The keep bits are generated inside the kernels, forward and backward alike; no mask is stored.  Element (window w, head h,
+ * query i, key j) is the counter-based generator of the linear layers' dropout (oracle: dropout_keep_mask) with
+ *     row m = (w * num_heads + h) * N + i,   column k = j,   stream 0x41  (the linear layers use stream 0)
+ * where w counts windows as the reference's (B_, nH, N, N) attention tensor does (image, window row, window column) and i, j are
+ * tokens of the window after the cyclic shift -- so both layouts draw the same mask.  keep <=> bits >= floor(p * 65536); a p below
+ * 2^-16 is off.  seed_offset: optional DEVICE word added to `seed` when the kernels run (as mtlora_linear_desc.seed_offset: a
+ * replayed graph draws fresh masks).  The backward must be given the forward's seed (and the same offset value).
+ * Arguments, scratch size (mtlora_window_attn_bwd_scratch_bytes) and statuses as the plain entry points; in addition a NULL
+ * dropout struct is MTLORA_ERR_NULL, a p outside [0, 1) or not finite MTLORA_ERR_SHAPE, and so is n_windows * num_heads * N >= 2^32
+ * (the row index is 32 bits).  p == 0 runs the plain kernels. */
+typedef struct mtlora_attn_dropout {
+    float p;
+    uint64_t seed;
+    const uint64_t* seed_offset;
+} mtlora_attn_dropout;
+int mtlora_window_attn_drop_fwd(const mtlora_attn_desc* d, const mtlora_attn_dropout* drop, const void* qkv, const float* bias,
+                                const float* mask, const int32_t* mask_ids, void* out, void* stream);
+int mtlora_window_attn_drop_bwd(const mtlora_attn_desc* d, const mtlora_attn_dropout* drop, const void* qkv, const float* bias,
+                                const float* mask, const int32_t* mask_ids, const void* dout, void* dqkv, float* dbias, void* scratch,
+                                int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * LayerNorm over the last dim (block glue around the path: norm1 / norm2 / PatchMerging.norm,
  * swin_transformer_mtlora.py:331-333, 395-396, 469) -- replaces aten::native_layer_norm + the autocast cast:

@@ -41,6 +41,11 @@ class AttnDesc(Structure):
                 ("scale", c_float), ("mask_value", c_float)]
 
 
+class AttnDropout(Structure):
+    """mtlora_attn_dropout: attention dropout of the mtlora_window_attn_drop_* entry points"""
+    _fields_ = [("p", c_float), ("seed", c_uint64), ("seed_offset", c_void_p)]
+
+
 class BlockDesc(Structure):
     """mtlora_block_desc (ABI v7): one SwinTransformerBlock without task outputs"""
     _fields_ = [("B", c_int64), ("H", c_int32), ("W", c_int32), ("C", c_int32), ("hidden", c_int32), ("num_heads", c_int32),
@@ -160,6 +165,10 @@ _SIGS = {
     "mtlora_window_attn_fwd": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mtlora_window_attn_bwd": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_int64, c_void_p]),
+    "mtlora_window_attn_drop_fwd": (c_int, [POINTER(AttnDesc), POINTER(AttnDropout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]),
+    "mtlora_window_attn_drop_bwd": (c_int, [POINTER(AttnDesc), POINTER(AttnDropout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mtlora_layernorm_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float,
                                      c_int, c_int, c_int, c_int, c_void_p]),
     "mtlora_layernorm_bwd_scratch_bytes": (c_int64, [c_int64, c_int64, c_int]),

@@ -22,6 +22,8 @@
 // The k-slot <-> key assignment of every register-fed operand follows the accumulator layout
 // (row = (r&3) + 8(r>>2) + 4(lane>>5)); the LDS-fed partner operand is gathered in the same order.
 #include <atomic>
+#include <cmath>
+#include <type_traits>
 
 #include "common.h"
 
@@ -70,6 +72,8 @@ struct AttnParams {
     int G;
     float scale;
 };
+
+#include "attention_dropout.h"  // AttnDropParams + the keep-bit generators of the DROP variants below
 
 // Token addressing without per-token divisions.  A window id is decomposed ONCE per window (wave-uniform, 32-bit);
 // a token's (ty, tx) inside the window is a per-lane constant computed before the persistent loop; the cyclic shift
@@ -589,8 +593,10 @@ __device__ __forceinline__ int64_t xcd_remap(int64_t b, int64_t n) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
 }
 
-template <typename T, bool DENSE>
-__global__ __launch_bounds__(64, MTL_ATTN_FWD_WPS) void k_attn_fwd(const AttnParams p) {
+// The kernel bodies are shared by the plain kernels (P = AttnParams) and their attention-dropout variants (P = AttnDropParams,
+// DROP): every DROP statement is a discarded `if constexpr` branch in the plain instantiations.
+template <typename T, bool DENSE, bool DROP, typename P>
+__device__ __forceinline__ void attn_fwd_body(const P p) {
     constexpr int RS = AC<T>::RS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int IB = ((img_rows(p.N) * RS + 15) / 16) * 16;  // bytes per image
@@ -599,7 +605,7 @@ __global__ __launch_bounds__(64, MTL_ATTN_FWD_WPS) void k_attn_fwd(const AttnPar
     unsigned char* sV = smem + 2 * IB;
     int* tok = reinterpret_cast<int*>(smem + 3 * IB);
     int* srid = tok + AN;
-    const int lane = threadIdx.x;
+    const int lane0 = threadIdx.x, lane = lane0;
     const int64_t L = xcd_remap(blockIdx.x, gridDim.x);
     const int head = (int)(L % p.nH);
     const int g = (int)(L / p.nH);
@@ -626,8 +632,11 @@ __global__ __launch_bounds__(64, MTL_ATTN_FWD_WPS) void k_attn_fwd(const AttnPar
         rid_next = (p.mask_ids && lane < p.N) ? p.mask_ids[(int)(w % nWimg) * p.N + lane] : 0;
     };
     if (g < p.n_windows) prefetch(g);
+    [[maybe_unused]] DropoutCfg dc;
+    if constexpr (DROP) dc = attn_drop_cfg(p);
 
     for (int64_t w = g; w < p.n_windows; w += p.G) {
+        const int lane = attn_opaque_lane<DROP>(lane0);  // (DROP: nothing derived from the lane id lives across the windows)
         const int wm = (int)(w % nWimg);
         const WinPos wq = win_pos(p, w);
         __syncthreads();  // previous item's LDS reads are done
@@ -642,11 +651,24 @@ __global__ __launch_bounds__(64, MTL_ATTN_FWD_WPS) void k_attn_fwd(const AttnPar
         if (w + p.G < p.n_windows) prefetch(w + p.G);  // next window's rows fly while this one is multiplied
         T* ob = out + wq.base * p.C;  // wave-uniform
         auto half = [&](int si) __attribute__((always_inline)) {
+            const int lane = attn_opaque_lane<DROP>(lane0);  // (and per query half)
             f32x16 st[2];
             scores_t<T, DENSE>(st, sK, sQ, si, p, B, srid, masked, wm, lane);
             // 16-bit: numerators only, the 16 outputs are scaled by 1 / sum instead; fp32: P itself, as in rounds 1-3
             const float inv_raw = softmax_t<sizeof(T) == 4, sizeof(T) == 4>(st, B.c);
-            const float inv_l = sizeof(T) == 4 ? 1.f : inv_raw;
+            float inv_l = sizeof(T) == 4 ? 1.f : inv_raw;
+            if constexpr (DROP) {  // P' = keep . P / (1 - p): dropped elements leave the product, the factor joins the output scale
+                const uint32_t rh = attn_drop_rowhash(dc, p, w, head, si * 32 + (lane & 31));
+#pragma unroll
+                for (int sj = 0; sj < 2; ++sj) {
+                    __builtin_amdgcn_sched_barrier(0);  // one tile's hashes at a time (register pressure)
+                    attn_keep_tile(dc, rh, sj * 32 + 4 * (lane >> 5), [&](int r, bool keep) __attribute__((always_inline)) {
+                        st[sj][r] = keep ? st[sj][r] : 0.f;
+                    });
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                inv_l *= p.keep_scale;
+            }
             f32x16 o;
             zero(o);
 #pragma unroll
@@ -669,6 +691,14 @@ __global__ __launch_bounds__(64, MTL_ATTN_FWD_WPS) void k_attn_fwd(const AttnPar
         }
     }
 }
+template <typename T, bool DENSE>
+__global__ __launch_bounds__(64, MTL_ATTN_FWD_WPS) void k_attn_fwd(const AttnParams p) {
+    attn_fwd_body<T, DENSE, false>(p);
+}
+template <typename T, bool DENSE>
+__global__ __launch_bounds__(64, MTL_ATTN_FWD_WPS) void k_attn_drop_fwd(const AttnDropParams p) {
+    attn_fwd_body<T, DENSE, true>(p);
+}
 
 // One wave per workgroup and (LDS-limited) one workgroup per SIMD: the whole 512-entry register file is this wave's,
 // so the next window's Q / K / V / dO rows are prefetched into registers while the current window is multiplied.
@@ -676,8 +706,8 @@ __global__ __launch_bounds__(64, MTL_ATTN_FWD_WPS) void k_attn_fwd(const AttnPar
 // dS^T of the half are handed over through two small LDS images and read back TRANSPOSED (key per lane, queries along k)
 // to accumulate dK^T += Q^T dS and dV^T += dO^T P -- instead of a second, key-owned pass that recomputed S, P and dP from
 // the row statistics (16 MFMAs, 64 exps per lane and a long element-wise section per window).
-template <typename T, bool DENSE>
-__global__ __launch_bounds__(64, MTL_ATTN_BWD_WPS) void k_attn_bwd(const AttnParams p) {
+template <typename T, bool DENSE, bool DROP, typename P>
+__device__ __forceinline__ void attn_bwd_body(const P p) {
     constexpr int RS = AC<T>::RS;
     constexpr int KQ = 32 / (AC<T>::KT_N == 2 ? 32 : 16);  // k-tiles per 32-query half (bf16: 1, f32: 2)
     // Q, K, V, dO images + P / dS hand-over images + token table + region ids + bias[head]
@@ -691,7 +721,7 @@ __global__ __launch_bounds__(64, MTL_ATTN_BWD_WPS) void k_attn_bwd(const AttnPar
     unsigned char* sDi = sPi + 32 * IMG<T>::RS;         // [32][64] dS
     int* tok = reinterpret_cast<int*>(sDi + 32 * IMG<T>::RS);
     int* srid = tok + AN;
-    const int lane = threadIdx.x;
+    const int lane0 = threadIdx.x, lane = lane0;
     const int64_t L = xcd_remap(blockIdx.x, gridDim.x);
     const int head = (int)(L % p.nH);
     const int g = (int)(L / p.nH);
@@ -728,8 +758,17 @@ __global__ __launch_bounds__(64, MTL_ATTN_BWD_WPS) void k_attn_bwd(const AttnPar
         load_rows<T>(ro, dout + q.base * p.C, offo);
         rid_next = (p.mask_ids && lane < p.N) ? p.mask_ids[(int)(w % nWimg) * p.N + lane] : 0;
     };
-    if (g < p.n_windows) prefetch(g);
+    // fp32 with dropout: the 128 registers of the prefetched rows are what the kernel lacks (96 B of scratch per lane with them), so
+    // the window's rows are loaded at the top of its own iteration instead of one window ahead
+    constexpr bool PIPE = !(DROP && sizeof(T) == 4);
+    if constexpr (PIPE) {
+        if (g < p.n_windows) prefetch(g);
+    }
+    [[maybe_unused]] DropoutCfg dc;
+    if constexpr (DROP) dc = attn_drop_cfg(p);
     for (int64_t w = g; w < p.n_windows; w += p.G) {
+        const int lane = attn_opaque_lane<DROP>(lane0);  // (as in attn_fwd_body)
+        if constexpr (!PIPE) prefetch(w);
         const int wm = (int)(w % nWimg);
         const WinPos wq = win_pos(p, w);
         __syncthreads();
@@ -742,7 +781,9 @@ __global__ __launch_bounds__(64, MTL_ATTN_BWD_WPS) void k_attn_bwd(const AttnPar
         store_rows<T>(sV, rv, p.N, lane);
         store_rows<T>(sO, ro, p.N, lane);
         __syncthreads();
-        if (w + p.G < p.n_windows) prefetch(w + p.G);
+        if constexpr (PIPE) {
+            if (w + p.G < p.n_windows) prefetch(w + p.G);
+        }
 
         f32x16 dk[2], dv[2];  // [sj]: dK^T / dV^T [d][key], accumulated over the query halves
         zero(dk[0]);
@@ -752,6 +793,7 @@ __global__ __launch_bounds__(64, MTL_ATTN_BWD_WPS) void k_attn_bwd(const AttnPar
 #pragma unroll
         for (int si = 0; si < 2; ++si) {
             if (si * 32 >= p.N) break;
+            const int lane = attn_opaque_lane<DROP>(lane0);  // (and per query half)
             f32x16 pt[2];
             scores_t<T, DENSE>(pt, sK, sQ, si, p, B, srid, masked, wm, lane);
             (void)softmax_t<true, sizeof(T) == 4>(pt, B.c);
@@ -768,6 +810,19 @@ __global__ __launch_bounds__(64, MTL_ATTN_BWD_WPS) void k_attn_bwd(const AttnPar
                     mtl_mma(fv, fo, dp[sj]);
                 }
             }
+            [[maybe_unused]] uint32_t kept = 0u;  // DROP: keep bit of element (sj, r) at 16 sj + r
+            if constexpr (DROP) {  // dP = keep . (dO V^T) / (1 - p)
+                const uint32_t rh = attn_drop_rowhash(dc, p, w, head, si * 32 + (lane & 31));
+#pragma unroll
+                for (int sj = 0; sj < 2; ++sj) {
+                    __builtin_amdgcn_sched_barrier(0);  // one tile's hashes at a time (register pressure)
+                    attn_keep_tile(dc, rh, sj * 32 + h4, [&](int r, bool keep) __attribute__((always_inline)) {
+                        dp[sj][r] = keep ? dp[sj][r] * p.keep_scale : 0.f;
+                        kept |= keep ? 1u << (16 * sj + r) : 0u;
+                    });
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
             float D = 0.f;
 #pragma unroll
             for (int sj = 0; sj < 2; ++sj)
@@ -783,6 +838,12 @@ __global__ __launch_bounds__(64, MTL_ATTN_BWD_WPS) void k_attn_bwd(const AttnPar
                     dp[sj][r] = ds;
                     dbacc[si][sj][r] += ds;
                 }
+            if constexpr (DROP) {  // dV takes P'
+#pragma unroll
+                for (int sj = 0; sj < 2; ++sj)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) pt[sj][r] = ((kept >> (16 * sj + r)) & 1u) ? pt[sj][r] * p.keep_scale : 0.f;
+            }
             // hand P^T / dS^T of this half over for the key-owned products (previous half's reads are complete: the
             // wave executes in order and the MFMAs below consumed their fragments)
             __builtin_amdgcn_wave_barrier();
@@ -833,6 +894,14 @@ __global__ __launch_bounds__(64, MTL_ATTN_BWD_WPS) void k_attn_bwd(const AttnPar
                 const int i = si * 32 + (lane & 31), j = sj * 32 + (r & 3) + 8 * (r >> 2) + h4;
                 if (i < p.N && j < p.N) dst[j * p.N + i] = dbacc[si][sj][r];
             }
+}
+template <typename T, bool DENSE>
+__global__ __launch_bounds__(64, MTL_ATTN_BWD_WPS) void k_attn_bwd(const AttnParams p) {
+    attn_bwd_body<T, DENSE, false>(p);
+}
+template <typename T, bool DENSE>
+__global__ __launch_bounds__(64, MTL_ATTN_BWD_WPS) void k_attn_drop_bwd(const AttnDropParams p) {
+    attn_bwd_body<T, DENSE, true>(p);
 }
 
 // dbias[h][i][j] = sum_g part[g][h][j][i]: one workgroup per 64 outputs, 4 waves stride over g, fixed-order combine
@@ -919,36 +988,36 @@ AttnParams make_params(const mtlora_attn_desc* d) {
 
 #include "attention_wide.h"
 
-}  // namespace
-
-extern "C" {
-
-int64_t mtlora_window_attn_bwd_scratch_bytes(const mtlora_attn_desc* d) {
-    if (check(d) != MTLORA_OK) return -1;
-    const int N = d->window_size * d->window_size;
-    if (N > AN) return (int64_t)wide_groups(d) * d->num_heads * N * N * 4 + 256;
-    return (int64_t)bwd_groups(d) * d->num_heads * N * N * 4 + 256;
+// the one-wave kernel of a parameter block: plain (AttnParams) or attention dropout (AttnDropParams)
+template <typename T, bool DENSE>
+static const void* narrow_kernel(const AttnParams&, bool bwd) {
+    return bwd ? reinterpret_cast<const void*>(k_attn_bwd<T, DENSE>) : reinterpret_cast<const void*>(k_attn_fwd<T, DENSE>);
+}
+template <typename T, bool DENSE>
+static const void* narrow_kernel(const AttnDropParams&, bool bwd) {
+    return bwd ? reinterpret_cast<const void*>(k_attn_drop_bwd<T, DENSE>) : reinterpret_cast<const void*>(k_attn_drop_fwd<T, DENSE>);
+}
+template <typename P>
+static void narrow_launch(int dtype, bool bwd, const P& p, size_t lds, hipStream_t s) {
+    const bool dense = p.mask && !p.mask_ids;
+    const void* k;
+    if (dtype == MTLORA_F32)
+        k = dense ? narrow_kernel<float, true>(p, bwd) : narrow_kernel<float, false>(p, bwd);
+    else if (dtype == MTLORA_F16)
+        k = dense ? narrow_kernel<f16, true>(p, bwd) : narrow_kernel<f16, false>(p, bwd);
+    else
+        k = dense ? narrow_kernel<bf16, true>(p, bwd) : narrow_kernel<bf16, false>(p, bwd);
+    void* args[] = {const_cast<P*>(&p)};
+    (void)hipLaunchKernel(k, dim3((unsigned)(p.G * p.nH)), dim3(64), args, lds, s);  // (the caller's MTL_CHECK_LAUNCH reads the status)
 }
 
-int mtlora_window_attn_fwd(const mtlora_attn_desc* d, const void* qkv, const float* bias, const float* mask,
-                           const int32_t* mask_ids, void* out, void* stream) {
-    int st = check(d);
-    if (st != MTLORA_OK) return st;
-    if (!qkv || !bias || !out) return MTLORA_ERR_NULL;
-    if (((uintptr_t)qkv | (uintptr_t)out) & 15u) return MTLORA_ERR_ALIGN;
-    AttnParams p = make_params(d);
-    if (p.n_windows == 0) return MTLORA_OK;
-    p.qkv = qkv;
-    p.bias = bias;
-    p.mask = mask;
-    p.mask_ids = mask_ids;
-    p.mask_value = d->mask_value;
-    p.out = out;
+// p: every field but G set
+template <typename P>
+static int attn_fwd_run(const mtlora_attn_desc* d, P& p, hipStream_t s) {
+    const double ab = 4.0 * mtl_elem_size(d->dtype) * (double)p.n_windows * p.N * p.C;
+    MtlProfScope prof(PK_ATTN_FWD, ab, s, ab, 4.0 * (double)p.n_windows * p.N * p.N * p.C);
     if (p.N > AN) {
-        hipStream_t ws = (hipStream_t)stream;
-        const double wab = 4.0 * mtl_elem_size(d->dtype) * (double)p.n_windows * p.N * p.C;
-        MtlProfScope prof(PK_ATTN_FWD, wab, ws, wab, 4.0 * (double)p.n_windows * p.N * p.N * p.C);
-        const int wst = wide_fwd(d, p, ws);
+        const int wst = wide_fwd(d, p, s);
         if (wst != MTLORA_OK) return wst;
         MTL_CHECK_LAUNCH();
         return MTLORA_OK;
@@ -957,40 +1026,77 @@ int mtlora_window_attn_fwd(const mtlora_attn_desc* d, const void* qkv, const flo
     const size_t ib = (size_t)((img_rows_h(p.N) * rs + 15) / 16) * 16;
     const size_t lds = 3 * ib + 2 * AN * 4 + (d->dtype == MTLORA_F32 ? STG<float>::BYTES : STG<bf16>::BYTES) + (d->dtype == MTLORA_F32 ? (size_t)p.N * bias_stride_c(p.N) * 4 : 0);  // (fp32: bias image)
     p.G = groups_for(lds, 4 * MTL_ATTN_FWD_WPS, p.nH, p.n_windows);  // persistent grid: exactly the resident workgroups
-    const unsigned grid = (unsigned)(p.G * p.nH);
-    hipStream_t s = (hipStream_t)stream;
-    const double ab = 4.0 * mtl_elem_size(d->dtype) * (double)p.n_windows * p.N * p.C;
-    MtlProfScope prof(PK_ATTN_FWD, ab, s, ab, 4.0 * (double)p.n_windows * p.N * p.N * p.C);
-    const bool dense = p.mask && !p.mask_ids;
-    if (d->dtype == MTLORA_F32) {
-        if (dense)
-            hipLaunchKernelGGL((k_attn_fwd<float, true>), dim3(grid), dim3(64), lds, s, p);
-        else
-            hipLaunchKernelGGL((k_attn_fwd<float, false>), dim3(grid), dim3(64), lds, s, p);
-    } else if (d->dtype == MTLORA_F16) {
-        if (dense)
-            hipLaunchKernelGGL((k_attn_fwd<f16, true>), dim3(grid), dim3(64), lds, s, p);
-        else
-            hipLaunchKernelGGL((k_attn_fwd<f16, false>), dim3(grid), dim3(64), lds, s, p);
-    } else {
-        if (dense)
-            hipLaunchKernelGGL((k_attn_fwd<bf16, true>), dim3(grid), dim3(64), lds, s, p);
-        else
-            hipLaunchKernelGGL((k_attn_fwd<bf16, false>), dim3(grid), dim3(64), lds, s, p);
+    narrow_launch(d->dtype, false, p, lds, s);
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+template <typename P>
+static int attn_bwd_run(const mtlora_attn_desc* d, P& p, float* dbias, hipStream_t s) {
+    {
+        const double ab = 7.0 * mtl_elem_size(d->dtype) * (double)p.n_windows * p.N * p.C;
+        MtlProfScope prof(PK_ATTN_BWD, ab, s, ab, 8.0 * (double)p.n_windows * p.N * p.N * p.C);
+        if (p.N > AN) {
+            const int wst = wide_bwd(d, p, s);
+            if (wst != MTLORA_OK) return wst;
+        } else {
+            p.G = bwd_groups(d);
+            narrow_launch(d->dtype, true, p, bwd_lds_bytes(d), s);
+        }
     }
+    const int total = p.nH * p.N * p.N;
+    hipLaunchKernelGGL(k_dbias_reduce, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, s, (const float*)p.dbias_part, dbias, p.G,
+                       p.nH, p.N);
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }
 
-int mtlora_window_attn_bwd(const mtlora_attn_desc* d, const void* qkv, const float* bias, const float* mask,
-                           const int32_t* mask_ids, const void* dout, void* dqkv, float* dbias, void* scratch,
-                           int64_t scratch_bytes, void* stream) {
+// attention dropout of an entry point (dr = null: the plain entry points).  `on`: the dropout kernels run -- a p whose keep threshold
+// is 0 (p < 2^-16, as in the linear kernels) takes the plain ones
+static int drop_setup(const mtlora_attn_desc* d, const mtlora_attn_dropout* dr, bool plain, AttnDropParams& p, bool& on) {
+    on = false;
+    if (plain) return MTLORA_OK;
+    if (!dr) return MTLORA_ERR_NULL;
+    if (!std::isfinite(dr->p) || dr->p < 0.f || dr->p >= 1.f) return MTLORA_ERR_SHAPE;
+    p.drop = mtl_make_dropout(dr->p, dr->seed, dr->seed_offset);
+    on = p.drop.enabled();
+    p.keep_scale = on ? 1.f / (1.f - dr->p) : 1.f;
+    const int64_t nwin = d->B * (d->H / d->window_size) * (d->W / d->window_size);
+    if (on && nwin * d->num_heads * d->window_size * d->window_size >= ((int64_t)1 << 32)) return MTLORA_ERR_SHAPE;  // 32-bit mask rows
+    return MTLORA_OK;
+}
+
+static int attn_fwd_entry(const mtlora_attn_desc* d, const mtlora_attn_dropout* dr, bool plain, const void* qkv, const float* bias,
+                          const float* mask, const int32_t* mask_ids, void* out, void* stream) {
     int st = check(d);
     if (st != MTLORA_OK) return st;
+    AttnDropParams p = {};
+    bool drop_on;
+    if ((st = drop_setup(d, dr, plain, p, drop_on)) != MTLORA_OK) return st;
+    if (!qkv || !bias || !out) return MTLORA_ERR_NULL;
+    if (((uintptr_t)qkv | (uintptr_t)out) & 15u) return MTLORA_ERR_ALIGN;
+    static_cast<AttnParams&>(p) = make_params(d);
+    if (p.n_windows == 0) return MTLORA_OK;
+    p.qkv = qkv;
+    p.bias = bias;
+    p.mask = mask;
+    p.mask_ids = mask_ids;
+    p.mask_value = d->mask_value;
+    p.out = out;
+    return drop_on ? attn_fwd_run(d, p, (hipStream_t)stream) : attn_fwd_run(d, static_cast<AttnParams&>(p), (hipStream_t)stream);
+}
+
+static int attn_bwd_entry(const mtlora_attn_desc* d, const mtlora_attn_dropout* dr, bool plain, const void* qkv, const float* bias,
+                          const float* mask, const int32_t* mask_ids, const void* dout, void* dqkv, float* dbias, void* scratch,
+                          int64_t scratch_bytes, void* stream) {
+    int st = check(d);
+    if (st != MTLORA_OK) return st;
+    AttnDropParams p = {};
+    bool drop_on;
+    if ((st = drop_setup(d, dr, plain, p, drop_on)) != MTLORA_OK) return st;
     if (!qkv || !bias || !dout || !dqkv || !dbias || !scratch) return MTLORA_ERR_NULL;
     if (((uintptr_t)qkv | (uintptr_t)dout | (uintptr_t)dqkv | (uintptr_t)scratch) & 15u) return MTLORA_ERR_ALIGN;
     if (scratch_bytes < mtlora_window_attn_bwd_scratch_bytes(d) - 256) return MTLORA_ERR_WORKSPACE;
-    AttnParams p = make_params(d);
+    static_cast<AttnParams&>(p) = make_params(d);
     hipStream_t s = (hipStream_t)stream;
     if (p.n_windows == 0) {
         mtl_zero_async(dbias, (size_t)p.nH * p.N * p.N * 4, s);
@@ -1004,47 +1110,39 @@ int mtlora_window_attn_bwd(const mtlora_attn_desc* d, const void* qkv, const flo
     p.dout = dout;
     p.dqkv = dqkv;
     p.dbias_part = reinterpret_cast<float*>(scratch);
-    if (p.N > AN) {
-        {
-            const double wab = 7.0 * mtl_elem_size(d->dtype) * (double)p.n_windows * p.N * p.C;
-            MtlProfScope prof(PK_ATTN_BWD, wab, s, wab, 8.0 * (double)p.n_windows * p.N * p.N * p.C);
-            const int wst = wide_bwd(d, p, s);
-            if (wst != MTLORA_OK) return wst;
-        }
-        const int wtotal = p.nH * p.N * p.N;
-        hipLaunchKernelGGL(k_dbias_reduce, dim3((unsigned)((wtotal + 63) / 64)), dim3(256), 0, s, (const float*)p.dbias_part, dbias,
-                           p.G, p.nH, p.N);
-        MTL_CHECK_LAUNCH();
-        return MTLORA_OK;
-    }
-    p.G = bwd_groups(d);
-    const unsigned grid = (unsigned)(p.G * p.nH);
-    const size_t lds = bwd_lds_bytes(d);
-    {
-        const double ab = 7.0 * mtl_elem_size(d->dtype) * (double)p.n_windows * p.N * p.C;
-        MtlProfScope prof(PK_ATTN_BWD, ab, s, ab, 8.0 * (double)p.n_windows * p.N * p.N * p.C);
-        const bool dense = p.mask && !p.mask_ids;
-        if (d->dtype == MTLORA_F32) {
-            if (dense)
-                hipLaunchKernelGGL((k_attn_bwd<float, true>), dim3(grid), dim3(64), lds, s, p);
-            else
-                hipLaunchKernelGGL((k_attn_bwd<float, false>), dim3(grid), dim3(64), lds, s, p);
-        } else if (d->dtype == MTLORA_F16) {
-            if (dense)
-                hipLaunchKernelGGL((k_attn_bwd<f16, true>), dim3(grid), dim3(64), lds, s, p);
-            else
-                hipLaunchKernelGGL((k_attn_bwd<f16, false>), dim3(grid), dim3(64), lds, s, p);
-        } else {
-            if (dense)
-                hipLaunchKernelGGL((k_attn_bwd<bf16, true>), dim3(grid), dim3(64), lds, s, p);
-            else
-                hipLaunchKernelGGL((k_attn_bwd<bf16, false>), dim3(grid), dim3(64), lds, s, p);
-        }
-    }
-    const int total = p.nH * p.N * p.N;
-    hipLaunchKernelGGL(k_dbias_reduce, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, s, (const float*)p.dbias_part,
-                       dbias, p.G, p.nH, p.N);
-    MTL_CHECK_LAUNCH();
-    return MTLORA_OK;
+    return drop_on ? attn_bwd_run(d, p, dbias, s) : attn_bwd_run(d, static_cast<AttnParams&>(p), dbias, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mtlora_window_attn_bwd_scratch_bytes(const mtlora_attn_desc* d) {
+    if (check(d) != MTLORA_OK) return -1;
+    const int N = d->window_size * d->window_size;
+    if (N > AN) return (int64_t)wide_groups(d) * d->num_heads * N * N * 4 + 256;
+    return (int64_t)bwd_groups(d) * d->num_heads * N * N * 4 + 256;
+}
+
+int mtlora_window_attn_fwd(const mtlora_attn_desc* d, const void* qkv, const float* bias, const float* mask,
+                           const int32_t* mask_ids, void* out, void* stream) {
+    return attn_fwd_entry(d, nullptr, true, qkv, bias, mask, mask_ids, out, stream);
+}
+
+int mtlora_window_attn_bwd(const mtlora_attn_desc* d, const void* qkv, const float* bias, const float* mask,
+                           const int32_t* mask_ids, const void* dout, void* dqkv, float* dbias, void* scratch,
+                           int64_t scratch_bytes, void* stream) {
+    return attn_bwd_entry(d, nullptr, true, qkv, bias, mask, mask_ids, dout, dqkv, dbias, scratch, scratch_bytes, stream);
+}
+
+int mtlora_window_attn_drop_fwd(const mtlora_attn_desc* d, const mtlora_attn_dropout* drop, const void* qkv, const float* bias,
+                                const float* mask, const int32_t* mask_ids, void* out, void* stream) {
+    return attn_fwd_entry(d, drop, false, qkv, bias, mask, mask_ids, out, stream);
+}
+
+int mtlora_window_attn_drop_bwd(const mtlora_attn_desc* d, const mtlora_attn_dropout* drop, const void* qkv, const float* bias,
+                                const float* mask, const int32_t* mask_ids, const void* dout, void* dqkv, float* dbias, void* scratch,
+                                int64_t scratch_bytes, void* stream) {
+    return attn_bwd_entry(d, drop, false, qkv, bias, mask, mask_ids, dout, dqkv, dbias, scratch, scratch_bytes, stream);
 }
 }

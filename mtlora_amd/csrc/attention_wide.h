@@ -193,8 +193,8 @@ __device__ __forceinline__ void wide_probs_t(f32x16 (&st)[WT], float& m_out, flo
     inv_out = inv;
 }
 
-template <typename T, bool DENSE>
-__global__ __launch_bounds__(W_THREADS) void k_attn_wide_fwd(const AttnParams p) {
+template <typename T, bool DENSE, bool DROP, typename P>
+__device__ __forceinline__ void attn_wide_fwd_body(const P p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int N = p.N;
     const int IB = wide_img_bytes<T>(N);
@@ -220,6 +220,8 @@ __global__ __launch_bounds__(W_THREADS) void k_attn_wide_fwd(const AttnParams p)
     wide_zero_row(sQ, N, AC<T>::RS, tid);
     wide_zero_row(sK, N, AC<T>::RS, tid);
     wide_zero_row(sV, N, AC<T>::RS, tid);
+    [[maybe_unused]] DropoutCfg dc;
+    if constexpr (DROP) dc = attn_drop_cfg(p);
 
     for (int64_t w = g; w < p.n_windows; w += p.G) {
         const int wm = (int)(w % nWimg);
@@ -238,18 +240,38 @@ __global__ __launch_bounds__(W_THREADS) void k_attn_wide_fwd(const AttnParams p)
             f32x16 st[WT];
             float m, inv;
             wide_probs_t<T, DENSE>(st, m, inv, sK, sQ, qb, nt, p, bias_h, tb.srid, wm, lane);
+            float mul = 1.f;
+            [[maybe_unused]] uint32_t rh = 0u;
+            if constexpr (DROP) {  // P' = keep . P / (1 - p): the factor joins the output scale
+                rh = attn_drop_rowhash(dc, p, w, head, qb * 32 + (lane & 31));
+                mul = p.keep_scale;
+            }
             f32x16 o;
             zero(o);
 #pragma unroll
             for (int sj = 0; sj < WT; ++sj)
-                if (sj < nt) wide_mma_col<T>(o, sV, sj, st[sj], lane, N);
-            store_dt_lds<T>(stg, out + wq.base * p.C, tb.tokC + qb * 32, N - qb * 32, o, 1.f, lane);
+                if (sj < nt) {
+                    if constexpr (DROP)  // the tile's bits, right where the tile is consumed
+                        attn_keep_tile(dc, rh, sj * 32 + 4 * (lane >> 5), [&](int r, bool keep) __attribute__((always_inline)) {
+                            st[sj][r] = keep ? st[sj][r] : 0.f;
+                        });
+                    wide_mma_col<T>(o, sV, sj, st[sj], lane, N);
+                }
+            store_dt_lds<T>(stg, out + wq.base * p.C, tb.tokC + qb * 32, N - qb * 32, o, mul, lane);
         }
     }
 }
-
 template <typename T, bool DENSE>
-__global__ __launch_bounds__(WB_THREADS) void k_attn_wide_bwd(const AttnParams p) {
+__global__ __launch_bounds__(W_THREADS) void k_attn_wide_fwd(const AttnParams p) {
+    attn_wide_fwd_body<T, DENSE, false>(p);
+}
+template <typename T, bool DENSE>
+__global__ __launch_bounds__(W_THREADS) void k_attn_drop_wide_fwd(const AttnDropParams p) {
+    attn_wide_fwd_body<T, DENSE, true>(p);
+}
+
+template <typename T, bool DENSE, bool DROP, typename P>
+__device__ __forceinline__ void attn_wide_bwd_body(const P p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int N = p.N;
     const int IB = wide_img_bytes<T>(N);
@@ -266,6 +288,10 @@ __global__ __launch_bounds__(WB_THREADS) void k_attn_wide_bwd(const AttnParams p
     float* sD = sL + WN;
     const int tid = threadIdx.x, lane0 = tid & 63, wv = tid >> 6;
     unsigned char* stg = reinterpret_cast<unsigned char*>(sD + WN) + wv * STG<T>::BYTES;
+    // DROP: row hashes of the window's queries for phase 2, where a lane's registers span the queries (behind the staging images)
+    [[maybe_unused]] uint32_t* sRH = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(sD + WN) + WB_WAVES * STG<T>::BYTES);
+    [[maybe_unused]] DropoutCfg dc;
+    if constexpr (DROP) dc = attn_drop_cfg(p);
     const int64_t L = xcd_remap(blockIdx.x, gridDim.x);
     const int head = (int)(L % p.nH);
     const int g = (int)(L / p.nH);
@@ -294,6 +320,9 @@ __global__ __launch_bounds__(WB_THREADS) void k_attn_wide_bwd(const AttnParams p
         const WinPos wq = win_pos(p, w);
         __syncthreads();
         wide_tables(tb, p, wq, wm, my_tyx, tid);
+        if constexpr (DROP) {
+            if (tid < WN) sRH[tid] = attn_drop_rowhash(dc, p, w, head, tid);
+        }
         __syncthreads();
         const T* wb = qkv + wq.base * C3;
         T* gb = dqkv + wq.base * C3;
@@ -313,15 +342,29 @@ __global__ __launch_bounds__(WB_THREADS) void k_attn_wide_bwd(const AttnParams p
             float m, inv;
             wide_probs_t<T, DENSE>(pt, m, inv, sK, sQ, qb, nt, p, bias_h, tb.srid, wm, lane);
             float D = 0.f;
+            // DROP: dP = keep . (dO V^T) / (1 - p).  The bits of a tile are drawn once, in the first sweep, and carried to the second as 16
+            // bits per tile (three registers for the five tiles)
+            [[maybe_unused]] uint32_t kept[(WT + 1) / 2] = {};
+            [[maybe_unused]] uint32_t rh = 0u;
+            if constexpr (DROP) rh = attn_drop_rowhash(dc, p, w, head, qb * 32 + il);
 #pragma unroll
             for (int sj = 0; sj < WT; ++sj)
                 if (sj < nt) {
                     f32x16 dp;  // dP^T[j][i] = sum_d V[j][d] dO[i][d]
                     zero(dp);
                     wide_mma_row<T>(dp, sV, sj, sO, qb, lane, N);
+                    if constexpr (DROP) {
+                        uint32_t kb = 0u;
+                        attn_keep_tile(dc, rh, sj * 32 + 4 * (lane >> 5), [&](int r, bool keep) __attribute__((always_inline)) {
+                            dp[r] = keep ? dp[r] : 0.f;
+                            kb |= keep ? 1u << r : 0u;
+                        });
+                        kept[sj >> 1] |= kb << (16 * (sj & 1));
+                    }
 #pragma unroll
                     for (int r = 0; r < 16; ++r) D += pt[sj][r] * dp[r];
                 }
+            if constexpr (DROP) D *= p.keep_scale;
             D += __shfl_xor(D, 32);
             if (lane < 32) {
                 sM[qb * 32 + il] = m;
@@ -338,7 +381,9 @@ __global__ __launch_bounds__(WB_THREADS) void k_attn_wide_bwd(const AttnParams p
                     wide_mma_row<T>(ds, sV, sj, sO, qb, lane, N);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const float v = pt[sj][r] * (ds[r] - D);  // (padded keys: P = 0)
+                        float dpr = ds[r];
+                        if constexpr (DROP) dpr = ((kept[sj >> 1] >> (16 * (sj & 1) + r)) & 1u) ? dpr * p.keep_scale : 0.f;
+                        const float v = pt[sj][r] * (dpr - D);  // (padded keys: P = 0)
                         ds[r] = v;
                         dbacc[qi][sj][r] += v;
                     }
@@ -367,6 +412,16 @@ __global__ __launch_bounds__(WB_THREADS) void k_attn_wide_bwd(const AttnParams p
                 zero(dp);
                 wide_mma_row<T>(s, sQ, si, sK, kb, lane, N);
                 wide_mma_row<T>(dp, sO, si, sV, kb, lane, N);
+                [[maybe_unused]] uint32_t kept = 0u;  // DROP: keep bit of query row r of this tile for the lane's key
+                if constexpr (DROP) {
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) {  // rows 2t, 2t + 1 are adjacent queries
+                        const int i0 = si * 32 + ((2 * t) & 3) + 8 * (t >> 1) + h4;
+                        bool k0, k1;
+                        attn_keep_keypair(dc, sRH[i0], sRH[i0 + 1], j, k0, k1);  // (i0 + 1 < WN: the table spans the padded rows)
+                        kept |= (k0 ? 1u : 0u) << (2 * t) | (k1 ? 2u : 0u) << (2 * t);
+                    }
+                }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int i = si * 32 + (r & 3) + 8 * (r >> 2) + h4;
@@ -377,8 +432,14 @@ __global__ __launch_bounds__(WB_THREADS) void k_attn_wide_bwd(const AttnParams p
                     if (ids) add += tb.srid[ic] != rid_j ? p.mask_value : 0.f;
                     const float v = s[r] * p.scale + add;
                     const float pr = (iv && jv) ? __builtin_amdgcn_exp2f((v - sM[ic]) * W_LOG2E) * sL[ic] : 0.f;
-                    s[r] = pr;
-                    dp[r] = pr * (dp[r] - sD[ic]);
+                    if constexpr (DROP) {  // dS from dP = keep . dP / (1 - p); dV takes P'
+                        const bool keep = (kept >> r) & 1u;
+                        s[r] = keep ? pr * p.keep_scale : 0.f;
+                        dp[r] = pr * ((keep ? dp[r] * p.keep_scale : 0.f) - sD[ic]);
+                    } else {
+                        s[r] = pr;
+                        dp[r] = pr * (dp[r] - sD[ic]);
+                    }
                 }
                 wide_mma_col<T>(dk, sQ, si, dp, lane, N);  // dK^T[d][j] += sum_i Q[i][d] dS[i][j]
                 wide_mma_col<T>(dv, sO, si, s, lane, N);   // dV^T[d][j] += sum_i dO[i][d] P[i][j]
@@ -401,13 +462,21 @@ __global__ __launch_bounds__(WB_THREADS) void k_attn_wide_bwd(const AttnParams p
             }
     }
 }
+template <typename T, bool DENSE>
+__global__ __launch_bounds__(WB_THREADS) void k_attn_wide_bwd(const AttnParams p) {
+    attn_wide_bwd_body<T, DENSE, false>(p);
+}
+template <typename T, bool DENSE>
+__global__ __launch_bounds__(WB_THREADS) void k_attn_drop_wide_bwd(const AttnDropParams p) {
+    attn_wide_bwd_body<T, DENSE, true>(p);
+}
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-static size_t wide_lds_bytes(int dtype, int N, bool bwd) {
+static size_t wide_lds_bytes(int dtype, int N, bool bwd, bool drop = false) {
     const size_t rs = dtype == MTLORA_F32 ? AC<float>::RS : AC<bf16>::RS;
     const size_t ib = (((size_t)(N + 1) * rs + 15) / 16) * 16;
     const size_t stg = dtype == MTLORA_F32 ? STG<float>::BYTES : STG<bf16>::BYTES;
-    return (bwd ? 4 : 3) * ib + (bwd ? 6 : 3) * WN * 4 + (bwd ? WB_WAVES : WT) * stg;
+    return (bwd ? 4 : 3) * ib + (bwd ? 6 : 3) * WN * 4 + (bwd ? WB_WAVES : WT) * stg + (bwd && drop ? WN * 4 : 0);  // (row hashes)
 }
 // persistent grid of `per_cu` resident workgroups per CU.  Backward: one (4 waves on the whole register file).  Forward: two where
 // both the registers (151: three waves on a SIMD, i.e. two 5-wave workgroups) and the LDS (48 KB each) admit them -- the 16-bit
@@ -435,35 +504,39 @@ static bool wide_allow_lds(std::atomic<unsigned long long>& done, const void* ke
     if (cached) done.fetch_or(1ull << dev, std::memory_order_relaxed);
     return true;
 }
+// the kernel of a parameter block: plain (AttnParams) or attention dropout (AttnDropParams)
 template <typename T, bool DENSE>
-static int wide_launch_fwd(const AttnParams& p, unsigned grid, size_t lds, hipStream_t s) {
+static const void* wide_kernel(const AttnParams&, bool bwd) {
+    return bwd ? reinterpret_cast<const void*>(k_attn_wide_bwd<T, DENSE>) : reinterpret_cast<const void*>(k_attn_wide_fwd<T, DENSE>);
+}
+template <typename T, bool DENSE>
+static const void* wide_kernel(const AttnDropParams&, bool bwd) {
+    return bwd ? reinterpret_cast<const void*>(k_attn_drop_wide_bwd<T, DENSE>) : reinterpret_cast<const void*>(k_attn_drop_wide_fwd<T, DENSE>);
+}
+template <typename T, bool DENSE, bool BWD, typename P>
+static int wide_launch(const P& p, unsigned grid, size_t lds, hipStream_t s) {
     static std::atomic<unsigned long long> done{0};  // (one per kernel instantiation)
-    if (!wide_allow_lds(done, reinterpret_cast<const void*>(k_attn_wide_fwd<T, DENSE>), lds)) return MTLORA_ERR_HIP;
-    hipLaunchKernelGGL((k_attn_wide_fwd<T, DENSE>), dim3(grid), dim3(W_THREADS), lds, s, p);
+    const void* kernel = wide_kernel<T, DENSE>(p, BWD);
+    if (!wide_allow_lds(done, kernel, lds)) return MTLORA_ERR_HIP;
+    void* args[] = {const_cast<P*>(&p)};
+    if (hipLaunchKernel(kernel, dim3(grid), dim3(BWD ? WB_THREADS : W_THREADS), args, lds, s) != hipSuccess) return MTLORA_ERR_HIP;
     return MTLORA_OK;
 }
-template <typename T, bool DENSE>
-static int wide_launch_bwd(const AttnParams& p, unsigned grid, size_t lds, hipStream_t s) {
-    static std::atomic<unsigned long long> done{0};
-    if (!wide_allow_lds(done, reinterpret_cast<const void*>(k_attn_wide_bwd<T, DENSE>), lds)) return MTLORA_ERR_HIP;
-    hipLaunchKernelGGL((k_attn_wide_bwd<T, DENSE>), dim3(grid), dim3(WB_THREADS), lds, s, p);
-    return MTLORA_OK;
+template <bool BWD, typename P>
+static int wide_dispatch(int dtype, bool dense, const P& p, unsigned grid, size_t lds, hipStream_t s) {
+    if (dtype == MTLORA_F32) return dense ? wide_launch<float, true, BWD>(p, grid, lds, s) : wide_launch<float, false, BWD>(p, grid, lds, s);
+    if (dtype == MTLORA_F16) return dense ? wide_launch<f16, true, BWD>(p, grid, lds, s) : wide_launch<f16, false, BWD>(p, grid, lds, s);
+    return dense ? wide_launch<bf16, true, BWD>(p, grid, lds, s) : wide_launch<bf16, false, BWD>(p, grid, lds, s);
 }
-static int wide_fwd(const mtlora_attn_desc* d, AttnParams& p, hipStream_t s) {
+template <typename P>
+static int wide_fwd(const mtlora_attn_desc* d, P& p, hipStream_t s) {
     const bool dense = p.mask && !p.mask_ids;
     p.G = wide_groups(d, d->dtype != MTLORA_F32 && !dense ? 2 : 1);
-    const unsigned grid = (unsigned)(p.G * p.nH);
-    const size_t lds = wide_lds_bytes(d->dtype, p.N, false);
-    if (d->dtype == MTLORA_F32) return dense ? wide_launch_fwd<float, true>(p, grid, lds, s) : wide_launch_fwd<float, false>(p, grid, lds, s);
-    if (d->dtype == MTLORA_F16) return dense ? wide_launch_fwd<f16, true>(p, grid, lds, s) : wide_launch_fwd<f16, false>(p, grid, lds, s);
-    return dense ? wide_launch_fwd<bf16, true>(p, grid, lds, s) : wide_launch_fwd<bf16, false>(p, grid, lds, s);
+    return wide_dispatch<false>(d->dtype, dense, p, (unsigned)(p.G * p.nH), wide_lds_bytes(d->dtype, p.N, false), s);
 }
-static int wide_bwd(const mtlora_attn_desc* d, AttnParams& p, hipStream_t s) {
+template <typename P>
+static int wide_bwd(const mtlora_attn_desc* d, P& p, hipStream_t s) {
     p.G = wide_groups(d);
-    const unsigned grid = (unsigned)(p.G * p.nH);
-    const size_t lds = wide_lds_bytes(d->dtype, p.N, true);
     const bool dense = p.mask && !p.mask_ids;
-    if (d->dtype == MTLORA_F32) return dense ? wide_launch_bwd<float, true>(p, grid, lds, s) : wide_launch_bwd<float, false>(p, grid, lds, s);
-    if (d->dtype == MTLORA_F16) return dense ? wide_launch_bwd<f16, true>(p, grid, lds, s) : wide_launch_bwd<f16, false>(p, grid, lds, s);
-    return dense ? wide_launch_bwd<bf16, true>(p, grid, lds, s) : wide_launch_bwd<bf16, false>(p, grid, lds, s);
+    return wide_dispatch<true>(d->dtype, dense, p, (unsigned)(p.G * p.nH), wide_lds_bytes(d->dtype, p.N, true, std::is_same<P, AttnDropParams>::value), s);
 }

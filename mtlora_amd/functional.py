@@ -803,10 +803,13 @@ class AttnMeta:
 class WindowAttentionFn(torch.autograd.Function):
     """out = softmax(scale * q k^T + bias[h] + mask[w]) v per (window, head)  (swin_transformer_mtlora.py:194-220).
     qkv: (..., 3C) [3][nH][hd]; bias: (nH, N, N) fp32 dense.  The shift mask is either ``mask_ids`` (nW, N) int32
-    region ids (fast path: mask(i,j) = ids differ ? meta.mask_value : 0) or a general dense ``mask`` (nW, N, N)."""
+    region ids (fast path: mask(i,j) = ids differ ? meta.mask_value : 0) or a general dense ``mask`` (nW, N, N).
+    Optional ``p, seed``: attention dropout on the softmax output (reference :216), generated inside the kernels from ``seed`` (plus
+    the device seed-offset word of :func:`set_seed_offset`, as the linear layers); the backward regenerates the same bits."""
 
     @staticmethod
-    def forward(ctx, meta: AttnMeta, qkv, bias, mask, mask_ids):
+    def forward(ctx, meta: AttnMeta, qkv, bias, mask, mask_ids, *drop):
+        p, seed = (float(drop[0]), int(drop[1])) if drop else (0.0, 0)
         L.require_gpu(qkv, bias, mask, mask_ids)
         dt = qkv.dtype
         if dt not in _HOT_DTYPES:
@@ -821,10 +824,18 @@ class WindowAttentionFn(torch.autograd.Function):
         C = meta.num_heads * meta.head_dim
         out = torch.empty(qkv_c.shape[:-1] + (C,), dtype=dt, device=qkv.device)
         d = meta.desc(dt)
-        st = L.lib().mtlora_window_attn_fwd(ctypes.byref(d), L.ptr(qkv_c), L.ptr(bias_c), L.ptr(mask), L.ptr(mask_ids),
-                                            L.ptr(out), L.stream_ptr())
-        L.check(st, "mtlora_window_attn_fwd")
-        ctx.meta = meta
+        if p > 0.0:
+            dr = L.AttnDropout()
+            dr.p, dr.seed, dr.seed_offset = p, seed, (0 if _seed_offset is None else _seed_offset.data_ptr())
+            st = L.lib().mtlora_window_attn_drop_fwd(ctypes.byref(d), ctypes.byref(dr), L.ptr(qkv_c), L.ptr(bias_c), L.ptr(mask),
+                                                     L.ptr(mask_ids), L.ptr(out), L.stream_ptr())
+            L.check(st, "mtlora_window_attn_drop_fwd")
+        else:
+            dr = None
+            st = L.lib().mtlora_window_attn_fwd(ctypes.byref(d), L.ptr(qkv_c), L.ptr(bias_c), L.ptr(mask), L.ptr(mask_ids),
+                                                L.ptr(out), L.stream_ptr())
+            L.check(st, "mtlora_window_attn_fwd")
+        ctx.meta, ctx.drop, ctx.n_drop = meta, dr, len(drop)
         ctx.save_for_backward(qkv_c, bias_c, mask, mask_ids)
         return out
 
@@ -839,10 +850,16 @@ class WindowAttentionFn(torch.autograd.Function):
         scratch = torch.empty(sb, dtype=torch.uint8, device=qkv.device)
         dqkv = torch.empty_like(qkv)
         dbias = torch.empty_like(bias)
-        st = lib.mtlora_window_attn_bwd(ctypes.byref(d), L.ptr(qkv), L.ptr(bias), L.ptr(mask), L.ptr(mask_ids),
-                                        L.ptr(dout), L.ptr(dqkv), L.ptr(dbias), L.ptr(scratch), sb, L.stream_ptr())
-        L.check(st, "mtlora_window_attn_bwd")
-        return None, dqkv, dbias, None, None
+        if ctx.drop is not None:
+            st = lib.mtlora_window_attn_drop_bwd(ctypes.byref(d), ctypes.byref(ctx.drop), L.ptr(qkv), L.ptr(bias), L.ptr(mask),
+                                                 L.ptr(mask_ids), L.ptr(dout), L.ptr(dqkv), L.ptr(dbias), L.ptr(scratch), sb,
+                                                 L.stream_ptr())
+            L.check(st, "mtlora_window_attn_drop_bwd")
+        else:
+            st = lib.mtlora_window_attn_bwd(ctypes.byref(d), L.ptr(qkv), L.ptr(bias), L.ptr(mask), L.ptr(mask_ids),
+                                            L.ptr(dout), L.ptr(dqkv), L.ptr(dbias), L.ptr(scratch), sb, L.stream_ptr())
+            L.check(st, "mtlora_window_attn_bwd")
+        return (None, dqkv, dbias, None, None) + (None,) * ctx.n_drop
 
 
 # ----------------------------------------------------------------------------------------------

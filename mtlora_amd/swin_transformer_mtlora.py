@@ -267,9 +267,8 @@ class WindowAttention(nn.Module):
             return (table.float().t() @ oh).view(-1, n, n)
 
     def _core(self, qkv: Tensor, meta: Fn.AttnMeta, mask: Optional[Tensor], mask_ids: Optional[Tensor]) -> Tensor:
-        if self.training and self.attn_drop.p > 0:
-            raise NotImplementedError("mtlora_amd: attn_drop > 0 is not supported by the fused attention kernel "
-                                      "(every MTLoRA config uses 0)")
+        if self.training and self.attn_drop.p > 0:  # dropout on the softmax output (:216), generated inside the kernels
+            return Fn.WindowAttentionFn.apply(meta, qkv, self.dense_bias(), mask, mask_ids, self.attn_drop.p, Fn.next_seed())
         return Fn.WindowAttentionFn.apply(meta, qkv, self.dense_bias(), mask, mask_ids)
 
     def _project(self, a: Tensor):
