@@ -25,7 +25,7 @@
 #include <cmath>
 #include <type_traits>
 
-#include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -932,7 +932,7 @@ constexpr int WIDE_MAX_N = 144;  // 64 < N <= 144 (ws 9..12): the multi-wave ker
 
 int check(const mtlora_attn_desc* d) {
     if (!d) return MTLORA_ERR_NULL;
-    if (d->dtype != MTLORA_F32 && d->dtype != MTLORA_BF16 && d->dtype != MTLORA_F16) return MTLORA_ERR_DTYPE;
+    if (!mtl_dtype_in(d->dtype, MTL_DT_ALL)) return MTLORA_ERR_DTYPE;
     if (d->head_dim != HD) return MTLORA_ERR_UNSUPPORTED;
     if (d->window_size <= 0 || d->window_size * d->window_size > WIDE_MAX_N) return MTLORA_ERR_UNSUPPORTED;
     if (d->B < 0 || d->H <= 0 || d->W <= 0 || d->num_heads <= 0) return MTLORA_ERR_SHAPE;
@@ -955,18 +955,24 @@ static int groups_for(size_t lds_bytes, int cap, int nH, int64_t n_windows) {
     return (int)G;
 }
 
-static size_t bwd_lds_bytes(const mtlora_attn_desc* d) {
-    const int N = d->window_size * d->window_size;
-    const int rs = d->dtype == MTLORA_F32 ? AC<float>::RS : AC<bf16>::RS;
-    const size_t ib = (size_t)((img_rows_h(N) * rs + 15) / 16) * 16;
-    const size_t img = d->dtype == MTLORA_F32 ? IMG<float>::RS : IMG<bf16>::RS;  // P / dS hand-over images
-    return 4 * ib + 2 * 32 * img + 2 * AN * 4 + (d->dtype == MTLORA_F32 ? STG<float>::BYTES : STG<bf16>::BYTES) + (d->dtype == MTLORA_F32 ? (size_t)N * bias_stride_c(N) * 4 : 0);  // (fp32: bias image)
+struct AttnSizes {
+    size_t rs, img, stg;  // by element type (fp16 has bf16's): row stride of the q / k / v and of the P / dS hand-over images, staging bytes
+};
+static AttnSizes attn_sizes(int dtype) {
+    return mtl_dispatch_f32_bf16(dtype, [](auto t) -> AttnSizes {
+        return {AC<typename decltype(t)::type>::RS, IMG<typename decltype(t)::type>::RS, STG<typename decltype(t)::type>::BYTES};
+    });
+}
+static size_t narrow_lds_bytes(int dtype, int N, bool bwd) {  // dynamic LDS of the one-wave kernels
+    const AttnSizes z = attn_sizes(dtype);
+    const size_t ib = (img_rows_h(N) * z.rs + 15) / 16 * 16;
+    return (bwd ? 4 * ib + 2 * 32 * z.img : 3 * ib) + 2 * AN * 4 + z.stg + (dtype == MTLORA_F32 ? (size_t)N * bias_stride_c(N) * 4 : 0);  // (fp32: bias image)
 }
 
 int bwd_groups(const mtlora_attn_desc* d) {
     const int64_t nwin = d->B * (d->H / d->window_size) * (d->W / d->window_size);
     // MTL_ATTN_BWD_WPS single-wave workgroups per SIMD (the register budget the kernel is compiled for), LDS permitting
-    return groups_for(bwd_lds_bytes(d), 4 * MTL_ATTN_BWD_WPS, d->num_heads, nwin);
+    return groups_for(narrow_lds_bytes(d->dtype, d->window_size * d->window_size, true), 4 * MTL_ATTN_BWD_WPS, d->num_heads, nwin);
 }
 
 AttnParams make_params(const mtlora_attn_desc* d) {
@@ -1000,13 +1006,9 @@ static const void* narrow_kernel(const AttnDropParams&, bool bwd) {
 template <typename P>
 static void narrow_launch(int dtype, bool bwd, const P& p, size_t lds, hipStream_t s) {
     const bool dense = p.mask && !p.mask_ids;
-    const void* k;
-    if (dtype == MTLORA_F32)
-        k = dense ? narrow_kernel<float, true>(p, bwd) : narrow_kernel<float, false>(p, bwd);
-    else if (dtype == MTLORA_F16)
-        k = dense ? narrow_kernel<f16, true>(p, bwd) : narrow_kernel<f16, false>(p, bwd);
-    else
-        k = dense ? narrow_kernel<bf16, true>(p, bwd) : narrow_kernel<bf16, false>(p, bwd);
+    const void* k = mtl_dispatch_dtype(dtype, [&](auto t) {
+        return dense ? narrow_kernel<typename decltype(t)::type, true>(p, bwd) : narrow_kernel<typename decltype(t)::type, false>(p, bwd);
+    });
     void* args[] = {const_cast<P*>(&p)};
     (void)hipLaunchKernel(k, dim3((unsigned)(p.G * p.nH)), dim3(64), args, lds, s);  // (the caller's MTL_CHECK_LAUNCH reads the status)
 }
@@ -1022,9 +1024,7 @@ static int attn_fwd_run(const mtlora_attn_desc* d, P& p, hipStream_t s) {
         MTL_CHECK_LAUNCH();
         return MTLORA_OK;
     }
-    const int rs = d->dtype == MTLORA_F32 ? AC<float>::RS : AC<bf16>::RS;
-    const size_t ib = (size_t)((img_rows_h(p.N) * rs + 15) / 16) * 16;
-    const size_t lds = 3 * ib + 2 * AN * 4 + (d->dtype == MTLORA_F32 ? STG<float>::BYTES : STG<bf16>::BYTES) + (d->dtype == MTLORA_F32 ? (size_t)p.N * bias_stride_c(p.N) * 4 : 0);  // (fp32: bias image)
+    const size_t lds = narrow_lds_bytes(d->dtype, p.N, false);
     p.G = groups_for(lds, 4 * MTL_ATTN_FWD_WPS, p.nH, p.n_windows);  // persistent grid: exactly the resident workgroups
     narrow_launch(d->dtype, false, p, lds, s);
     MTL_CHECK_LAUNCH();
@@ -1040,7 +1040,7 @@ static int attn_bwd_run(const mtlora_attn_desc* d, P& p, float* dbias, hipStream
             if (wst != MTLORA_OK) return wst;
         } else {
             p.G = bwd_groups(d);
-            narrow_launch(d->dtype, true, p, bwd_lds_bytes(d), s);
+            narrow_launch(d->dtype, true, p, narrow_lds_bytes(d->dtype, p.N, true), s);
         }
     }
     const int total = p.nH * p.N * p.N;
@@ -1072,8 +1072,8 @@ static int attn_fwd_entry(const mtlora_attn_desc* d, const mtlora_attn_dropout* 
     AttnDropParams p = {};
     bool drop_on;
     if ((st = drop_setup(d, dr, plain, p, drop_on)) != MTLORA_OK) return st;
-    if (!qkv || !bias || !out) return MTLORA_ERR_NULL;
-    if (((uintptr_t)qkv | (uintptr_t)out) & 15u) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({qkv, bias, out})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({qkv, out})) return MTLORA_ERR_ALIGN;
     static_cast<AttnParams&>(p) = make_params(d);
     if (p.n_windows == 0) return MTLORA_OK;
     p.qkv = qkv;
@@ -1093,8 +1093,8 @@ static int attn_bwd_entry(const mtlora_attn_desc* d, const mtlora_attn_dropout* 
     AttnDropParams p = {};
     bool drop_on;
     if ((st = drop_setup(d, dr, plain, p, drop_on)) != MTLORA_OK) return st;
-    if (!qkv || !bias || !dout || !dqkv || !dbias || !scratch) return MTLORA_ERR_NULL;
-    if (((uintptr_t)qkv | (uintptr_t)dout | (uintptr_t)dqkv | (uintptr_t)scratch) & 15u) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({qkv, bias, dout, dqkv, dbias, scratch})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({qkv, dout, dqkv, scratch})) return MTLORA_ERR_ALIGN;
     if (scratch_bytes < mtlora_window_attn_bwd_scratch_bytes(d) - 256) return MTLORA_ERR_WORKSPACE;
     static_cast<AttnParams&>(p) = make_params(d);
     hipStream_t s = (hipStream_t)stream;

@@ -473,10 +473,9 @@ __global__ __launch_bounds__(WB_THREADS) void k_attn_drop_wide_bwd(const AttnDro
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
 static size_t wide_lds_bytes(int dtype, int N, bool bwd, bool drop = false) {
-    const size_t rs = dtype == MTLORA_F32 ? AC<float>::RS : AC<bf16>::RS;
-    const size_t ib = (((size_t)(N + 1) * rs + 15) / 16) * 16;
-    const size_t stg = dtype == MTLORA_F32 ? STG<float>::BYTES : STG<bf16>::BYTES;
-    return (bwd ? 4 : 3) * ib + (bwd ? 6 : 3) * WN * 4 + (bwd ? WB_WAVES : WT) * stg + (bwd && drop ? WN * 4 : 0);  // (row hashes)
+    const AttnSizes z = attn_sizes(dtype);
+    const size_t ib = (((size_t)(N + 1) * z.rs + 15) / 16) * 16;
+    return (bwd ? 4 : 3) * ib + (bwd ? 6 : 3) * WN * 4 + (bwd ? WB_WAVES : WT) * z.stg + (bwd && drop ? WN * 4 : 0);  // (row hashes)
 }
 // persistent grid of `per_cu` resident workgroups per CU.  Backward: one (4 waves on the whole register file).  Forward: two where
 // both the registers (151: three waves on a SIMD, i.e. two 5-wave workgroups) and the LDS (48 KB each) admit them -- the 16-bit
@@ -524,9 +523,9 @@ static int wide_launch(const P& p, unsigned grid, size_t lds, hipStream_t s) {
 }
 template <bool BWD, typename P>
 static int wide_dispatch(int dtype, bool dense, const P& p, unsigned grid, size_t lds, hipStream_t s) {
-    if (dtype == MTLORA_F32) return dense ? wide_launch<float, true, BWD>(p, grid, lds, s) : wide_launch<float, false, BWD>(p, grid, lds, s);
-    if (dtype == MTLORA_F16) return dense ? wide_launch<f16, true, BWD>(p, grid, lds, s) : wide_launch<f16, false, BWD>(p, grid, lds, s);
-    return dense ? wide_launch<bf16, true, BWD>(p, grid, lds, s) : wide_launch<bf16, false, BWD>(p, grid, lds, s);
+    return mtl_dispatch_dtype(dtype, [&](auto t) {
+        return dense ? wide_launch<typename decltype(t)::type, true, BWD>(p, grid, lds, s) : wide_launch<typename decltype(t)::type, false, BWD>(p, grid, lds, s);
+    });
 }
 template <typename P>
 static int wide_fwd(const mtlora_attn_desc* d, P& p, hipStream_t s) {

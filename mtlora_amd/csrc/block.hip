@@ -15,7 +15,6 @@ namespace {
 
 constexpr int64_t kAlign = 256;
 
-inline int64_t es_of(int dtype) { return dtype == MTLORA_F32 ? 4 : 2; }
 inline int64_t up(int64_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
 
 // ---- the `save` buffer (written by fwd, read by bwd) ----
@@ -51,7 +50,7 @@ bool desc_ok(const mtlora_block_desc* d) {
 
 int save_layout(const mtlora_block_desc* d, SaveLayout& L) {
     if (!desc_ok(d)) return MTLORA_ERR_SHAPE;
-    const int64_t M = d->B * d->H * d->W, C = d->C, Hd = d->hidden, es = es_of(d->dtype), xs = es_of(d->x_dtype);
+    const int64_t M = d->B * d->H * d->W, C = d->C, Hd = d->hidden, es = mtl_elem_size(d->dtype), xs = mtl_elem_size(d->x_dtype);
     int64_t o = 0;
     auto take = [&](int64_t bytes) { int64_t at = o; o += up(bytes); return at; };
     L.xn = L.mean1 = L.rstd1 = -1;
@@ -97,7 +96,7 @@ mtlora_attn_desc attn_desc(const mtlora_block_desc* d) {
 
 int bwd_layout(const mtlora_block_desc* d, BwdLayout& L) {
     if (!desc_ok(d)) return MTLORA_ERR_SHAPE;
-    const int64_t M = d->B * d->H * d->W, C = d->C, Hd = d->hidden, es = es_of(d->dtype), xs = es_of(d->x_dtype);
+    const int64_t M = d->B * d->H * d->W, C = d->C, Hd = d->hidden, es = mtl_elem_size(d->dtype), xs = mtl_elem_size(d->x_dtype);
     int64_t o = 0;
     auto take = [&](int64_t bytes) { int64_t at = o; o += up(bytes); return at; };
     L.d_m = take(M * C * es);
@@ -144,7 +143,7 @@ int64_t mtlora_block_save_bytes(const mtlora_block_desc* d) {
 
 int64_t mtlora_block_fwd_tmp_bytes(const mtlora_block_desc* d) {
     if (!desc_ok(d)) return -1;
-    return up(d->B * d->H * d->W * d->C * es_of(d->dtype));  // one (M, C) branch tensor: proj's output, then fc2's
+    return up(d->B * d->H * d->W * d->C * mtl_elem_size(d->dtype));  // one (M, C) branch tensor: proj's output, then fc2's
 }
 
 int64_t mtlora_block_bwd_scratch_bytes(const mtlora_block_desc* d) {

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/mtlora_hip.h"
+#include "internal.h"  // (the C ABI header, and mtl_elem_size)
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -41,7 +41,6 @@ static inline void mtl_zero_async(void* p, size_t bytes, hipStream_t s) {
 
 __host__ __device__ static inline int64_t mtl_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t mtl_round_up(int64_t a, int64_t b) { return mtl_ceil_div(a, b) * b; }
-static inline int mtl_elem_size(int dtype) { return dtype == MTLORA_F32 ? 4 : 2; }  // bf16 and f16: 2
 
 // ---------------------------------------------------------------------------------------------
 // counter-based dropout (restated in oracle/mtlora_oracle.py:dropout_keep_mask)

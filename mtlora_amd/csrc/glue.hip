@@ -1,6 +1,6 @@
 // glue.hip -- streaming glue kernels beside the LayerNorm family (ln.h / layernorm.hip): the decoder heads' training-mode
 // BatchNorm + ReLU and the residual + DropPath of a block half.  HBM-bound; the 16-byte vector helpers are in vec.h.
-#include "common.h"
+#include "dispatch.h"
 #include "internal.h"
 #include "vec.h"
 
@@ -267,8 +267,8 @@ __global__ __launch_bounds__(512) void k_bn_apply(const BnParams p) {
 }
 
 int bn_setup(BnParams& p, int64_t R, int64_t C, int dtype) {
-    if (dtype != MTLORA_F32 && dtype != MTLORA_BF16 && dtype != MTLORA_F16) return MTLORA_ERR_DTYPE;
-    const int ve = dtype == MTLORA_F32 ? 4 : 8;
+    if (!mtl_dtype_in(dtype, MTL_DT_ALL)) return MTLORA_ERR_DTYPE;
+    const int ve = mtl_vec_elems(dtype);
     if (R <= 0 || C <= 0 || C % ve) return MTLORA_ERR_SHAPE;
     p.R = R;
     p.C = (int)C;
@@ -300,9 +300,8 @@ int mtlora_bn_relu_fwd(const void* x, const float* gamma, const float* beta, flo
     BnParams p = {};
     int st = bn_setup(p, R, C, dtype);
     if (st != MTLORA_OK) return st;
-    if (!x || !gamma || !beta || !y || !save_mean || !save_rstd || !save_scale || !save_shift || !scratch)
-        return MTLORA_ERR_NULL;
-    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)scratch) & 15u) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({x, gamma, beta, y, save_mean, save_rstd, save_scale, save_shift, scratch})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({x, y, scratch})) return MTLORA_ERR_ALIGN;
     if (scratch_bytes < mtlora_bn_scratch_bytes(R, C, dtype) - 256) return MTLORA_ERR_WORKSPACE;
     p.x = x;
     p.y = y;
@@ -325,22 +324,16 @@ int mtlora_bn_relu_fwd(const void* x, const float* gamma, const float* beta, flo
     const int es = mtl_elem_size(dtype);
     {
         MtlProfScope prof(PK_BN, (double)R * C * es, s);
-        if (dtype == MTLORA_F32)
-            hipLaunchKernelGGL((k_bn_colsum<float, false>), dim3(p.nblk), dim3(threads), lds, s, p);
-        else if (dtype == MTLORA_F16)
-            hipLaunchKernelGGL((k_bn_colsum<f16, false>), dim3(p.nblk), dim3(threads), lds, s, p);
-        else
-            hipLaunchKernelGGL((k_bn_colsum<bf16, false>), dim3(p.nblk), dim3(threads), lds, s, p);
+        mtl_dispatch_dtype(dtype, [&](auto t) {
+            hipLaunchKernelGGL((k_bn_colsum<typename decltype(t)::type, false>), dim3(p.nblk), dim3(threads), lds, s, p);
+        });
     }
     hipLaunchKernelGGL(k_bn_finalize, dim3((unsigned)mtl_ceil_div(C, 64)), dim3(64 * BN_FW), 0, s, p);
     {
         MtlProfScope prof(PK_BN, (double)R * C * es * 2, s);
-        if (dtype == MTLORA_F32)
-            hipLaunchKernelGGL((k_bn_apply<float, false>), dim3(apply_blocks), dim3(threads), 0, s, p);
-        else if (dtype == MTLORA_F16)
-            hipLaunchKernelGGL((k_bn_apply<f16, false>), dim3(apply_blocks), dim3(threads), 0, s, p);
-        else
-            hipLaunchKernelGGL((k_bn_apply<bf16, false>), dim3(apply_blocks), dim3(threads), 0, s, p);
+        mtl_dispatch_dtype(dtype, [&](auto t) {
+            hipLaunchKernelGGL((k_bn_apply<typename decltype(t)::type, false>), dim3(apply_blocks), dim3(threads), 0, s, p);
+        });
     }
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
@@ -352,9 +345,8 @@ int mtlora_bn_relu_bwd(const void* dy, const void* x, const float* save_mean, co
     BnParams p = {};
     int st = bn_setup(p, R, C, dtype);
     if (st != MTLORA_OK) return st;
-    if (!dy || !x || !save_mean || !save_rstd || !save_scale || !save_shift || !dx || !dgamma || !dbeta || !scratch)
-        return MTLORA_ERR_NULL;
-    if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)scratch) & 15u) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({dy, x, save_mean, save_rstd, save_scale, save_shift, dx, dgamma, dbeta, scratch})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({x, dy, dx, scratch})) return MTLORA_ERR_ALIGN;
     if (scratch_bytes < mtlora_bn_scratch_bytes(R, C, dtype) - 256) return MTLORA_ERR_WORKSPACE;
     p.x = x;
     p.dy = dy;
@@ -376,22 +368,16 @@ int mtlora_bn_relu_bwd(const void* dy, const void* x, const float* save_mean, co
     const int es = mtl_elem_size(dtype);
     {
         MtlProfScope prof(PK_BN, (double)R * C * es * 2, s);
-        if (dtype == MTLORA_F32)
-            hipLaunchKernelGGL((k_bn_colsum<float, true>), dim3(p.nblk), dim3(threads), lds, s, p);
-        else if (dtype == MTLORA_F16)
-            hipLaunchKernelGGL((k_bn_colsum<f16, true>), dim3(p.nblk), dim3(threads), lds, s, p);
-        else
-            hipLaunchKernelGGL((k_bn_colsum<bf16, true>), dim3(p.nblk), dim3(threads), lds, s, p);
+        mtl_dispatch_dtype(dtype, [&](auto t) {
+            hipLaunchKernelGGL((k_bn_colsum<typename decltype(t)::type, true>), dim3(p.nblk), dim3(threads), lds, s, p);
+        });
     }
     hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)mtl_ceil_div(C, 64)), dim3(64 * BN_FW), 0, s, p);
     {
         MtlProfScope prof(PK_BN, (double)R * C * es * 3, s);
-        if (dtype == MTLORA_F32)
-            hipLaunchKernelGGL((k_bn_apply<float, true>), dim3(apply_blocks), dim3(threads), 0, s, p);
-        else if (dtype == MTLORA_F16)
-            hipLaunchKernelGGL((k_bn_apply<f16, true>), dim3(apply_blocks), dim3(threads), 0, s, p);
-        else
-            hipLaunchKernelGGL((k_bn_apply<bf16, true>), dim3(apply_blocks), dim3(threads), 0, s, p);
+        mtl_dispatch_dtype(dtype, [&](auto t) {
+            hipLaunchKernelGGL((k_bn_apply<typename decltype(t)::type, true>), dim3(apply_blocks), dim3(threads), 0, s, p);
+        });
     }
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
@@ -491,8 +477,7 @@ __global__ __launch_bounds__(256) void k_residual_bwd(const ResParams p) {
 }
 
 int res_check(int n, int64_t M, int64_t C, int64_t B, int rdt, int ydt) {
-    if (rdt < MTLORA_F32 || rdt > MTLORA_F16 || ydt < MTLORA_F32 || ydt > MTLORA_F16) return MTLORA_ERR_DTYPE;
-    if (rdt != MTLORA_F32 && ydt != MTLORA_F32 && rdt != ydt) return MTLORA_ERR_DTYPE;
+    if (!mtl_dtype_pair_ok(rdt, ydt)) return MTLORA_ERR_DTYPE;
     if (n < 1 || n > MTLORA_MAX_TASKS + 1 || M < 0 || C <= 0 || C % 8 || B <= 0 || M % B) return MTLORA_ERR_SHAPE;
     return MTLORA_OK;
 }
@@ -506,11 +491,11 @@ int mtlora_residual_droppath_fwd(int n, const void* const* res, const void* cons
                                  void* stream) {
     int st = res_check(n, M, C, B, res_dtype, y_dtype);
     if (st != MTLORA_OK) return st;
-    if (!res || !y || !out) return MTLORA_ERR_NULL;
+    if (mtl_any_null({res, y, out})) return MTLORA_ERR_NULL;
     ResParams p = {};
-    for (int k = 0; k < n; ++k) {
-        if (!res[k] || !y[k] || !out[k]) return MTLORA_ERR_NULL;
-        if (((uintptr_t)res[k] | (uintptr_t)y[k] | (uintptr_t)out[k]) & 15u) return MTLORA_ERR_ALIGN;
+    for (int k = 0; k < n; ++k) {  // (stream by stream: the first bad stream decides between NULL and ALIGN)
+        if (mtl_any_null({res[k], y[k], out[k]})) return MTLORA_ERR_NULL;
+        if (mtl_any_misaligned({res[k], y[k], out[k]})) return MTLORA_ERR_ALIGN;
         p.res[k] = res[k];
         p.y[k] = y[k];
         p.out[k] = out[k];
@@ -528,21 +513,9 @@ int mtlora_residual_droppath_fwd(int n, const void* const* res, const void* cons
     dim3 g((unsigned)blocks, (unsigned)n);
     const int er = mtl_elem_size(res_dtype), ey = mtl_elem_size(y_dtype);
     MtlProfScope prof(PK_RESIDUAL, (double)n * M * C * (2 * er + ey), s);
-    if (res_dtype == MTLORA_F32 && y_dtype == MTLORA_F32)
-        hipLaunchKernelGGL((k_residual_fwd<float, float>), g, dim3(256), 0, s, p);
-    else if (res_dtype == MTLORA_F16 || y_dtype == MTLORA_F16) {
-        if (res_dtype == MTLORA_F32)
-            hipLaunchKernelGGL((k_residual_fwd<float, f16>), g, dim3(256), 0, s, p);
-        else if (y_dtype == MTLORA_F32)
-            hipLaunchKernelGGL((k_residual_fwd<f16, float>), g, dim3(256), 0, s, p);
-        else
-            hipLaunchKernelGGL((k_residual_fwd<f16, f16>), g, dim3(256), 0, s, p);
-    } else if (res_dtype == MTLORA_F32)
-        hipLaunchKernelGGL((k_residual_fwd<float, bf16>), g, dim3(256), 0, s, p);
-    else if (y_dtype == MTLORA_F32)
-        hipLaunchKernelGGL((k_residual_fwd<bf16, float>), g, dim3(256), 0, s, p);
-    else
-        hipLaunchKernelGGL((k_residual_fwd<bf16, bf16>), g, dim3(256), 0, s, p);
+    mtl_dispatch_dtype_pair(res_dtype, y_dtype, [&](auto tr, auto ty) {
+        hipLaunchKernelGGL((k_residual_fwd<typename decltype(tr)::type, typename decltype(ty)::type>), g, dim3(256), 0, s, p);
+    });
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }
@@ -552,10 +525,10 @@ int mtlora_residual_droppath_bwd(int n, const void* const* g, void* const* dy, v
                                  int64_t M, int64_t C, int64_t B, int res_dtype, int y_dtype, void* stream) {
     int st = res_check(n, M, C, B, res_dtype, y_dtype);
     if (st != MTLORA_OK) return st;
-    if (!g || !dy) return MTLORA_ERR_NULL;
+    if (mtl_any_null({g, dy})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({}, n, {g, mtl_arr(dy)})) return MTLORA_ERR_ALIGN;  // (null elements of g / dy are allowed)
     ResParams p = {};
     for (int k = 0; k < n; ++k) {
-        if (((uintptr_t)g[k] | (uintptr_t)dy[k]) & 15u) return MTLORA_ERR_ALIGN;
         p.y[k] = g[k];
         p.out[k] = g[k] ? dy[k] : nullptr;
     }
@@ -572,21 +545,9 @@ int mtlora_residual_droppath_bwd(int n, const void* const* g, void* const* dy, v
     if (blocks > 2048) blocks = 2048;
     const int er = mtl_elem_size(res_dtype), ey = mtl_elem_size(y_dtype);
     MtlProfScope prof(PK_RESIDUAL, (double)M * C * (n * (er + ey) + (dres ? er : 0)), s);
-    if (res_dtype == MTLORA_F32 && y_dtype == MTLORA_F32)
-        hipLaunchKernelGGL((k_residual_bwd<float, float>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else if (res_dtype == MTLORA_F16 || y_dtype == MTLORA_F16) {
-        if (res_dtype == MTLORA_F32)
-            hipLaunchKernelGGL((k_residual_bwd<float, f16>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-        else if (y_dtype == MTLORA_F32)
-            hipLaunchKernelGGL((k_residual_bwd<f16, float>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-        else
-            hipLaunchKernelGGL((k_residual_bwd<f16, f16>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    } else if (res_dtype == MTLORA_F32)
-        hipLaunchKernelGGL((k_residual_bwd<float, bf16>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else if (y_dtype == MTLORA_F32)
-        hipLaunchKernelGGL((k_residual_bwd<bf16, float>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else
-        hipLaunchKernelGGL((k_residual_bwd<bf16, bf16>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+    mtl_dispatch_dtype_pair(res_dtype, y_dtype, [&](auto tr, auto ty) {
+        hipLaunchKernelGGL((k_residual_bwd<typename decltype(tr)::type, typename decltype(ty)::type>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+    });
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }

@@ -17,7 +17,7 @@
 // the rows together; the row-wise reductions (P2 / Q1: r_t values per task and row) go through a halving butterfly inside the wave (17 shuffles
 // for 16 values) and a small double-buffered LDS table across the waves, one barrier per HID_RB rows.
 
-#include "common.h"
+#include "dispatch.h"
 #include "internal.h"
 #include "hid_params.h"
 #include <atomic>
@@ -856,22 +856,18 @@ void hid_go(const HidLaunch& L, const HidParams& q, hipStream_t s) {
 
 MTL_INTERNAL void mtli_hid_launch(const HidLaunch* L, const HidParams* q, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (L->dtype == MTLORA_F16)
-        hid_go<f16>(*L, *q, s);
-    else
-        hid_go<bf16>(*L, *q, s);
+    mtl_dispatch_dtype16(L->dtype, [&](auto t) { hid_go<typename decltype(t)::type>(*L, *q, s); });
 }
 MTL_INTERNAL void mtli_hid_rows_finish(int dtype, const float* rowpart, int n_chunk, int64_t M, int nt, const float* alpha, const int* off,
                                        void* out, int ldo, void* stream) {
     HidOff o;
     for (int i = 0; i < HID_TG; ++i) o.v[i] = off[i];
     const unsigned blocks = (unsigned)((M * nt + 255) / 256);
-    if (dtype == MTLORA_F16)
-        hipLaunchKernelGGL(k_hid_rows_finish<f16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rowpart, n_chunk, M, nt, alpha, o,
-                           reinterpret_cast<f16*>(out), ldo);
-    else
-        hipLaunchKernelGGL(k_hid_rows_finish<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rowpart, n_chunk, M, nt, alpha, o,
-                           reinterpret_cast<bf16*>(out), ldo);
+    mtl_dispatch_dtype16(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(k_hid_rows_finish<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rowpart, n_chunk, M, nt, alpha, o,
+                           reinterpret_cast<T*>(out), ldo);
+    });
 }
 MTL_INTERNAL void mtli_hid_reduce(const HidRedParams* r, int64_t per, void* stream) {
     hipLaunchKernelGGL(k_hid_reduce, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *r);

@@ -12,6 +12,9 @@
 
 #define MTL_INTERNAL extern "C" __attribute__((visibility("hidden")))
 
+// bytes per element; here and not in common.h so that block.hip, which has no kernels, need not include the device helpers
+static inline int mtl_elem_size(int dtype) { return dtype == MTLORA_F32 ? 4 : 2; }  // bf16 and f16: 2
+
 MTL_INTERNAL int mtli_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx,
                                     float* dgamma, float* dbeta, int64_t M, int64_t C, int x_dtype, int dy_dtype, void* scratch,
                                     int64_t scratch_bytes, const void* dx_addend, int phase, void* stream);

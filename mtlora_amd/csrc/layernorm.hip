@@ -7,9 +7,7 @@
 //   plan       ln_plan_fwd / ln_plan_bwd: LPR, vectors per lane, grid and LDS bytes from (M, C, x dtype); the scratch-size queries
 //              are derived from ln_plan_bwd, so size and launch cannot disagree
 //   launch     ln_run_fwd / ln_run_bwd through ln_dispatch, the one dtype x LPR x MAXV ladder
-#include <initializer_list>
-#include <type_traits>
-
+#include "dispatch.h"
 #include "ln.h"
 
 namespace {
@@ -33,7 +31,7 @@ int ln_grid(int64_t M, int lpr, int cap = 256 * 4, int unr = 1) {
 int ln_merge(LnParams& p, int64_t M, int64_t C, int xdt, int mh, int mw) {
     p.mg_H = p.mg_W = 0;
     if (mh == 0 && mw == 0) return MTLORA_OK;
-    const int ve = xdt == MTLORA_F32 ? 4 : 8;
+    const int ve = mtl_vec_elems(xdt);
     if (mh <= 0 || mw <= 0 || (mh & 1) || (mw & 1) || C % 4 || (C / 4) % ve) return MTLORA_ERR_SHAPE;
     if (M % ((int64_t)(mh / 2) * (mw / 2))) return MTLORA_ERR_SHAPE;
     p.mg_H = mh;
@@ -42,46 +40,14 @@ int ln_merge(LnParams& p, int64_t M, int64_t C, int xdt, int mh, int mw) {
 }
 
 int ln_check(int64_t M, int64_t C, int xdt, int ydt) {
-    if (xdt < MTLORA_F32 || xdt > MTLORA_F16 || ydt < MTLORA_F32 || ydt > MTLORA_F16) return MTLORA_ERR_DTYPE;
-    if (xdt != MTLORA_F32 && ydt != MTLORA_F32 && xdt != ydt) return MTLORA_ERR_DTYPE;  // (bf16 <-> fp16 mixes: none)
-    const int ve = xdt == MTLORA_F32 ? 4 : 8;
+    if (!mtl_dtype_pair_ok(xdt, ydt)) return MTLORA_ERR_DTYPE;  // (bf16 <-> fp16 mixes: none)
+    const int ve = mtl_vec_elems(xdt);
     if (M < 0 || C <= 0 || C % ve) return MTLORA_ERR_SHAPE;
     if (mtl_ceil_div(C / ve, 64) > LN_MAXV) return MTLORA_ERR_UNSUPPORTED;
     return MTLORA_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// validation: single pointers and per-stream arrays (arrays[j][k], k < n) go through the same helper
-// ------------------------------------------------------------------------------------------------
-using Ptrs = std::initializer_list<const void*>;
-using Arrs = std::initializer_list<const void* const*>;
-template <typename T>
-const void* const* arr(T* const* a) {
-    return reinterpret_cast<const void* const*>(a);
-}
-
 bool ln_n_bad(int n) { return n < 1 || n > LN_MAXN; }
-
-// every pointer, every array and every array element is required
-bool ln_null(Ptrs one, int n = 0, Arrs per = {}) {
-    for (const void* q : one)
-        if (!q) return true;
-    for (const void* const* a : per) {
-        if (!a) return true;
-        for (int k = 0; k < n; ++k)
-            if (!a[k]) return true;
-    }
-    return false;
-}
-
-// optional pointers / arrays / elements may be null (0 is aligned)
-bool ln_misaligned(Ptrs one, int n = 0, Arrs per = {}) {
-    uintptr_t bits = 0;
-    for (const void* q : one) bits |= (uintptr_t)q;
-    for (const void* const* a : per)
-        for (int k = 0; a && k < n; ++k) bits |= (uintptr_t)a[k];
-    return (bits & 15u) != 0;
-}
 
 bool ln_samples_bad(int64_t M, int64_t B) { return B <= 0 || M % B; }
 
@@ -96,7 +62,7 @@ struct LnPlan {
 };
 
 LnPlan ln_plan_row(int64_t C, int xdt) {
-    const int nvec = (int)(C / (xdt == MTLORA_F32 ? 4 : 8));
+    const int nvec = (int)(C / mtl_vec_elems(xdt));
     LnPlan pl = {};
     pl.lpr = pick_lpr(nvec);
     pl.vpl = (nvec + pl.lpr - 1) / pl.lpr;
@@ -121,50 +87,24 @@ LnPlan ln_plan_bwd(int64_t M, int64_t C, int xdt) {
 // bytes of the [n][grid_x][2][C] fp32 partials the backward kernels write and k_ln_reduce reads
 int64_t ln_part_bytes(int64_t M, int64_t C, int xdt, int n = 1) { return (int64_t)ln_plan_bwd(M, C, xdt).grid_x * 2 * C * 4 * n; }
 
-// ------------------------------------------------------------------------------------------------
-// the ladder: f(Tag<TX>, Tag<TO>, integral_constant LPR, integral_constant MAXV) for the seven dtype pairs (fp32 / fp32, and fp32
-// on either side or neither for fp16 and bf16), the four LPR and MAXV 3 / LN_MAXV
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-struct Tag {
-    using type = T;
-};
-template <int V>
-using Int = std::integral_constant<int, V>;
-
+// the ladder: f(MtlTag<TX>, MtlTag<TO>, MtlInt<LPR>, MtlInt<MAXV>) for the seven dtype pairs of mtl_dispatch_dtype_pair, the four LPR
+// and MAXV 3 / LN_MAXV
 template <typename F>
 void ln_dispatch(int xdt, int odt, const LnPlan& pl, F&& f) {
-    auto rows = [&](auto tx, auto to) {
+    mtl_dispatch_dtype_pair(xdt, odt, [&](auto tx, auto to) {
         auto maxv = [&](auto lpr) {
             if (pl.vpl <= 3)
-                f(tx, to, lpr, Int<3>{});
+                f(tx, to, lpr, MtlInt<3>{});
             else
-                f(tx, to, lpr, Int<LN_MAXV>{});
+                f(tx, to, lpr, MtlInt<LN_MAXV>{});
         };
         switch (pl.lpr) {
-            case 8: maxv(Int<8>{}); break;
-            case 16: maxv(Int<16>{}); break;
-            case 32: maxv(Int<32>{}); break;
-            default: maxv(Int<64>{}); break;
+            case 8: maxv(MtlInt<8>{}); break;
+            case 16: maxv(MtlInt<16>{}); break;
+            case 32: maxv(MtlInt<32>{}); break;
+            default: maxv(MtlInt<64>{}); break;
         }
-    };
-    if (xdt == MTLORA_F32 && odt == MTLORA_F32) {
-        rows(Tag<float>{}, Tag<float>{});
-    } else if (xdt == MTLORA_F16 || odt == MTLORA_F16) {  // fp16 autocast (the reference's default, main.py:341)
-        if (xdt == MTLORA_F32) {
-            rows(Tag<float>{}, Tag<f16>{});
-        } else if (odt == MTLORA_F32) {
-            rows(Tag<f16>{}, Tag<float>{});
-        } else {
-            rows(Tag<f16>{}, Tag<f16>{});
-        }
-    } else if (xdt == MTLORA_F32) {
-        rows(Tag<float>{}, Tag<bf16>{});
-    } else if (odt == MTLORA_F32) {
-        rows(Tag<bf16>{}, Tag<float>{});
-    } else {
-        rows(Tag<bf16>{}, Tag<bf16>{});
-    }
+    });
 }
 
 // k_ln_fwd over (grid_x, ny) workgroups; res: the fused-residual instances.  prof_bytes: the entry's profiler byte figure
@@ -225,8 +165,8 @@ int ln_fwd(const void* x, const float* gamma, const float* beta, void* y, float*
            void* stream) {
     int st = ln_check(M, C, x_dtype, y_dtype);
     if (st != MTLORA_OK) return st;
-    if (ln_null({x, gamma, beta, y, mean, rstd})) return MTLORA_ERR_NULL;
-    if (ln_misaligned({x, y, branch, x_new})) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({x, gamma, beta, y, mean, rstd})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({x, y, branch, x_new})) return MTLORA_ERR_ALIGN;
     if (branch && ln_samples_bad(M, B)) return MTLORA_ERR_SHAPE;
     if (M == 0) return MTLORA_OK;
     LnParams p = {};
@@ -256,8 +196,8 @@ int ln_bwd(const void* dy, const void* x, const float* gamma, const float* mean,
            int merge_h, int merge_w, void* d_branch, const float* scale, int64_t B, void* stream, int phase = 0) {
     int st = ln_check(M, C, x_dtype, dy_dtype);
     if (st != MTLORA_OK) return st;
-    if (ln_null({dy, x, gamma, mean, rstd, dx, dgamma, dbeta, scratch})) return MTLORA_ERR_NULL;
-    if (ln_misaligned({x, dy, dx, scratch, dx_addend, d_branch})) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({dy, x, gamma, mean, rstd, dx, dgamma, dbeta, scratch})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({x, dy, dx, scratch, dx_addend, d_branch})) return MTLORA_ERR_ALIGN;
     if (d_branch && ln_samples_bad(M, B)) return MTLORA_ERR_SHAPE;
     if (scratch_bytes < ln_part_bytes(M, C, x_dtype)) return MTLORA_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -292,9 +232,9 @@ int ln_streams_fwd(int n, const void* const* x, const float* gamma, const float*
     int st = ln_check(M, C, x_dtype, y_dtype);
     if (st != MTLORA_OK) return st;
     if (ln_n_bad(n)) return MTLORA_ERR_SHAPE;
-    if (ln_null({gamma, beta}, n, {x, arr(y), arr(mean), arr(rstd)})) return MTLORA_ERR_NULL;
-    if (branch && ln_null({}, n, {branch, arr(x_new)})) return MTLORA_ERR_NULL;
-    if (ln_misaligned({}, n, {x, arr(y), branch, arr(x_new)})) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({gamma, beta}, n, {x, mtl_arr(y), mtl_arr(mean), mtl_arr(rstd)})) return MTLORA_ERR_NULL;
+    if (branch && mtl_any_null({}, n, {branch, mtl_arr(x_new)})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({}, n, {x, mtl_arr(y), branch, mtl_arr(x_new)})) return MTLORA_ERR_ALIGN;
     if (branch && ln_samples_bad(M, B)) return MTLORA_ERR_SHAPE;
     if (M == 0) return MTLORA_OK;
     LnParams p = {};
@@ -339,8 +279,8 @@ int ln_streams_bwd(int n, const void* const* dy, const void* const* x, const flo
     int st = ln_check(M, C, x_dtype, dy_dtype);
     if (st != MTLORA_OK) return st;
     if (ln_n_bad(n)) return MTLORA_ERR_SHAPE;
-    if (ln_null({gamma, dgamma, dbeta, scratch}, n, {dy, x, arr(mean), arr(rstd), arr(dx)})) return MTLORA_ERR_NULL;
-    if (ln_misaligned({scratch}, n, {dy, x, arr(dx), dx_addend, arr(d_branch)})) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({gamma, dgamma, dbeta, scratch}, n, {dy, x, mtl_arr(mean), mtl_arr(rstd), mtl_arr(dx)})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({scratch}, n, {dy, x, mtl_arr(dx), dx_addend, mtl_arr(d_branch)})) return MTLORA_ERR_ALIGN;
     if (d_branch && ln_samples_bad(M, B)) return MTLORA_ERR_SHAPE;
     if (scratch_bytes < ln_part_bytes(M, C, x_dtype, n)) return MTLORA_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -482,8 +422,8 @@ int mtlora_residual_layernorm_multi_fwd(int n, const void* shortcut, const void*
     int st = ln_check(M, C, x_dtype, y_dtype);
     if (st != MTLORA_OK) return st;
     if (ln_n_bad(n)) return MTLORA_ERR_SHAPE;
-    if (ln_null({shortcut, gamma, beta}, n, {branch, arr(x_new), arr(y), arr(mean), arr(rstd)})) return MTLORA_ERR_NULL;
-    if (ln_misaligned({shortcut}, n, {branch, arr(x_new), arr(y)})) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({shortcut, gamma, beta}, n, {branch, mtl_arr(x_new), mtl_arr(y), mtl_arr(mean), mtl_arr(rstd)})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({shortcut}, n, {branch, mtl_arr(x_new), mtl_arr(y)})) return MTLORA_ERR_ALIGN;
     if (ln_samples_bad(M, B)) return MTLORA_ERR_SHAPE;
     if (M == 0) return MTLORA_OK;
     LnParams p = {};
@@ -523,8 +463,8 @@ int mtlora_residual_layernorm_multi_bwd(int n, const void* const* dy, const void
     int st = ln_check(M, C, x_dtype, dy_dtype);
     if (st != MTLORA_OK) return st;
     if (ln_n_bad(n)) return MTLORA_ERR_SHAPE;
-    if (ln_null({gamma, d_shortcut, dgamma, dbeta, scratch}, n, {dy, x_new, arr(mean), arr(rstd)})) return MTLORA_ERR_NULL;
-    if (ln_misaligned({d_shortcut, scratch}, n, {dy, x_new, dx_addend, arr(d_branch)})) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({gamma, d_shortcut, dgamma, dbeta, scratch}, n, {dy, x_new, mtl_arr(mean), mtl_arr(rstd)})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({d_shortcut, scratch}, n, {dy, x_new, dx_addend, mtl_arr(d_branch)})) return MTLORA_ERR_ALIGN;
     if (ln_samples_bad(M, B)) return MTLORA_ERR_SHAPE;
     if (scratch_bytes < ln_part_bytes(M, C, x_dtype)) return MTLORA_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;

@@ -43,7 +43,7 @@
 #include <atomic>
 #include <type_traits>
 
-#include "common.h"
+#include "dispatch.h"
 #include "internal.h"
 #include "hid_params.h"
 #include "nt.h"
@@ -110,11 +110,11 @@ static CtxLayout ctx_layout(const mtlora_linear_desc* d, const Segs& s) {
 // ------------------------------------------------------------------------------------------------
 static int check_desc(const mtlora_linear_desc* d) {
     if (!d) return MTLORA_ERR_NULL;
-    if (d->dtype != MTLORA_F32 && d->dtype != MTLORA_BF16 && d->dtype != MTLORA_F16) return MTLORA_ERR_DTYPE;
+    if (!mtl_dtype_in(d->dtype, MTL_DT_ALL)) return MTLORA_ERR_DTYPE;
     if (d->M < 0 || d->K <= 0 || d->N <= 0 || d->T < 0 || d->T > MTLORA_MAX_TASKS || d->r_s < 0)
         return MTLORA_ERR_SHAPE;
     if (d->M >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
-    const int vec = d->dtype == MTLORA_F32 ? 4 : 8;
+    const int vec = mtl_vec_elems(d->dtype);
     if (d->K % vec || d->N % vec) return MTLORA_ERR_ALIGN;
     for (int t = 0; t < d->T; ++t)
         if (d->r_t[t] <= 0) return MTLORA_ERR_SHAPE;
@@ -1685,7 +1685,7 @@ static int hid_check(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2)
     if (st != MTLORA_OK) return st;
     st = check_desc(d2);
     if (st != MTLORA_OK) return st;
-    if (d1->dtype == MTLORA_F32 || d1->dtype != d2->dtype) return MTLORA_ERR_UNSUPPORTED;
+    if (!mtl_dtype_in(d1->dtype, MTL_DT_16) || d1->dtype != d2->dtype) return MTLORA_ERR_UNSUPPORTED;
     if (d1->M != d2->M || d1->N != d2->K || d1->T != d2->T || d1->T < 1) return MTLORA_ERR_UNSUPPORTED;
     if (d1->mode != 0 || d2->mode != 0 || !d1->has_x_tasks || !d2->has_x_tasks) return MTLORA_ERR_UNSUPPORTED;
     if (d1->N % 128 != 0 || d1->M <= 0) return MTLORA_ERR_UNSUPPORTED;
@@ -1960,8 +1960,7 @@ int mtlora_mlp_hid_proj(const mtlora_linear_desc* d1, const mtlora_linear_desc* 
         return MTLORA_ERR_ALIGN;
     if (scratch_bytes < hid_fwd_scratch_bytes(d1, d2)) return MTLORA_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int r = d1->dtype == MTLORA_F16 ? hid_proj_impl<f16>(d1, d2, h_base, ctx1, ctx2, scratch, s)
-                                          : hid_proj_impl<bf16>(d1, d2, h_base, ctx1, ctx2, scratch, s);
+    const int r = mtl_dispatch_dtype16(d1->dtype, [&](auto t) { return hid_proj_impl<typename decltype(t)::type>(d1, d2, h_base, ctx1, ctx2, scratch, s); });
     if (r != MTLORA_OK) return r;
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
@@ -1979,8 +1978,9 @@ int mtlora_mlp_hid_bwd(const mtlora_linear_desc* d1, const mtlora_linear_desc* d
         return MTLORA_ERR_ALIGN;
     if (part_bytes < hid_bwd_part_bytes(d1, d2)) return MTLORA_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int r = d1->dtype == MTLORA_F16 ? hid_bwd_impl<f16>(d1, d2, h_base, dh_s, ctx1, ctx2, scratch2, scratch1, g, dB1_t, dA2_t, part, s)
-                                          : hid_bwd_impl<bf16>(d1, d2, h_base, dh_s, ctx1, ctx2, scratch2, scratch1, g, dB1_t, dA2_t, part, s);
+    const int r = mtl_dispatch_dtype16(d1->dtype, [&](auto t) {
+        return hid_bwd_impl<typename decltype(t)::type>(d1, d2, h_base, dh_s, ctx1, ctx2, scratch2, scratch1, g, dB1_t, dA2_t, part, s);
+    });
     if (r != MTLORA_OK) return r;
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
@@ -2008,11 +2008,10 @@ static int pack_check(const mtlora_linear_desc* d, const float* A_s, const float
                       const void* packed, int64_t packed_bytes) {
     const int st = check_desc(d);
     if (st != MTLORA_OK) return st;
-    if (!packed) return MTLORA_ERR_NULL;
-    if (misaligned(packed)) return MTLORA_ERR_ALIGN;
-    if (d->r_s > 0 && (!A_s || !B_s)) return MTLORA_ERR_NULL;
-    for (int t = 0; t < d->T; ++t)
-        if (!A_t || !B_t || !A_t[t] || !B_t[t]) return MTLORA_ERR_NULL;
+    if (mtl_any_null({packed})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({packed})) return MTLORA_ERR_ALIGN;
+    if (d->r_s > 0 && mtl_any_null({A_s, B_s})) return MTLORA_ERR_NULL;
+    if (d->T > 0 && mtl_any_null({}, d->T, {mtl_arr(A_t), mtl_arr(B_t)})) return MTLORA_ERR_NULL;
     const Segs sg = make_segs(d);
     if (packed_bytes < ctx_layout(d, sg).pack_total) return MTLORA_ERR_WORKSPACE;
     return MTLORA_OK;
@@ -2027,12 +2026,7 @@ int mtlora_linear_pack(const mtlora_linear_desc* d, const float* A_s, const floa
     const CtxLayout L = ctx_layout(d, sg);
     unsigned char* pk = reinterpret_cast<unsigned char*>(packed);
     hipStream_t s = (hipStream_t)stream;
-    if (d->dtype == MTLORA_F32)
-        launch_pack<float>(d, sg, L, pk, A_s, B_s, A_t, B_t, s);
-    else if (d->dtype == MTLORA_F16)
-        launch_pack<f16>(d, sg, L, pk, A_s, B_s, A_t, B_t, s);
-    else
-        launch_pack<bf16>(d, sg, L, pk, A_s, B_s, A_t, B_t, s);
+    mtl_dispatch_dtype(d->dtype, [&](auto t) { launch_pack<typename decltype(t)::type>(d, sg, L, pk, A_s, B_s, A_t, B_t, s); });
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }
@@ -2058,21 +2052,16 @@ int mtlora_linear_pack_entry(const mtlora_linear_desc* d, const float* A_s, cons
 }
 
 int mtlora_linear_pack_table(const void* table_dev, int n_entries, int dtype, void* stream) {
-    if (dtype != MTLORA_F32 && dtype != MTLORA_BF16 && dtype != MTLORA_F16) return MTLORA_ERR_DTYPE;
+    if (!mtl_dtype_in(dtype, MTL_DT_ALL)) return MTLORA_ERR_DTYPE;
     if (n_entries < 0 || n_entries > 65535) return MTLORA_ERR_SHAPE;
     if (n_entries == 0) return MTLORA_OK;
-    if (!table_dev) return MTLORA_ERR_NULL;
-    if (((uintptr_t)table_dev & 7u) != 0) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({table_dev})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({table_dev}, 0, {}, 8)) return MTLORA_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
     const PackEntry* tb = reinterpret_cast<const PackEntry*>(table_dev);
     MtlProfScope prof(PK_PACK, 0.0, s);
     const dim3 g(256, (unsigned)n_entries);  // up to 256 workgroups per layer walk its 20 - 800 tiles (the others leave at once)
-    if (dtype == MTLORA_F32)
-        hipLaunchKernelGGL(k_pack_table<float>, g, dim3(256), 0, s, tb);
-    else if (dtype == MTLORA_F16)
-        hipLaunchKernelGGL(k_pack_table<f16>, g, dim3(256), 0, s, tb);
-    else
-        hipLaunchKernelGGL(k_pack_table<bf16>, g, dim3(256), 0, s, tb);
+    mtl_dispatch_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(k_pack_table<typename decltype(t)::type>, g, dim3(256), 0, s, tb); });
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }
@@ -2105,12 +2094,9 @@ static int linear_fwd_entry(const mtlora_linear_desc* d, const void* x, const vo
     }
     if (d->M == 0) return MTLORA_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (d->dtype == MTLORA_F32)
-        st = fwd_impl<float>(d, x, x_t, W, bias, A_s, B_s, A_t, B_t, y_s, y_t, ctx, s, a_s, a_t);
-    else if (d->dtype == MTLORA_F16)
-        st = fwd_impl<f16>(d, x, x_t, W, bias, A_s, B_s, A_t, B_t, y_s, y_t, ctx, s, a_s, a_t);
-    else
-        st = fwd_impl<bf16>(d, x, x_t, W, bias, A_s, B_s, A_t, B_t, y_s, y_t, ctx, s, a_s, a_t);
+    st = mtl_dispatch_dtype(d->dtype, [&](auto t) {
+        return fwd_impl<typename decltype(t)::type>(d, x, x_t, W, bias, A_s, B_s, A_t, B_t, y_s, y_t, ctx, s, a_s, a_t);
+    });
     if (st != MTLORA_OK) return st;
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
@@ -2162,12 +2148,9 @@ static int linear_bwd_entry(const mtlora_linear_desc* d, const void* x, const vo
     }
     if (d->M == 0) return MTLORA_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (d->dtype == MTLORA_F32)
-        st = bwd_impl<float>(d, x, x_t, Wt, dy_s, dy_t, ctx, dx, dx_t, dA_s, dB_s, dA_t, dB_t, scratch, s, gate_s, gate_t);
-    else if (d->dtype == MTLORA_F16)
-        st = bwd_impl<f16>(d, x, x_t, Wt, dy_s, dy_t, ctx, dx, dx_t, dA_s, dB_s, dA_t, dB_t, scratch, s, gate_s, gate_t);
-    else
-        st = bwd_impl<bf16>(d, x, x_t, Wt, dy_s, dy_t, ctx, dx, dx_t, dA_s, dB_s, dA_t, dB_t, scratch, s, gate_s, gate_t);
+    st = mtl_dispatch_dtype(d->dtype, [&](auto t) {
+        return bwd_impl<typename decltype(t)::type>(d, x, x_t, Wt, dy_s, dy_t, ctx, dx, dx_t, dA_s, dB_s, dA_t, dB_t, scratch, s, gate_s, gate_t);
+    });
     if (st != MTLORA_OK) return st;
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
@@ -2221,13 +2204,13 @@ int64_t mtlora_gemm_tn_scratch_bytes(int64_t M, int Na, int Nb) {
 
 int mtlora_gemm_tn(const void* a, const void* b, float* out, int64_t M, int Na, int Nb, int64_t lda, int64_t ldb,
                    int dtype, void* scratch, int64_t scratch_bytes, void* stream) {
-    if (dtype != MTLORA_F32 && dtype != MTLORA_BF16 && dtype != MTLORA_F16) return MTLORA_ERR_DTYPE;
-    const int vec = dtype == MTLORA_F32 ? 4 : 8;
+    if (!mtl_dtype_in(dtype, MTL_DT_ALL)) return MTLORA_ERR_DTYPE;
+    const int vec = mtl_vec_elems(dtype);
     if (M < 0 || M >= ((int64_t)1 << 31) || Na <= 0 || Nb <= 0 || lda < Na || ldb < Nb) return MTLORA_ERR_SHAPE;
     if (Na % vec || Nb % vec || lda % vec || ldb % vec) return MTLORA_ERR_ALIGN;
     if (Na > 1024) return MTLORA_ERR_UNSUPPORTED;  // narrow side only (every a-tile re-reads b)
-    if (!out || !scratch || (M > 0 && (!a || !b))) return MTLORA_ERR_NULL;
-    if (misaligned(a) || misaligned(b) || misaligned(scratch) || ((uintptr_t)out & 3u)) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({out, scratch}) || (M > 0 && mtl_any_null({a, b}))) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({a, b, scratch}) || mtl_any_misaligned({out}, 0, {}, 4)) return MTLORA_ERR_ALIGN;
     if (scratch_bytes < mtlora_gemm_tn_scratch_bytes(M, Na, Nb) - 256) return MTLORA_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     if (M == 0) {
@@ -2262,12 +2245,9 @@ int mtlora_gemm_tn(const void* a, const void* b, float* out, int64_t M, int Na, 
     {
         mtl_prof_tag("M%lld Na%d Nb%d", (long long)M, Na, Nb);
         MtlProfScope prof(PK_TN_PLAIN, (double)es * M * ((double)ta * Nb + Na), s, 0.0, 2.0 * M * (double)Na * Nb);
-        if (dtype == MTLORA_F32)
-            hipLaunchKernelGGL(k_tn<float>, dim3((unsigned)tp.nsplit, (unsigned)(ta * tb), 1), dim3(256), 0, s, tp);
-        else if (dtype == MTLORA_F16)
-            hipLaunchKernelGGL(k_tn<f16>, dim3((unsigned)tp.nsplit, (unsigned)(ta * tb), 1), dim3(256), 0, s, tp);
-        else
-            hipLaunchKernelGGL(k_tn<bf16>, dim3((unsigned)tp.nsplit, (unsigned)(ta * tb), 1), dim3(256), 0, s, tp);
+        mtl_dispatch_dtype(dtype, [&](auto t) {
+            hipLaunchKernelGGL(k_tn<typename decltype(t)::type>, dim3((unsigned)tp.nsplit, (unsigned)(ta * tb), 1), dim3(256), 0, s, tp);
+        });
     }
     MtlProfScope prof(PK_REDUCE, 0.0, s);
     hipLaunchKernelGGL(k_tn_reduce, dim3(TN_TILE / 1024, (unsigned)(ta * tb), 1), dim3(256 * TN_RG), 0, s, tp);

@@ -31,7 +31,7 @@
 //   kind 3  DepthLoss l1           (:132-148)                   |up - label| over label != ignore, mean over valid pixels
 // (the per-pixel formulas live in up_pixel.h, shared with metrics.hip)
 // Label-only statistics (valid count, mask sum, w) come from the caller (they do not depend on the prediction).
-#include "common.h"
+#include "dispatch.h"
 #include "up_pixel.h"
 
 namespace {
@@ -298,9 +298,9 @@ int64_t mtlora_upsample_loss_partials(int64_t B, int h, int w, int scale) {
 int mtlora_upsample_loss(int kind, const void* low, const float* label, const float* stat, void* dlow, float* partials,
                          int64_t B, int h, int w, int C, int scale, int dtype, float ignore_index, void* stream) {
     if (B < 0 || h <= 0 || w <= 0 || C <= 0 || scale <= 0) return MTLORA_ERR_SHAPE;
-    if (dtype != MTLORA_F32 && dtype != MTLORA_BF16) return MTLORA_ERR_DTYPE;
+    if (!mtl_dtype_in(dtype, MTL_DT_F32_BF16)) return MTLORA_ERR_DTYPE;
     if (B == 0) return MTLORA_OK;
-    if (!low || !label || !stat || !dlow || !partials) return MTLORA_ERR_NULL;
+    if (mtl_any_null({low, label, stat, dlow, partials})) return MTLORA_ERR_NULL;
     if (scale > 32) return MTLORA_ERR_UNSUPPORTED;
     const int64_t blocks = mtlora_upsample_loss_partials(B, h, w, scale);
     if (blocks >= ((int64_t)1 << 31) || (int64_t)h * scale * (int64_t)w * scale >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
@@ -319,7 +319,7 @@ int mtlora_upsample_loss(int kind, const void* low, const float* label, const fl
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     MtlProfScope prof(PK_LOSS, (double)B * h * w * C * 2.0 * mtl_elem_size(dtype) +
                                    (double)B * h * scale * w * scale * 4.0 * (kind == 1 ? C : 1), s);
-    const int rc = dtype == MTLORA_F32 ? dispatch_up<float>(kind, p, blocks, s) : dispatch_up<bf16>(kind, p, blocks, s);
+    const int rc = mtl_dispatch_f32_bf16(dtype, [&](auto t) { return dispatch_up<typename decltype(t)::type>(kind, p, blocks, s); });
     if (rc != MTLORA_OK) return rc;
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;

@@ -36,7 +36,7 @@
 //                         sum (log gt - log p)^2 over label != ignore (eval_depth.py:71-89)
 //   kind 4  edge          floats: loss (kind 2's formula with the constant stat[0]), and the meter's value, which is the same
 //                         formula applied to q (eval_edge.py:31-37 feeds the PROCESSED prediction to the loss)
-#include "common.h"
+#include "dispatch.h"
 #include "up_pixel.h"
 
 namespace {
@@ -444,9 +444,9 @@ int mtlora_upsample_metrics(int kind, const void* low, const float* label, const
     int64_t ni = 0, nfp = 0;
     const int rc0 = mtlora_upsample_metrics_sizes(kind, B, h, w, C, scale, &ni, &nfp);
     if (rc0 != MTLORA_OK) return rc0;
-    if (dtype != MTLORA_F32 && dtype != MTLORA_BF16) return MTLORA_ERR_DTYPE;
+    if (!mtl_dtype_in(dtype, MTL_DT_F32_BF16)) return MTLORA_ERR_DTYPE;
     if (B == 0) return MTLORA_OK;
-    if (!low || !label || !stat || !fpartials || (ni > 0 && !counts)) return MTLORA_ERR_NULL;
+    if (mtl_any_null({low, label, stat, fpartials}) || (ni > 0 && !counts)) return MTLORA_ERR_NULL;
     const int64_t tiles = met_tiles(kind, B, h, w, C, scale);
     if (tiles >= ((int64_t)1 << 31) || (int64_t)h * scale * (int64_t)w * scale >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
     UpMetParams p;
@@ -466,7 +466,7 @@ int mtlora_upsample_metrics(int kind, const void* low, const float* label, const
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     MtlProfScope prof(PK_LOSS, (double)B * h * w * C * mtl_elem_size(dtype) +
                                    (double)B * h * scale * w * scale * 4.0 * (kind == 1 ? C : 1), s);
-    const int rc = dtype == MTLORA_F32 ? dispatch_met<float>(kind, p, s) : dispatch_met<bf16>(kind, p, s);
+    const int rc = mtl_dispatch_f32_bf16(dtype, [&](auto t) { return dispatch_met<typename decltype(t)::type>(kind, p, s); });
     if (rc != MTLORA_OK) return rc;
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;

@@ -30,7 +30,7 @@
 //   kind 2  sigmoid    255 / (1 + exp(-up)), C = 1; fp32 or uint8 (B, H, W)
 //   kind 3  identity   up, C = 1; fp32 (B, H, W, 1)
 // uint8 is the fp32 value truncated, as tensor.to(torch.uint8) does for values in [0, 255].
-#include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -256,10 +256,10 @@ int mtlora_upsample_predict(int kind, const void* low, void* out, int64_t B, int
     const int tr = pred_tr(C, scale, px_bytes);
     const size_t lds = pred_lds_bytes(C, scale, tr, px_bytes);
     if (lds > 64 * 1024) return MTLORA_ERR_UNSUPPORTED;
-    if (dtype != MTLORA_F32 && dtype != MTLORA_BF16 && dtype != MTLORA_F16) return MTLORA_ERR_DTYPE;
+    if (!mtl_dtype_in(dtype, MTL_DT_ALL)) return MTLORA_ERR_DTYPE;
     if (B == 0) return MTLORA_OK;
-    if (!low || !out) return MTLORA_ERR_NULL;
-    if (!u8 && (reinterpret_cast<uintptr_t>(out) & 3)) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({low, out})) return MTLORA_ERR_NULL;
+    if (!u8 && mtl_any_misaligned({out}, 0, {}, 4)) return MTLORA_ERR_ALIGN;
     const int tq = 64 / scale;
     const int64_t tiles = B * (int64_t)((h + tr - 1) / tr) * ((w + tq - 1) / tq);
     if (tiles >= ((int64_t)1 << 31) || (int64_t)h * scale * (int64_t)w * scale >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
@@ -277,12 +277,7 @@ int mtlora_upsample_predict(int kind, const void* low, void* out, int64_t B, int
     p.tiles = (int)tiles;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     MtlProfScope prof(PK_UPSAMPLE, (double)B * h * w * C * mtl_elem_size(dtype) + (double)B * h * scale * w * scale * px_bytes, s);
-    if (dtype == MTLORA_F32)
-        dispatch_pred<float>(kind, u8, p, lds, s);
-    else if (dtype == MTLORA_BF16)
-        dispatch_pred<bf16>(kind, u8, p, lds, s);
-    else
-        dispatch_pred<f16>(kind, u8, p, lds, s);
+    mtl_dispatch_dtype(dtype, [&](auto t) { dispatch_pred<typename decltype(t)::type>(kind, u8, p, lds, s); });
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }

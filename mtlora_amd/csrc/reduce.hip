@@ -8,7 +8,7 @@
 //                                                                  (dL/db of reference models/seg_hrnet.py:498-526 layers)
 //   mtlora_label_stat   kind 0: #{ lab != ignore }                 valid-pixel count / mask sum of mtl_loss_schemes.py:22-39,
 //                       kind 1: mean(1 - (lab >= 0.5))             :162-220; class balance w of :42-89
-#include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -133,11 +133,11 @@ int64_t mtlora_colsum_scratch_bytes(int64_t M, int64_t N) {
 }
 
 int mtlora_colsum(const void* x, int64_t M, int64_t N, int dtype, float* out, void* scratch, int64_t scratch_bytes, void* stream) {
-    if (dtype != MTLORA_F32 && dtype != MTLORA_BF16) return MTLORA_ERR_DTYPE;
-    const int ve = dtype == MTLORA_F32 ? 4 : 8;
+    if (!mtl_dtype_in(dtype, MTL_DT_F32_BF16)) return MTLORA_ERR_DTYPE;
+    const int ve = mtl_vec_elems(dtype);
     if (M < 0 || N <= 0 || N % ve || N > (1 << 20)) return MTLORA_ERR_SHAPE;
-    if (!x || !out || !scratch) return MTLORA_ERR_NULL;
-    if (((uintptr_t)x | (uintptr_t)scratch) & 15u) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({x, out, scratch})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({x, scratch})) return MTLORA_ERR_ALIGN;
     if (scratch_bytes < mtlora_colsum_scratch_bytes(M, N)) return MTLORA_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int nvec = (int)(N / ve);
@@ -146,10 +146,10 @@ int mtlora_colsum(const void* x, int64_t M, int64_t N, int dtype, float* out, vo
     if (g > RD_MAXBLK) g = RD_MAXBLK;
     if (g < 1) g = 1;
     float* part = reinterpret_cast<float*>(scratch);
-    if (dtype == MTLORA_F32)
-        hipLaunchKernelGGL(k_colsum_part<float>, dim3((unsigned)g), dim3(256), 0, s, reinterpret_cast<const float*>(x), M, (int)N, part);
-    else
-        hipLaunchKernelGGL(k_colsum_part<bf16>, dim3((unsigned)g), dim3(256), 0, s, reinterpret_cast<const bf16*>(x), M, (int)N, part);
+    mtl_dispatch_f32_bf16(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(k_colsum_part<T>, dim3((unsigned)g), dim3(256), 0, s, reinterpret_cast<const T*>(x), M, (int)N, part);
+    });
     hipLaunchKernelGGL(k_colsum_combine, dim3((unsigned)mtl_ceil_div(N, 64)), dim3(64 * RD_RW), 0, s, (const float*)part, out, (int)g,
                        (int)N, 1.f);
     MTL_CHECK_LAUNCH();
@@ -165,8 +165,8 @@ int mtlora_label_stat(const float* label, int64_t n, int kind, float ignore_inde
                       int64_t scratch_bytes, void* stream) {
     if (kind != 0 && kind != 1) return MTLORA_ERR_UNSUPPORTED;
     if (n <= 0) return MTLORA_ERR_SHAPE;
-    if (!label || !out || !scratch) return MTLORA_ERR_NULL;
-    if ((uintptr_t)label & 15u) return MTLORA_ERR_ALIGN;
+    if (mtl_any_null({label, out, scratch})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({label})) return MTLORA_ERR_ALIGN;
     if (scratch_bytes < mtlora_label_stat_scratch_bytes(n)) return MTLORA_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int g = rd_blocks(n / 4 + 1);

@@ -6,7 +6,7 @@
 // copies disappear.  Backward is the transpose of the interpolation written as a GATHER over the <= (2S)^2 fine pixels
 // that tap a coarse pixel (deterministic; ATen's nhwc backward takes 135 us per map at B = 32).
 // Index / weight arithmetic is PyTorch's area_pixel_compute_source_index (see loss.hip).  4 channels per thread.
-#include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -144,11 +144,10 @@ __global__ __launch_bounds__(256) void k_up_bwd(const UpParams p) {
 
 static int check_up(const void* a, const void* b, int64_t B, int h, int w, int C, int S, int64_t ld, int dtype) {
     if (B < 0 || h <= 0 || w <= 0 || C <= 0 || S <= 0 || ld < C) return MTLORA_ERR_SHAPE;
-    if (dtype != MTLORA_F32 && dtype != MTLORA_BF16 && dtype != MTLORA_F16) return MTLORA_ERR_DTYPE;
+    if (!mtl_dtype_in(dtype, MTL_DT_ALL)) return MTLORA_ERR_DTYPE;
     if (C % 4 || ld % 4) return MTLORA_ERR_ALIGN;
-    if (B > 0 && (!a || !b)) return MTLORA_ERR_NULL;
-    const size_t al = dtype == MTLORA_F32 ? 16 : 8;
-    if (((uintptr_t)a % al) || ((uintptr_t)b % al)) return MTLORA_ERR_ALIGN;
+    if (B > 0 && mtl_any_null({a, b})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({a, b}, 0, {}, dtype == MTLORA_F32 ? 16 : 8)) return MTLORA_ERR_ALIGN;  // (one 4-element vector)
     if (B * (int64_t)h * S * w * S >= ((int64_t)1 << 40)) return MTLORA_ERR_SHAPE;
     return MTLORA_OK;
 }
@@ -167,12 +166,9 @@ int mtlora_upsample_cl_fwd(const void* coarse, void* fine, int64_t B, int h, int
     int64_t blocks = mtl_ceil_div(total, 256);
     if (blocks > 65536) blocks = 65536;
     MtlProfScope prof(PK_UPSAMPLE, (double)mtl_elem_size(dtype) * B * h * w * C * (1.0 + (double)scale * scale), s);
-    if (dtype == MTLORA_F32)
-        hipLaunchKernelGGL(k_up_fwd<float>, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else if (dtype == MTLORA_F16)
-        hipLaunchKernelGGL(k_up_fwd<f16>, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else
-        hipLaunchKernelGGL(k_up_fwd<bf16>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    mtl_dispatch_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_up_fwd<typename decltype(t)::type>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    });
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }
@@ -187,12 +183,9 @@ int mtlora_upsample_cl_bwd(const void* grad_fine, void* grad_coarse, int64_t B, 
     int64_t blocks = mtl_ceil_div(total, 256 / UB);
     if (blocks > 65536) blocks = 65536;
     MtlProfScope prof(PK_UPSAMPLE, (double)mtl_elem_size(dtype) * B * h * w * C * (1.0 + (double)scale * scale), s);
-    if (dtype == MTLORA_F32)
-        hipLaunchKernelGGL(k_up_bwd<float>, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else if (dtype == MTLORA_F16)
-        hipLaunchKernelGGL(k_up_bwd<f16>, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else
-        hipLaunchKernelGGL(k_up_bwd<bf16>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    mtl_dispatch_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_up_bwd<typename decltype(t)::type>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    });
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }

@@ -178,6 +178,36 @@ def test_layernorm_host_matches_fixture(built_lib):
     assert {k.split(":")[0] for k in keys} == {e for e in _lib.EXPORTS if "layernorm" in e and not e.endswith("_bytes")}
 
 
+def test_host_rejects_match_fixture(built_lib):
+    """the return code of every entry whose host code selects types and checks arguments through csrc/dispatch.h, for every call of
+    make_golden_host_rejects.reject_table() (one defect per call, rejected on the host; calls without work return OK without a
+    launch), equals tests/golden/host_rejects.json, recorded from the library before those entries moved to the shared helpers."""
+    import importlib.util
+    import json
+    from mtlora_amd import _lib
+    spec = importlib.util.spec_from_file_location("make_golden_host_rejects",
+                                                  os.path.join(ROOT, "tests", "golden", "make_golden_host_rejects.py"))
+    G = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(G)
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "host_rejects.json")))["reject"]
+    L = _lib.lib()
+    keys = []
+    for key, entry, edits, no_work in G.reject_table():
+        keys.append(key)
+        # (checked BEFORE the call: a row the fixture has as accepted must be a call without work -- nothing may launch)
+        assert want[key] not in (0, G.ERR_HIP) or (want[key] == 0 and no_work), key
+        assert G.call(L, entry, edits) == want[key], key
+    assert len(keys) == len(set(keys)) == len(want) and len(keys) >= 928
+    covered = {k.split(":")[0] for k in keys}
+    assert covered == {
+        "mtlora_bn_relu_fwd", "mtlora_bn_relu_bwd", "mtlora_residual_droppath_fwd", "mtlora_residual_droppath_bwd",
+        "mtlora_upsample_cl_fwd", "mtlora_upsample_cl_bwd", "mtlora_upsample_loss", "mtlora_upsample_metrics", "mtlora_upsample_predict",
+        "mtlora_colsum", "mtlora_label_stat", "mtlora_window_attn_fwd", "mtlora_window_attn_bwd", "mtlora_window_attn_drop_fwd",
+        "mtlora_window_attn_drop_bwd", "mtlora_linear_pack", "mtlora_linear_pack_entry", "mtlora_linear_pack_table", "mtlora_gemm_tn", "mtlora_mlp_hid_proj",
+        "mtlora_mlp_hid_bwd", "mtlora_linear_fwd", "mtlora_linear_fwd_gelu", "mtlora_linear_bwd", "mtlora_linear_bwd_gelu"}
+    assert covered <= set(_lib.EXPORTS)
+
+
 def test_linear_sources_have_no_ablation_build():
     """no source file of the project (package, kernels, header, tools, oracle, entry points; documents and recorded profiles
     aside) carries an ablation switch, and the kernel sources read no environment variable outside the profiler (selftest.hip)"""

@@ -1008,6 +1008,69 @@ def test_residual_droppath(shared, rdt, ydt):
     assert ys[1].grad is None
 
 
+_ULP = {torch.float32: 2.0 ** -23, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
+_SEVEN_PAIRS = [(torch.float32, torch.float32), (torch.float32, torch.float16), (torch.float16, torch.float32),
+                (torch.float16, torch.float16), (torch.float32, torch.bfloat16), (torch.bfloat16, torch.float32),
+                (torch.bfloat16, torch.bfloat16)]
+
+
+@pytest.mark.parametrize("rdt,ydt", _SEVEN_PAIRS)
+def test_residual_droppath_every_dtype_pair(rdt, ydt):
+    """mtlora_residual_droppath_fwd / _bwd called directly for each of the seven (res, y) dtype pairs of the host ladder, at the
+    smallest shape (n = 2, B = 2, M = 64, C = 8), against the same formula in fp64 on the rounded inputs.  One multiply-add per element:
+    the result is within one unit in the last place of its dtype of the exact value, taken relative to the result and to the
+    scale * y term (the sum of the gradients for dres); a swapped branch of the ladder reads the wrong element size and is off by
+    order one."""
+    from mtlora_amd import _lib
+    n, B, M, C = 2, 2, 64, 8
+    torch.manual_seed(11)
+    res = [torch.randn(M, C, device=dev()).to(rdt) for _ in range(n)]
+    ys = [torch.randn(M, C, device=dev()).to(ydt) for _ in range(n)]
+    scale = ((torch.rand(n, B, device=dev()) < 0.7).float() / 0.7).contiguous()
+    scale[0, 0] = 1.0 / 0.7  # (at least one kept sample)
+    outs = [torch.full((M, C), float("nan"), device=dev(), dtype=rdt) for _ in range(n)]
+    L, P9 = _lib.lib(), _lib.ptr_array9
+    rc, yc = _lib.dtype_code(res[0]), _lib.dtype_code(ys[0])
+    _lib.check(L.mtlora_residual_droppath_fwd(n, P9(res), P9(ys), P9(outs), _lib.ptr(scale), M, C, B, rc, yc, _lib.stream_ptr()), "fwd")
+    s64 = scale.double().repeat_interleave(M // B, dim=1).unsqueeze(-1)  # (n, M, 1)
+    for k in range(n):
+        term = s64[k] * ys[k].double()
+        ref = res[k].double() + term
+        err = (outs[k].double() - ref).abs()
+        assert (err <= _ULP[rdt] * (ref.abs() + term.abs())).all(), (k, err.max().item())
+    gs = [torch.randn(M, C, device=dev()).to(rdt) for _ in range(n)]
+    dys = [torch.full((M, C), float("nan"), device=dev(), dtype=ydt) for _ in range(n)]
+    dres = torch.full((M, C), float("nan"), device=dev(), dtype=rdt)
+    _lib.check(L.mtlora_residual_droppath_bwd(n, P9(gs), P9(dys), _lib.ptr(dres), _lib.ptr(scale), M, C, B, rc, yc, _lib.stream_ptr()), "bwd")
+    for k in range(n):
+        ref = s64[k] * gs[k].double()
+        assert ((dys[k].double() - ref).abs() <= 2 * _ULP[ydt] * ref.abs()).all(), k
+    ref = sum(g.double() for g in gs)
+    assert ((dres.double() - ref).abs() <= _ULP[rdt] * (ref.abs() + sum(g.double().abs() for g in gs))).all()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+def test_upsample_cl_every_dtype(dtype):
+    """mtlora_upsample_cl_fwd / _bwd called directly for each dtype of the host ladder at the smallest shape (B = 1, h = w = 2,
+    C = 4, scale 2) against F.interpolate(bilinear) and its transpose in fp64 on the rounded inputs; tolerance of
+    test_concat_upsample_vs_torch for the dtype."""
+    from mtlora_amd import _lib
+    B, h, w, C, S = 1, 2, 2, 4, 2
+    torch.manual_seed(3)
+    coarse = torch.randn(B, h, w, C, device=dev()).to(dtype)
+    fine = torch.full((B, h * S, w * S, C), float("nan"), device=dev(), dtype=dtype)
+    L, code = _lib.lib(), _lib.dtype_code(coarse)
+    _lib.check(L.mtlora_upsample_cl_fwd(_lib.ptr(coarse), _lib.ptr(fine), B, h, w, C, S, C, code, _lib.stream_ptr()), "fwd")
+    c64 = coarse.double().cpu().requires_grad_(True)
+    ref = torch.nn.functional.interpolate(c64.permute(0, 3, 1, 2), scale_factor=S, mode="bilinear").permute(0, 2, 3, 1)
+    assert_close(fine, ref, dtype, "fine")
+    g = torch.randn(B, h * S, w * S, C, device=dev()).to(dtype)
+    gc = torch.full((B, h, w, C), float("nan"), device=dev(), dtype=dtype)
+    _lib.check(L.mtlora_upsample_cl_bwd(_lib.ptr(g), _lib.ptr(gc), B, h, w, C, S, C, code, _lib.stream_ptr()), "bwd")
+    ref.backward(g.double().cpu())
+    assert_close(gc, c64.grad, dtype, "grad_coarse")
+
+
 @pytest.mark.parametrize("use_scale", [True, False])
 @pytest.mark.parametrize("B,Ltok,C", [(6, 49, 96), (3, 200, 384), (2, 50, 1536), (5, 7, 768)])
 @pytest.mark.parametrize("rdt,ydt", [(torch.float32, torch.bfloat16), (torch.bfloat16, torch.bfloat16), (torch.float32, torch.float32),
@@ -2113,7 +2176,33 @@ def test_task_streams_match_single_stream():
             assert torch.equal(g0[n], g1[n]), n
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+def test_pack_table_equals_per_call_pack(dtype):
+    """mtlora_linear_pack_table over a two-layer table writes, for each dtype of the host ladder, exactly the bytes that
+    mtlora_linear_pack writes layer by layer (smallest shapes: one layer with task factors, one with the shared factor only)."""
+    import ctypes
+    from mtlora_amd import _lib
+    from mtlora_amd import functional as Fn
+    torch.manual_seed(17)
+    entries, want = [], []
+    for K, N, r_s, r_t in ((8, 8, 4, (4, 4)), (16, 24, 8, ())):
+        meta = Fn.LinearMeta(K=K, N=N, r_s=r_s, r_t=r_t, scale_s=2.0, scale_t=tuple(0.5 + t for t in range(len(r_t))), mode=0,
+                             has_x_tasks=bool(r_t), dropout_p=0.0, seed=0, dtype=dtype)
+        A_s, B_s = torch.randn(r_s, K, device=dev()), torch.randn(N, r_s, device=dev())
+        A_t, B_t = [torch.randn(r, K, device=dev()) for r in r_t], [torch.randn(N, r, device=dev()) for r in r_t]
+        nbytes = Fn.packed_bytes(meta)
+        ref, buf = torch.zeros(nbytes, dtype=torch.uint8, device=dev()), torch.zeros(nbytes, dtype=torch.uint8, device=dev())
+        d = meta.desc(1)
+        _lib.check(_lib.lib().mtlora_linear_pack(ctypes.byref(d), _lib.ptr(A_s), _lib.ptr(B_s), _lib.ptr_array(A_t), _lib.ptr_array(B_t),
+                                                 _lib.ptr(ref), nbytes, _lib.stream_ptr()), "mtlora_linear_pack")
+        entries.append((meta, A_s, B_s, A_t, B_t, buf))
+        want.append(ref)
+    Fn.PackTable(entries, dev(), dtype).pack()
+    for (*_, buf), ref in zip(entries, want):
+        assert bool(ref.any()) and torch.equal(buf, ref)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("M,Na,Nb", [(20000, 24, 1080), (4099, 8, 264), (70001, 136, 40), (300, 64, 256), (0, 8, 8)])
 def test_gemm_tn_vs_torch(dtype, M, Na, Nb):
     """mtlora_gemm_tn: out = a^T b (the narrow-output weight gradient), ragged M, several a-tiles, empty input."""

@@ -163,6 +163,15 @@ def test_argmax_vs_fp64(task, B, h, w, S, dtype):
     check_argmax(name(task, B, h, w, S, dtype), Fn.upsample_predict("argmax", low_q.to(dev()), S), ref)
 
 
+@pytest.mark.parametrize("task", ["depth", "normals"])
+def test_fp16_input_vs_fp64(task):
+    """the fp16 branch of the host's dtype ladder (DTYPES above covers fp32 and bf16): the same bound on the fp16-rounded input"""
+    from mtlora_amd import functional as Fn
+    B, h, w, S = 1, 10, 21, 8
+    low_q, ref = case(task, B, h, w, S, torch.float16)
+    check_float(name(task, B, h, w, S, torch.float16), Fn.upsample_predict(KIND_OF[task], low_q.to(dev()), S), ref)
+
+
 def test_argmax_exact_tie_takes_the_lower_index():
     """scale 1 copies the source pixel (both weights of the second corner are exactly 0), so equal bf16 logits stay equal:
     the class id must be torch.max's, the FIRST maximum."""
