@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import struct
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
 
@@ -125,6 +126,28 @@ def factor_stream() -> Optional["torch.cuda.Stream"]:
     return _factor_stream
 
 
+def _run_factor_phases(params, fgrads, M: int, dev, extra_ok: bool, run, keep) -> None:
+    """a node's backward launches, ``run(phase, stream_ptr)`` with the library's ``bwd_phase`` meaning (0 all, 1 the chain, 2 the
+    factor gradients): ``run(0)`` here, or ``run(1)`` here, an event and ``run(2)`` on the side stream, which then holds the gradients
+    of ``params``; ``keep()`` lists what phase 2 touches.  ``extra_ok``: nothing in this backward reads ``fgrads`` on this stream."""
+    side = _factor_stream
+    use_side = (side is not None and bool(fgrads) and extra_ok and side.device == dev and M >= _FACTOR_MIN_M
+                and _side_safe_params(params))
+    if _side_join_pending(params, dev):
+        use_side = False  # same layer earlier in THIS backward pass: autograd sums the two gradients on this stream
+    if not use_side:
+        run(0, L.stream_ptr())
+        return
+    run(1, L.stream_ptr())
+    ev = torch.cuda.Event()
+    ev.record()
+    side.wait_event(ev)
+    run(2, ctypes.c_void_p(side.cuda_stream))
+    _side_mark_pending(params, side)
+    for t in keep():
+        t.record_stream(side)
+
+
 # ----------------------------------------------------------------------------------------------
 # DropPath keep / scale vectors, drawn in bulk.  Every residual of the backbone needs n x B per-sample factors
 # bernoulli(keep) / keep (timm DropPath, swin_transformer_mtlora.py:388-426): 22 draws per Swin-T step = 44 tiny launches
@@ -241,7 +264,6 @@ def next_seed() -> int:
 
 _HOT_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 _GLUE_DTYPES = (torch.float32, torch.bfloat16, torch.float16)  # LayerNorm family, residual + DropPath, BatchNorm + ReLU kernels
-_DT_CODE = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}
 
 
 def compute_dtype(x: torch.Tensor) -> torch.dtype:
@@ -295,7 +317,7 @@ class LinearMeta:
     def desc(self, M: int) -> L.LinearDesc:
         d = L.LinearDesc()
         d.M, d.K, d.N = M, self.K, self.N
-        d.dtype = _DT_CODE[self.dtype]
+        d.dtype = L._DT[self.dtype]
         d.mode, d.T, d.r_s = self.mode, self.T, self.r_s
         for i, r in enumerate(self.r_t):
             d.r_t[i] = r
@@ -309,13 +331,6 @@ class LinearMeta:
         d.sel_stream, d.sel_dense, d.sel_tn, d.sel_projk, d.max_cu = tu["stream"], tu["dense"], tu["tn"], tu["projk"], tu["max_cu"]
         d.packed = 0 if self.packed is None else self.packed.data_ptr()
         return d
-
-
-def _as2d(t: torch.Tensor, cols: int, dtype: torch.dtype) -> torch.Tensor:
-    """t viewed as a contiguous (-1, cols) matrix of ``dtype`` (no op at all in the common case)."""
-    if t.dtype == dtype and t.is_contiguous():
-        return t.view(-1, cols)
-    return t.reshape(-1, cols).to(dtype).contiguous()
 
 
 def _flat(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
@@ -333,15 +348,43 @@ def _f32c(p):
     return p.detach().float().contiguous()
 
 
-_bytes_cache: dict = {}  # (kind, M, K, N, r_s, r_t, T-independent fields ...) -> ctx / scratch bytes (one ctypes call per new shape)
+def _f32_param(t: torch.Tensor) -> torch.Tensor:
+    """a parameter as the glue kernels read it (LayerNorm / BatchNorm affine, attention bias): detached, fp32, contiguous"""
+    return t.detach().float().contiguous()
 
 
-def _desc_bytes(kind: str, fn, meta: "LinearMeta", M: int, d) -> int:
-    key = (kind, M, meta.K, meta.N, meta.r_s, meta.r_t, meta.has_x_tasks, meta.dtype, meta.mode, meta.packed is not None)
-    v = _bytes_cache.get(key)
+def _scratch(nbytes: int, device, what: str, *dims, floor: int = 0) -> torch.Tensor:
+    """the uint8 buffer of a size query's answer, at least ``floor`` bytes; a negative answer refuses the shape ``dims`` of ``what``"""
+    if nbytes < 0:
+        raise RuntimeError(f"mtlora_amd: invalid {what} {dims}")
+    return torch.empty(nbytes if nbytes > floor else floor, dtype=torch.uint8, device=device)
+
+
+# size queries of the linear family, cached: one ctypes call per new descriptor, whatever the query
+_D = L.LinearDesc
+# the key's four runs of bytes -- [M, K, N, dtype, mode, T, r_s, r_t] [has_x_tasks] [sel_stream, sel_dense, sel_tn, sel_projk, max_cu]
+# [hid] -- cut out of the struct by ONE unpack (the buffer protocol of ctypes structures; the cheapest way found to read 20 fields)
+_KEY_CUT = struct.Struct(f"{_D.scale_s.offset}s{_D.has_x_tasks.offset - _D.scale_s.offset}x4s{_D.sel_stream.offset - _D.has_x_tasks.offset - 4}x"
+                         f"{_D.packed.offset - _D.sel_stream.offset}s{_D.hid.offset - _D.packed.offset}x4s"
+                         f"{ctypes.sizeof(_D) - _D.hid.offset - 4}x").unpack
+_size_cache: dict = {}
+
+
+def _size_query(kind: str, fn, d, d2=None) -> int:
+    """``fn(&d)`` / ``fn(&d, &d2)`` of a size (or yes / no) query of the library, asked once per ``kind`` (a name for ``fn``: ctypes
+    functions do not hash) and key.  The key is cut out of the descriptor(s): every field but the pointers' values (seed_offset,
+    hid_ptr; of ``packed`` only whether it is set), the per-call seed and bwd_phase, and the scales and dropout_p, which enter no
+    size.  What csrc/linear.hip reads (check_desc, first in every query, only VALIDATES; a value out of range answers -1):
+      ctx_layout (ctx bytes)                        M, K, N, dtype, T, r_s, r_t, packed != 0
+      bwd_scratch with sp_tn_part_bytes             M, K, N, dtype, T, r_s, r_t
+      hid_check (hid_supported, every hid query)    both: M, K, N, dtype, T, r_t, mode, has_x_tasks; d1.sel_stream
+      hid_fwd_scratch_bytes / hid_bwd_part_bytes    d1: M, N, T, r_t, sel_stream, max_cu; d2: r_t
+    A superset: mode, has_x_tasks, every sel_* and the hid flags are in the key of every query."""
+    key = (kind, _KEY_CUT(d), d.packed is None) if d2 is None else (kind, _KEY_CUT(d), d.packed is None, _KEY_CUT(d2), d2.packed is None)
+    v = _size_cache.get(key)
     if v is None:
-        v = fn(ctypes.byref(d))
-        _bytes_cache[key] = v
+        v = fn(ctypes.byref(d)) if d2 is None else fn(ctypes.byref(d), ctypes.byref(d2))
+        _size_cache[key] = v
     return v
 
 
@@ -365,7 +408,7 @@ class PackTable:
                                               packed.numel(), ctypes.byref(host, i * eb))
             L.check(st, "mtlora_linear_pack_entry")
         self.n = len(entries)
-        self.dtype_code = _DT_CODE[dtype]
+        self.dtype_code = L._DT[dtype]
         self.table = torch.frombuffer(host, dtype=torch.uint8).clone().to(device)
 
     def pack(self) -> None:
@@ -407,11 +450,8 @@ class MTLoRALinearFn(torch.autograd.Function):
             raise RuntimeError(f"mtlora_amd: MTLoRALinear input of shape {tuple(x.shape)} for in_features = {meta.K}")
         d = meta.desc(M)
         lib = L.lib()
-        ctx_bytes = _desc_bytes("ctx", lib.mtlora_linear_ctx_bytes, meta, M, d)
-        if ctx_bytes < 0:
-            raise RuntimeError(f"mtlora_amd: invalid MTLoRALinear shape M={M} K={meta.K} N={meta.N} (K, N must be "
-                               "multiples of 8)")
-        ctxbuf = torch.empty(ctx_bytes, dtype=torch.uint8, device=x.device)
+        ctx_bytes = _size_query("ctx", lib.mtlora_linear_ctx_bytes, d)
+        ctxbuf = _scratch(ctx_bytes, x.device, "MTLoRALinear shape (M, K, N; K and N must be multiples of 8)", M, meta.K, meta.N)
         oshape = (*lead, meta.N)
         ys = torch.empty(oshape, dtype=meta.dtype, device=x.device)
         yt = [torch.empty(oshape, dtype=meta.dtype, device=x.device) for _ in range(T)]
@@ -467,8 +507,8 @@ class MTLoRALinearFn(torch.autograd.Function):
         dy_s, dy_t = g2[0], g2[1:1 + T]
         d = meta.desc(M)
         lib = L.lib()
-        scratch_bytes = _desc_bytes("bwd", lib.mtlora_linear_bwd_scratch_bytes, meta, M, d)
-        scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+        scratch_bytes = _size_query("bwd", lib.mtlora_linear_bwd_scratch_bytes, d)
+        scratch = _scratch(scratch_bytes, dev, "MTLoRALinear backward shape (M, K, N)", M, meta.K, meta.N)
         need = ctx.needs_input_grad  # (meta, x, W_c, Wt_c, bias_f32, W_master, bias_master, A_s, B_s, scale_s, *rest)
         ishape = (*ctx.lead, meta.K)
         dx = torch.empty(ishape, dtype=meta.dtype, device=dev)
@@ -487,7 +527,9 @@ class MTLoRALinearFn(torch.autograd.Function):
             for t in range(T):
                 if dy_t[t] is None:
                     dxt[t].zero_()
-        def launch(stream_ptr):
+
+        def launch(phase, stream_ptr):
+            d.bwd_phase = phase
             if gates:  # the inputs were gelu(gate): the dX epilogue also applies gelu'(gate) (GELU backward fused)
                 st = lib.mtlora_linear_bwd_gelu(ctypes.byref(d), L.ptr(x2), L.ptr_array(xt2), L.ptr(Wt_c), L.ptr(dy_s),
                                                 L.ptr_array(dy_t), L.ptr(ctxbuf), ctxbuf.numel(), L.ptr(dx), L.ptr_array(dxt),
@@ -501,27 +543,10 @@ class MTLoRALinearFn(torch.autograd.Function):
                                            scratch_bytes, stream_ptr)
                 L.check(st, "mtlora_linear_bwd")
 
-        side = _factor_stream
         fgrads = [t for t in [dA_s, dB_s, *dA_t, *dB_t] if t is not None]
-        # the factor gradients go to the side stream only when nothing on this stream reads them inside backward: no
-        # trainable-scale gradient (formed from dB below) and no gradient accumulation into an existing .grad
-        use_side = (side is not None and fgrads and not ctx.has_scale_s and meta.n_scale_t == 0
-                    and side.device == dev and M >= _FACTOR_MIN_M and _side_safe_params(ctx.factor_params))
-        if _side_join_pending(ctx.factor_params, dev):
-            use_side = False  # same layer earlier in THIS backward pass: autograd sums the two gradients on this stream
-        if use_side:
-            d.bwd_phase = 1
-            launch(L.stream_ptr())
-            ev = torch.cuda.Event()
-            ev.record()
-            side.wait_event(ev)
-            d.bwd_phase = 2
-            launch(ctypes.c_void_p(side.cuda_stream))
-            _side_mark_pending(ctx.factor_params, side)
-            for t in [x2, ctxbuf, scratch, *xt2, *fgrads] + [g for g in g2 if g is not None]:
-                t.record_stream(side)  # allocated on this stream, still in use on the side stream when freed here
-        else:
-            launch(L.stream_ptr())
+        # no side stream with a trainable scale: its gradient is formed from dB below, on this stream, inside backward
+        _run_factor_phases(ctx.factor_params, fgrads, M, dev, not ctx.has_scale_s and meta.n_scale_t == 0, launch,
+                           lambda: [x2, ctxbuf, scratch, *xt2, *fgrads] + [g for g in g2 if g is not None])
         dW = dbias = None
         if need[5] or need[6]:
             # pretrained weight and / or bias left trainable (MTLORA.FREEZE_PRETRAINED False; mark_only_lora_as_trainable
@@ -553,7 +578,6 @@ class MTLoRALinearFn(torch.autograd.Function):
 # Task-enabled Mlp with IMPLICIT task hidden tensors (csrc/hid.hip, ABI v8)
 # ----------------------------------------------------------------------------------------------
 _MLP_HID = os.environ.get("MTLORA_MLP_HID", "1") != "0"
-_hid_ok_cache: dict = {}
 
 
 def mlp_hid_enabled() -> bool:
@@ -568,14 +592,7 @@ def set_mlp_hid(on: bool) -> bool:
 
 
 def mlp_hid_supported(meta1: "LinearMeta", meta2: "LinearMeta", M: int) -> bool:
-    key = (M, meta1.K, meta1.N, meta2.N, meta1.r_t, meta2.r_t, meta1.dtype, meta1.mode, meta2.mode, meta1.has_x_tasks, meta2.has_x_tasks,
-           _tuning["stream"])
-    v = _hid_ok_cache.get(key)
-    if v is None:
-        d1, d2 = meta1.desc(M), meta2.desc(M)
-        v = bool(L.lib().mtlora_mlp_hid_supported(ctypes.byref(d1), ctypes.byref(d2)))
-        _hid_ok_cache[key] = v
-    return v
+    return bool(_size_query("hid_ok", L.lib().mtlora_mlp_hid_supported, meta1.desc(M), meta2.desc(M)))
 
 
 def _ensure_packed(meta: "LinearMeta", A_s, B_s, A_t, B_t, device) -> None:
@@ -622,12 +639,10 @@ class MlpHidFn(torch.autograd.Function):
         _ensure_packed(meta2, *f2, dev)
         lib = L.lib()
         d1, d2 = meta1.desc(M), meta2.desc(M)
-        cb1 = _desc_bytes("ctx", lib.mtlora_linear_ctx_bytes, meta1, M, d1)
-        cb2 = _desc_bytes("ctx", lib.mtlora_linear_ctx_bytes, meta2, M, d2)
-        if cb1 < 0 or cb2 < 0:
-            raise RuntimeError(f"mtlora_amd: invalid Mlp shape M={M} K={meta1.K} hidden={H} N={meta2.N}")
-        ctx1 = torch.empty(cb1, dtype=torch.uint8, device=dev)
-        ctx2 = torch.empty(cb2, dtype=torch.uint8, device=dev)
+        cb1 = _size_query("ctx", lib.mtlora_linear_ctx_bytes, d1)
+        cb2 = _size_query("ctx", lib.mtlora_linear_ctx_bytes, d2)
+        ctx1 = _scratch(cb1, dev, "Mlp shape (M, K, hidden, N)", M, meta1.K, H, meta2.N)
+        ctx2 = _scratch(cb2, dev, "Mlp shape (M, K, hidden, N)", M, meta1.K, H, meta2.N)
         hshape = (*lead, H)
         h_s = torch.empty(hshape, dtype=dt, device=dev)
         a_s = torch.empty(hshape, dtype=dt, device=dev)
@@ -640,12 +655,8 @@ class MlpHidFn(torch.autograd.Function):
         L.check(st, "mtlora_linear_fwd_gelu (fc1, implicit task hiddens)")
         d1.hid, d1.hid_ptr = 0, 0
         # the task columns of fc2's P straight from h_base and P1
-        key = ("hidfwd", M, meta1.K, H, meta2.N, meta1.r_t, meta2.r_t, dt, _tuning["stream"], _tuning["max_cu"])
-        fb = _bytes_cache.get(key)
-        if fb is None:
-            fb = lib.mtlora_mlp_hid_fwd_scratch_bytes(ctypes.byref(d1), ctypes.byref(d2))
-            _bytes_cache[key] = fb
-        fscr = torch.empty(fb, dtype=torch.uint8, device=dev)
+        fb = _size_query("hid_fwd", lib.mtlora_mlp_hid_fwd_scratch_bytes, d1, d2)
+        fscr = _scratch(fb, dev, "Mlp shape (M, K, hidden, N) for implicit task hiddens", M, meta1.K, H, meta2.N)
         st = lib.mtlora_mlp_hid_proj(ctypes.byref(d1), ctypes.byref(d2), L.ptr(h_base), L.ptr(ctx1), L.ptr(ctx2), L.ptr(fscr), fb,
                                      L.stream_ptr())
         L.check(st, "mtlora_mlp_hid_proj")
@@ -676,16 +687,12 @@ class MlpHidFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         lib = L.lib()
         d1, d2 = meta1.desc(M), meta2.desc(M)
-        sb1 = _desc_bytes("bwd", lib.mtlora_linear_bwd_scratch_bytes, meta1, M, d1)
-        sb2 = _desc_bytes("bwd", lib.mtlora_linear_bwd_scratch_bytes, meta2, M, d2)
-        key = ("hidpart", M, meta1.K, H, meta2.N, meta1.r_t, meta2.r_t, dt, _tuning["stream"], _tuning["max_cu"])
-        pb = _bytes_cache.get(key)
-        if pb is None:
-            pb = lib.mtlora_mlp_hid_bwd_scratch_bytes(ctypes.byref(d1), ctypes.byref(d2))
-            _bytes_cache[key] = pb
-        scratch1 = torch.empty(sb1, dtype=torch.uint8, device=dev)
-        scratch2 = torch.empty(sb2, dtype=torch.uint8, device=dev)
-        part = torch.empty(pb, dtype=torch.uint8, device=dev)
+        sb1 = _size_query("bwd", lib.mtlora_linear_bwd_scratch_bytes, d1)
+        sb2 = _size_query("bwd", lib.mtlora_linear_bwd_scratch_bytes, d2)
+        pb = _size_query("hid_bwd", lib.mtlora_mlp_hid_bwd_scratch_bytes, d1, d2)
+        scratch1 = _scratch(sb1, dev, "Mlp backward shape (M, K, hidden)", M, meta1.K, H)
+        scratch2 = _scratch(sb2, dev, "Mlp backward shape (M, hidden, N)", M, H, meta2.N)
+        part = _scratch(pb, dev, "Mlp backward shape (M, K, hidden, N) for implicit task hiddens", M, meta1.K, H, meta2.N)
         f32 = torch.float32
         hshape, ishape = (*ctx.lead, H), (*ctx.lead, meta1.K)
         dh_s = torch.empty(hshape, dtype=dt, device=dev)
@@ -728,31 +735,18 @@ class MlpHidFn(torch.autograd.Function):
                                        L.ptr_array(dA1_t), L.ptr_array(None), L.ptr(scratch1), sb1, stream_ptr)
             L.check(st, "mtlora_linear_bwd (fc1, implicit task hiddens)")
 
-        side = _factor_stream
+        def run(phase, stream_ptr):  # fc2(1), hid, fc1(1) | fc2(2), fc1(2)
+            if phase != 2:
+                fc2(1, stream_ptr)
+                hid(stream_ptr)
+                fc1(1, stream_ptr)
+            if phase != 1:
+                fc2(2, stream_ptr)
+                fc1(2, stream_ptr)
+
         fgrads = [t for t in [dA1_s, dB1_s, dA2_s, dB2_s, *dA1_t, *dB1_t, *dA2_t, *dB2_t] if t is not None]
-        use_side = (side is not None and fgrads and side.device == dev and M >= _FACTOR_MIN_M and _side_safe_params(ctx.factor_params))
-        if _side_join_pending(ctx.factor_params, dev):
-            use_side = False
-        main = L.stream_ptr()
-        if use_side:
-            fc2(1, main)
-            hid(main)
-            fc1(1, main)
-            ev = torch.cuda.Event()
-            ev.record()
-            side.wait_event(ev)
-            sp = ctypes.c_void_p(side.cuda_stream)
-            fc2(2, sp)
-            fc1(2, sp)
-            _side_mark_pending(ctx.factor_params, side)
-            for t in [x2, ctx1, ctx2, a_s, dh_s, scratch1, scratch2, *xt2, *fgrads] + [g for g in g2 if g is not None]:
-                t.record_stream(side)
-        else:
-            fc2(1, main)
-            hid(main)
-            fc1(1, main)
-            fc2(2, main)
-            fc1(2, main)
+        _run_factor_phases(ctx.factor_params, fgrads, M, dev, True, run,
+                           lambda: [x2, ctx1, ctx2, a_s, dh_s, scratch1, scratch2, *xt2, *fgrads] + [g for g in g2 if g is not None])
         dxo = dx if ctx.in_dtypes[0] == dt else dx.to(ctx.in_dtypes[0])
         dxto = [dxt[t] if ctx.in_dtypes[1 + t] == dt else dxt[t].to(ctx.in_dtypes[1 + t]) for t in range(T)]
         return (None, None, dxo, None, None, None, None, None, None, dA1_s, dB1_s, dA2_s, dB2_s, *dxto, *dA1_t, *dB1_t, *dA2_t, *dB2_t)
@@ -794,7 +788,7 @@ class AttnMeta:
         d.window_size, d.shift = self.window_size, self.shift
         d.num_heads, d.head_dim = self.num_heads, self.head_dim
         d.image_layout = 1 if self.image_layout else 0
-        d.dtype = _DT_CODE[dtype]
+        d.dtype = L._DT[dtype]
         d.scale = self.scale
         d.mask_value = self.mask_value
         return d
@@ -815,7 +809,7 @@ class WindowAttentionFn(torch.autograd.Function):
         if dt not in _HOT_DTYPES:
             raise RuntimeError(f"mtlora_amd: window attention supports fp32 / bf16 / fp16, got {dt}")
         qkv_c = qkv.contiguous()
-        bias_c = bias.detach().float().contiguous()
+        bias_c = _f32_param(bias)
         if mask_ids is not None:
             mask_ids = mask_ids.to(torch.int32).contiguous()
             mask = None
@@ -847,7 +841,7 @@ class WindowAttentionFn(torch.autograd.Function):
         d = meta.desc(qkv.dtype)
         lib = L.lib()
         sb = lib.mtlora_window_attn_bwd_scratch_bytes(ctypes.byref(d))
-        scratch = torch.empty(sb, dtype=torch.uint8, device=qkv.device)
+        scratch = _scratch(sb, qkv.device, "window attention geometry (B, H, W, window)", meta.B, meta.H, meta.W, meta.window_size)
         dqkv = torch.empty_like(qkv)
         dbias = torch.empty_like(bias)
         if ctx.drop is not None:
@@ -922,7 +916,38 @@ def _ln_vec(x: torch.Tensor) -> int:
 
 def _ln_affine(weight, bias):
     """(gamma, beta) as the kernels read them: fp32, contiguous"""
-    return weight.detach().float().contiguous(), bias.detach().float().contiguous()
+    return _f32_param(weight), _f32_param(bias)
+
+
+def _kernel_dtype(dt: torch.dtype) -> torch.dtype:
+    """a gradient's own dtype if the glue kernels read it, else fp32"""
+    return dt if dt in _GLUE_DTYPES else torch.float32
+
+
+def _canon_grad(g: Optional[torch.Tensor], shape, dtype: torch.dtype) -> Optional[torch.Tensor]:
+    """an incoming gradient as a kernel reads it: of ``shape``, contiguous, in the ``dtype`` the caller names (None stays None)"""
+    if g is None:
+        return None
+    g = g.reshape(shape)
+    return (g if g.dtype == dtype else g.to(dtype)).contiguous()
+
+
+def _droppath_scale_for(n: int, B: int, drop_prob: float, training: bool, device) -> Optional[torch.Tensor]:
+    """the (n, B) DropPath factors of a residual (``droppath_scale``), or None when DropPath is off"""
+    if training and drop_prob > 0.0:
+        return droppath_scale(n, B, 1.0 - drop_prob, device)
+    return None
+
+
+def _merge_ok(mod: torch.nn.Module, x: torch.Tensor, H: int, W: int) -> bool:
+    """may the PatchMerging forms gather the 2x2 neighbourhoods of the (B, H*W, C) token tensor ``x`` for ``mod``?"""
+    _, Lt, C = x.shape
+    return (_ln_module_ok(mod) and _ln_width_ok(x, multiple=_ln_vec(x), width=4 * C) and Lt == H * W and H % 2 == 0 and W % 2 == 0)
+
+
+def _streams_ok(xs) -> bool:
+    """2 .. MAX_TASKS + 1 device tensors of one dtype and shape"""
+    return (2 <= len(xs) <= L.MAX_TASKS + 1 and all(x.is_cuda and x.dtype == xs[0].dtype and x.shape == xs[0].shape for x in xs))
 
 
 def _ln_row_stats(M: int, device):
@@ -942,7 +967,7 @@ def _ln_bwd_buffers(M: int, C: int, x: torch.Tensor, n=None):
     lib, code = L.lib(), L.dtype_code(x)
     sb = (lib.mtlora_layernorm_bwd_scratch_bytes(M, C, code) if n is None
           else lib.mtlora_layernorm_multi_bwd_scratch_bytes(n, M, C, code))
-    scratch = torch.empty(sb, dtype=torch.uint8, device=x.device)
+    scratch = _scratch(sb, x.device, "LayerNorm backward shape (M, C)", M, C)
     dg = torch.empty(C, dtype=torch.float32, device=x.device)
     db = torch.empty(C, dtype=torch.float32, device=x.device)
     return scratch, sb, dg, db
@@ -979,12 +1004,8 @@ def _ln_backward(ctx, dy, addend=None):
     x2, w, mean, rstd = ctx.saved_tensors
     M, C = ctx.MC
     mh, mw = ctx.merge
-    dy2 = dy.reshape(M, C).contiguous()
-    if dy2.dtype not in _GLUE_DTYPES:
-        dy2 = dy2.float()
-    add2 = None
-    if addend is not None:
-        add2 = addend.reshape(x2.shape).to(x2.dtype).contiguous()
+    dy2 = _canon_grad(dy, (M, C), _kernel_dtype(dy.dtype))
+    add2 = _canon_grad(addend, x2.shape, x2.dtype)
     scratch, sb, dg, db = _ln_bwd_buffers(M, C, x2)
     dx = torch.empty_like(x2)
     st = L.lib().mtlora_layernorm_bwd(L.ptr(dy2), L.ptr(x2), L.ptr(w), L.ptr(mean), L.ptr(rstd), L.ptr(dx), L.ptr(dg),
@@ -995,39 +1016,28 @@ def _ln_backward(ctx, dy, addend=None):
 
 
 class LayerNormFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias, eps: float, out_dtype: torch.dtype, merge=None):
-        return _ln_forward(ctx, x, weight, bias, eps, out_dtype, merge)
+    """y = LayerNorm(x) (``merge``: of the 2x2 neighbourhoods, see ``_ln_forward``).  ``fork``: (x_skip, y) = (x, LayerNorm(x)) --
+    the block input feeds the LayerNorm AND the residual connection.  Routing both uses through one node lets the backward form
+    d x = g_skip + LN-backward(g_y)  inside the LayerNorm kernel (``dx_addend``) instead of autograd's separate full-size
+    gradient add (one per stream per half block)."""
 
     @staticmethod
-    def backward(ctx, dy):
-        dx, dg, db = _ln_backward(ctx, dy)
-        return dx, dg, db, None, None, None
-
-
-class LayerNormForkFn(torch.autograd.Function):
-    """(x_skip, y) = (x, LayerNorm(x)): the block input feeds the LayerNorm AND the residual connection.  Routing both
-    uses through one node lets the backward form  d x = g_skip + LN-backward(g_y)  inside the LayerNorm kernel
-    (``dx_addend``) instead of autograd's separate full-size gradient add (one per stream per half block)."""
+    def forward(ctx, x, weight, bias, eps: float, out_dtype: torch.dtype, merge=None, fork: bool = False):
+        y = _ln_forward(ctx, x, weight, bias, eps, out_dtype, merge)
+        ctx.fork = fork
+        return (x.view_as(x), y) if fork else y
 
     @staticmethod
-    def forward(ctx, x, weight, bias, eps: float, out_dtype: torch.dtype):
-        y = _ln_forward(ctx, x, weight, bias, eps, out_dtype)
-        return x.view_as(x), y
-
-    @staticmethod
-    def backward(ctx, g_skip, gy):
-        if gy is None:  # the normalised output was not used
-            return g_skip, None, None, None, None
-        dx, dg, db = _ln_backward(ctx, gy, g_skip)
-        return dx, dg, db, None, None
+    def backward(ctx, *grads):  # (g_y), or (g_skip, g_y) of the fork form: both materialised
+        dx, dg, db = _ln_backward(ctx, grads[-1], grads[0] if ctx.fork else None)
+        return dx, dg, db, None, None, None, None
 
 
 class ResidualLayerNormFn(torch.autograd.Function):
     """(x_new, y) = (shortcut + scale[sample] * branch, LayerNorm(x_new)) as ONE kernel; x_new is the next skip path
-    (a ``LayerNormForkFn``-style fork), y feeds the following linear.  Backward: d_shortcut = g_x_new +
+    (a fork, as ``LayerNormFn(fork=True)``), y feeds the following linear.  Backward: d_shortcut = g_x_new +
     LN-backward(g_y), d_branch = scale * d_shortcut, both written by the LayerNorm backward kernel
-    (``mtlora_residual_layernorm_fwd/bwd``).  Replaces ResidualDropPathFn + LayerNormForkFn for a single stream."""
+    (``mtlora_residual_layernorm_fwd/bwd``).  Replaces ResidualDropPathFn + the LayerNorm fork for a single stream."""
 
     @staticmethod
     def forward(ctx, shortcut, branch, scale, weight, bias, eps: float, out_dtype: torch.dtype):
@@ -1060,10 +1070,8 @@ class ResidualLayerNormFn(torch.autograd.Function):
             g = g_skip.reshape(ctx.B, -1, C)
             db_ = g if scale is None else g * scale.view(-1, 1, 1).to(g.dtype)
             return g_skip, db_.to(ctx.bdtype).reshape(ctx.shape), None, None, None, None, None
-        dy2 = gy.reshape(M, C).contiguous()
-        if dy2.dtype != ctx.bdtype:
-            dy2 = dy2.to(ctx.bdtype)
-        add2 = None if g_skip is None else g_skip.reshape(M, C).to(x_new.dtype).contiguous()
+        dy2 = _canon_grad(gy, (M, C), ctx.bdtype)
+        add2 = _canon_grad(g_skip, (M, C), x_new.dtype)
         scratch, sb, dg, db = _ln_bwd_buffers(M, C, x_new)
         dx = torch.empty_like(x_new)
         dbr = torch.empty((M, C), dtype=ctx.bdtype, device=x_new.device)
@@ -1107,8 +1115,8 @@ class ResidualLayerNormMultiFn(torch.autograd.Function):
         n, (M, C) = ctx.n, ctx.MC
         g_skip, g_y = grads[:n], grads[n:]
         dev = xs[0].device
-        dys = [g.reshape(M, C).to(ctx.bdtype).contiguous() for g in g_y]             # (materialised: zeros if unused)
-        adds = [g.reshape(M, C).to(xs[0].dtype).contiguous() for g in g_skip]
+        dys = [_canon_grad(g, (M, C), ctx.bdtype) for g in g_y]             # (materialised: zeros if unused)
+        adds = [_canon_grad(g, (M, C), xs[0].dtype) for g in g_skip]
         scratch, sb, dg, db = _ln_bwd_buffers(M, C, xs[0])
         dsh = torch.empty_like(xs[0])
         dbr = [torch.empty((M, C), dtype=ctx.bdtype, device=dev) for _ in range(n)]
@@ -1135,10 +1143,7 @@ def residual_layer_norm_multi(mod: torch.nn.Module, shortcut: torch.Tensor, bran
         r = residual_droppath(shortcut, list(branches), drop_prob, training)
         forks = [layer_norm_fork(mod, x) for x in r]
         return [f[0] for f in forks], [f[1] for f in forks]
-    scale = None
-    if training and drop_prob > 0.0:
-        keep = 1.0 - drop_prob
-        scale = droppath_scale(n, shortcut.shape[0], keep, shortcut.device)
+    scale = _droppath_scale_for(n, shortcut.shape[0], drop_prob, training, shortcut.device)
     outs = ResidualLayerNormMultiFn.apply(scale, mod.weight, mod.bias, mod.eps, out_dtype, n, shortcut, *branches)
     return list(outs[:n]), list(outs[n:])
 
@@ -1155,15 +1160,14 @@ def residual_layer_norm(mod: torch.nn.Module, shortcut: torch.Tensor, branch: to
     if not ok:
         x = residual_droppath(shortcut, [branch], drop_prob, training)[0]
         return layer_norm_fork(mod, x)
-    scale = None
-    if training and drop_prob > 0.0:
-        keep = 1.0 - drop_prob
-        scale = droppath_scale(1, shortcut.shape[0], keep, shortcut.device)[0]
+    scale = _droppath_scale_for(1, shortcut.shape[0], drop_prob, training, shortcut.device)
+    if scale is not None:
+        scale = scale[0]
     return ResidualLayerNormFn.apply(shortcut, branch, scale, mod.weight, mod.bias, mod.eps, out_dtype)
 
 
 def layer_norm_fork(mod: torch.nn.Module, x: torch.Tensor):
-    """(x for the skip connection, LayerNorm(x) for the following linear): see LayerNormForkFn.  Same dispatch rules as
+    """(x for the skip connection, LayerNorm(x) for the following linear): LayerNormFn's fork form.  Same dispatch rules as
     ``layer_norm`` (falls back to two separate uses of x when the fused kernel does not apply)."""
     y = layer_norm(mod, x, _fork=True)
     return y if isinstance(y, tuple) else (x, y)
@@ -1173,62 +1177,21 @@ def layer_norm_merge(mod: torch.nn.Module, x: torch.Tensor, H: int, W: int) -> t
     """PatchMerging's ``norm(cat of the 2x2 neighbourhood)`` on a (B, H*W, C) token tensor -> (B, H*W/4, 4C): the gather is
     done by the LayerNorm kernels' addressing (forward reads, backward scatters), not by a strided copy.  Falls back to
     the explicit gather when the kernel does not apply."""
-    B, Lt, C = x.shape
-    ok = (_ln_module_ok(mod) and _ln_width_ok(x, multiple=_ln_vec(x), width=4 * C)
-          and Lt == H * W and H % 2 == 0 and W % 2 == 0)
-    if not ok:
+    B, _, C = x.shape
+    if not _merge_ok(mod, x, H, W):
         g = x.view(B, H // 2, 2, W // 2, 2, C).permute(0, 1, 3, 4, 2, 5).reshape(B, (H // 2) * (W // 2), 4 * C)
         return layer_norm(mod, g)
     return LayerNormFn.apply(x, mod.weight, mod.bias, mod.eps, glue_dtype(x), (H, W))
 
 
-class LayerNormMergeMultiFn(torch.autograd.Function):
-    """PatchMerging's ``norm(2x2 neighbourhood concat)`` applied to n token tensors (B, H*W, C) at once: returns ONE stacked
-    (n*B, H*W/4, 4C) tensor (stream-major), so that the following reduction runs as a single GEMM over all streams; one launch
-    forward, one backward (+ one reduce) with dgamma / dbeta summed over the streams (``mtlora_layernorm_multi_fwd/bwd``)."""
-
-    @staticmethod
-    def forward(ctx, weight, bias, eps: float, out_dtype: torch.dtype, H: int, W: int, n: int, *xs):
-        L.require_gpu(weight, bias, *xs)
-        B, Lt, Ct = xs[0].shape
-        C, M = 4 * Ct, B * Lt // 4
-        x2 = [x.contiguous() for x in xs]
-        w, b = _ln_affine(weight, bias)
-        y = torch.empty((n, M, C), dtype=out_dtype, device=x2[0].device)
-        stats, means, rstds = _ln_stream_stats(n, M, x2[0].device)
-        st = L.lib().mtlora_layernorm_multi_fwd(n, L.ptr_array9(x2), L.ptr(w), L.ptr(b), L.ptr_array9([y[k] for k in range(n)]),
-                                                L.ptr_array9(means), L.ptr_array9(rstds), M, C, float(eps), L.dtype_code(x2[0]),
-                                                L.dtype_code(y), H, W, L.stream_ptr())
-        L.check(st, "mtlora_layernorm_multi_fwd")
-        ctx.save_for_backward(w, stats, *x2)
-        ctx.cfg = (n, M, C, H, W, xs[0].shape)
-        return y.view(n * B, Lt // 4, C)
-
-    @staticmethod
-    def backward(ctx, g):
-        w, stats, *x2 = ctx.saved_tensors
-        n, M, C, H, W, shape = ctx.cfg
-        g3 = g.reshape(n, M, C)
-        if g3.dtype not in _GLUE_DTYPES:
-            g3 = g3.float()
-        g3 = g3.contiguous()
-        scratch, sb, dg, db = _ln_bwd_buffers(M, C, x2[0], n)
-        dxs = [torch.empty_like(x) for x in x2]
-        _, means, rstds = _ln_stream_stats(n, M, stats=stats)
-        st = L.lib().mtlora_layernorm_multi_bwd(n, L.ptr_array9([g3[k] for k in range(n)]), L.ptr_array9(x2), L.ptr(w),
-                                            L.ptr_array9(means), L.ptr_array9(rstds), L.ptr_array9(dxs), L.ptr(dg), L.ptr(db), M, C,
-                                            L.dtype_code(x2[0]), L.dtype_code(g3), L.ptr(scratch), sb, L.ptr_array9(None), H, W,
-                                            L.stream_ptr())
-        L.check(st, "mtlora_layernorm_multi_bwd")
-        return (dg, db, None, None, None, None, None, *[d.view(shape) for d in dxs])
-
-
 class ResidualMergeNormStreamsFn(torch.autograd.Function):
-    """n independent streams: x_new_k = res_k + scale[k] * branch_k (the MLP residual + DropPath of the task-enabled block),
-    then PatchMerging's ``norm(2x2 neighbourhood concat)`` of every x_new_k -> ONE stacked (n*B, H*W/4, 4C) tensor.  One launch
-    forward, one backward (+ reduce): d_res_k = LN'(g)_k scattered back, d_branch_k = scale[k] * d_res_k; x_new_k is only kept
-    for the backward (the block output feeds nothing but the merging).
-    args: scale ((n, B) fp32 or None), weight, bias, eps, out_dtype, H, W, n, *res(n), *branches(n)"""
+    """PatchMerging's ``norm(2x2 neighbourhood concat)`` of n independent streams (B, H*W, C) at once -> ONE stacked
+    (n*B, H*W/4, 4C) tensor (stream-major), so that the following reduction runs as a single GEMM over all streams.  One launch
+    forward, one backward (+ reduce), dgamma / dbeta summed over the streams.  Two forms of the same kernels (csrc/layernorm.hip):
+      * n tensors: the streams themselves are normalised (``mtlora_layernorm_multi_fwd/bwd``);
+      * 2n tensors, res then branches: x_new_k = res_k + scale[k] * branch_k (MLP residual + DropPath of the task-enabled block) is
+        formed first and kept for the backward only (``mtlora_residual_layernorm_streams_fwd/bwd``): d_branch_k = scale[k] * d_res_k.
+    args: scale ((n, B) fp32 or None; None without branches), weight, bias, eps, out_dtype, H, W, n, *res(n) [, *branches(n)]"""
 
     @staticmethod
     def forward(ctx, scale, weight, bias, eps: float, out_dtype: torch.dtype, H: int, W: int, n: int, *tensors):
@@ -1237,38 +1200,50 @@ class ResidualMergeNormStreamsFn(torch.autograd.Function):
         B, Lt, Ct = res[0].shape
         C, M = 4 * Ct, B * Lt // 4
         r2 = [x.contiguous() for x in res]
-        b2 = [x.contiguous() for x in brs]
         w, b = _ln_affine(weight, bias)
-        xs = [torch.empty_like(x) for x in r2]
         y = torch.empty((n, M, C), dtype=out_dtype, device=r2[0].device)
+        ys = [y[k] for k in range(n)]
         stats, means, rstds = _ln_stream_stats(n, M, r2[0].device)
-        st = L.lib().mtlora_residual_layernorm_streams_fwd(n, L.ptr_array9(r2), L.ptr_array9(b2), L.ptr(scale), B, L.ptr(w), L.ptr(b),
-                                                           L.ptr_array9(xs), L.ptr_array9([y[k] for k in range(n)]),
-                                                           L.ptr_array9(means), L.ptr_array9(rstds), M, C, float(eps),
-                                                           L.dtype_code(r2[0]), L.dtype_code(y), H, W, L.stream_ptr())
-        L.check(st, "mtlora_residual_layernorm_streams_fwd")
-        ctx.save_for_backward(w, stats, scale, *xs)
-        ctx.cfg = (n, M, C, H, W, B, res[0].shape, brs[0].dtype)
+        if brs:
+            b2 = [x.contiguous() for x in brs]
+            xs = [torch.empty_like(x) for x in r2]
+            st = L.lib().mtlora_residual_layernorm_streams_fwd(n, L.ptr_array9(r2), L.ptr_array9(b2), L.ptr(scale), B, L.ptr(w), L.ptr(b),
+                                                               L.ptr_array9(xs), L.ptr_array9(ys), L.ptr_array9(means),
+                                                               L.ptr_array9(rstds), M, C, float(eps), L.dtype_code(r2[0]),
+                                                               L.dtype_code(y), H, W, L.stream_ptr())
+            L.check(st, "mtlora_residual_layernorm_streams_fwd")
+            ctx.save_for_backward(w, stats, scale, *xs)
+        else:
+            st = L.lib().mtlora_layernorm_multi_fwd(n, L.ptr_array9(r2), L.ptr(w), L.ptr(b), L.ptr_array9(ys), L.ptr_array9(means),
+                                                    L.ptr_array9(rstds), M, C, float(eps), L.dtype_code(r2[0]), L.dtype_code(y), H, W,
+                                                    L.stream_ptr())
+            L.check(st, "mtlora_layernorm_multi_fwd")
+            ctx.save_for_backward(w, stats, None, *r2)
+        ctx.cfg = (n, M, C, H, W, B, res[0].shape, brs[0].dtype if brs else None)
         return y.view(n * B, Lt // 4, C)
 
     @staticmethod
     def backward(ctx, g):
         w, stats, scale, *xs = ctx.saved_tensors
         n, M, C, H, W, B, shape, bdt = ctx.cfg
-        g3 = g.reshape(n, M, C)
-        if g3.dtype != bdt:
-            g3 = g3.to(bdt)
-        g3 = g3.contiguous()
-        dev = xs[0].device
+        # with branches the kernel writes their gradients (of their dtype) from g; without, it takes g's own dtype
+        g3 = _canon_grad(g, (n, M, C), _kernel_dtype(g.dtype) if bdt is None else bdt)
+        gs = [g3[k] for k in range(n)]
         scratch, sb, dg, db = _ln_bwd_buffers(M, C, xs[0], n)
         dres = [torch.empty_like(x) for x in xs]
-        dbr = [torch.empty(shape, dtype=bdt, device=dev) for _ in range(n)]
         _, means, rstds = _ln_stream_stats(n, M, stats=stats)
-        st = L.lib().mtlora_residual_layernorm_streams_bwd(n, L.ptr_array9([g3[k] for k in range(n)]), L.ptr_array9(xs), L.ptr(w),
-                                                       L.ptr_array9(means), L.ptr_array9(rstds), L.ptr_array9(dres),
-                                                       L.ptr_array9(dbr), L.ptr(dg), L.ptr(db), L.ptr(scale), B, M, C,
-                                                       L.dtype_code(xs[0]), L.dtype_code(g3), L.ptr(scratch), sb, L.ptr_array9(None),
-                                                       H, W, L.stream_ptr())
+        if bdt is None:
+            st = L.lib().mtlora_layernorm_multi_bwd(n, L.ptr_array9(gs), L.ptr_array9(xs), L.ptr(w), L.ptr_array9(means),
+                                                    L.ptr_array9(rstds), L.ptr_array9(dres), L.ptr(dg), L.ptr(db), M, C,
+                                                    L.dtype_code(xs[0]), L.dtype_code(g3), L.ptr(scratch), sb, L.ptr_array9(None), H, W,
+                                                    L.stream_ptr())
+            L.check(st, "mtlora_layernorm_multi_bwd")
+            return (None, dg, db, None, None, None, None, None, *[d.view(shape) for d in dres])
+        dbr = [torch.empty(shape, dtype=bdt, device=xs[0].device) for _ in range(n)]
+        st = L.lib().mtlora_residual_layernorm_streams_bwd(n, L.ptr_array9(gs), L.ptr_array9(xs), L.ptr(w), L.ptr_array9(means),
+                                                           L.ptr_array9(rstds), L.ptr_array9(dres), L.ptr_array9(dbr), L.ptr(dg),
+                                                           L.ptr(db), L.ptr(scale), B, M, C, L.dtype_code(xs[0]), L.dtype_code(g3),
+                                                           L.ptr(scratch), sb, L.ptr_array9(None), H, W, L.stream_ptr())
         L.check(st, "mtlora_residual_layernorm_streams_bwd")
         return (None, dg, db, None, None, None, None, None, *[d.view(shape) for d in dres], *dbr)
 
@@ -1277,33 +1252,23 @@ def residual_merge_norm_streams(mod: torch.nn.Module, res, branches, H: int, W: 
     """stacked PatchMerging-norm of (res_k + DropPath_k(branches_k)) over the streams, or None when the fused kernels do not
     apply (the caller then forms the residuals and calls ``layer_norm_merge_multi`` / per-stream code)."""
     n = len(res)
-    B, Lt, C = res[0].shape
-    ok = (_ln_module_ok(mod) and 2 <= n <= L.MAX_TASKS + 1
-          and len(branches) == n and all(x.is_cuda and x.dtype == res[0].dtype and x.shape == res[0].shape for x in res)
+    ok = (_streams_ok(res) and len(branches) == n
           and all(x.shape == res[0].shape and x.dtype == branches[0].dtype for x in branches)
-          and _ln_width_ok(res[0], multiple=_ln_vec(res[0]), width=4 * C) and Lt == H * W and H % 2 == 0 and W % 2 == 0
-          and torch.is_grad_enabled())
+          and _merge_ok(mod, res[0], H, W) and torch.is_grad_enabled())
     if ok:
         out_dtype = glue_dtype(res[0])
         ok = branches[0].dtype == out_dtype
     if not ok:
         return None
-    scale = None
-    if training and drop_prob > 0.0:
-        keep = 1.0 - drop_prob
-        scale = droppath_scale(n, B, keep, res[0].device)
+    scale = _droppath_scale_for(n, res[0].shape[0], drop_prob, training, res[0].device)
     return ResidualMergeNormStreamsFn.apply(scale, mod.weight, mod.bias, mod.eps, out_dtype, H, W, n, *res, *branches)
 
 
 def layer_norm_merge_multi(mod: torch.nn.Module, xs, H: int, W: int):
     """stacked (n*B, H*W/4, 4C) = cat_k PatchMerging-norm(xs[k]) (stream-major), or None when the fused kernel does not apply."""
-    B, Lt, C = xs[0].shape
-    ok = (_ln_module_ok(mod) and 2 <= len(xs) <= L.MAX_TASKS + 1
-          and all(x.is_cuda and x.dtype == xs[0].dtype and x.shape == xs[0].shape for x in xs)
-          and _ln_width_ok(xs[0], multiple=_ln_vec(xs[0]), width=4 * C) and Lt == H * W and H % 2 == 0 and W % 2 == 0)
-    if not ok:
+    if not (_streams_ok(xs) and _merge_ok(mod, xs[0], H, W)):
         return None
-    return LayerNormMergeMultiFn.apply(mod.weight, mod.bias, mod.eps, glue_dtype(xs[0]), H, W, len(xs), *xs)
+    return ResidualMergeNormStreamsFn.apply(None, mod.weight, mod.bias, mod.eps, glue_dtype(xs[0]), H, W, len(xs), *xs)
 
 
 def layer_norm(mod: torch.nn.Module, x: torch.Tensor, feeds_linear: bool = True, _fork: bool = False):
@@ -1319,9 +1284,7 @@ def layer_norm(mod: torch.nn.Module, x: torch.Tensor, feeds_linear: bool = True,
         out_dtype = glue_dtype(x)
     else:
         out_dtype = torch.float32 if torch.is_autocast_enabled() else x.dtype
-    if _fork and x.requires_grad:
-        return LayerNormForkFn.apply(x, mod.weight, mod.bias, mod.eps, out_dtype)  # (x_skip, y)
-    return LayerNormFn.apply(x, mod.weight, mod.bias, mod.eps, out_dtype)
+    return LayerNormFn.apply(x, mod.weight, mod.bias, mod.eps, out_dtype, None, _fork and x.requires_grad)  # fork: (x_skip, y)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1333,14 +1296,12 @@ class BatchNormReluFn(torch.autograd.Function):
         L.require_gpu(x, weight, bias)
         R, C = x.shape
         x = x.contiguous()
-        w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
+        w, b = _f32_param(weight), _f32_param(bias)
         y = torch.empty_like(x)
         saves = torch.empty(4, C, dtype=torch.float32, device=x.device)  # mean, rstd, scale, shift
         lib = L.lib()
         sb = lib.mtlora_bn_scratch_bytes(R, C, L.dtype_code(x))
-        if sb < 0:
-            raise RuntimeError(f"mtlora_amd: unsupported BatchNorm shape ({R}, {C}) {x.dtype}")
-        scratch = torch.empty(sb, dtype=torch.uint8, device=x.device)
+        scratch = _scratch(sb, x.device, "BatchNorm shape (rows, C, dtype)", R, C, x.dtype)
         st = lib.mtlora_bn_relu_fwd(L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(running_mean), L.ptr(running_var), float(momentum),
                                     float(eps), int(relu), L.ptr(y), L.ptr(saves[0]), L.ptr(saves[1]), L.ptr(saves[2]),
                                     L.ptr(saves[3]), R, C, L.dtype_code(x), L.ptr(scratch), sb, L.stream_ptr())
@@ -1356,7 +1317,7 @@ class BatchNormReluFn(torch.autograd.Function):
         dy = dy.to(x.dtype).contiguous()
         lib = L.lib()
         sb = lib.mtlora_bn_scratch_bytes(R, C, L.dtype_code(x))
-        scratch = torch.empty(sb, dtype=torch.uint8, device=x.device)
+        scratch = _scratch(sb, x.device, "BatchNorm shape (rows, C, dtype)", R, C, x.dtype)
         dx = torch.empty_like(x)
         dg = torch.empty(C, dtype=torch.float32, device=x.device)
         db = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -1407,7 +1368,7 @@ class ResidualDropPathFn(torch.autograd.Function):
         dres = torch.empty(shape, dtype=rdt, device=dev) if shared else None
         st = L.lib().mtlora_residual_droppath_bwd(n, L.ptr_array9(gs), L.ptr_array9(dys), L.ptr(dres), L.ptr(scale), M, C, B,
                                                   L.dtype_code(gs[[g is not None for g in gs].index(True)]),
-                                                  _DT_CODE.get(ydt, L.F32), L.stream_ptr())
+                                                  L._DT.get(ydt, L.F32), L.stream_ptr())
         L.check(st, "mtlora_residual_droppath_bwd")
         dres_out = [dres] if shared else gs          # separate residuals: identity (the incoming gradient itself)
         return (None, None, None, *dres_out, *dys)
@@ -1422,10 +1383,7 @@ def residual_droppath(res, ys, drop_prob: float, training: bool):
     ok = (rl[0].is_cuda and rl[0].shape[-1] % 8 == 0 and all(t.dtype in _GLUE_DTYPES for t in rl + list(ys))
           and len({t.dtype for t in rl}) == 1 and len({t.dtype for t in ys}) == 1 and n <= L.MAX_TASKS + 1
           and all(t.shape == rl[0].shape for t in list(ys) + rl))
-    scale = None
-    if training and drop_prob > 0.0:
-        keep = 1.0 - drop_prob
-        scale = droppath_scale(n, rl[0].shape[0], keep, rl[0].device)
+    scale = _droppath_scale_for(n, rl[0].shape[0], drop_prob, training, rl[0].device)
     if not ok:
         out = []
         for k in range(n):
@@ -1445,7 +1403,7 @@ def column_sum(g2: torch.Tensor) -> torch.Tensor:
         return g2.sum(0, dtype=torch.float32)
     lib = L.lib()
     sb = lib.mtlora_colsum_scratch_bytes(M, N)
-    scratch = torch.empty(sb, dtype=torch.uint8, device=g2.device)
+    scratch = _scratch(sb, g2.device, "column-sum shape (M, N)", M, N)
     out = torch.empty(N, dtype=torch.float32, device=g2.device)
     L.check(lib.mtlora_colsum(L.ptr(g2), M, N, L.dtype_code(g2), L.ptr(out), L.ptr(scratch), sb, L.stream_ptr()), "mtlora_colsum")
     return out
@@ -1457,7 +1415,7 @@ def label_stat(lab: torch.Tensor, kind: int, ignore_index: float) -> torch.Tenso
     n = lab.numel()
     lib = L.lib()
     sb = lib.mtlora_label_stat_scratch_bytes(n)
-    scratch = torch.empty(sb, dtype=torch.uint8, device=lab.device)
+    scratch = _scratch(sb, lab.device, "label count", n)
     out = torch.empty(1, dtype=torch.float32, device=lab.device)
     L.check(lib.mtlora_label_stat(L.ptr(lab), n, kind, float(ignore_index), L.ptr(out), L.ptr(scratch), sb, L.stream_ptr()),
             "mtlora_label_stat")
@@ -1725,14 +1683,14 @@ def augment_batch(jobs, size, coef, side, out_size, cubic_q15=None, cubic_f32=No
 # ----------------------------------------------------------------------------------------------
 def _layout_weight(weight, bias, cdtype, col_index, n_cols, pad_rows):
     """the weight as the kernel takes it: ``col_index`` scatters its columns into ``n_cols`` (zero elsewhere: the padded channel
-    layout of ConcatUpsampleFn), ``pad_rows`` appends zero rows (classes padded to a multiple of 8).  Done inside the Function: no
-    autograd nodes of their own for the scatter / cat, the matching gather / slice of the gradient is part of its backward.
+    layout of ConcatUpsampleFn), ``pad_rows`` appends zero rows (classes padded to a multiple of 8).  BigLinearFn hands in DETACHED
+    parameters (no autograd nodes for the scatter / cat: ``_unlayout_grads`` is part of its backward), ``linear_big_m`` the parameters.
     (Round 5 also tried the weight / bias gradients of these linears on the factor-gradient side stream -- nothing in the backward
     chain reads them: c2 -0.7 %, c4 -1.0 %, c5:4 -1.0 %: they leave four concurrent task streams for one.  Removed.)"""
-    w = weight.detach().to(cdtype)
+    w = weight.to(cdtype)
     if col_index is not None:
         w = w.new_zeros(w.shape[0], n_cols).index_copy(1, col_index, w)
-    b = None if bias is None else bias.detach()
+    b = bias
     if pad_rows:
         w = torch.cat([w, w.new_zeros(pad_rows, w.shape[1])], 0)
         b = None if b is None else torch.cat([b, b.new_zeros(pad_rows)], 0)
@@ -1750,124 +1708,85 @@ def _unlayout_grads(dw, db, col_index, pad_rows):
     return dw, db
 
 
-class SplitKLinearFn(torch.autograd.Function):
-    """y = x W^T + b on hipBLASLt, like F.linear, but with dW = dY^T X evaluated as a batched GEMM over S row chunks
-    + a sum: with M = 100k..400k rows and an output of a few hundred x a few hundred elements the single GEMM runs on
-    17-34 workgroups of the 256 CUs (568 us for 1080x270 over 401k rows), the batched form fills the GPU.
-    ``weight`` / ``bias`` are the (fp32) master parameters: they are cast to ``cdtype`` inside (no autograd cast nodes) and
-    their gradients are returned in the masters' dtype straight from the fp32 chunk sum (no bf16 round trip)."""
+class BigLinearFn(torch.autograd.Function):
+    """y = x W^T + b like F.linear for M = 100k..400k rows, with dW = dY^T X evaluated as a batched GEMM over S row chunks + a sum:
+    with an output of a few hundred x a few hundred elements the single GEMM runs on 17-34 workgroups of the 256 CUs (568 us for
+    1080x270 over 401k rows), the batched form fills the GPU.  ``weight`` / ``bias`` are the (fp32) master parameters: they are
+    cast to ``cdtype`` inside (no autograd cast nodes) and their gradients are returned in the masters' dtype straight from the
+    fp32 chunk sum (no bf16 round trip).
+    ``via_knt``: forward and dX through the library's fused-GEMM kernel used at rank 0 (``mtlora_linear_fwd/bwd`` with r_s = 0,
+    T = 0) instead of hipBLASLt: for the skinny-K / huge-M GEMMs of the heads (e.g. 100k x 272 -> 1080) hipBLASLt reaches ~1.3 TB/s
+    and ~12 % of the MFMA peak, k_nt ~3 TB/s (W^T re-materialised per step: the weight is trained); a narrow dW (N <= 64) then
+    comes from the library's split-M TN reduction."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, splits: int, zero_bias_grad: bool, cdtype, col_index=None, n_cols=0, pad_rows=0):
-        w, bl = _layout_weight(weight, bias, cdtype, col_index, n_cols, pad_rows)
-        ctx.save_for_backward(x, w)
+    def forward(ctx, x, weight, bias, splits: int, zero_bias_grad: bool, cdtype, via_knt: bool, col_index=None, n_cols=0, pad_rows=0):
+        w, bl = _layout_weight(weight.detach(), None if bias is None else bias.detach(), cdtype, col_index, n_cols, pad_rows)
         ctx.wlayout = (col_index, pad_rows)
-        ctx.has_bias = bias is not None
-        ctx.splits = splits
-        ctx.zero_bias_grad = zero_bias_grad
-        ctx.wdtype = weight.dtype
+        ctx.via_knt, ctx.splits, ctx.zero_bias_grad = via_knt, splits, zero_bias_grad
+        ctx.has_bias, ctx.wdtype = bias is not None, weight.dtype
         ctx.bdtype = None if bias is None else bias.dtype
-        return torch.nn.functional.linear(x, w, None if bl is None else bl.to(cdtype))
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, w = ctx.saved_tensors
-        gy = gy.contiguous()
-        M, K = x.shape
-        N = w.shape[0]
-        S = ctx.splits
-        dx = gy @ w if ctx.needs_input_grad[0] else None
-
-        def wgrads():
-            dw = None
-            if ctx.needs_input_grad[1]:
-                part = torch.bmm(gy.view(S, M // S, N).transpose(1, 2), x.view(S, M // S, K))  # (S, N, K)
-                dw = part.sum(0, dtype=torch.float32).to(ctx.wdtype)
-            db = None
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                # zero_bias_grad: the output feeds a training-mode BatchNorm, whose backward returns columns that sum to zero
-                # EXACTLY (dx = scale (dy' - mean(dy') - xhat mean(dy' xhat)), sum(xhat) = 0): the bias gradient is 0, and
-                # summing 400k x 1080 elements only to obtain rounding noise costs a full pass over the gradient
-                if ctx.zero_bias_grad:
-                    db = torch.zeros(N, dtype=ctx.bdtype, device=gy.device)
-                else:  # two-stage column sum: a (400k x 21) sum(0) runs on 64 workgroups for 256 us in one stage
-                    db = column_sum(gy).to(ctx.bdtype)
-            return _unlayout_grads(dw, db, *ctx.wlayout)
-
-        dw, db = wgrads()
-        return dx, dw, db, None, None, None, None, None, None
-
-
-class PlainLinearFn(torch.autograd.Function):
-    """y = x W^T + b through the library's fused-GEMM kernel used at rank 0 (``mtlora_linear_fwd/bwd`` with r_s = 0, T = 0):
-    for the skinny-K / huge-M GEMMs of the heads (e.g. 100k x 272 -> 1080) hipBLASLt reaches ~1.3 TB/s and ~12 % of the
-    MFMA peak, k_nt ~3 TB/s.  dX comes from the same kernel (W^T re-materialised per step: the weight is trained); dW / db
-    stay on hipBLASLt as the split-reduction batched GEMM of SplitKLinearFn."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, splits: int, zero_bias_grad: bool, cdtype, col_index=None, n_cols=0, pad_rows=0):
+        if not via_knt:
+            ctx.save_for_backward(x, w)
+            return torch.nn.functional.linear(x, w, None if bl is None else bl.to(cdtype))
         L.require_gpu(x, weight)
         M, K = x.shape
-        w, bias_l = _layout_weight(weight, bias, cdtype, col_index, n_cols, pad_rows)
         N = w.shape[0]
-        meta = LinearMeta(K=K, N=N, r_s=0, r_t=(), scale_s=0.0, scale_t=(), mode=0, has_x_tasks=False, dropout_p=0.0, seed=0,
-                          dtype=cdtype)
+        ctx.meta = meta = LinearMeta(K=K, N=N, r_s=0, r_t=(), scale_s=0.0, scale_t=(), mode=0, has_x_tasks=False, dropout_p=0.0,
+                                     seed=0, dtype=cdtype)
         d = meta.desc(M)
         lib = L.lib()
-        ctx_bytes = _desc_bytes("ctx", lib.mtlora_linear_ctx_bytes, meta, M, d)
-        if ctx_bytes < 0:
-            raise RuntimeError(f"mtlora_amd: invalid plain-linear shape M={M} K={K} N={N}")
-        ctxbuf = torch.empty(max(ctx_bytes, 16), dtype=torch.uint8, device=x.device)
+        ctx_bytes = _size_query("ctx", lib.mtlora_linear_ctx_bytes, d)
+        ctxbuf = _scratch(ctx_bytes, x.device, "plain-linear shape (M, K, N)", M, K, N, floor=16)
         y = torch.empty((M, N), dtype=cdtype, device=x.device)
-        bf = None if bias_l is None else bias_l.float().contiguous()
+        bf = None if bl is None else bl.float().contiguous()
         st = lib.mtlora_linear_fwd(ctypes.byref(d), L.ptr(x), L.ptr_array(None), L.ptr(w), L.ptr(bf), L.ptr(None), L.ptr(None),
                                    L.ptr_array(None), L.ptr_array(None), L.ptr(y), L.ptr_array(None), L.ptr(ctxbuf), ctx_bytes,
                                    L.stream_ptr())
         L.check(st, "mtlora_linear_fwd (rank 0)")
         ctx.save_for_backward(x, w, ctxbuf)
-        ctx.wlayout = (col_index, pad_rows)
-        ctx.meta, ctx.splits, ctx.zero_bias_grad = meta, splits, zero_bias_grad
-        ctx.has_bias, ctx.wdtype = bias is not None, weight.dtype
-        ctx.bdtype = None if bias is None else bias.dtype
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        x, w, ctxbuf = ctx.saved_tensors
+        x, w, *ctxbuf = ctx.saved_tensors
         gy = gy.contiguous()
         M, K = x.shape
         N = w.shape[0]
         S = ctx.splits
+        need = ctx.needs_input_grad
         dx = None
-        if ctx.needs_input_grad[0]:
+        if need[0] and not ctx.via_knt:
+            dx = gy @ w
+        elif need[0]:
             d = ctx.meta.desc(M)
             lib = L.lib()
-            sb = _desc_bytes("bwd", lib.mtlora_linear_bwd_scratch_bytes, ctx.meta, M, d)
-            scratch = torch.empty(max(sb, 16), dtype=torch.uint8, device=x.device)
+            sb = _size_query("bwd", lib.mtlora_linear_bwd_scratch_bytes, d)
+            scratch = _scratch(sb, x.device, "plain-linear backward shape (M, K, N)", M, K, N, floor=16)
             wt = w.t().contiguous()
             dx = torch.empty((M, K), dtype=x.dtype, device=x.device)
             st = lib.mtlora_linear_bwd(ctypes.byref(d), L.ptr(x), L.ptr_array(None), L.ptr(wt), L.ptr(gy), L.ptr_array(None),
-                                       L.ptr(ctxbuf), ctxbuf.numel(), L.ptr(dx), L.ptr_array(None), L.ptr(None), L.ptr(None),
+                                       L.ptr(ctxbuf[0]), ctxbuf[0].numel(), L.ptr(dx), L.ptr_array(None), L.ptr(None), L.ptr(None),
                                        L.ptr_array(None), L.ptr_array(None), L.ptr(scratch), sb, L.stream_ptr())
             L.check(st, "mtlora_linear_bwd (rank 0)")
-        def wgrads():
-            dw = None
-            if ctx.needs_input_grad[1]:
-                if N <= 64:  # narrow output: the library's split-M TN reduction reads x once (hipBLASLt: 0.8 TB/s here)
-                    dw = gemm_tn(gy, x).to(ctx.wdtype)
-                else:
-                    part = torch.bmm(gy.view(S, M // S, N).transpose(1, 2), x.view(S, M // S, K))
-                    dw = part.sum(0, dtype=torch.float32).to(ctx.wdtype)
-            db = None
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                if ctx.zero_bias_grad:
-                    db = torch.zeros(N, dtype=ctx.bdtype, device=gy.device)
-                else:
-                    db = column_sum(gy).to(ctx.bdtype)
-            return _unlayout_grads(dw, db, *ctx.wlayout)
-
-        dw, db = wgrads()
-        return dx, dw, db, None, None, None, None, None, None
+        dw = None
+        if need[1]:
+            if ctx.via_knt and N <= 64:  # narrow output: the library's split-M TN reduction reads x once (hipBLASLt: 0.8 TB/s here)
+                dw = gemm_tn(gy, x).to(ctx.wdtype)
+            else:
+                part = torch.bmm(gy.view(S, M // S, N).transpose(1, 2), x.view(S, M // S, K))  # (S, N, K)
+                dw = part.sum(0, dtype=torch.float32).to(ctx.wdtype)
+        db = None
+        if ctx.has_bias and need[2]:
+            # zero_bias_grad: the output feeds a training-mode BatchNorm, whose backward returns columns that sum to zero
+            # EXACTLY (dx = scale (dy' - mean(dy') - xhat mean(dy' xhat)), sum(xhat) = 0): the bias gradient is 0, and
+            # summing 400k x 1080 elements only to obtain rounding noise costs a full pass over the gradient
+            if ctx.zero_bias_grad:
+                db = torch.zeros(N, dtype=ctx.bdtype, device=gy.device)
+            else:  # two-stage column sum: a (400k x 21) sum(0) runs on 64 workgroups for 256 us in one stage
+                db = column_sum(gy).to(ctx.bdtype)
+        dw, db = _unlayout_grads(dw, db, *ctx.wlayout)
+        return dx, dw, db, None, None, None, None, None, None, None
 
 
 def gemm_tn(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -1880,11 +1799,9 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     Nb = b.shape[1]
     lib = L.lib()
     sb = lib.mtlora_gemm_tn_scratch_bytes(M, Na, Nb)
-    if sb < 0:
-        raise RuntimeError(f"mtlora_amd: invalid gemm_tn shape M={M} Na={Na} Nb={Nb}")
-    scratch = torch.empty(sb, dtype=torch.uint8, device=a.device)
+    scratch = _scratch(sb, a.device, "gemm_tn shape (M, Na, Nb)", M, Na, Nb)
     out = torch.empty((Na, Nb), dtype=torch.float32, device=a.device)
-    st = lib.mtlora_gemm_tn(L.ptr(a), L.ptr(b), L.ptr(out), M, Na, Nb, Na, Nb, _DT_CODE[a.dtype],
+    st = lib.mtlora_gemm_tn(L.ptr(a), L.ptr(b), L.ptr(out), M, Na, Nb, Na, Nb, L._DT[a.dtype],
                             L.ptr(scratch), sb, L.stream_ptr())
     L.check(st, "mtlora_gemm_tn")
     return out
@@ -1895,15 +1812,13 @@ _PLAIN_VIA_KNT = os.environ.get("MTLORA_HEAD_GEMM", "knt") != "blas"
 
 def _big_linear(x, weight, bias, S, feeds_batchnorm, cdtype, col_index=None, pad_rows=0):
     K, N = x.shape[1], weight.shape[0] + pad_rows
-    if (_PLAIN_VIA_KNT and cdtype in _HOT_DTYPES and K % 8 == 0 and N % 8 == 0
-            and x.dtype == cdtype):
-        return PlainLinearFn.apply(x, weight, bias, S, feeds_batchnorm, cdtype, col_index, K, pad_rows)
-    return SplitKLinearFn.apply(x, weight, bias, S, feeds_batchnorm, cdtype, col_index, K, pad_rows)
+    via_knt = _PLAIN_VIA_KNT and cdtype in _HOT_DTYPES and K % 8 == 0 and N % 8 == 0 and x.dtype == cdtype
+    return BigLinearFn.apply(x, weight, bias, S, feeds_batchnorm, cdtype, via_knt, col_index, K, pad_rows)
 
 
 def linear_big_m(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
                  feeds_batchnorm: bool = False, col_index: Optional[torch.Tensor] = None, pad_rows: int = 0) -> torch.Tensor:
-    """F.linear for (M, K) inputs; switches to SplitKLinearFn when M is large and the weight is trained.
+    """F.linear for (M, K) inputs through BigLinearFn when the weight is trained (else plain F.linear).
     feeds_batchnorm=True: the output goes straight into a training-mode BatchNorm -> the bias gradient is exactly 0.
     col_index: x has MORE columns than the weight -- column c of the weight multiplies column col_index[c] of x (the padded channel
     layout of ConcatUpsampleFn; the other columns of x meet zeros).  pad_rows: the output gets that many extra all-zero columns."""
@@ -1925,11 +1840,8 @@ def linear_big_m(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
             with torch.autocast("cuda", enabled=False):
                 return _big_linear(x.to(dt), weight, bias, S, feeds_batchnorm, dt, col_index, pad_rows)
         return _big_linear(x, weight, bias, S, feeds_batchnorm, x.dtype, col_index, pad_rows)
-    if col_index is not None:
-        weight = weight.new_zeros(weight.shape[0], x.shape[1]).index_copy(1, col_index, weight)
-    if pad_rows:
-        weight = torch.cat([weight, weight.new_zeros(pad_rows, weight.shape[1])], 0)
-        bias = None if bias is None else torch.cat([bias, bias.new_zeros(pad_rows)], 0)
+    if col_index is not None or pad_rows:
+        weight, bias = _layout_weight(weight, bias, weight.dtype, col_index, x.shape[1], pad_rows)
     return torch.nn.functional.linear(x, weight, bias)
 
 
@@ -2023,7 +1935,7 @@ class BlockCall:
         d = L.BlockDesc()
         d.B, d.H, d.W, d.C, d.hidden = B, self.H, self.W, C, self.hidden
         d.num_heads, d.window_size, d.shift = self.num_heads, self.window_size, self.shift
-        d.dtype, d.x_dtype, d.has_norm1 = _DT_CODE[cdtype], _DT_CODE[x_dtype], 1 if self.has_norm1 else 0
+        d.dtype, d.x_dtype, d.has_norm1 = L._DT[cdtype], L._DT[x_dtype], 1 if self.has_norm1 else 0
         d.eps1, d.eps2, d.eps_next = self.eps
         d.attn_scale, d.mask_value = self.attn_scale, self.mask_value
         M = B * self.H * self.W
@@ -2142,7 +2054,6 @@ class SwinBlockRunFn(torch.autograd.Function):
         lib = L.lib()
         g_x = g_x.contiguous() if g_x.dtype == xs[0].dtype else g_x.to(xs[0].dtype).contiguous()
         g_n = g_n.contiguous() if g_n.dtype == cdtype else g_n.to(cdtype).contiguous()
-        side = _factor_stream
         grads_flat = []
         for bi in range(n - 1, -1, -1):
             c = calls[bi]
@@ -2166,24 +2077,12 @@ class SwinBlockRunFn(torch.autograd.Function):
                 g.dA[i], g.dB[i] = fg[2 * i].data_ptr(), fg[2 * i + 1].data_ptr()
             # everything phase 2 writes on the side stream: the eight factor gradients and the LayerNorm dgamma / dbeta (their
             # second-stage reduces ride along, csrc/internal.h) -- none of their Parameters may have a .grad to accumulate into
-            fparams = c.factor_params + c.norm_params
-            use_side = side is not None and side.device == dev and M >= _FACTOR_MIN_M and _side_safe_params(fparams)
-            if _side_join_pending(fparams, dev):
-                use_side = False
             args = (ctypes.byref(d), ctypes.byref(p), xs[bi].data_ptr(), 0 if ns[bi] is None else ns[bi].data_ptr(),
                     xs[bi + 1].data_ptr(), g_x.data_ptr(), g_n.data_ptr(), saves[bi].data_ptr(), saves[bi].numel(), ctypes.byref(g),
                     scratch.data_ptr(), scb)
-            if use_side:
-                L.check(lib.mtlora_block_bwd(*args, 1, L.stream_ptr()), "mtlora_block_bwd")
-                ev = torch.cuda.Event()
-                ev.record()
-                side.wait_event(ev)
-                L.check(lib.mtlora_block_bwd(*args, 2, ctypes.c_void_p(side.cuda_stream)), "mtlora_block_bwd (factor gradients)")
-                _side_mark_pending(fparams, side)
-                for t in (xs[bi], xs[bi + 1], saves[bi], scratch, lnw, g_n, *fg) + (() if ns[bi] is None else (ns[bi],)):
-                    t.record_stream(side)  # allocated on this stream, still in use on the side stream when freed here
-            else:
-                L.check(lib.mtlora_block_bwd(*args, 0, L.stream_ptr()), "mtlora_block_bwd")
+            _run_factor_phases(c.factor_params + c.norm_params, fg, M, dev, True,
+                               lambda phase, sp: L.check(lib.mtlora_block_bwd(*args, phase, sp), "mtlora_block_bwd"),
+                               lambda: (xs[bi], xs[bi + 1], saves[bi], scratch, lnw, g_n, *fg) + (() if ns[bi] is None else (ns[bi],)))
             blk = [dbias, None, None]
             if c.has_norm1:
                 blk += [lnw[0], lnw[1]]

@@ -449,7 +449,7 @@ class SwinTransformerBlock(nn.Module):
         B, L, C = x.shape
         assert L == H * W, "input feature has wrong size"
         # x feeds norm1 AND the skip connection: one autograd node for both, so that the skip gradient is added inside the
-        # LayerNorm backward kernel instead of by a separate full-size add (functional.LayerNormForkFn)
+        # LayerNorm backward kernel instead of by a separate full-size add (functional.LayerNormFn, fork form)
         if normed is None:
             shortcut, xn = Fn.layer_norm_fork(self.norm1, x)
         else:
