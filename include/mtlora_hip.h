@@ -745,6 +745,55 @@ int mtlora_adamw_sched_update_dev(const void* table, const void* grads, int64_t 
                                   double backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes,
                                   float* acc, const int64_t* acc_offsets, int accum_steps, void* sched_dev, void* stream);
 
+/* The other two optimizers of the reference's optimizer.py:53-66 on the same machinery (additive, ABI stays 12): the table of
+ * mtlora_adamw_sizes / mtlora_adamw_table, the gradient-pointer array, the norm and finish launches, the control block (words
+ * [0..4] as above), the skip on inf / nan, the GradScaler words and the fixed-order reductions are those of mtlora_adamw_update;
+ * only what follows the finish launch differs.  Every argument that mtlora_adamw_update has means the same here.  Each has a
+ * by-value entry (`groups`: HOST records) and a _dev entry (`groups_dev`: a DEVICE buffer of MTLORA_ADAMW_GROUPS_DEV_BYTES whose
+ * first n_groups records the caller writes and whose tail is the library's; a record the by-value entry rejects sets found_inf
+ * on the device: the step is skipped, the norm is nan).  With equal records the two entries give bit-identical results.
+ *   mtlora_sgd_update[_dev]   torch.optim.SGD(momentum, dampening=0, weight_decay, nesterov) -- optimizer.py:56 -- in THREE
+ *                        launches (norm, finish, step).  Only `m` of the table is used: the momentum buffer (`v` must still
+ *                        be non-null; pass m).  With g the unscaled, clipped gradient (g_stored * ctrl[3]), per element:
+ *                            g' = g + wd p;  m = mu m + g';  p -= lr (g' + mu m) if nesterov, else p -= lr m
+ *                        A zero-initialised m gives torch's first step (m = g') because dampening is 0.  mu == 0: plain SGD,
+ *                        p -= lr g', and m is neither read nor written.  Rejected records: lr, momentum or weight_decay
+ *                        negative or nan, nesterov not 0 or 1.
+ *   mtlora_lamb_update[_dev]  apex FusedLAMB(bias_correction, grad_averaging, adam_w_mode all True) in FOUR launches (norm,
+ *                        finish, moments + partials, apply).  The records are mtlora_adamw_group.  `scratch`: TWICE the
+ *                        scratch_bytes mtlora_adamw_sizes reports (four words per chunk).  `max_grad_norm` <= 0 disables
+ *                        LAMB's own clip.  With n = ctrl[0] * ctrl[2], the norm of the gradients after the max_norm clip:
+ *                            c = n / max_grad_norm if n > max_grad_norm else 1   (ctrl[MTLORA_LAMB_CTRL_CLIP]);  ctrl[3] = ctrl[2] / *scale / c
+ *                            g = g_stored * ctrl[3];  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2        (launch 3, stored)
+ *                            u = (m / (1 - b1^t)) / (sqrt(v) / sqrt(1 - b2^t) + eps) + wd p                    (never stored)
+ *                            per tensor |p| and |u|: launch 3 writes one fp32 partial of each per chunk, launch 4 adds a
+ *                            tensor's partials in double in a fixed order (no float atomics; a chunk never spans tensors)
+ *                            ratio = lr |p| / |u| if (wd != 0 or use_nvlamb) and |p| != 0 and |u| != 0, else lr
+ *                            p -= ratio u     (launch 4 forms u again from the stored m, v and the still unmodified p)
+ *                        A skipped step leaves p, m, v and t bitwise unchanged: launches 3 and 4 read found_inf before they
+ *                        write.  max_grad_norm and use_nvlamb are launch arguments: a captured graph keeps those of its capture. */
+#define MTLORA_LAMB_CTRL_CLIP 7
+typedef struct mtlora_sgd_group {
+    double lr, momentum, nesterov, reserved, weight_decay; /* nesterov: 0.0 or 1.0; reserved: 0.0 */
+} mtlora_sgd_group;
+int mtlora_sgd_update(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const mtlora_sgd_group* groups,
+                      int n_groups, float max_norm, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker,
+                      float growth_factor, float backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes,
+                      void* stream);
+int mtlora_sgd_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks,
+                          const mtlora_sgd_group* groups_dev, int n_groups, float max_norm, float* ctrl, float* norm_out,
+                          float* scale, int32_t* growth_tracker, double growth_factor, double backoff_factor,
+                          int growth_interval, void* scratch, int64_t scratch_bytes, void* stream);
+int mtlora_lamb_update(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks,
+                       const mtlora_adamw_group* groups, int n_groups, float max_norm, float max_grad_norm, int use_nvlamb,
+                       float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker, float growth_factor,
+                       float backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes, void* stream);
+int mtlora_lamb_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks,
+                           const mtlora_adamw_group* groups_dev, int n_groups, float max_norm, float max_grad_norm,
+                           int use_nvlamb, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker,
+                           double growth_factor, double backoff_factor, int growth_interval, void* scratch,
+                           int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Batch ingest (ABI v12): the tail of the reference's loader pipelines on the device -- RandomHorizontalFlip,
  * AddIgnoreRegions, ToTensor and Normalize of data/custom_transforms.py:192-209 and :266-341 -- for one batch in the

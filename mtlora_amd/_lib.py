@@ -72,6 +72,11 @@ class AdamwGroup(Structure):
     _fields_ = [("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double)]
 
 
+class SgdGroup(Structure):
+    """mtlora_sgd_group: one parameter group of mtlora_sgd_update, laid out like AdamwGroup (nesterov is 0.0 or 1.0)"""
+    _fields_ = [("lr", c_double), ("momentum", c_double), ("nesterov", c_double), ("reserved", c_double), ("weight_decay", c_double)]
+
+
 class LrSchedule(Structure):
     """mtlora_lr_schedule: the record of a device-side learning-rate schedule (mtlora_adamw_sched_update_dev); counts are int64,
     values doubles"""
@@ -106,6 +111,7 @@ ADAMW_CHUNK, ADAMW_MAX_GROUPS, ADAMW_CTRL_WORDS = 4096, 16, 64
 ADAMW_GROUPS_DEV_BYTES = 1152  # device buffer of mtlora_adamw_update_dev: MAX_GROUPS records, then the library's derived values
 ADAMW_CTRL_MICRO, ADAMW_CTRL_UPDATED = 5, 6  # mtlora_adamw_accum_update_dev: the micro-step counter, "the last call updated"
 ADAMW_MAX_ACCUM_STEPS = 1 << 24
+LAMB_CTRL_CLIP = 7  # mtlora_lamb_update: the divisor of LAMB's own max_grad_norm clip
 LR_MAX_MILESTONES = 16
 LR_COSINE, LR_STEP, LR_LINEAR, LR_MULTISTEP = 1, 2, 3, 4
 # the schedule buffer of mtlora_adamw_sched_update_dev: the record, the int64 count of update calls, lr_used[MAX_GROUPS]
@@ -246,6 +252,14 @@ _SIGS = {
     "mtlora_adamw_sched_update_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_float, c_void_p, c_void_p,
                                               c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_int64, c_void_p, c_void_p,
                                               c_int, c_void_p, c_void_p]),
+    "mtlora_sgd_update": (c_int, [c_void_p, c_void_p, c_int64, c_int64, POINTER(SgdGroup), c_int, c_float, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_float, c_float, c_int, c_void_p, c_int64, c_void_p]),
+    "mtlora_sgd_update_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_float, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_int64, c_void_p]),
+    "mtlora_lamb_update": (c_int, [c_void_p, c_void_p, c_int64, c_int64, POINTER(AdamwGroup), c_int, c_float, c_float, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p, c_int64, c_void_p]),
+    "mtlora_lamb_update_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_float, c_float, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_int64, c_void_p]),
     "mtlora_ingest_scratch_bytes": (c_int64, [c_int, c_int64]),
     "mtlora_ingest_batch": (c_int, [POINTER(IngestJob), c_int, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                     c_void_p]),

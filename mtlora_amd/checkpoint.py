@@ -28,7 +28,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .lora import MTLoRALinear, map_old_state_dict_weights
-from .optim import FusedAdamW, LossScaler
+from .optim import FusedOptimizer, LossScaler
 
 _LOG = logging.getLogger("mtlora_amd.checkpoint")
 
@@ -267,7 +267,7 @@ class SnapshotHandle:
             model._metadata = lay.model_metadata
         out: Dict[str, Any] = {"model": model, "optimizer": None, "scaler": None}
         opt = own.optimizer
-        if isinstance(opt, FusedAdamW):
+        if isinstance(opt, FusedOptimizer):
             tensors = {n: fix(self._view(("optimizer", n))) for n in lay.fused_names}
             out["optimizer"] = opt.state_dict_from(tensors, self._host["optimizer"])
         elif opt is not None:
@@ -324,7 +324,8 @@ class _Layout:
 
 class TrainState:
     """Everything a train step mutates, enumerated ONCE: every parameter with ``requires_grad``, every module buffer, the
-    optimizer's state (a ``FusedAdamW``'s two moment buffers, its control block -- step count, accumulation counter -- and its
+    optimizer's state (a fused optimizer's flat state buffers -- ``FusedAdamW``'s and ``FusedLAMB``'s two moment buffers, ``FusedSGD``'s
+    momentum buffer --, its control block -- step count, accumulation counter -- and its
     schedule buffer; a torch optimizer's state tensors, enumerated at the first snapshot after a step), the ``LossScaler``'s two
     device words and the meters' bank.  GPU only.
 
@@ -368,7 +369,7 @@ class TrainState:
         entries, host = list(self._model_entries), {}
         opt, sc = self.optimizer, self.loss_scaler
         fused_names: List[str] = []
-        if isinstance(opt, FusedAdamW):
+        if isinstance(opt, FusedOptimizer):
             tensors = opt.state_tensors()
             fused_names = list(tensors)
             entries += [(("optimizer", n), t) for n, t in tensors.items()]

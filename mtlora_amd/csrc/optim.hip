@@ -53,6 +53,9 @@
 //                         place of the record's lr; thread 0 writes u + 1.  A record opt_sched_ok rejects raises found_inf like a
 //                         bad hyper-parameter record.  An accumulating micro-step leaves before any of this.
 //   k_optim_norm, k_optim_step  the instantiations above, unchanged: what they read of the schedule is h.lr[g] in the groups' tail.
+//
+// mtlora_sgd_update[_dev] and mtlora_lamb_update[_dev] run the reference's other two optimizers on the same table, norm and finish
+// launches: see "SGD and LAMB" below.
 #include "common.h"
 
 namespace {
@@ -124,6 +127,29 @@ __host__ __device__ inline bool opt_derive(const mtlora_adamw_group& s, OptHyper
     return s.lr >= 0.0 && s.eps >= 0.0 && s.weight_decay >= 0.0 && s.beta1 >= 0.0 && s.beta1 < 1.0 && s.beta2 >= 0.0 && s.beta2 < 1.0;
 }
 
+// the other optimizers on this machinery (see "SGD and LAMB" below).  Their derived values use the same arrays: SGD keeps the
+// weight decay itself in `decay`, the momentum in b1 and nesterov (0 / 1) in b2; LAMB is AdamW's set with the weight decay itself
+enum { OPT_ADAMW = 0, OPT_SGD = 1, OPT_LAMB = 2 };
+static_assert(sizeof(mtlora_sgd_group) == sizeof(mtlora_adamw_group) && __builtin_offsetof(mtlora_sgd_group, momentum) == __builtin_offsetof(mtlora_adamw_group, beta1) &&
+                  __builtin_offsetof(mtlora_sgd_group, nesterov) == __builtin_offsetof(mtlora_adamw_group, beta2) &&
+                  __builtin_offsetof(mtlora_sgd_group, weight_decay) == __builtin_offsetof(mtlora_adamw_group, weight_decay),
+              "an SGD record is read through the AdamW record's fields: beta1 = momentum, beta2 = nesterov");
+template <int ALG>
+__host__ __device__ inline bool opt_derive_as(const mtlora_adamw_group& s, OptHyper& h) {
+    if constexpr (ALG == OPT_ADAMW) return opt_derive(s, h);
+    if constexpr (ALG == OPT_SGD) {
+        h.lr = (float)s.lr;
+        h.decay = (float)s.weight_decay;
+        h.b1 = (float)s.beta1;
+        h.b2 = s.beta2 != 0.0 ? 1.f : 0.f;
+        h.omb1 = h.omb2 = h.eps = 0.f;
+        return s.lr >= 0.0 && s.weight_decay >= 0.0 && s.beta1 >= 0.0 && (s.beta2 == 0.0 || s.beta2 == 1.0);
+    }
+    const bool ok = opt_derive(s, h);  // LAMB
+    h.decay = (float)s.weight_decay;
+    return ok;
+}
+
 // the schedule buffer of mtlora_adamw_sched_update_dev
 struct OptSched {
     mtlora_lr_schedule rec;
@@ -187,6 +213,8 @@ enum { OC_NORM = 0, OC_FOUND_INF = 1, OC_COEF = 2, OC_GMUL = 3, OC_STEP = 4, OC_
 enum { OC_MICRO = MTLORA_ADAMW_CTRL_MICRO, OC_UPDATED = MTLORA_ADAMW_CTRL_UPDATED };  // gradient accumulation only
 static_assert(OC_MICRO > OC_STEP && OC_UPDATED > OC_MICRO && OC_UPDATED < OC_BC, "control block");
 static_assert(OC_BC + 2 * OPT_MAXG <= MTLORA_ADAMW_CTRL_WORDS, "control block");
+enum { OC_LAMB_CLIP = MTLORA_LAMB_CTRL_CLIP };  // LAMB only: the divisor of its own max_grad_norm clip
+static_assert(OC_LAMB_CLIP > OC_UPDATED && OC_LAMB_CLIP < OC_BC, "control block");
 
 // where k_optim_step finds a tensor's gradient, and whether this launch may write at all
 struct OptGradPtrs {  // the caller's gradient pointers
@@ -306,14 +334,17 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_norm(const OptTensor* __r
 
 // G: OptGroups (by value) or OptGroupsDev.  ACC: gradient accumulation over accum_steps micro-steps -- ctrl[OC_MICRO] decides, on
 // the device, whether this call is the cycle's last; if it is not, the counter moves and NOTHING else is written.  SCHED (with
-// OptGroupsDev and ACC): an update call takes each group's lr from the schedule in `sch` and counts itself there.
-template <class G, bool ACC, bool SCHED = false>
+// OptGroupsDev and ACC): an update call takes each group's lr from the schedule in `sch` and counts itself there.  ALG: whose
+// records these are -- SGD has no bias corrections; LAMB folds its own clip at `lamb_max_norm` (of the norm AFTER the max_norm
+// clip) into ctrl[OC_GMUL].
+template <class G, bool ACC, bool SCHED = false, int ALG = OPT_ADAMW>
 __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __restrict__ partials, const uint32_t* __restrict__ flags,
                                                               int n_chunks, const G grp, float max_norm, float* __restrict__ ctrl,
                                                               float* __restrict__ norm_out, float* __restrict__ scale,
                                                               int32_t* __restrict__ tracker, float growth, float backoff, int interval,
-                                                              int accum_steps, OptSched* __restrict__ sch) {
+                                                              int accum_steps, OptSched* __restrict__ sch, float lamb_max_norm) {
     static_assert(!SCHED || (ACC && __is_same(G, OptGroupsDev)), "the schedule rides on the accumulating device-record entry");
+    static_assert(ALG == OPT_ADAMW || (!ACC && !SCHED), "accumulation and the schedule are AdamW's");
     __shared__ double red[OPT_THREADS];
     __shared__ uint32_t fl[OPT_THREADS];
     __shared__ float step_new;
@@ -343,7 +374,7 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __res
                 sch->lr_used[tid] = r.lr;
             }
             OptHyper h;
-            if (!opt_derive(r, h)) f = 1u;  // what the host entry rejects: found_inf, a skipped step
+            if (!opt_derive_as<ALG>(r, h)) f = 1u;  // what the host entry rejects: found_inf, a skipped step
             opt_put(*grp.hyp, tid, h);
             b1d = r.beta1;
             b2d = r.beta2;
@@ -377,7 +408,14 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __res
         ctrl[OC_NORM] = norm;
         ctrl[OC_FOUND_INF] = found ? 1.f : 0.f;
         ctrl[OC_COEF] = coef;
-        ctrl[OC_GMUL] = coef * inv;
+        if constexpr (ALG == OPT_LAMB) {
+            const float n2 = norm * coef;  // (a nan norm compares false: c = 1, and the step is skipped anyway)
+            const float c = lamb_max_norm > 0.f && n2 > lamb_max_norm ? n2 / lamb_max_norm : 1.f;
+            ctrl[OC_LAMB_CLIP] = c;
+            ctrl[OC_GMUL] = coef * inv / c;
+        } else {
+            ctrl[OC_GMUL] = coef * inv;
+        }
         ctrl[OC_STEP] = st;
         if constexpr (ACC) {  // the cycle ends here, whether the step was taken or skipped
             ctrl[OC_MICRO] = 0.f;
@@ -402,6 +440,7 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_finish(const float* __res
             }
         }
     }
+    if constexpr (ALG == OPT_SGD) return;  // no bias corrections
     __syncthreads();
     if (tid < grp.n) {
         const double t = (double)step_new;
@@ -500,6 +539,213 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_step(const OptTensor* __r
     }
 }
 
+// ---- SGD and LAMB (optimizer.py:53-66: the reference's `sgd` and `fused_lamb`) -----------------------------------------------
+// The same table, chunk grid, gradient-pointer array, k_optim_norm and k_optim_finish (ALG picks the record's meaning); what
+// follows the finish launch is:
+//   k_sgd_step      torch.optim.SGD(momentum = mu, dampening = 0, nesterov): g' = g gmul + wd p;  m = mu m + g';
+//                   p -= lr (nesterov ? g' + mu m : m).  mu == 0: p -= lr g' and m is not touched.  v is never touched.
+//   k_lamb_moments  g = g gmul (gmul carries both clips);  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2, stored;
+//                   u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + wd p;  pn[chunk] = sum p^2, un[chunk] = sum u^2 (one workgroup
+//                   owns both words).  p is only read.
+//   k_lamb_apply    every workgroup adds the partials of ITS tensor's chunks (a tensor's chunks are consecutive and a chunk never
+//                   spans tensors) in double in a fixed order -- all workgroups of a tensor get the same bits --, forms the trust
+//                   ratio, forms u AGAIN from the stored m, v and the p that nothing has written yet (12 bytes read per element
+//                   instead of 4 written and 4 read for a stored u, and no buffer the size of the parameters), and p -= ratio u.
+// All three leave on found_inf before they read or write anything else.
+
+// one chunk, element by element: f(g, p, m, v) on registers.  A: which of g / m / v are read (p always is) and which of p / m / v
+// are written.  16-byte accesses where every pointer in use is 16-byte aligned, with the last n % 4 elements scalar; scalar else.
+enum { OS_G = 1, OS_M = 2, OS_V = 4, OS_WP = 8, OS_WM = 16, OS_WV = 32 };
+template <int A, class F>
+__device__ __forceinline__ void opt_stream(int n, const float* __restrict__ g, float* __restrict__ p, float* __restrict__ m,
+                                           float* __restrict__ v, F f) {
+    const int tid = threadIdx.x;
+    uintptr_t al = (uintptr_t)p;
+    if constexpr ((A & OS_G) != 0) al |= (uintptr_t)g;
+    if constexpr ((A & (OS_M | OS_WM)) != 0) al |= (uintptr_t)m;
+    if constexpr ((A & (OS_V | OS_WV)) != 0) al |= (uintptr_t)v;
+    auto one = [&](int i) {
+        float gg = 0.f, pp = p[i], mm = 0.f, vv = 0.f;
+        if constexpr ((A & OS_G) != 0) gg = g[i];
+        if constexpr ((A & OS_M) != 0) mm = m[i];
+        if constexpr ((A & OS_V) != 0) vv = v[i];
+        f(gg, pp, mm, vv);
+        if constexpr ((A & OS_WP) != 0) p[i] = pp;
+        if constexpr ((A & OS_WM) != 0) m[i] = mm;
+        if constexpr ((A & OS_WV) != 0) v[i] = vv;
+    };
+    if ((al & 15u) == 0) {
+        const int nv = n >> 2;
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        f32x4 xg[OPT_VPT], xp[OPT_VPT], xm[OPT_VPT], xv[OPT_VPT];
+#pragma unroll
+        for (int k = 0; k < OPT_VPT; ++k) {
+            const int i = k * OPT_THREADS + tid;
+            xg[k] = xp[k] = xm[k] = xv[k] = zero;
+            if (i < nv) {
+                xp[k] = *reinterpret_cast<const f32x4*>(p + 4 * i);
+                if constexpr ((A & OS_G) != 0) xg[k] = *reinterpret_cast<const f32x4*>(g + 4 * i);
+                if constexpr ((A & OS_M) != 0) xm[k] = *reinterpret_cast<const f32x4*>(m + 4 * i);
+                if constexpr ((A & OS_V) != 0) xv[k] = *reinterpret_cast<const f32x4*>(v + 4 * i);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < OPT_VPT; ++k) {
+            const int i = k * OPT_THREADS + tid;
+            if (i < nv) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float pp = xp[k][e], mm = xm[k][e], vv = xv[k][e];
+                    f(xg[k][e], pp, mm, vv);
+                    xp[k][e] = pp;
+                    xm[k][e] = mm;
+                    xv[k][e] = vv;
+                }
+                if constexpr ((A & OS_WP) != 0) *reinterpret_cast<f32x4*>(p + 4 * i) = xp[k];
+                if constexpr ((A & OS_WM) != 0) *reinterpret_cast<f32x4*>(m + 4 * i) = xm[k];
+                if constexpr ((A & OS_WV) != 0) *reinterpret_cast<f32x4*>(v + 4 * i) = xv[k];
+            }
+        }
+        const int i = 4 * nv + tid;  // the last n % 4 elements
+        if (tid < 4 && i < n) one(i);
+    } else {
+        for (int i = tid; i < n; i += OPT_THREADS) one(i);
+    }
+}
+
+// the chunk this workgroup owns: false if its tensor has no gradient this step (workgroup-uniform)
+struct OptSlice {
+    const float* g;
+    float *p, *m, *v;
+    int n, group;
+    int64_t numel;
+};
+__device__ __forceinline__ bool opt_slice(const OptTensor* __restrict__ tens, const OptChunk& ck, const float* const* __restrict__ grads,
+                                          OptSlice& s) {
+    const float* g = grads[ck.tensor];
+    if (!g) return false;
+    const OptTensor t = tens[ck.tensor];
+    const int64_t off = (int64_t)ck.index * OPT_CHUNK;
+    const int64_t left = t.n - off;
+    s.n = left < OPT_CHUNK ? (int)left : OPT_CHUNK;
+    s.g = g + off;
+    s.p = t.p + off;
+    s.m = t.m + off;
+    s.v = t.v + off;
+    s.group = t.group;
+    s.numel = t.n;
+    return true;
+}
+
+template <class G>
+__global__ __launch_bounds__(OPT_THREADS) void k_sgd_step(const OptTensor* __restrict__ tens, const OptChunk* __restrict__ chunks,
+                                                          const float* const* __restrict__ grads, const float* __restrict__ ctrl,
+                                                          const G grp) {
+    if (ctrl[OC_FOUND_INF] != 0.f) return;  // skipped step: nothing is written
+    OptSlice s;
+    if (!opt_slice(tens, chunks[blockIdx.x], grads, s)) return;
+    const OptHyperArr& h = opt_hyper(grp);
+    const float gmul = ctrl[OC_GMUL], lr = h.lr[s.group], wd = h.decay[s.group], mu = h.b1[s.group];
+    const bool nesterov = h.b2[s.group] != 0.f;
+    if (mu == 0.f) {  // (workgroup-uniform) no momentum: no buffer
+        opt_stream<OS_G | OS_WP>(s.n, s.g, s.p, nullptr, nullptr, [&](float g, float& p, float&, float&) {
+            g = g * gmul + wd * p;
+            p -= lr * g;
+        });
+    } else {
+        opt_stream<OS_G | OS_M | OS_WP | OS_WM>(s.n, s.g, s.p, s.m, nullptr, [&](float g, float& p, float& m, float&) {
+            g = g * gmul + wd * p;
+            m = mu * m + g;
+            p -= lr * (nesterov ? g + mu * m : m);
+        });
+    }
+}
+
+struct LambCoef {
+    float gmul, wd, b1, omb1, b2, omb2, inv_bc1, inv_bc2s, eps;
+};
+template <class G>
+__device__ __forceinline__ LambCoef lamb_coef(const float* __restrict__ ctrl, const G& grp, int gi) {
+    const OptHyperArr& h = opt_hyper(grp);
+    LambCoef c;
+    c.gmul = ctrl[OC_GMUL];
+    c.wd = h.decay[gi];
+    c.b1 = h.b1[gi];
+    c.omb1 = h.omb1[gi];
+    c.b2 = h.b2[gi];
+    c.omb2 = h.omb2[gi];
+    c.inv_bc1 = 1.f / ctrl[OC_BC + 2 * gi];
+    c.inv_bc2s = 1.f / ctrl[OC_BC + 2 * gi + 1];
+    c.eps = h.eps[gi];
+    return c;
+}
+// the one expression both LAMB kernels form u with
+__device__ __forceinline__ float lamb_u(float p, float m, float v, const LambCoef& c) {
+    return (m * c.inv_bc1) / (sqrtf(v) * c.inv_bc2s + c.eps) + c.wd * p;
+}
+
+template <class G>
+__global__ __launch_bounds__(OPT_THREADS) void k_lamb_moments(const OptTensor* __restrict__ tens, const OptChunk* __restrict__ chunks,
+                                                              const float* const* __restrict__ grads, const float* __restrict__ ctrl,
+                                                              const G grp, float* __restrict__ pn, float* __restrict__ un) {
+    __shared__ float red_p[4], red_u[4];
+    if (ctrl[OC_FOUND_INF] != 0.f) return;  // skipped step: m and v stay as they are (and launch 4 reads no partial)
+    OptSlice s;
+    if (!opt_slice(tens, chunks[blockIdx.x], grads, s)) return;
+    const LambCoef c = lamb_coef(ctrl, grp, s.group);
+    float sp = 0.f, su = 0.f;
+    opt_stream<OS_G | OS_M | OS_V | OS_WM | OS_WV>(s.n, s.g, s.p, s.m, s.v, [&](float g, float& p, float& m, float& v) {
+        g *= c.gmul;
+        m = c.b1 * m + c.omb1 * g;
+        v = c.b2 * v + c.omb2 * g * g;
+        const float u = lamb_u(p, m, v, c);
+        sp += p * p;
+        su += u * u;
+    });
+    const float tp = opt_block_sum(sp, red_p), tu = opt_block_sum(su, red_u);
+    if (threadIdx.x == 0) {
+        pn[blockIdx.x] = tp;
+        un[blockIdx.x] = tu;
+    }
+}
+
+template <class G>
+__global__ __launch_bounds__(OPT_THREADS) void k_lamb_apply(const OptTensor* __restrict__ tens, const OptChunk* __restrict__ chunks,
+                                                            const float* const* __restrict__ grads, const float* __restrict__ ctrl,
+                                                            const G grp, const float* __restrict__ pn, const float* __restrict__ un,
+                                                            int use_nvlamb) {
+    __shared__ double red_p[4], red_u[4];
+    if (ctrl[OC_FOUND_INF] != 0.f) return;
+    const OptChunk ck = chunks[blockIdx.x];
+    OptSlice s;
+    if (!opt_slice(tens, ck, grads, s)) return;
+    const int tid = threadIdx.x;
+    const int first = (int)blockIdx.x - ck.index;                         // the tensor's chunks are [first, first + cnt)
+    const int cnt = (int)((s.numel + OPT_CHUNK - 1) / OPT_CHUNK);  // (< 2^31: opt_count)
+    double sp = 0.0, su = 0.0;
+    for (int i = tid; i < cnt; i += OPT_THREADS) {
+        sp += (double)pn[first + i];
+        su += (double)un[first + i];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sp += __shfl_xor(sp, o);
+        su += __shfl_xor(su, o);
+    }
+    if ((tid & 63) == 0) {
+        red_p[tid >> 6] = sp;
+        red_u[tid >> 6] = su;
+    }
+    __syncthreads();
+    const float pnorm = (float)sqrt(red_p[0] + red_p[1] + red_p[2] + red_p[3]);
+    const float unorm = (float)sqrt(red_u[0] + red_u[1] + red_u[2] + red_u[3]);
+    const LambCoef c = lamb_coef(ctrl, grp, s.group);
+    const float lr = opt_hyper(grp).lr[s.group];
+    const float ratio = ((c.wd != 0.f || use_nvlamb) && pnorm != 0.f && unorm != 0.f) ? lr * (pnorm / unorm) : lr;
+    opt_stream<OS_M | OS_V | OS_WP>(s.n, nullptr, s.p, s.m, s.v,
+                                    [&](float, float& p, float& m, float& v) { p -= ratio * lamb_u(p, m, v, c); });
+}
+
 static int opt_count(int64_t n_tensors, const int64_t* numel, int64_t* n_chunks) {
     if (n_tensors <= 0 || n_tensors >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
     if (!numel) return MTLORA_ERR_NULL;
@@ -553,7 +799,7 @@ static int opt_launch(const void* table, const void* grads, int64_t n_tensors, i
         hipLaunchKernelGGL(k_optim_norm<false>, l.grid, block, 0, l.s, l.te, l.ce, l.gp, l.partials, l.flags, (float*)nullptr,
                            (const int64_t*)nullptr, (const float*)nullptr);
     hipLaunchKernelGGL((k_optim_finish<G, false>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g, max_norm, ctrl, norm_out,
-                       scale, growth_tracker, growth_factor, backoff_factor, growth_interval, 0, (OptSched*)nullptr);
+                       scale, growth_tracker, growth_factor, backoff_factor, growth_interval, 0, (OptSched*)nullptr, 0.f);
     if (n_chunks > 0) hipLaunchKernelGGL((k_optim_step<G, OptGradPtrs>), l.grid, block, 0, l.s, l.te, l.ce, OptGradPtrs{l.gp}, ctrl, g);
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
@@ -579,11 +825,11 @@ static int opt_launch_accum(const void* table, const void* grads, int64_t n_tens
     }
     if (sch)
         hipLaunchKernelGGL((k_optim_finish<OptGroupsDev, true, true>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g,
-                           max_norm, ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, accum_steps, sch);
+                           max_norm, ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, accum_steps, sch, 0.f);
     else
         hipLaunchKernelGGL((k_optim_finish<OptGroupsDev, true>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g, max_norm,
                            ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, accum_steps,
-                           (OptSched*)nullptr);
+                           (OptSched*)nullptr, 0.f);
     if (n_chunks > 0) {
         if (sum)
             hipLaunchKernelGGL((k_optim_step<OptGroupsDev, OptGradAcc>), l.grid, block, 0, l.s, l.te, l.ce, OptGradAcc{l.gp, acc, acc_off},
@@ -591,6 +837,33 @@ static int opt_launch_accum(const void* table, const void* grads, int64_t n_tens
         else
             hipLaunchKernelGGL((k_optim_step<OptGroupsDev, OptGradPtrs>), l.grid, block, 0, l.s, l.te, l.ce, OptGradPtrs{l.gp},
                                (const float*)ctrl, g);
+    }
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
+template <int ALG, class G>
+static int opt_launch_as(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const G& g, float max_norm,
+                         float lamb_max_norm, int use_nvlamb, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker,
+                         float growth_factor, float backoff_factor, int growth_interval, void* scratch, void* stream) {
+    static_assert(ALG == OPT_SGD || ALG == OPT_LAMB, "AdamW has opt_launch");
+    const OptLaunch l(table, grads, n_tensors, n_chunks, scratch, stream);
+    const dim3 block(OPT_THREADS);
+    if (n_chunks > 0)
+        hipLaunchKernelGGL(k_optim_norm<false>, l.grid, block, 0, l.s, l.te, l.ce, l.gp, l.partials, l.flags, (float*)nullptr,
+                           (const int64_t*)nullptr, (const float*)nullptr);
+    hipLaunchKernelGGL((k_optim_finish<G, false, false, ALG>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g, max_norm, ctrl,
+                       norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, 0, (OptSched*)nullptr, lamb_max_norm);
+    if (n_chunks > 0) {
+        if constexpr (ALG == OPT_SGD) {
+            hipLaunchKernelGGL((k_sgd_step<G>), l.grid, block, 0, l.s, l.te, l.ce, l.gp, (const float*)ctrl, g);
+        } else {
+            float* pn = reinterpret_cast<float*>(l.flags + n_chunks);  // the scratch's second half: [n_chunks] |p|^2, [n_chunks] |u|^2
+            float* un = pn + n_chunks;
+            hipLaunchKernelGGL((k_lamb_moments<G>), l.grid, block, 0, l.s, l.te, l.ce, l.gp, (const float*)ctrl, g, pn, un);
+            hipLaunchKernelGGL((k_lamb_apply<G>), l.grid, block, 0, l.s, l.te, l.ce, l.gp, (const float*)ctrl, g, (const float*)pn,
+                               (const float*)un, use_nvlamb);
+        }
     }
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
@@ -675,6 +948,83 @@ int mtlora_adamw_update_dev(const void* table, const void* grads, int64_t n_tens
     g.n = n_groups;
     return opt_launch(table, grads, n_tensors, n_chunks, g, max_norm, ctrl, norm_out, scale, growth_tracker, growth, backoff,
                       growth_interval, scratch, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the by-value and the device-record entry of SGD / LAMB: the records have one layout (an SGD record is read through the AdamW
+// record's fields), so one function serves both optimizers
+template <int ALG>
+int opt_update_as(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const mtlora_adamw_group* groups, bool dev,
+                  int n_groups, float max_norm, float lamb_max_norm, int use_nvlamb, float* ctrl, float* norm_out, float* scale,
+                  int32_t* growth_tracker, float growth, float backoff, int growth_interval, void* scratch, int64_t scratch_bytes,
+                  void* stream) {
+    const int rc = opt_check(table, grads, n_tensors, n_chunks, groups, n_groups, ctrl, norm_out, scale, growth_tracker, growth, backoff,
+                             growth_interval, scratch, scratch_bytes);
+    if (rc != MTLORA_OK) return rc;
+    if (ALG == OPT_LAMB && scratch_bytes < n_chunks * 16) return MTLORA_ERR_WORKSPACE;  // two more words per chunk: |p|^2, |u|^2
+    if (ALG == OPT_LAMB && !(lamb_max_norm == lamb_max_norm)) return MTLORA_ERR_SHAPE;
+    if (dev) {
+        if ((uintptr_t)groups & 7u) return MTLORA_ERR_ALIGN;
+        OptGroupsDev g;
+        g.rec = groups;  // the records are only read; the tail behind them is the library's
+        g.hyp = reinterpret_cast<OptHyperArr*>(const_cast<mtlora_adamw_group*>(groups) + OPT_MAXG);
+        g.n = n_groups;
+        return opt_launch_as<ALG>(table, grads, n_tensors, n_chunks, g, max_norm, lamb_max_norm, use_nvlamb, ctrl, norm_out, scale,
+                                  growth_tracker, growth, backoff, growth_interval, scratch, stream);
+    }
+    OptGroups g = {};
+    g.n = n_groups;
+    for (int i = 0; i < n_groups; ++i) {
+        OptHyper h;
+        if (!opt_derive_as<ALG>(groups[i], h)) return MTLORA_ERR_SHAPE;
+        opt_put(g.h, i, h);
+        g.b1d[i] = groups[i].beta1;  // (LAMB's bias corrections; SGD's finish does not read them)
+        g.b2d[i] = groups[i].beta2;
+    }
+    return opt_launch_as<ALG>(table, grads, n_tensors, n_chunks, g, max_norm, lamb_max_norm, use_nvlamb, ctrl, norm_out, scale,
+                              growth_tracker, growth, backoff, growth_interval, scratch, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtlora_sgd_update(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const mtlora_sgd_group* groups,
+                      int n_groups, float max_norm, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker,
+                      float growth_factor, float backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes, void* stream) {
+    return opt_update_as<OPT_SGD>(table, grads, n_tensors, n_chunks, reinterpret_cast<const mtlora_adamw_group*>(groups), false, n_groups,
+                                  max_norm, 0.f, 0, ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval,
+                                  scratch, scratch_bytes, stream);
+}
+
+int mtlora_sgd_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const mtlora_sgd_group* groups_dev,
+                          int n_groups, float max_norm, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker,
+                          double growth_factor, double backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes,
+                          void* stream) {
+    return opt_update_as<OPT_SGD>(table, grads, n_tensors, n_chunks, reinterpret_cast<const mtlora_adamw_group*>(groups_dev), true,
+                                  n_groups, max_norm, 0.f, 0, ctrl, norm_out, scale, growth_tracker, (float)growth_factor,
+                                  (float)backoff_factor, growth_interval, scratch, scratch_bytes, stream);
+}
+
+int mtlora_lamb_update(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const mtlora_adamw_group* groups,
+                       int n_groups, float max_norm, float max_grad_norm, int use_nvlamb, float* ctrl, float* norm_out, float* scale,
+                       int32_t* growth_tracker, float growth_factor, float backoff_factor, int growth_interval, void* scratch,
+                       int64_t scratch_bytes, void* stream) {
+    return opt_update_as<OPT_LAMB>(table, grads, n_tensors, n_chunks, groups, false, n_groups, max_norm, max_grad_norm, use_nvlamb != 0,
+                                   ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, scratch,
+                                   scratch_bytes, stream);
+}
+
+int mtlora_lamb_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const mtlora_adamw_group* groups_dev,
+                           int n_groups, float max_norm, float max_grad_norm, int use_nvlamb, float* ctrl, float* norm_out, float* scale,
+                           int32_t* growth_tracker, double growth_factor, double backoff_factor, int growth_interval, void* scratch,
+                           int64_t scratch_bytes, void* stream) {
+    return opt_update_as<OPT_LAMB>(table, grads, n_tensors, n_chunks, groups_dev, true, n_groups, max_norm, max_grad_norm, use_nvlamb != 0,
+                                   ctrl, norm_out, scale, growth_tracker, (float)growth_factor, (float)backoff_factor, growth_interval,
+                                   scratch, scratch_bytes, stream);
 }
 
 int mtlora_adamw_accum_layout(int64_t n_tensors, const int64_t* numel, int64_t* host_offsets, int64_t* acc_elems) {

@@ -25,7 +25,7 @@ import torch.nn.functional as F
 from . import functional as Fn
 from .functional import BatchNormReluFn, UpsampleLossFn
 from .lora import MTLoRALinear, mark_only_lora_as_trainable
-from .optim import FusedAdamW, accumulation_steps_of
+from .optim import FusedAdamW, FusedLAMB, FusedOptimizer, FusedSGD, accumulation_steps_of
 from .swin_transformer_mtlora import SwinTransformerMTLoRA
 
 NUM_OUTPUT = {"semseg": 21, "normals": 3, "sal": 1, "human_parts": 7, "depth": 1, "edge": 1}  # data/mtl_ds.py:749-780
@@ -372,14 +372,26 @@ def build_model(img_size=448, tasks=("semseg", "normals", "sal", "human_parts"),
 
 
 def build_optimizer(model: nn.Module, lr=5e-4, weight_decay=0.05, fused: Optional[bool] = None,
-                    capturable: bool = False, impl: str = "torch") -> torch.optim.Optimizer:
+                    capturable: bool = False, impl: str = "torch", name: str = "adamw", momentum: float = 0.9) -> torch.optim.Optimizer:
     """AdamW(betas .9/.999, eps 1e-8, wd .05) with the no-decay set of optimizer.py:71-85 (1-D tensors, biases,
     relative_position_bias_table); only trainable tensors are handed over (frozen ones never get a grad in the
     reference either).  ``impl="hip"``: the same two groups under ``optim.FusedAdamW`` (clip + unscale + AdamW as
     three launches, csrc/optim.hip; ``fused`` does not apply; ``capturable=True``: the form ``GraphedTrainStep`` can capture,
-    hyper-parameters read from device memory at replay)."""
+    hyper-parameters read from device memory at replay).
+
+    ``name`` is the reference's ``TRAIN.OPTIMIZER.NAME`` (optimizer.py:53-66) over the same two groups: ``"adamw"`` / ``"fused_adam"``
+    as above; ``"sgd"``: SGD(momentum=``momentum``, nesterov=True) -- ``optim.FusedSGD`` with ``impl="hip"``, ``torch.optim.SGD``
+    otherwise; ``"lamb"`` / ``"fused_lamb"``: ``optim.FusedLAMB`` (betas, eps and the rest at the reference's defaults), ``impl="hip"``
+    only -- the reference takes it from apex, and torch has none, so ``impl="torch"`` is a ``ValueError``."""
     if impl not in ("torch", "hip"):
         raise ValueError(f"build_optimizer: impl must be 'torch' or 'hip', got {impl!r}")
+    kinds = {"adamw": "adamw", "fused_adam": "adamw", "sgd": "sgd", "lamb": "lamb", "fused_lamb": "lamb"}
+    if str(name).lower() not in kinds:
+        raise ValueError(f"build_optimizer: name must be one of {sorted(kinds)}, got {name!r}")
+    kind = kinds[str(name).lower()]
+    if kind == "lamb" and impl != "hip":
+        raise ValueError("build_optimizer: name='lamb' needs impl='hip' (optim.FusedLAMB): the reference's fused_lamb is apex's, and "
+                         "torch has no LAMB")
     decay, no_decay = [], []
     for n, p in model.named_parameters():
         if not p.requires_grad:
@@ -389,6 +401,12 @@ def build_optimizer(model: nn.Module, lr=5e-4, weight_decay=0.05, fused: Optiona
         else:
             decay.append(p)
     groups = [{"params": decay}, {"params": no_decay, "weight_decay": 0.0}]
+    if kind == "sgd":
+        if impl == "hip":
+            return FusedSGD(groups, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=True, capturable=bool(capturable))
+        return torch.optim.SGD(groups, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=True)
+    if kind == "lamb":
+        return FusedLAMB(groups, lr=lr, weight_decay=weight_decay, capturable=bool(capturable))
     if impl == "hip":
         return FusedAdamW(groups, lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay, capturable=bool(capturable))
     if fused is None:
@@ -470,7 +488,7 @@ def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 
     ``meters.TrainMeters.for_train_step``): after the update, or after the backward of an accumulating micro-step, the loss, the
     per-task losses and -- on an update step -- the norm are written into the meters' device sources by one small kernel and
     ``meters.update()`` is launched; nothing is read back, and the step computes what it computes without them."""
-    fused_opt = isinstance(optimizer, FusedAdamW)
+    fused_opt = isinstance(optimizer, FusedOptimizer)
     if loss_scaler is not None and not fused_opt:
         raise TypeError("train_step: loss_scaler needs the HIP optimizer (build_optimizer(impl='hip'))")
     def fwd():
@@ -666,10 +684,14 @@ class GraphedTrainStep:
         if self.accumulation_steps > 1 and reducer is not None:
             raise ValueError("GraphedTrainStep: accumulation_steps > 1 with a reducer is not supported (the all-reduce would have to "
                              "sit between two graphs on every k-th call only); use train_step(..., reducer=, update_grad=)")
-        self.fused_opt = isinstance(optimizer, FusedAdamW)
+        self.fused_opt = isinstance(optimizer, FusedOptimizer)
         if self.accumulation_steps > 1 and not self.fused_opt:
             raise TypeError("GraphedTrainStep: accumulation_steps > 1 needs the HIP optimizer (build_optimizer(impl='hip', "
                             "capturable=True)): the decision to step is taken on the device by its kernels")
+        if self.fused_opt and not isinstance(optimizer, FusedAdamW) and (self.accumulation_steps > 1 or lr_scheduler is not None):
+            raise TypeError(f"GraphedTrainStep: {type(optimizer).__name__} supports neither accumulation_steps > 1 nor lr_scheduler= "
+                            "(both run inside FusedAdamW's kernels); accumulate with train_step(update_grad=False) and set "
+                            "param_groups' lr between calls")
         if self.fused_opt and not optimizer._capturable:
             raise TypeError("GraphedTrainStep: a FusedAdamW inside the graph must be built with capturable=True "
                             "(build_optimizer(impl='hip', capturable=True)): its hyper-parameters travel in the launch arguments, "

@@ -34,6 +34,16 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 HBM_COPY_TBS = 6.29  # the copy ceiling the project quotes for the MI355X
+# --optim: (the fused class, what the torch leg runs -- torch has no LAMB: its AdamW is the yardstick there --, bytes per element
+# the update must move, and how they add up)
+OPTIMS = {"adamw": ("FusedAdamW", "adamw", "AdamW", 28, "16 B read (p, g, m, v) + 12 B written (p, m, v)"),
+          "sgd": ("FusedSGD", "sgd", "SGD(nesterov, foreach)", 20, "12 B read (p, g, buf) + 8 B written (p, buf)"),
+          "lamb": ("FusedLAMB", "adamw", "AdamW", 40, "moments: 16 B read (p, g, m, v) + 8 B written (m, v); apply: 12 B read (p, m, v) "
+                   "again + 4 B written (p)")}
+
+
+def build(H, model, impl, a, capturable=False):
+    return H.build_optimizer(model, lr=5e-4, impl=impl, capturable=capturable, name=a.optim if impl == "hip" else OPTIMS[a.optim][1])
 
 
 def graph_leg(a):
@@ -43,7 +53,7 @@ def graph_leg(a):
     leg, dev = a.graph_leg, torch.device("cuda:0")
     impl = "hip" if leg == "hipsched" else leg
     model = H.build_config_model(a.config, seed=0).to(dev).train()
-    opt = H.build_optimizer(model, lr=5e-4, impl=impl, capturable=True)
+    opt = build(H, model, impl, a, capturable=True)
     sched = None
     if a.schedule and impl == "hip":  # (long enough that the timed replays stay on the cosine segment)
         sched = CosineLRScheduler(opt, t_initial=100 * (a.iters + a.warmup), lr_min=1e-6, warmup_t=5, warmup_lr_init=1e-7, t_in_epochs=False)
@@ -116,7 +126,7 @@ def graph_ab(a):
     for _ in range(a.runs):
         for impl in ("torch", "hip"):
             cmd = [sys.executable, os.path.abspath(__file__), "--graph-leg", impl, "--config", a.config, "--iters", str(a.iters),
-                   "--warmup", str(a.warmup)]
+                   "--warmup", str(a.warmup), "--optim", a.optim]
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
             line = [l for l in r.stdout.splitlines() if l.startswith("GRAPH_LEG ")]
             if r.returncode != 0 or not line:
@@ -126,14 +136,15 @@ def graph_ab(a):
             if not rows[impl][-1]["finite"]:
                 raise SystemExit(f"bench_optim: the {impl} leg left non-finite parameters")
     one = rows["hip"][0]
-    lines = [f"bench_optim --graph: clip + AdamW REPLAYED from a HIP graph on the trainable set of {a.config}: {one['tensors']} tensors, "
+    fused, _, torch_what, _, _ = OPTIMS[a.optim]
+    lines = [f"bench_optim --graph: clip + {fused[5:]} REPLAYED from a HIP graph on the trainable set of {a.config}: {one['tensors']} tensors, "
              f"{one['elements']} elements",
              f"box: {one['gpu']}, torch {torch.__version__}, HIP {torch.version.hip}; each leg in its own process, {a.runs} runs each, "
              f"alternating; {a.iters} timed replays after {a.warmup} warm-up replays",
              "per replay                                        device ms            host ms              wall ms (iters / sync)",
              "                                                  median  spread       median  spread       median  spread"]
     med = {}
-    for impl, what in (("torch", "torch: clip_grad_norm_ + AdamW(capturable)    "), ("hip", "hip:   FusedAdamW(capturable).clip_and_step   ")):
+    for impl, what in (("torch", f"torch: clip_grad_norm_ + {torch_what}".ljust(46)), ("hip", f"hip:   {fused}(capturable).clip_and_step".ljust(46))):
         cols = []
         for key in ("device_ms", "host_ms", "wall_ms"):
             v = [r[key] for r in rows[impl]]
@@ -198,10 +209,14 @@ def main():
     ap.add_argument("--runs", type=int, default=3, help="--graph: runs per leg")
     ap.add_argument("--schedule", action="store_true", help="--graph: host scheduler + per-step push against the device-side schedule")
     ap.add_argument("--graph-leg", choices=("torch", "hip", "hipsched"), default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--optim", choices=tuple(OPTIMS), default="adamw", help="which fused optimizer (build_optimizer(name=))")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.schedule and a.optim != "adamw":
+        raise SystemExit("bench_optim: --schedule is FusedAdamW's (the other classes have no device-side schedule)")
     a.iters = a.iters or (200 if (a.graph or a.graph_leg) else 50)
-    a.out = a.out or os.path.join("profiles", ("optim_graph_schedule.txt" if a.schedule else "optim_graph_ab.txt") if a.graph else "optim_ab.txt")
+    name = ("optim_graph_schedule" if a.schedule else "optim_graph_ab") if a.graph else "optim_ab"
+    a.out = a.out or os.path.join("profiles", name + ("" if a.optim == "adamw" else "_" + a.optim) + ".txt")
     if a.graph:
         return graph_ab(a)
     if not torch.cuda.is_available():
@@ -213,7 +228,7 @@ def main():
     side = {}
     for impl in ("torch", "hip"):
         model = H.build_config_model(a.config, seed=0).to(dev).train()
-        opt = H.build_optimizer(model, lr=5e-4, impl=impl)
+        opt = build(H, model, impl, a)
         ps = [p for g in opt.param_groups for p in g["params"]]
         gen = torch.Generator(device=dev).manual_seed(1)
         grads = [[torch.randn(p.shape, device=dev, generator=gen) * 1e-2 for p in ps] for _ in range(2)]
@@ -252,22 +267,25 @@ def main():
     for impl, (opt, ps, grads, host, events, norms) in side.items():
         devms = [e0.elapsed_time(e1) for e0, e1 in events]
         res[impl] = (statistics.median(host), min(host), statistics.median(devms), min(devms))
-    need = 28.0 * n_elems  # 16 B read (p, g, m, v) + 12 B written (p, m, v) per element
+    fused, _, torch_what, per_elem, how = OPTIMS[a.optim]
+    need = float(per_elem) * n_elems  # per element: see OPTIMS
+    launches = "four" if a.optim == "lamb" else "three"
     floor_us = need / (HBM_COPY_TBS * 1e12) * 1e6
     lines = [
-        f"bench_optim: clip + AdamW on the trainable set of {a.config}: {n_tensors} tensors, {n_elems} elements",
+        f"bench_optim: clip + {fused[5:]} on the trainable set of {a.config}: {n_tensors} tensors, {n_elems} elements",
         f"box: {torch.cuda.get_device_name(0)}, torch {torch.__version__}, HIP {torch.version.hip}; one process, the two "
         f"implementations alternating in {a.rounds} rounds of {a.iters} calls after {a.warmup} warm-up calls each",
         "per call                            host ms (median / min)   device ms (median / min)",
     ]
-    for impl, what in (("torch", "torch: clip_grad_norm_ + AdamW(fused)"), ("hip", "hip:   FusedAdamW.clip_and_step     ")):
+    for impl, what in (("torch", f"torch: clip_grad_norm_ + {torch_what + ('(fused)' if OPTIMS[a.optim][1] == 'adamw' else '')}"),
+                       ("hip", f"hip:   {fused}.clip_and_step".ljust(37))):
         h, hm, d, dm = res[impl]
         lines.append(f"{what}   {h:8.3f} / {hm:8.3f}        {d:8.3f} / {dm:8.3f}")
     lines.append(f"hip / torch: host {res['hip'][0] / res['torch'][0]:.3f}, device {res['hip'][2] / res['torch'][2]:.3f}")
-    lines.append(f"bytes the update must move: 28 B x {n_elems} = {need / 1e6:.2f} MB -> {floor_us:.1f} us at {HBM_COPY_TBS} TB/s; "
+    lines.append(f"bytes the update must move: {per_elem} B ({how}) x {n_elems} = {need / 1e6:.2f} MB -> {floor_us:.1f} us at {HBM_COPY_TBS} TB/s; "
                  f"hip device median {res['hip'][2] * 1e3:.1f} us = {need / (res['hip'][2] * 1e-3) / 1e12:.2f} TB/s "
-                 f"({100 * floor_us / (res['hip'][2] * 1e3):.0f} % of that ceiling; the span holds three launches, and the norm "
-                 "pass reads the gradients once more, 4 B per element, on top of the 28)")
+                 f"({100 * floor_us / (res['hip'][2] * 1e3):.0f} % of that ceiling; the span holds {launches} launches, and the norm "
+                 f"pass reads the gradients once more, 4 B per element, on top of the {per_elem})")
     text = "\n".join(lines) + "\n"
     print(text, end="")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
