@@ -9,9 +9,7 @@
 // gradient pointer switches the tensor's chunks off: nothing of it is read or written.
 //
 //   k_optim_norm    partials[chunk] = sum of g^2 over the chunk, of the gradients AS STORED (still multiplied by the loss scale);
-//                   flags[chunk] = 1 if a value of the chunk is inf / nan.  16-byte loads where the chunk's base is 16-byte
-//                   aligned (the last n % 4 elements, and every element of a misaligned tensor, go through the scalar path).
-//                   No float atomics: every workgroup owns its two words.
+//                   flags[chunk] = 1 if a value of the chunk is inf / nan.  No float atomics: every workgroup owns its two words.
 //   k_optim_finish  ONE workgroup: partials summed in a fixed order in double (thread t takes t, t + 256, ...; then a fixed
 //                   tree), so the norm is bit-reproducible from run to run.  Writes the control block (unscaled norm, found_inf,
 //                   clip coefficient, the factor coef / scale the update applies to the raw gradients, the step counter --
@@ -24,6 +22,9 @@
 //                       p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)
 //                   lr, wd, betas, eps per parameter group, BY VALUE in the launch arguments (lr moves every step under a
 //                   scheduler; nothing to upload).
+// Every chunk kernel of this file finds its chunk with opt_slice and -- k_optim_step apart, see there -- walks it with opt_stream:
+// 16-byte accesses where every pointer in use is 16-byte aligned, the last n % 4 elements and every element of a misaligned tensor
+// scalar.  Every update entry is opt_check, the entry's own checks, then opt_update<algorithm, groups type>, the one launcher.
 //
 // mtlora_adamw_update_dev is the same three launches with the hyper-parameters in DEVICE memory, for a step that is captured in a
 // HIP graph: launch arguments are frozen at capture, device memory is read at replay.  The group records (doubles) sit in a buffer
@@ -232,8 +233,9 @@ struct OptGradAcc {  // the accumulator's slices; a null gradient pointer still 
 
 __device__ __forceinline__ bool opt_nonfinite(float x) { return (__builtin_bit_cast(uint32_t, x) & 0x7F800000u) == 0x7F800000u; }
 
-// fixed-order sum over the workgroup's 4 waves; the result is valid in thread 0
-__device__ __forceinline__ float opt_block_sum(float s, float* red) {
+// fixed-order sum (float or double) over the workgroup's 4 waves; every thread gets the same bits.  `red`: 4 words of LDS per call
+template <class T>
+__device__ __forceinline__ T opt_block_sum(T s, T* red) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -241,10 +243,102 @@ __device__ __forceinline__ float opt_block_sum(float s, float* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
-// ACC: gradient accumulation -- the chunk of acc (at acc + acc_off[tensor]) becomes g (ctrl[OC_MICRO] == 0: whatever acc held is
-// overwritten, never read) or acc + g, and the partial / flag are those of the value stored.  Each element of acc has one writer.
+// what the walk below needs of every pointer it uses to take 16-byte accesses (OR the addresses), and what the accumulating
+// entries therefore ask of `acc`, whose slices all start at multiples of 4 elements
+__host__ __device__ inline bool opt_aligned16(uintptr_t bits) { return (bits & 15u) == 0; }
+
+// THE walk over one chunk, element by element: f(g, p, m, v) on registers.  A: which of g / p / m / v are read and which of
+// p / m / v are written; a pointer A does not name may be null.  16-byte accesses where every pointer in use is 16-byte aligned,
+// with the last n % 4 elements scalar on threads 0..3; scalar else.  A thread visits its elements in a fixed order (vector k
+// ascending, lane e ascending, then the tail element): a sum f accumulates is reproducible.
+enum { OS_G = 1, OS_P = 2, OS_M = 4, OS_V = 8, OS_WP = 16, OS_WM = 32, OS_WV = 64 };
+template <int A, class F>
+__device__ __forceinline__ void opt_stream(int n, const float* __restrict__ g, float* __restrict__ p, float* __restrict__ m,
+                                           float* __restrict__ v, F f) {
+    const int tid = threadIdx.x;
+    uintptr_t al = 0;
+    if constexpr ((A & (OS_P | OS_WP)) != 0) al |= (uintptr_t)p;
+    if constexpr ((A & OS_G) != 0) al |= (uintptr_t)g;
+    if constexpr ((A & (OS_M | OS_WM)) != 0) al |= (uintptr_t)m;
+    if constexpr ((A & (OS_V | OS_WV)) != 0) al |= (uintptr_t)v;
+    auto one = [&](int i) {
+        float gg = 0.f, pp = 0.f, mm = 0.f, vv = 0.f;
+        if constexpr ((A & OS_P) != 0) pp = p[i];
+        if constexpr ((A & OS_G) != 0) gg = g[i];
+        if constexpr ((A & OS_M) != 0) mm = m[i];
+        if constexpr ((A & OS_V) != 0) vv = v[i];
+        f(gg, pp, mm, vv);
+        if constexpr ((A & OS_WP) != 0) p[i] = pp;
+        if constexpr ((A & OS_WM) != 0) m[i] = mm;
+        if constexpr ((A & OS_WV) != 0) v[i] = vv;
+    };
+    if (opt_aligned16(al)) {
+        const int nv = n >> 2;
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        f32x4 xg[OPT_VPT], xp[OPT_VPT], xm[OPT_VPT], xv[OPT_VPT];
+#pragma unroll
+        for (int k = 0; k < OPT_VPT; ++k) {
+            const int i = k * OPT_THREADS + tid;
+            xg[k] = xp[k] = xm[k] = xv[k] = zero;
+            if (i < nv) {
+                if constexpr ((A & OS_P) != 0) xp[k] = *reinterpret_cast<const f32x4*>(p + 4 * i);
+                if constexpr ((A & OS_G) != 0) xg[k] = *reinterpret_cast<const f32x4*>(g + 4 * i);
+                if constexpr ((A & OS_M) != 0) xm[k] = *reinterpret_cast<const f32x4*>(m + 4 * i);
+                if constexpr ((A & OS_V) != 0) xv[k] = *reinterpret_cast<const f32x4*>(v + 4 * i);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < OPT_VPT; ++k) {
+            const int i = k * OPT_THREADS + tid;
+            if (i < nv) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float pp = xp[k][e], mm = xm[k][e], vv = xv[k][e];
+                    f(xg[k][e], pp, mm, vv);
+                    xp[k][e] = pp;
+                    xm[k][e] = mm;
+                    xv[k][e] = vv;
+                }
+                if constexpr ((A & OS_WP) != 0) *reinterpret_cast<f32x4*>(p + 4 * i) = xp[k];
+                if constexpr ((A & OS_WM) != 0) *reinterpret_cast<f32x4*>(m + 4 * i) = xm[k];
+                if constexpr ((A & OS_WV) != 0) *reinterpret_cast<f32x4*>(v + 4 * i) = xv[k];
+            }
+        }
+        const int i = 4 * nv + tid;  // the last n % 4 elements
+        if (tid < 4 && i < n) one(i);
+    } else {
+        for (int i = tid; i < n; i += OPT_THREADS) one(i);
+    }
+}
+
+// the chunk this workgroup owns, of the tensor whose gradient starts at `g`: false if it has none this step (workgroup-uniform)
+struct OptSlice {
+    const float* g;
+    float *p, *m, *v;
+    int n, group;
+    int64_t off, numel;  // the chunk's first element in its tensor; the tensor's size
+};
+__device__ __forceinline__ bool opt_slice(const OptTensor* __restrict__ tens, const OptChunk& ck, const float* g, OptSlice& s) {
+    if (!g) return false;
+    const OptTensor t = tens[ck.tensor];
+    s.off = (int64_t)ck.index * OPT_CHUNK;
+    const int64_t left = t.n - s.off;
+    s.n = left < OPT_CHUNK ? (int)left : OPT_CHUNK;
+    s.g = g + s.off;
+    s.p = t.p + s.off;
+    s.m = t.m + s.off;
+    s.v = t.v + s.off;
+    s.group = t.group;
+    s.numel = t.n;
+    return true;
+}
+
+// partials[chunk] / flags[chunk] of the gradients as stored.  ACC: gradient accumulation -- the chunk of acc (at acc +
+// acc_off[tensor]; it rides in the walk's p slot) becomes g (ctrl[OC_MICRO] == 0: whatever acc held is overwritten, never read)
+// or acc + g, and the partial / flag are those of the value stored.  Each element of acc has one writer.  (waves_per_eu: the
+// walk has all of a thread's g and acc vectors in flight at once; the attribute holds that within 64 VGPRs, 8 waves per SIMD.)
 template <bool ACC>
-__global__ __launch_bounds__(OPT_THREADS) void k_optim_norm(const OptTensor* __restrict__ tens, const OptChunk* __restrict__ chunks,
+__global__ __launch_bounds__(OPT_THREADS) __attribute__((amdgpu_waves_per_eu(8))) void k_optim_norm(const OptTensor* __restrict__ tens, const OptChunk* __restrict__ chunks,
                                                             const float* const* __restrict__ grads, float* __restrict__ partials,
                                                             uint32_t* __restrict__ flags, float* __restrict__ acc,
                                                             const int64_t* __restrict__ acc_off, const float* __restrict__ ctrl) {
@@ -252,76 +346,29 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_norm(const OptTensor* __r
     __shared__ int bad_any;
     const int tid = threadIdx.x;
     const OptChunk ck = chunks[blockIdx.x];
-    const float* g = grads[ck.tensor];
-    if (!g) {  // (workgroup-uniform) no gradient this step
+    OptSlice sl;
+    if (!opt_slice(tens, ck, grads[ck.tensor], sl)) {  // no gradient this step
         if (tid == 0) {
             partials[blockIdx.x] = 0.f;
             flags[blockIdx.x] = 0u;
         }
         return;
     }
-    const int64_t off = (int64_t)ck.index * OPT_CHUNK;
-    const int64_t left = tens[ck.tensor].n - off;
-    const int n = left < OPT_CHUNK ? (int)left : OPT_CHUNK;
-    g += off;
-    float* a = nullptr;
-    bool first = true;
-    if constexpr (ACC) {
-        a = acc + acc_off[ck.tensor] + off;
-        first = ctrl[OC_MICRO] == 0.f;  // (workgroup-uniform; k_optim_finish, the next launch, is the one that moves it)
-    }
     if (tid == 0) bad_any = 0;
     float s = 0.f;
     bool bad = false;
-    if ((((uintptr_t)g | (uintptr_t)a) & 15u) == 0) {
-        const int nv = n >> 2;
-        f32x4 x[OPT_VPT];
-#pragma unroll
-        for (int k = 0; k < OPT_VPT; ++k) {
-            const int i = k * OPT_THREADS + tid;
-            x[k] = i < nv ? *reinterpret_cast<const f32x4*>(g + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        if constexpr (ACC) {
-#pragma unroll
-            for (int k = 0; k < OPT_VPT; ++k) {
-                const int i = k * OPT_THREADS + tid;
-                if (i < nv) {
-                    if (!first) {
-                        const f32x4 y = *reinterpret_cast<const f32x4*>(a + 4 * i);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) x[k][e] = y[e] + x[k][e];
-                    }
-                    *reinterpret_cast<f32x4*>(a + 4 * i) = x[k];
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < OPT_VPT; ++k)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                s += x[k][e] * x[k][e];
-                bad |= opt_nonfinite(x[k][e]);
-            }
-        const int i = 4 * nv + tid;  // the last n % 4 elements
-        if (tid < 4 && i < n) {
-            float t = g[i];
-            if constexpr (ACC) {
-                if (!first) t = a[i] + t;
-                a[i] = t;
-            }
-            s += t * t;
-            bad |= opt_nonfinite(t);
-        }
+    auto add = [&](float x) {
+        s += x * x;
+        bad |= opt_nonfinite(x);
+    };
+    if constexpr (ACC) {
+        float* a = acc + acc_off[ck.tensor] + sl.off;
+        if (ctrl[OC_MICRO] == 0.f)  // (workgroup-uniform; k_optim_finish, the next launch, is the one that moves it)
+            opt_stream<OS_G | OS_WP>(sl.n, sl.g, a, nullptr, nullptr, [&](float g, float& x, float&, float&) { add(x = g); });
+        else
+            opt_stream<OS_G | OS_P | OS_WP>(sl.n, sl.g, a, nullptr, nullptr, [&](float g, float& x, float&, float&) { add(x = x + g); });
     } else {
-        for (int i = tid; i < n; i += OPT_THREADS) {
-            float t = g[i];
-            if constexpr (ACC) {
-                if (!first) t = a[i] + t;
-                a[i] = t;
-            }
-            s += t * t;
-            bad |= opt_nonfinite(t);
-        }
+        opt_stream<OS_G>(sl.n, sl.g, nullptr, nullptr, nullptr, [&](float g, float&, float&, float&) { add(g); });
     }
     __syncthreads();  // bad_any = 0 is visible
     if (bad) bad_any = 1;  // (LDS; every writer stores the same value)
@@ -466,19 +513,10 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_step(const OptTensor* __r
                                                             const S src, const float* __restrict__ ctrl, const G grp) {
     if (!src.live(ctrl)) return;            // an accumulating micro-step: nothing is written (ctrl[OC_FOUND_INF] is the last update's)
     if (ctrl[OC_FOUND_INF] != 0.f) return;  // skipped step: nothing is written
-    const int tid = threadIdx.x;
     const OptChunk ck = chunks[blockIdx.x];
-    const float* g = src.at(ck.tensor);
-    if (!g) return;
-    const OptTensor t = tens[ck.tensor];
-    const int64_t off = (int64_t)ck.index * OPT_CHUNK;
-    const int64_t left = t.n - off;
-    const int n = left < OPT_CHUNK ? (int)left : OPT_CHUNK;
-    g += off;
-    float* p = t.p + off;
-    float* m = t.m + off;
-    float* v = t.v + off;
-    const int gi = t.group;
+    OptSlice s;
+    if (!opt_slice(tens, ck, src.at(ck.tensor), s)) return;
+    const int gi = s.group;
     const OptHyperArr& h = opt_hyper(grp);
     OptCoef c;
     c.gmul = ctrl[OC_GMUL];
@@ -490,7 +528,13 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_step(const OptTensor* __r
     c.step_size = h.lr[gi] / ctrl[OC_BC + 2 * gi];
     c.inv_bc2s = 1.f / ctrl[OC_BC + 2 * gi + 1];
     c.eps = h.eps[gi];
-    if ((((uintptr_t)g | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15u) == 0) {
+    // NOT on opt_stream: there the compiler contracts opt_adamw's multiplies and adds into other fused multiply-adds than here
+    // (m, v and p then differ in the last bits from the second step on: tools/optim_digest.py).  The walk below is
+    // opt_stream<OS_G | OS_P | OS_M | OS_V | OS_WP | OS_WM | OS_WV>'s, statement for statement
+    const int tid = threadIdx.x, n = s.n;
+    const float* g = s.g;
+    float *p = s.p, *m = s.m, *v = s.v;
+    if (opt_aligned16((uintptr_t)g | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v)) {
         const int nv = n >> 2;
         f32x4 xg[OPT_VPT], xp[OPT_VPT], xm[OPT_VPT], xv[OPT_VPT];
 #pragma unroll
@@ -553,107 +597,24 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_step(const OptTensor* __r
 //                   instead of 4 written and 4 read for a stored u, and no buffer the size of the parameters), and p -= ratio u.
 // All three leave on found_inf before they read or write anything else.
 
-// one chunk, element by element: f(g, p, m, v) on registers.  A: which of g / m / v are read (p always is) and which of p / m / v
-// are written.  16-byte accesses where every pointer in use is 16-byte aligned, with the last n % 4 elements scalar; scalar else.
-enum { OS_G = 1, OS_M = 2, OS_V = 4, OS_WP = 8, OS_WM = 16, OS_WV = 32 };
-template <int A, class F>
-__device__ __forceinline__ void opt_stream(int n, const float* __restrict__ g, float* __restrict__ p, float* __restrict__ m,
-                                           float* __restrict__ v, F f) {
-    const int tid = threadIdx.x;
-    uintptr_t al = (uintptr_t)p;
-    if constexpr ((A & OS_G) != 0) al |= (uintptr_t)g;
-    if constexpr ((A & (OS_M | OS_WM)) != 0) al |= (uintptr_t)m;
-    if constexpr ((A & (OS_V | OS_WV)) != 0) al |= (uintptr_t)v;
-    auto one = [&](int i) {
-        float gg = 0.f, pp = p[i], mm = 0.f, vv = 0.f;
-        if constexpr ((A & OS_G) != 0) gg = g[i];
-        if constexpr ((A & OS_M) != 0) mm = m[i];
-        if constexpr ((A & OS_V) != 0) vv = v[i];
-        f(gg, pp, mm, vv);
-        if constexpr ((A & OS_WP) != 0) p[i] = pp;
-        if constexpr ((A & OS_WM) != 0) m[i] = mm;
-        if constexpr ((A & OS_WV) != 0) v[i] = vv;
-    };
-    if ((al & 15u) == 0) {
-        const int nv = n >> 2;
-        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        f32x4 xg[OPT_VPT], xp[OPT_VPT], xm[OPT_VPT], xv[OPT_VPT];
-#pragma unroll
-        for (int k = 0; k < OPT_VPT; ++k) {
-            const int i = k * OPT_THREADS + tid;
-            xg[k] = xp[k] = xm[k] = xv[k] = zero;
-            if (i < nv) {
-                xp[k] = *reinterpret_cast<const f32x4*>(p + 4 * i);
-                if constexpr ((A & OS_G) != 0) xg[k] = *reinterpret_cast<const f32x4*>(g + 4 * i);
-                if constexpr ((A & OS_M) != 0) xm[k] = *reinterpret_cast<const f32x4*>(m + 4 * i);
-                if constexpr ((A & OS_V) != 0) xv[k] = *reinterpret_cast<const f32x4*>(v + 4 * i);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < OPT_VPT; ++k) {
-            const int i = k * OPT_THREADS + tid;
-            if (i < nv) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float pp = xp[k][e], mm = xm[k][e], vv = xv[k][e];
-                    f(xg[k][e], pp, mm, vv);
-                    xp[k][e] = pp;
-                    xm[k][e] = mm;
-                    xv[k][e] = vv;
-                }
-                if constexpr ((A & OS_WP) != 0) *reinterpret_cast<f32x4*>(p + 4 * i) = xp[k];
-                if constexpr ((A & OS_WM) != 0) *reinterpret_cast<f32x4*>(m + 4 * i) = xm[k];
-                if constexpr ((A & OS_WV) != 0) *reinterpret_cast<f32x4*>(v + 4 * i) = xv[k];
-            }
-        }
-        const int i = 4 * nv + tid;  // the last n % 4 elements
-        if (tid < 4 && i < n) one(i);
-    } else {
-        for (int i = tid; i < n; i += OPT_THREADS) one(i);
-    }
-}
-
-// the chunk this workgroup owns: false if its tensor has no gradient this step (workgroup-uniform)
-struct OptSlice {
-    const float* g;
-    float *p, *m, *v;
-    int n, group;
-    int64_t numel;
-};
-__device__ __forceinline__ bool opt_slice(const OptTensor* __restrict__ tens, const OptChunk& ck, const float* const* __restrict__ grads,
-                                          OptSlice& s) {
-    const float* g = grads[ck.tensor];
-    if (!g) return false;
-    const OptTensor t = tens[ck.tensor];
-    const int64_t off = (int64_t)ck.index * OPT_CHUNK;
-    const int64_t left = t.n - off;
-    s.n = left < OPT_CHUNK ? (int)left : OPT_CHUNK;
-    s.g = g + off;
-    s.p = t.p + off;
-    s.m = t.m + off;
-    s.v = t.v + off;
-    s.group = t.group;
-    s.numel = t.n;
-    return true;
-}
-
 template <class G>
 __global__ __launch_bounds__(OPT_THREADS) void k_sgd_step(const OptTensor* __restrict__ tens, const OptChunk* __restrict__ chunks,
                                                           const float* const* __restrict__ grads, const float* __restrict__ ctrl,
                                                           const G grp) {
     if (ctrl[OC_FOUND_INF] != 0.f) return;  // skipped step: nothing is written
+    const OptChunk ck = chunks[blockIdx.x];
     OptSlice s;
-    if (!opt_slice(tens, chunks[blockIdx.x], grads, s)) return;
+    if (!opt_slice(tens, ck, grads[ck.tensor], s)) return;
     const OptHyperArr& h = opt_hyper(grp);
     const float gmul = ctrl[OC_GMUL], lr = h.lr[s.group], wd = h.decay[s.group], mu = h.b1[s.group];
     const bool nesterov = h.b2[s.group] != 0.f;
     if (mu == 0.f) {  // (workgroup-uniform) no momentum: no buffer
-        opt_stream<OS_G | OS_WP>(s.n, s.g, s.p, nullptr, nullptr, [&](float g, float& p, float&, float&) {
+        opt_stream<OS_G | OS_P | OS_WP>(s.n, s.g, s.p, nullptr, nullptr, [&](float g, float& p, float&, float&) {
             g = g * gmul + wd * p;
             p -= lr * g;
         });
     } else {
-        opt_stream<OS_G | OS_M | OS_WP | OS_WM>(s.n, s.g, s.p, s.m, nullptr, [&](float g, float& p, float& m, float&) {
+        opt_stream<OS_G | OS_P | OS_M | OS_WP | OS_WM>(s.n, s.g, s.p, s.m, nullptr, [&](float g, float& p, float& m, float&) {
             g = g * gmul + wd * p;
             m = mu * m + g;
             p -= lr * (nesterov ? g + mu * m : m);
@@ -690,11 +651,12 @@ __global__ __launch_bounds__(OPT_THREADS) void k_lamb_moments(const OptTensor* _
                                                               const G grp, float* __restrict__ pn, float* __restrict__ un) {
     __shared__ float red_p[4], red_u[4];
     if (ctrl[OC_FOUND_INF] != 0.f) return;  // skipped step: m and v stay as they are (and launch 4 reads no partial)
+    const OptChunk ck = chunks[blockIdx.x];
     OptSlice s;
-    if (!opt_slice(tens, chunks[blockIdx.x], grads, s)) return;
+    if (!opt_slice(tens, ck, grads[ck.tensor], s)) return;
     const LambCoef c = lamb_coef(ctrl, grp, s.group);
     float sp = 0.f, su = 0.f;
-    opt_stream<OS_G | OS_M | OS_V | OS_WM | OS_WV>(s.n, s.g, s.p, s.m, s.v, [&](float g, float& p, float& m, float& v) {
+    opt_stream<OS_G | OS_P | OS_M | OS_V | OS_WM | OS_WV>(s.n, s.g, s.p, s.m, s.v, [&](float g, float& p, float& m, float& v) {
         g *= c.gmul;
         m = c.b1 * m + c.omb1 * g;
         v = c.b2 * v + c.omb2 * g * g;
@@ -718,31 +680,19 @@ __global__ __launch_bounds__(OPT_THREADS) void k_lamb_apply(const OptTensor* __r
     if (ctrl[OC_FOUND_INF] != 0.f) return;
     const OptChunk ck = chunks[blockIdx.x];
     OptSlice s;
-    if (!opt_slice(tens, ck, grads, s)) return;
-    const int tid = threadIdx.x;
-    const int first = (int)blockIdx.x - ck.index;                         // the tensor's chunks are [first, first + cnt)
+    if (!opt_slice(tens, ck, grads[ck.tensor], s)) return;
+    const int first = (int)blockIdx.x - ck.index;                  // the tensor's chunks are [first, first + cnt)
     const int cnt = (int)((s.numel + OPT_CHUNK - 1) / OPT_CHUNK);  // (< 2^31: opt_count)
     double sp = 0.0, su = 0.0;
-    for (int i = tid; i < cnt; i += OPT_THREADS) {
+    for (int i = threadIdx.x; i < cnt; i += OPT_THREADS) {
         sp += (double)pn[first + i];
         su += (double)un[first + i];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sp += __shfl_xor(sp, o);
-        su += __shfl_xor(su, o);
-    }
-    if ((tid & 63) == 0) {
-        red_p[tid >> 6] = sp;
-        red_u[tid >> 6] = su;
-    }
-    __syncthreads();
-    const float pnorm = (float)sqrt(red_p[0] + red_p[1] + red_p[2] + red_p[3]);
-    const float unorm = (float)sqrt(red_u[0] + red_u[1] + red_u[2] + red_u[3]);
+    const float pnorm = (float)sqrt(opt_block_sum(sp, red_p)), unorm = (float)sqrt(opt_block_sum(su, red_u));
     const LambCoef c = lamb_coef(ctrl, grp, s.group);
     const float lr = opt_hyper(grp).lr[s.group];
     const float ratio = ((c.wd != 0.f || use_nvlamb) && pnorm != 0.f && unorm != 0.f) ? lr * (pnorm / unorm) : lr;
-    opt_stream<OS_M | OS_V | OS_WP>(s.n, nullptr, s.p, s.m, s.v,
+    opt_stream<OS_P | OS_M | OS_V | OS_WP>(s.n, nullptr, s.p, s.m, s.v,
                                     [&](float, float& p, float& m, float& v) { p -= ratio * lamb_u(p, m, v, c); });
 }
 
@@ -759,110 +709,107 @@ static int opt_count(int64_t n_tensors, const int64_t* numel, int64_t* n_chunks)
     return MTLORA_OK;
 }
 
-// argument checks shared by the two entries, before any launch
-static int opt_check(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const void* groups, int n_groups,
-                     const float* ctrl, const float* norm_out, const float* scale, const int32_t* growth_tracker, float growth_factor,
-                     float backoff_factor, int growth_interval, const void* scratch, int64_t scratch_bytes) {
-    if (n_tensors <= 0 || n_tensors >= ((int64_t)1 << 31) || n_chunks < 0 || n_chunks >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
-    if (n_groups < 1 || n_groups > OPT_MAXG) return MTLORA_ERR_UNSUPPORTED;
-    if (!table || !grads || !groups || !ctrl || !scratch) return MTLORA_ERR_NULL;
-    if ((scale == nullptr) != (growth_tracker == nullptr)) return MTLORA_ERR_NULL;
-    if (((uintptr_t)table | (uintptr_t)grads | (uintptr_t)scratch) & 7u) return MTLORA_ERR_ALIGN;
-    if (((uintptr_t)ctrl | (uintptr_t)norm_out | (uintptr_t)scale | (uintptr_t)growth_tracker) & 3u) return MTLORA_ERR_ALIGN;
-    if (scratch_bytes < n_chunks * 8) return MTLORA_ERR_WORKSPACE;
-    if (scale && (growth_interval < 1 || !(growth_factor > 1.f) || !(backoff_factor > 0.f && backoff_factor < 1.f))) return MTLORA_ERR_SHAPE;
-    return MTLORA_OK;
-}
-
-struct OptLaunch {  // what the three launches share
-    hipStream_t s;
-    const OptTensor* te;
-    const OptChunk* ce;
-    const float* const* gp;
-    float* partials;
-    uint32_t* flags;
-    dim3 grid;
-    OptLaunch(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, void* scratch, void* stream)
-        : s(reinterpret_cast<hipStream_t>(stream)), te(reinterpret_cast<const OptTensor*>(table)),
-          ce(reinterpret_cast<const OptChunk*>(te + n_tensors)), gp(reinterpret_cast<const float* const*>(grads)),
-          partials(reinterpret_cast<float*>(scratch)), flags(reinterpret_cast<uint32_t*>(partials + n_chunks)),
-          grid((unsigned)n_chunks) {}
+// the arguments of an update entry: what all seven have, then LAMB's two, then the accumulating entries' (accum_steps >= 1; 0: the
+// entry does not accumulate) and the scheduled entry's buffer
+struct OptCall {
+    const void *table, *grads;
+    int64_t n_tensors, n_chunks;
+    const mtlora_adamw_group* groups;  // host records, or device records (an SGD record is read through the AdamW record's fields)
+    int n_groups;
+    float max_norm, *ctrl, *norm_out, *scale;
+    int32_t* tracker;
+    float growth, backoff;
+    int interval;
+    void* scratch;
+    int64_t scratch_bytes;
+    void* stream;
+    float lamb_max_norm = 0.f;
+    int use_nvlamb = 0;
+    float* acc = nullptr;
+    const int64_t* acc_off = nullptr;
+    int accum_steps = 0;
+    OptSched* sch = nullptr;
 };
 
-template <class G>
-static int opt_launch(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const G& g, float max_norm, float* ctrl,
-                      float* norm_out, float* scale, int32_t* growth_tracker, float growth_factor, float backoff_factor,
-                      int growth_interval, void* scratch, void* stream) {
-    const OptLaunch l(table, grads, n_tensors, n_chunks, scratch, stream);
-    const dim3 block(OPT_THREADS);
-    if (n_chunks > 0)
-        hipLaunchKernelGGL(k_optim_norm<false>, l.grid, block, 0, l.s, l.te, l.ce, l.gp, l.partials, l.flags, (float*)nullptr,
-                           (const int64_t*)nullptr, (const float*)nullptr);
-    hipLaunchKernelGGL((k_optim_finish<G, false>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g, max_norm, ctrl, norm_out,
-                       scale, growth_tracker, growth_factor, backoff_factor, growth_interval, 0, (OptSched*)nullptr, 0.f);
-    if (n_chunks > 0) hipLaunchKernelGGL((k_optim_step<G, OptGradPtrs>), l.grid, block, 0, l.s, l.te, l.ce, OptGradPtrs{l.gp}, ctrl, g);
-    MTL_CHECK_LAUNCH();
+// argument checks shared by the update entries, before any launch
+template <int ALG>
+static int opt_check(const OptCall& a) {
+    if (a.n_tensors <= 0 || a.n_tensors >= ((int64_t)1 << 31) || a.n_chunks < 0 || a.n_chunks >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
+    if (a.n_groups < 1 || a.n_groups > OPT_MAXG) return MTLORA_ERR_UNSUPPORTED;
+    if (!a.table || !a.grads || !a.groups || !a.ctrl || !a.scratch) return MTLORA_ERR_NULL;
+    if ((a.scale == nullptr) != (a.tracker == nullptr)) return MTLORA_ERR_NULL;
+    if (((uintptr_t)a.table | (uintptr_t)a.grads | (uintptr_t)a.scratch) & 7u) return MTLORA_ERR_ALIGN;
+    if (((uintptr_t)a.ctrl | (uintptr_t)a.norm_out | (uintptr_t)a.scale | (uintptr_t)a.tracker) & 3u) return MTLORA_ERR_ALIGN;
+    if (a.scratch_bytes < a.n_chunks * 8) return MTLORA_ERR_WORKSPACE;
+    if (a.scale && (a.interval < 1 || !(a.growth > 1.f) || !(a.backoff > 0.f && a.backoff < 1.f))) return MTLORA_ERR_SHAPE;
+    if constexpr (ALG == OPT_LAMB) {
+        if (a.scratch_bytes < a.n_chunks * 16) return MTLORA_ERR_WORKSPACE;  // two more words per chunk: |p|^2, |u|^2
+        if (!(a.lamb_max_norm == a.lamb_max_norm)) return MTLORA_ERR_SHAPE;
+    }
     return MTLORA_OK;
 }
 
-// one micro-step of a cycle of accum_steps.  With accum_steps == 1 every call is the cycle's last and updates straight from the
-// caller's gradients: acc is not touched, and the bits are opt_launch's.  sch: the schedule buffer, or null -- the same launches
-// either way, only k_optim_finish differs.
-static int opt_launch_accum(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const OptGroupsDev& g,
-                            float max_norm, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker, float growth_factor,
-                            float backoff_factor, int growth_interval, void* scratch, void* stream, float* acc, const int64_t* acc_off,
-                            int accum_steps, OptSched* sch) {
-    const OptLaunch l(table, grads, n_tensors, n_chunks, scratch, stream);
-    const dim3 block(OPT_THREADS);
-    const bool sum = accum_steps > 1;
-    if (n_chunks > 0) {
-        if (sum)
-            hipLaunchKernelGGL(k_optim_norm<true>, l.grid, block, 0, l.s, l.te, l.ce, l.gp, l.partials, l.flags, acc, acc_off,
-                               (const float*)ctrl);
-        else
-            hipLaunchKernelGGL(k_optim_norm<false>, l.grid, block, 0, l.s, l.te, l.ce, l.gp, l.partials, l.flags, (float*)nullptr,
-                               (const int64_t*)nullptr, (const float*)nullptr);
-    }
-    if (sch)
-        hipLaunchKernelGGL((k_optim_finish<OptGroupsDev, true, true>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g,
-                           max_norm, ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, accum_steps, sch, 0.f);
-    else
-        hipLaunchKernelGGL((k_optim_finish<OptGroupsDev, true>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g, max_norm,
-                           ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, accum_steps,
-                           (OptSched*)nullptr, 0.f);
-    if (n_chunks > 0) {
-        if (sum)
-            hipLaunchKernelGGL((k_optim_step<OptGroupsDev, OptGradAcc>), l.grid, block, 0, l.s, l.te, l.ce, OptGradAcc{l.gp, acc, acc_off},
-                               (const float*)ctrl, g);
-        else
-            hipLaunchKernelGGL((k_optim_step<OptGroupsDev, OptGradPtrs>), l.grid, block, 0, l.s, l.te, l.ce, OptGradPtrs{l.gp},
-                               (const float*)ctrl, g);
-    }
-    MTL_CHECK_LAUNCH();
-    return MTLORA_OK;
-}
-
+// THE host path of the update entries, behind opt_check and the entry's own checks: the kernels' groups argument G -- OptGroups,
+// derived here from the host records, or OptGroupsDev, the device records k_optim_finish derives from -- and the launches of
+// algorithm ALG: norm, finish, and its step kernel(s).  a.accum_steps >= 1 (AdamW on device records only): one micro-step of a
+// cycle of accum_steps.  With accum_steps == 1 every call is the cycle's last and updates straight from the caller's gradients:
+// acc is not touched, and the bits are the plain entry's.  a.sch: the schedule buffer, or null -- the same launches either way,
+// only k_optim_finish differs.
 template <int ALG, class G>
-static int opt_launch_as(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const G& g, float max_norm,
-                         float lamb_max_norm, int use_nvlamb, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker,
-                         float growth_factor, float backoff_factor, int growth_interval, void* scratch, void* stream) {
-    static_assert(ALG == OPT_SGD || ALG == OPT_LAMB, "AdamW has opt_launch");
-    const OptLaunch l(table, grads, n_tensors, n_chunks, scratch, stream);
-    const dim3 block(OPT_THREADS);
-    if (n_chunks > 0)
-        hipLaunchKernelGGL(k_optim_norm<false>, l.grid, block, 0, l.s, l.te, l.ce, l.gp, l.partials, l.flags, (float*)nullptr,
-                           (const int64_t*)nullptr, (const float*)nullptr);
-    hipLaunchKernelGGL((k_optim_finish<G, false, false, ALG>), dim3(1), block, 0, l.s, l.partials, l.flags, (int)n_chunks, g, max_norm, ctrl,
-                       norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, 0, (OptSched*)nullptr, lamb_max_norm);
-    if (n_chunks > 0) {
+static int opt_update(const OptCall& a) {
+    G g = {};
+    g.n = a.n_groups;
+    if constexpr (__is_same(G, OptGroupsDev)) {
+        if ((uintptr_t)a.groups & 7u) return MTLORA_ERR_ALIGN;
+        g.rec = a.groups;  // the records are only read; the tail behind them is the library's
+        g.hyp = reinterpret_cast<OptHyperArr*>(const_cast<mtlora_adamw_group*>(a.groups) + OPT_MAXG);
+    } else {
+        for (int i = 0; i < a.n_groups; ++i) {
+            OptHyper h;
+            if (!opt_derive_as<ALG>(a.groups[i], h)) return MTLORA_ERR_SHAPE;
+            opt_put(g.h, i, h);
+            g.b1d[i] = a.groups[i].beta1;  // (the bias corrections; SGD's finish does not read them)
+            g.b2d[i] = a.groups[i].beta2;
+        }
+    }
+    constexpr bool CYCLE = ALG == OPT_ADAMW && __is_same(G, OptGroupsDev);  // the entries with a micro-step counter
+    hipStream_t s = reinterpret_cast<hipStream_t>(a.stream);
+    const OptTensor* te = reinterpret_cast<const OptTensor*>(a.table);
+    const OptChunk* ce = reinterpret_cast<const OptChunk*>(te + a.n_tensors);
+    const float* const* gp = reinterpret_cast<const float* const*>(a.grads);
+    float* partials = reinterpret_cast<float*>(a.scratch);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(partials + a.n_chunks);
+    const float* ctrl = a.ctrl;
+    const dim3 grid((unsigned)a.n_chunks), block(OPT_THREADS);
+    const bool sum = a.accum_steps > 1;
+    if (a.n_chunks > 0) {
+        if (sum)
+            hipLaunchKernelGGL(k_optim_norm<true>, grid, block, 0, s, te, ce, gp, partials, flags, a.acc, a.acc_off, ctrl);
+        else
+            hipLaunchKernelGGL(k_optim_norm<false>, grid, block, 0, s, te, ce, gp, partials, flags, (float*)nullptr, (const int64_t*)nullptr,
+                               (const float*)nullptr);
+    }
+    auto* finish = k_optim_finish<G, false, false, ALG>;
+    if constexpr (CYCLE) {
+        if (a.sch)
+            finish = k_optim_finish<G, true, true>;
+        else if (a.accum_steps > 0)
+            finish = k_optim_finish<G, true>;
+    }
+    hipLaunchKernelGGL(finish, dim3(1), block, 0, s, partials, flags, (int)a.n_chunks, g, a.max_norm, a.ctrl, a.norm_out, a.scale, a.tracker,
+                       a.growth, a.backoff, a.interval, a.accum_steps, a.sch, a.lamb_max_norm);
+    if (a.n_chunks > 0) {
         if constexpr (ALG == OPT_SGD) {
-            hipLaunchKernelGGL((k_sgd_step<G>), l.grid, block, 0, l.s, l.te, l.ce, l.gp, (const float*)ctrl, g);
+            hipLaunchKernelGGL((k_sgd_step<G>), grid, block, 0, s, te, ce, gp, ctrl, g);
+        } else if constexpr (ALG == OPT_LAMB) {
+            float* pn = reinterpret_cast<float*>(flags + a.n_chunks);  // the scratch's second half: [n_chunks] |p|^2, [n_chunks] |u|^2
+            float* un = pn + a.n_chunks;
+            hipLaunchKernelGGL((k_lamb_moments<G>), grid, block, 0, s, te, ce, gp, ctrl, g, pn, un);
+            hipLaunchKernelGGL((k_lamb_apply<G>), grid, block, 0, s, te, ce, gp, ctrl, g, (const float*)pn, (const float*)un, a.use_nvlamb);
         } else {
-            float* pn = reinterpret_cast<float*>(l.flags + n_chunks);  // the scratch's second half: [n_chunks] |p|^2, [n_chunks] |u|^2
-            float* un = pn + n_chunks;
-            hipLaunchKernelGGL((k_lamb_moments<G>), l.grid, block, 0, l.s, l.te, l.ce, l.gp, (const float*)ctrl, g, pn, un);
-            hipLaunchKernelGGL((k_lamb_apply<G>), l.grid, block, 0, l.s, l.te, l.ce, l.gp, (const float*)ctrl, g, (const float*)pn,
-                               (const float*)un, use_nvlamb);
+            if constexpr (CYCLE)
+                if (sum) hipLaunchKernelGGL((k_optim_step<G, OptGradAcc>), grid, block, 0, s, te, ce, OptGradAcc{gp, a.acc, a.acc_off}, ctrl, g);
+            if (!sum) hipLaunchKernelGGL((k_optim_step<G, OptGradPtrs>), grid, block, 0, s, te, ce, OptGradPtrs{gp}, ctrl, g);
         }
     }
     MTL_CHECK_LAUNCH();
@@ -917,114 +864,62 @@ int mtlora_adamw_update(const void* table, const void* grads, int64_t n_tensors,
                         int n_groups, float max_norm, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker,
                         float growth_factor, float backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes,
                         void* stream) {
-    const int rc = opt_check(table, grads, n_tensors, n_chunks, groups, n_groups, ctrl, norm_out, scale, growth_tracker, growth_factor,
-                             backoff_factor, growth_interval, scratch, scratch_bytes);
-    if (rc != MTLORA_OK) return rc;
-    OptGroups g = {};
-    g.n = n_groups;
-    for (int i = 0; i < n_groups; ++i) {
-        OptHyper h;
-        if (!opt_derive(groups[i], h)) return MTLORA_ERR_SHAPE;
-        opt_put(g.h, i, h);
-        g.b1d[i] = groups[i].beta1;
-        g.b2d[i] = groups[i].beta2;
-    }
-    return opt_launch(table, grads, n_tensors, n_chunks, g, max_norm, ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor,
-                      growth_interval, scratch, stream);
+    const OptCall a = {table, grads, n_tensors, n_chunks, groups, n_groups, max_norm, ctrl, norm_out, scale, growth_tracker,
+                       growth_factor, backoff_factor, growth_interval, scratch, scratch_bytes, stream};
+    const int rc = opt_check<OPT_ADAMW>(a);
+    return rc != MTLORA_OK ? rc : opt_update<OPT_ADAMW, OptGroups>(a);
 }
 
 int mtlora_adamw_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks,
                             const mtlora_adamw_group* groups_dev, int n_groups, float max_norm, float* ctrl, float* norm_out, float* scale,
                             int32_t* growth_tracker, double growth_factor, double backoff_factor, int growth_interval, void* scratch,
                             int64_t scratch_bytes, void* stream) {
-    const float growth = (float)growth_factor, backoff = (float)backoff_factor;
-    const int rc = opt_check(table, grads, n_tensors, n_chunks, groups_dev, n_groups, ctrl, norm_out, scale, growth_tracker, growth, backoff,
-                             growth_interval, scratch, scratch_bytes);
-    if (rc != MTLORA_OK) return rc;
-    if ((uintptr_t)groups_dev & 7u) return MTLORA_ERR_ALIGN;
-    OptGroupsDev g;
-    g.rec = groups_dev;  // the records are only read; the tail behind them is the library's
-    g.hyp = reinterpret_cast<OptHyperArr*>(const_cast<mtlora_adamw_group*>(groups_dev) + OPT_MAXG);
-    g.n = n_groups;
-    return opt_launch(table, grads, n_tensors, n_chunks, g, max_norm, ctrl, norm_out, scale, growth_tracker, growth, backoff,
-                      growth_interval, scratch, stream);
+    const OptCall a = {table, grads, n_tensors, n_chunks, groups_dev, n_groups, max_norm, ctrl, norm_out, scale, growth_tracker,
+                       (float)growth_factor, (float)backoff_factor, growth_interval, scratch, scratch_bytes, stream};
+    const int rc = opt_check<OPT_ADAMW>(a);
+    return rc != MTLORA_OK ? rc : opt_update<OPT_ADAMW, OptGroupsDev>(a);
 }
 
-}  // extern "C"
-
-namespace {
-
-// the by-value and the device-record entry of SGD / LAMB: the records have one layout (an SGD record is read through the AdamW
-// record's fields), so one function serves both optimizers
-template <int ALG>
-int opt_update_as(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const mtlora_adamw_group* groups, bool dev,
-                  int n_groups, float max_norm, float lamb_max_norm, int use_nvlamb, float* ctrl, float* norm_out, float* scale,
-                  int32_t* growth_tracker, float growth, float backoff, int growth_interval, void* scratch, int64_t scratch_bytes,
-                  void* stream) {
-    const int rc = opt_check(table, grads, n_tensors, n_chunks, groups, n_groups, ctrl, norm_out, scale, growth_tracker, growth, backoff,
-                             growth_interval, scratch, scratch_bytes);
-    if (rc != MTLORA_OK) return rc;
-    if (ALG == OPT_LAMB && scratch_bytes < n_chunks * 16) return MTLORA_ERR_WORKSPACE;  // two more words per chunk: |p|^2, |u|^2
-    if (ALG == OPT_LAMB && !(lamb_max_norm == lamb_max_norm)) return MTLORA_ERR_SHAPE;
-    if (dev) {
-        if ((uintptr_t)groups & 7u) return MTLORA_ERR_ALIGN;
-        OptGroupsDev g;
-        g.rec = groups;  // the records are only read; the tail behind them is the library's
-        g.hyp = reinterpret_cast<OptHyperArr*>(const_cast<mtlora_adamw_group*>(groups) + OPT_MAXG);
-        g.n = n_groups;
-        return opt_launch_as<ALG>(table, grads, n_tensors, n_chunks, g, max_norm, lamb_max_norm, use_nvlamb, ctrl, norm_out, scale,
-                                  growth_tracker, growth, backoff, growth_interval, scratch, stream);
-    }
-    OptGroups g = {};
-    g.n = n_groups;
-    for (int i = 0; i < n_groups; ++i) {
-        OptHyper h;
-        if (!opt_derive_as<ALG>(groups[i], h)) return MTLORA_ERR_SHAPE;
-        opt_put(g.h, i, h);
-        g.b1d[i] = groups[i].beta1;  // (LAMB's bias corrections; SGD's finish does not read them)
-        g.b2d[i] = groups[i].beta2;
-    }
-    return opt_launch_as<ALG>(table, grads, n_tensors, n_chunks, g, max_norm, lamb_max_norm, use_nvlamb, ctrl, norm_out, scale,
-                              growth_tracker, growth, backoff, growth_interval, scratch, stream);
-}
-
-}  // namespace
-
-extern "C" {
-
+// SGD's records have the AdamW record's layout (see opt_derive_as)
 int mtlora_sgd_update(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const mtlora_sgd_group* groups,
                       int n_groups, float max_norm, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker,
                       float growth_factor, float backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes, void* stream) {
-    return opt_update_as<OPT_SGD>(table, grads, n_tensors, n_chunks, reinterpret_cast<const mtlora_adamw_group*>(groups), false, n_groups,
-                                  max_norm, 0.f, 0, ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval,
-                                  scratch, scratch_bytes, stream);
+    const OptCall a = {table, grads, n_tensors, n_chunks, reinterpret_cast<const mtlora_adamw_group*>(groups), n_groups, max_norm, ctrl,
+                       norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, scratch, scratch_bytes, stream};
+    const int rc = opt_check<OPT_SGD>(a);
+    return rc != MTLORA_OK ? rc : opt_update<OPT_SGD, OptGroups>(a);
 }
 
 int mtlora_sgd_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const mtlora_sgd_group* groups_dev,
                           int n_groups, float max_norm, float* ctrl, float* norm_out, float* scale, int32_t* growth_tracker,
                           double growth_factor, double backoff_factor, int growth_interval, void* scratch, int64_t scratch_bytes,
                           void* stream) {
-    return opt_update_as<OPT_SGD>(table, grads, n_tensors, n_chunks, reinterpret_cast<const mtlora_adamw_group*>(groups_dev), true,
-                                  n_groups, max_norm, 0.f, 0, ctrl, norm_out, scale, growth_tracker, (float)growth_factor,
-                                  (float)backoff_factor, growth_interval, scratch, scratch_bytes, stream);
+    const OptCall a = {table, grads, n_tensors, n_chunks, reinterpret_cast<const mtlora_adamw_group*>(groups_dev), n_groups, max_norm, ctrl,
+                       norm_out, scale, growth_tracker, (float)growth_factor, (float)backoff_factor, growth_interval, scratch, scratch_bytes,
+                       stream};
+    const int rc = opt_check<OPT_SGD>(a);
+    return rc != MTLORA_OK ? rc : opt_update<OPT_SGD, OptGroupsDev>(a);
 }
 
 int mtlora_lamb_update(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const mtlora_adamw_group* groups,
                        int n_groups, float max_norm, float max_grad_norm, int use_nvlamb, float* ctrl, float* norm_out, float* scale,
                        int32_t* growth_tracker, float growth_factor, float backoff_factor, int growth_interval, void* scratch,
                        int64_t scratch_bytes, void* stream) {
-    return opt_update_as<OPT_LAMB>(table, grads, n_tensors, n_chunks, groups, false, n_groups, max_norm, max_grad_norm, use_nvlamb != 0,
-                                   ctrl, norm_out, scale, growth_tracker, growth_factor, backoff_factor, growth_interval, scratch,
-                                   scratch_bytes, stream);
+    const OptCall a = {table, grads, n_tensors, n_chunks, groups, n_groups, max_norm, ctrl, norm_out, scale, growth_tracker,
+                       growth_factor, backoff_factor, growth_interval, scratch, scratch_bytes, stream, max_grad_norm, use_nvlamb != 0};
+    const int rc = opt_check<OPT_LAMB>(a);
+    return rc != MTLORA_OK ? rc : opt_update<OPT_LAMB, OptGroups>(a);
 }
 
 int mtlora_lamb_update_dev(const void* table, const void* grads, int64_t n_tensors, int64_t n_chunks, const mtlora_adamw_group* groups_dev,
                            int n_groups, float max_norm, float max_grad_norm, int use_nvlamb, float* ctrl, float* norm_out, float* scale,
                            int32_t* growth_tracker, double growth_factor, double backoff_factor, int growth_interval, void* scratch,
                            int64_t scratch_bytes, void* stream) {
-    return opt_update_as<OPT_LAMB>(table, grads, n_tensors, n_chunks, groups_dev, true, n_groups, max_norm, max_grad_norm, use_nvlamb != 0,
-                                   ctrl, norm_out, scale, growth_tracker, (float)growth_factor, (float)backoff_factor, growth_interval,
-                                   scratch, scratch_bytes, stream);
+    const OptCall a = {table, grads, n_tensors, n_chunks, groups_dev, n_groups, max_norm, ctrl, norm_out, scale, growth_tracker,
+                       (float)growth_factor, (float)backoff_factor, growth_interval, scratch, scratch_bytes, stream, max_grad_norm,
+                       use_nvlamb != 0};
+    const int rc = opt_check<OPT_LAMB>(a);
+    return rc != MTLORA_OK ? rc : opt_update<OPT_LAMB, OptGroupsDev>(a);
 }
 
 int mtlora_adamw_accum_layout(int64_t n_tensors, const int64_t* numel, int64_t* host_offsets, int64_t* acc_elems) {
@@ -1046,20 +941,16 @@ int mtlora_adamw_accum_update_dev(const void* table, const void* grads, int64_t 
                                   float* scale, int32_t* growth_tracker, double growth_factor, double backoff_factor, int growth_interval,
                                   void* scratch, int64_t scratch_bytes, float* acc, const int64_t* acc_offsets, int accum_steps,
                                   void* stream) {
-    const float growth = (float)growth_factor, backoff = (float)backoff_factor;
-    const int rc = opt_check(table, grads, n_tensors, n_chunks, groups_dev, n_groups, ctrl, norm_out, scale, growth_tracker, growth, backoff,
-                             growth_interval, scratch, scratch_bytes);
+    const OptCall a = {table, grads, n_tensors, n_chunks, groups_dev, n_groups, max_norm, ctrl, norm_out, scale, growth_tracker,
+                       (float)growth_factor, (float)backoff_factor, growth_interval, scratch, scratch_bytes, stream, 0.f, 0, acc, acc_offsets,
+                       accum_steps};
+    const int rc = opt_check<OPT_ADAMW>(a);
     if (rc != MTLORA_OK) return rc;
     if (!acc || !acc_offsets) return MTLORA_ERR_NULL;
     if (accum_steps < 1 || accum_steps > MTLORA_ADAMW_MAX_ACCUM_STEPS) return MTLORA_ERR_SHAPE;
     if (((uintptr_t)groups_dev | (uintptr_t)acc_offsets) & 7u) return MTLORA_ERR_ALIGN;
-    if ((uintptr_t)acc & 15u) return MTLORA_ERR_ALIGN;
-    OptGroupsDev g;
-    g.rec = groups_dev;
-    g.hyp = reinterpret_cast<OptHyperArr*>(const_cast<mtlora_adamw_group*>(groups_dev) + OPT_MAXG);
-    g.n = n_groups;
-    return opt_launch_accum(table, grads, n_tensors, n_chunks, g, max_norm, ctrl, norm_out, scale, growth_tracker, growth, backoff,
-                            growth_interval, scratch, stream, acc, acc_offsets, accum_steps, nullptr);
+    if (!opt_aligned16((uintptr_t)acc)) return MTLORA_ERR_ALIGN;
+    return opt_update<OPT_ADAMW, OptGroupsDev>(a);
 }
 
 int mtlora_lr_schedule_check(const mtlora_lr_schedule* host_record, int n_groups) {
@@ -1082,21 +973,17 @@ int mtlora_adamw_sched_update_dev(const void* table, const void* grads, int64_t 
                                   float* scale, int32_t* growth_tracker, double growth_factor, double backoff_factor, int growth_interval,
                                   void* scratch, int64_t scratch_bytes, float* acc, const int64_t* acc_offsets, int accum_steps,
                                   void* sched_dev, void* stream) {
-    const float growth = (float)growth_factor, backoff = (float)backoff_factor;
-    const int rc = opt_check(table, grads, n_tensors, n_chunks, groups_dev, n_groups, ctrl, norm_out, scale, growth_tracker, growth, backoff,
-                             growth_interval, scratch, scratch_bytes);
+    const OptCall a = {table, grads, n_tensors, n_chunks, groups_dev, n_groups, max_norm, ctrl, norm_out, scale, growth_tracker,
+                       (float)growth_factor, (float)backoff_factor, growth_interval, scratch, scratch_bytes, stream, 0.f, 0, acc, acc_offsets,
+                       accum_steps, reinterpret_cast<OptSched*>(sched_dev)};
+    const int rc = opt_check<OPT_ADAMW>(a);
     if (rc != MTLORA_OK) return rc;
     if (!sched_dev) return MTLORA_ERR_NULL;
     if (accum_steps < 1 || accum_steps > MTLORA_ADAMW_MAX_ACCUM_STEPS) return MTLORA_ERR_SHAPE;
     if (accum_steps > 1 && (!acc || !acc_offsets)) return MTLORA_ERR_NULL;  // (k = 1 updates straight from `grads`)
     if (((uintptr_t)groups_dev | (uintptr_t)acc_offsets | (uintptr_t)sched_dev) & 7u) return MTLORA_ERR_ALIGN;
-    if ((uintptr_t)acc & 15u) return MTLORA_ERR_ALIGN;
-    OptGroupsDev g;
-    g.rec = groups_dev;
-    g.hyp = reinterpret_cast<OptHyperArr*>(const_cast<mtlora_adamw_group*>(groups_dev) + OPT_MAXG);
-    g.n = n_groups;
-    return opt_launch_accum(table, grads, n_tensors, n_chunks, g, max_norm, ctrl, norm_out, scale, growth_tracker, growth, backoff,
-                            growth_interval, scratch, stream, acc, acc_offsets, accum_steps, reinterpret_cast<OptSched*>(sched_dev));
+    if (!opt_aligned16((uintptr_t)acc)) return MTLORA_ERR_ALIGN;
+    return opt_update<OPT_ADAMW, OptGroupsDev>(a);
 }
 
 }  // extern "C"
