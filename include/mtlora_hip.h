@@ -404,6 +404,38 @@ int mtlora_residual_droppath_bwd(int n, const void* const* g, void* const* dy, v
                                  int64_t M, int64_t C, int64_t B, int res_dtype, int y_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Activation dropout (MODEL.DROP_RATE: Mlp.drop on the hidden tensors and on fc2's outputs, WindowAttention.proj_drop, pos_drop;
+ * swin_transformer_mtlora.py:172-178, :274-279, :739) generated inside the kernels that consume the activation.  No mask is stored:
+ * forward and backward regenerate the keep bits from the counter-based generator of the linear layers' dropout (oracle:
+ * dropout_keep_mask).  Element (row m, channel c) of tensor k of a call uses
+ *     row m (of the (M, C) row-major matrix),   column c,   stream  site + 0x100 * k
+ * with site = 0x42 hidden, 0x43 projection, 0x44 Mlp output, 0x45 position, and k = 0 for the shared tensor, 1 + i for task i: every
+ * tensor of a call has an independent mask.  keep <=> bits >= floor(p * 65536), kept values are scaled by 1 / (1 - p), a p below
+ * 2^-16 is off.  The dropout argument is a mtlora_attn_dropout {p, seed, seed_offset}; seed_offset as there (a replayed graph draws
+ * fresh masks); the backward must be given the forward's seed, site and offset value.
+ *
+ *   mtlora_act_dropout_fwd:  a[k]  = keep[k] . act(h[k]) / (1 - p)                      act: 0 identity, 1 exact (erf) GELU
+ *   mtlora_act_dropout_bwd:  dh[k] = g[k] . keep[k] / (1 - p) . act'(h[k])              (h is not read, and may be NULL, for act 0)
+ *   mtlora_residual_droppath_drop_fwd:  out[k] = res[k] + scale[k][sample] * keep[k] / (1 - p) * y[k]
+ *   mtlora_residual_droppath_drop_bwd:  dy[k]  = scale[k][sample] * keep[k] / (1 - p) * g[k];  dres = sum_k g[k]
+ * n <= 1 + MTLORA_MAX_TASKS tensors of (M, C), C % 8 == 0, one launch; fp32 / bf16 / fp16 (the residual pair as the plain entries);
+ * products in fp32, rounded once.  The residual forms take the arguments of the plain entries (the dropped branch is never written);
+ * p == 0 there runs the plain kernels.  Statuses, in the order they are checked: dtype; n (and act) out of range SHAPE; a NULL
+ * pointer or dropout argument NULL; a tensor not 16-byte aligned ALIGN; C % 8, M % B, p outside [0, 1) or not finite, M >= 2^32
+ * (the row index is 32 bits) SHAPE.  M == 0 returns OK without a launch.
+ * ------------------------------------------------------------------------------------------ */
+int mtlora_act_dropout_fwd(int n, const void* const* h, void* const* a, const mtlora_attn_dropout* drop, int site, int act,
+                           int64_t M, int64_t C, int dtype, void* stream);
+int mtlora_act_dropout_bwd(int n, const void* const* g, const void* const* h, void* const* dh, const mtlora_attn_dropout* drop,
+                           int site, int act, int64_t M, int64_t C, int dtype, void* stream);
+int mtlora_residual_droppath_drop_fwd(int n, const void* const* res, const void* const* y, void* const* out, const float* scale,
+                                      const mtlora_attn_dropout* drop, int site, int64_t M, int64_t C, int64_t B, int res_dtype,
+                                      int y_dtype, void* stream);
+int mtlora_residual_droppath_drop_bwd(int n, const void* const* g, void* const* dy, void* dres, const float* scale,
+                                      const mtlora_attn_dropout* drop, int site, int64_t M, int64_t C, int64_t B, int res_dtype,
+                                      int y_dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Loss end of the train step, fused (callers): replaces the final
  * F.interpolate(pred, img_size, mode="bilinear") of models/swin_mtl.py:245 TOGETHER WITH the per-task loss of
  * mtl_loss_schemes.py and their autograd backward.

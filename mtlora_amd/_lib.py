@@ -42,8 +42,14 @@ class AttnDesc(Structure):
 
 
 class AttnDropout(Structure):
-    """mtlora_attn_dropout: attention dropout of the mtlora_window_attn_drop_* entry points"""
+    """mtlora_attn_dropout: the dropout argument of the mtlora_window_attn_drop_*, mtlora_act_dropout_* and
+    mtlora_residual_droppath_drop_* entry points"""
     _fields_ = [("p", c_float), ("seed", c_uint64), ("seed_offset", c_void_p)]
+
+
+# activation dropout sites (MTL_ACT_DROP_* of csrc/common.h): tensor k of a call draws from stream  site + ACT_DROP_TENSOR_STRIDE * k
+ACT_DROP_HIDDEN, ACT_DROP_PROJ, ACT_DROP_MLP_OUT, ACT_DROP_POS, ACT_DROP_TENSOR_STRIDE = 0x42, 0x43, 0x44, 0x45, 0x100
+ACT_IDENTITY, ACT_GELU = 0, 1
 
 
 class BlockDesc(Structure):
@@ -216,6 +222,14 @@ _SIGS = {
                                              c_int64, c_int64, c_int64, c_int, c_int, c_void_p]),
     "mtlora_residual_droppath_bwd": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p, c_int64,
                                              c_int64, c_int64, c_int, c_int, c_void_p]),
+    "mtlora_act_dropout_fwd": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(AttnDropout), c_int, c_int, c_int64, c_int64,
+                                       c_int, c_void_p]),
+    "mtlora_act_dropout_bwd": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(AttnDropout), c_int, c_int,
+                                       c_int64, c_int64, c_int, c_void_p]),
+    "mtlora_residual_droppath_drop_fwd": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_void_p,
+                                                  POINTER(AttnDropout), c_int, c_int64, c_int64, c_int64, c_int, c_int, c_void_p]),
+    "mtlora_residual_droppath_drop_bwd": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p, POINTER(AttnDropout),
+                                                  c_int, c_int64, c_int64, c_int64, c_int, c_int, c_void_p]),
     "mtlora_upsample_loss_partials": (c_int64, [c_int64, c_int, c_int, c_int]),
     "mtlora_colsum_scratch_bytes": (c_int64, [c_int64, c_int64]),
     "mtlora_colsum": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p]),

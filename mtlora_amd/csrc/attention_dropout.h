@@ -9,7 +9,7 @@
 //                                                window column; i, j: tokens of the window AFTER the cyclic shift, so both layouts
 //                                                draw the same mask for the same logical window)
 //       column  k = j
-//       stream  MTL_ATTN_DROP_STREAM            (the linear layers' activation dropout is stream 0, the only other one in use)
+//       stream  MTL_ATTN_DROP_STREAM            (the linear layers' dropout is stream 0; the activation dropout sites: common.h)
 //   keep threshold floor(p * 65536) and the 1 / (1 - p) factor exactly as the linear kernels use them (mtl_make_dropout; a p below
 //   2^-16 has threshold 0 and is "off").  m must fit 32 bits: the host refuses n_windows * nH * N >= 2^32.
 // One mix32 yields the bits of two adjacent keys (k >> 1).  Where a lane owns a QUERY its accumulator registers hold runs of four

@@ -94,6 +94,14 @@ __device__ __forceinline__ bool mtl_dropout_keep(const DropoutCfg& c, uint32_t r
     uint32_t bits = (k & 1u) ? (h >> 16) : (h & 0xFFFFu);
     return bits >= c.thr16;
 }
+// streams in use: 0 the linear layers' LoRA dropout, 0x41 attention dropout (MTL_ATTN_DROP_STREAM, attention_dropout.h), and the
+// activation dropout sites of MODEL.DROP_RATE below (act_dropout.h).  Tensor k of a call (0 the shared tensor, 1 + i task i) draws
+// from stream  site + MTL_ACT_DROP_TENSOR_STRIDE * k : every tensor gets an independent mask, as separate nn.Dropout calls give.
+constexpr uint32_t MTL_ACT_DROP_HIDDEN = 0x42u;    // Mlp: drop(act(fc1(x)))
+constexpr uint32_t MTL_ACT_DROP_PROJ = 0x43u;      // WindowAttention: proj_drop(proj(a))
+constexpr uint32_t MTL_ACT_DROP_MLP_OUT = 0x44u;   // Mlp: drop(fc2(h))
+constexpr uint32_t MTL_ACT_DROP_POS = 0x45u;       // backbone: pos_drop(patch_embed(x))
+constexpr uint32_t MTL_ACT_DROP_TENSOR_STRIDE = 0x100u;
 
 // ---------------------------------------------------------------------------------------------
 // element traits: one 16-byte vector = VEC elements
@@ -260,6 +268,38 @@ __device__ __forceinline__ u32x4 mtl_gelu_gate_pk4(const u32x4& g, const u32x4& 
     return o;
 }
 
+// ---- the same for fp32 tensors ----
+// d/dh of the exact (erf) GELU, the factor ATen's GeluBackward applies: Phi(h) + h * phi(h)
+// erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. fp32 rounding level) sharing its exp(-h^2/2) with the density:
+// ~16 VALU operations per element -- with ocml's erff + expf (~60) the epilogue of the hidden-width dX launches became
+// VALU-bound and gave back most of the saved pass.
+__device__ __forceinline__ float gelu_grad(float h) {
+    const float z = fabsf(h) * 0.70710678118654752f;
+    const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * z);
+    const float e = __expf(-z * z);  // exp(-h^2 / 2)
+    float p = 1.061405429f;
+    p = p * t - 1.453152027f;
+    p = p * t + 1.421413741f;
+    p = p * t - 0.284496736f;
+    p = p * t + 0.254829592f;
+    const float erf_abs = 1.f - p * t * e;  // erf(|h| / sqrt 2)
+    const float cdf = 0.5f + 0.5f * copysignf(erf_abs, h);
+    return cdf + h * e * 0.39894228040143268f;
+}
+
+// exact (erf) GELU with the same erf: h * Phi(h)
+__device__ __forceinline__ float gelu_fwd(float h) {
+    const float z = fabsf(h) * 0.70710678118654752f;
+    const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * z);
+    float p = 1.061405429f;
+    p = p * t - 1.453152027f;
+    p = p * t + 1.421413741f;
+    p = p * t - 0.284496736f;
+    p = p * t + 0.254829592f;
+    const float erf_abs = 1.f - p * t * __expf(-z * z);
+    return h * (0.5f + 0.5f * copysignf(erf_abs, h));
+}
+
 template <typename T>
 struct VOps;
 template <>
@@ -388,6 +428,7 @@ enum MtlProfKind {
     PK_NT_PLAIN_FWD = 17,  // k_nt at rank 0: y = x W^T + b of the callers (heads, PatchMerging reduction, patch embed)
     PK_NT_PLAIN_DX = 18,   // k_nt at rank 0: dX = dY W of the same
     PK_TN_PLAIN = 19,      // k_tn through mtlora_gemm_tn: narrow-output weight gradients of the callers
+    PK_ACT_DROP = 20,      // k_act_dropout: drop(act(h)) over 1+T tensors, one direction     2 (fwd) or 3 (bwd) tensors of M*C
     PK_COUNT = 24
 };
 int mtl_prof_start(int kind, double alg_bytes, hipStream_t s, double s8d_bytes = 0.0, double flops = 0.0);

@@ -1,5 +1,6 @@
 // glue.hip -- streaming glue kernels beside the LayerNorm family (ln.h / layernorm.hip): the decoder heads' training-mode
 // BatchNorm + ReLU and the residual + DropPath of a block half.  HBM-bound; the 16-byte vector helpers are in vec.h.
+#include "act_dropout.h"
 #include "dispatch.h"
 #include "internal.h"
 #include "vec.h"
@@ -405,11 +406,17 @@ struct ResParams {
     int64_t rows_per_sample;
 };
 
-// TR: dtype of res / out / g ; TY: dtype of y / dy
-template <typename TR, typename TY>
-__global__ __launch_bounds__(256) void k_residual_fwd(const ResParams p) {
+// TR: dtype of res / out / g ; TY: dtype of y / dy.  DROP: dropout on the branch (proj_drop / the Mlp's output drop, act_dropout.h):
+//   out_k = res_k + s_k * keep_k / (1 - p) * y_k ,   dy_k = s_k * keep_k / (1 - p) * g_k   -- the dropped branch never exists in memory
+template <typename TR, typename TY, bool DROP>
+__global__ __launch_bounds__(256) void k_residual_fwd(const ResParams p, const ActDrop dr) {
     const int64_t nvec = p.M * p.C / 8;
     const int k = blockIdx.y;
+    DropoutCfg cfg;
+    if constexpr (DROP) {
+        cfg = dr.cfg;
+        mtl_dropout_resolve(cfg);
+    }
     const TR* res = reinterpret_cast<const TR*>(p.res[k]);
     const TY* y = reinterpret_cast<const TY*>(p.y[k]);
     TR* out = reinterpret_cast<TR*>(p.out[k]);
@@ -435,15 +442,27 @@ __global__ __launch_bounds__(256) void k_residual_fwd(const ResParams p) {
         } else {
             ld_vec<TY>(y + i * 8, fy);
         }
+        if constexpr (DROP) {
+            const uint32_t keep = mtl_act_keep8(cfg, mtl_act_rowhash(cfg, dr.site, k, row), (uint32_t)(i * 8 - row * p.C));
+            const float sk = s * dr.inv_keep;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = fr[e] + s * fy[e];
+            for (int e = 0; e < 8; ++e) o[e] = (keep >> e & 1u) ? fr[e] + sk * fy[e] : fr[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = fr[e] + s * fy[e];
+        }
         st_vec<TR, 8>(out + i * 8, o);
     }
 }
 
-template <typename TR, typename TY>
-__global__ __launch_bounds__(256) void k_residual_bwd(const ResParams p) {
+template <typename TR, typename TY, bool DROP>
+__global__ __launch_bounds__(256) void k_residual_bwd(const ResParams p, const ActDrop dr) {
     const int64_t nvec = p.M * p.C / 8;
+    DropoutCfg cfg;
+    if constexpr (DROP) {
+        cfg = dr.cfg;
+        mtl_dropout_resolve(cfg);
+    }
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
         const int64_t row = (i * 8) / p.C;
         const int64_t b = row / p.rows_per_sample;
@@ -465,10 +484,20 @@ __global__ __launch_bounds__(256) void k_residual_bwd(const ResParams p) {
             }
             const float s = p.scale ? p.scale[(int64_t)k * p.B + b] : 1.f;
             float o[8];
+            if constexpr (DROP) {
+                const uint32_t keep = mtl_act_keep8(cfg, mtl_act_rowhash(cfg, dr.site, k, row), (uint32_t)(i * 8 - row * p.C));
+                const float sk = s * dr.inv_keep;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                acc[e] += fg[e];
-                o[e] = s * fg[e];
+                for (int e = 0; e < 8; ++e) {
+                    acc[e] += fg[e];
+                    o[e] = (keep >> e & 1u) ? sk * fg[e] : 0.f;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    acc[e] += fg[e];
+                    o[e] = s * fg[e];
+                }
             }
             if (p.out[k]) st_vec<TY, 8>(reinterpret_cast<TY*>(p.out[k]) + i * 8, o);
         }
@@ -480,6 +509,63 @@ int res_check(int n, int64_t M, int64_t C, int64_t B, int rdt, int ydt) {
     if (!mtl_dtype_pair_ok(rdt, ydt)) return MTLORA_ERR_DTYPE;
     if (n < 1 || n > MTLORA_MAX_TASKS + 1 || M < 0 || C <= 0 || C % 8 || B <= 0 || M % B) return MTLORA_ERR_SHAPE;
     return MTLORA_OK;
+}
+
+void res_shape(ResParams& p, const float* scale, int n, int64_t M, int64_t C, int64_t B) {
+    p.scale = scale;
+    p.M = M;
+    p.C = (int)C;
+    p.n = n;
+    p.B = (int)B;
+    p.rows_per_sample = M / B;
+}
+
+// dr: null = the plain kernels
+int res_fwd_launch(const ResParams& p, int res_dtype, int y_dtype, const ActDrop* dr, hipStream_t s) {
+    int64_t blocks = mtl_ceil_div(p.M * p.C / 8, 256);
+    if (blocks > 2048) blocks = 2048;
+    dim3 g((unsigned)blocks, (unsigned)p.n);
+    const int er = mtl_elem_size(res_dtype), ey = mtl_elem_size(y_dtype);
+    MtlProfScope prof(PK_RESIDUAL, (double)p.n * p.M * p.C * (2 * er + ey), s);
+    mtl_dispatch_dtype_pair(res_dtype, y_dtype, [&](auto tr, auto ty) {
+        using TR = typename decltype(tr)::type;
+        using TY = typename decltype(ty)::type;
+        if (dr)
+            hipLaunchKernelGGL((k_residual_fwd<TR, TY, true>), g, dim3(256), 0, s, p, *dr);
+        else
+            hipLaunchKernelGGL((k_residual_fwd<TR, TY, false>), g, dim3(256), 0, s, p, ActDrop{});
+    });
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
+int res_bwd_launch(const ResParams& p, int res_dtype, int y_dtype, const ActDrop* dr, hipStream_t s) {
+    int64_t blocks = mtl_ceil_div(p.M * p.C / 8, 256);
+    if (blocks > 2048) blocks = 2048;
+    const int er = mtl_elem_size(res_dtype), ey = mtl_elem_size(y_dtype);
+    MtlProfScope prof(PK_RESIDUAL, (double)p.M * p.C * (p.n * (er + ey) + (p.dres ? er : 0)), s);
+    mtl_dispatch_dtype_pair(res_dtype, y_dtype, [&](auto tr, auto ty) {
+        using TR = typename decltype(tr)::type;
+        using TY = typename decltype(ty)::type;
+        if (dr)
+            hipLaunchKernelGGL((k_residual_bwd<TR, TY, true>), dim3((unsigned)blocks), dim3(256), 0, s, p, *dr);
+        else
+            hipLaunchKernelGGL((k_residual_bwd<TR, TY, false>), dim3((unsigned)blocks), dim3(256), 0, s, p, ActDrop{});
+    });
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
+// the _drop entries: one condition per step, in the order dtype, n, pointers, alignment, C, M / B, p, row range
+int res_drop_check_head(int n, int rdt, int ydt) {
+    if (!mtl_dtype_pair_ok(rdt, ydt)) return MTLORA_ERR_DTYPE;
+    if (n < 1 || n > MTLORA_MAX_TASKS + 1) return MTLORA_ERR_SHAPE;
+    return MTLORA_OK;
+}
+int res_drop_check_tail(const mtlora_attn_dropout* drop, int site, int64_t M, int64_t C, int64_t B, ActDrop& dr) {
+    if (C <= 0 || C % 8 || C > INT32_MAX) return MTLORA_ERR_SHAPE;
+    if (M < 0 || B <= 0 || B > INT32_MAX || M % B) return MTLORA_ERR_SHAPE;
+    return mtl_act_drop_make(drop, site, M, dr);
 }
 
 }  // namespace
@@ -501,23 +587,8 @@ int mtlora_residual_droppath_fwd(int n, const void* const* res, const void* cons
         p.out[k] = out[k];
     }
     if (M == 0) return MTLORA_OK;
-    p.scale = scale;
-    p.M = M;
-    p.C = (int)C;
-    p.n = n;
-    p.B = (int)B;
-    p.rows_per_sample = M / B;
-    hipStream_t s = (hipStream_t)stream;
-    int64_t blocks = mtl_ceil_div(M * C / 8, 256);
-    if (blocks > 2048) blocks = 2048;
-    dim3 g((unsigned)blocks, (unsigned)n);
-    const int er = mtl_elem_size(res_dtype), ey = mtl_elem_size(y_dtype);
-    MtlProfScope prof(PK_RESIDUAL, (double)n * M * C * (2 * er + ey), s);
-    mtl_dispatch_dtype_pair(res_dtype, y_dtype, [&](auto tr, auto ty) {
-        hipLaunchKernelGGL((k_residual_fwd<typename decltype(tr)::type, typename decltype(ty)::type>), g, dim3(256), 0, s, p);
-    });
-    MTL_CHECK_LAUNCH();
-    return MTLORA_OK;
+    res_shape(p, scale, n, M, C, B);
+    return res_fwd_launch(p, res_dtype, y_dtype, nullptr, (hipStream_t)stream);
 }
 
 /* g[k]: gradient of out_k (res dtype) or NULL; dy[k]: written (y dtype) where non-NULL; dres: sum_k g_k or NULL */
@@ -534,21 +605,49 @@ int mtlora_residual_droppath_bwd(int n, const void* const* g, void* const* dy, v
     }
     if (M == 0) return MTLORA_OK;
     p.dres = dres;
-    p.scale = scale;
-    p.M = M;
-    p.C = (int)C;
-    p.n = n;
-    p.B = (int)B;
-    p.rows_per_sample = M / B;
-    hipStream_t s = (hipStream_t)stream;
-    int64_t blocks = mtl_ceil_div(M * C / 8, 256);
-    if (blocks > 2048) blocks = 2048;
-    const int er = mtl_elem_size(res_dtype), ey = mtl_elem_size(y_dtype);
-    MtlProfScope prof(PK_RESIDUAL, (double)M * C * (n * (er + ey) + (dres ? er : 0)), s);
-    mtl_dispatch_dtype_pair(res_dtype, y_dtype, [&](auto tr, auto ty) {
-        hipLaunchKernelGGL((k_residual_bwd<typename decltype(tr)::type, typename decltype(ty)::type>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    });
-    MTL_CHECK_LAUNCH();
-    return MTLORA_OK;
+    res_shape(p, scale, n, M, C, B);
+    return res_bwd_launch(p, res_dtype, y_dtype, nullptr, (hipStream_t)stream);
+}
+
+/* the same with dropout on the branch; a p below 2^-16 runs the plain kernels */
+int mtlora_residual_droppath_drop_fwd(int n, const void* const* res, const void* const* y, void* const* out, const float* scale,
+                                      const mtlora_attn_dropout* drop, int site, int64_t M, int64_t C, int64_t B, int res_dtype,
+                                      int y_dtype, void* stream) {
+    int st = res_drop_check_head(n, res_dtype, y_dtype);
+    if (st != MTLORA_OK) return st;
+    if (mtl_any_null({res, y, out, drop})) return MTLORA_ERR_NULL;
+    ResParams p = {};
+    for (int k = 0; k < n; ++k) {
+        if (mtl_any_null({res[k], y[k], out[k]})) return MTLORA_ERR_NULL;
+        if (mtl_any_misaligned({res[k], y[k], out[k]})) return MTLORA_ERR_ALIGN;
+        p.res[k] = res[k];
+        p.y[k] = y[k];
+        p.out[k] = out[k];
+    }
+    ActDrop dr = {};
+    if ((st = res_drop_check_tail(drop, site, M, C, B, dr)) != MTLORA_OK) return st;
+    if (M == 0) return MTLORA_OK;
+    res_shape(p, scale, n, M, C, B);
+    return res_fwd_launch(p, res_dtype, y_dtype, dr.cfg.enabled() ? &dr : nullptr, (hipStream_t)stream);
+}
+
+int mtlora_residual_droppath_drop_bwd(int n, const void* const* g, void* const* dy, void* dres, const float* scale,
+                                      const mtlora_attn_dropout* drop, int site, int64_t M, int64_t C, int64_t B, int res_dtype,
+                                      int y_dtype, void* stream) {
+    int st = res_drop_check_head(n, res_dtype, y_dtype);
+    if (st != MTLORA_OK) return st;
+    if (mtl_any_null({g, dy, drop})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({dres}, n, {g, mtl_arr(dy)})) return MTLORA_ERR_ALIGN;  // (null elements of g / dy are allowed)
+    ResParams p = {};
+    for (int k = 0; k < n; ++k) {
+        p.y[k] = g[k];
+        p.out[k] = g[k] ? dy[k] : nullptr;
+    }
+    ActDrop dr = {};
+    if ((st = res_drop_check_tail(drop, site, M, C, B, dr)) != MTLORA_OK) return st;
+    if (M == 0) return MTLORA_OK;
+    p.dres = dres;
+    res_shape(p, scale, n, M, C, B);
+    return res_bwd_launch(p, res_dtype, y_dtype, dr.cfg.enabled() ? &dr : nullptr, (hipStream_t)stream);
 }
 }

@@ -455,37 +455,6 @@ __device__ __forceinline__ NtCursor nt_seek(NtPtr P, int q, int nseq, int bn) {
 // NW = waves per workgroup.  The 128 x 128 tile is unchanged; with 8 waves a wave owns 64 n x 32 m (half the
 // accumulators, half the staging registers, half the loads / LDS traffic / MFMAs per step), fits 128 VGPRs and runs
 // 4 waves per SIMD instead of 2 -- the kernel is latency- and issue-bound, not bandwidth-bound.
-// d/dh of the exact (erf) GELU, the factor ATen's GeluBackward applies: Phi(h) + h * phi(h)
-// erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. fp32 rounding level) sharing its exp(-h^2/2) with the density:
-// ~16 VALU operations per element -- with ocml's erff + expf (~60) the epilogue of the hidden-width dX launches became
-// VALU-bound and gave back most of the saved pass.
-__device__ __forceinline__ float gelu_grad(float h) {
-    const float z = fabsf(h) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * z);
-    const float e = __expf(-z * z);  // exp(-h^2 / 2)
-    float p = 1.061405429f;
-    p = p * t - 1.453152027f;
-    p = p * t + 1.421413741f;
-    p = p * t - 0.284496736f;
-    p = p * t + 0.254829592f;
-    const float erf_abs = 1.f - p * t * e;  // erf(|h| / sqrt 2)
-    const float cdf = 0.5f + 0.5f * copysignf(erf_abs, h);
-    return cdf + h * e * 0.39894228040143268f;
-}
-
-// exact (erf) GELU with the same erf: h * Phi(h)
-__device__ __forceinline__ float gelu_fwd(float h) {
-    const float z = fabsf(h) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * z);
-    float p = 1.061405429f;
-    p = p * t - 1.453152027f;
-    p = p * t + 1.421413741f;
-    p = p * t - 0.284496736f;
-    p = p * t + 0.254829592f;
-    const float erf_abs = 1.f - p * t * __expf(-z * z);
-    return h * (0.5f + 0.5f * copysignf(erf_abs, h));
-}
-
 template <typename T, bool MULTI, bool MS, bool MLR, int NW, bool GATE = false, bool ACT = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void k_nt(const NtParams Pv) {
     constexpr int SM = 8 / NW;       // 32-row m sub-blocks per wave

@@ -186,6 +186,7 @@ extern "C" const char* mtlora_prof_kind_name(int kind) {
         case PK_NT_PLAIN_FWD: return "k_nt:plain_fwd";
         case PK_NT_PLAIN_DX: return "k_nt:plain_dX";
         case PK_TN_PLAIN: return "k_tn:plain_dW";
+        case PK_ACT_DROP: return "k_act_dropout";
         default: return "";
     }
 }

@@ -1129,10 +1129,14 @@ class ResidualLayerNormMultiFn(torch.autograd.Function):
         return (None, dg, db, None, None, None, dsh.view(ctx.shape), *[d.view(ctx.shape) for d in dbr])
 
 
-def residual_layer_norm_multi(mod: torch.nn.Module, shortcut: torch.Tensor, branches, drop_prob: float, training: bool):
+def residual_layer_norm_multi(mod: torch.nn.Module, shortcut: torch.Tensor, branches, drop_prob: float, training: bool, drop=None):
     """([x_new_k], [mod(x_new_k)]) with x_new_k = shortcut + DropPath_k(branches[k]) (an independent per-sample mask per k):
-    the fused multi-stream kernels when they apply, else residual_droppath + layer_norm_fork per stream."""
+    the fused multi-stream kernels when they apply, else residual_droppath + layer_norm_fork per stream.  ``drop``: a pending
+    activation dropout of the branches (``residual_droppath``): the fused residual + LayerNorm forms have no dropout."""
     C, n = shortcut.shape[-1], len(branches)
+    if drop is not None:
+        forks = [layer_norm_fork(mod, x) for x in residual_droppath(shortcut, list(branches), drop_prob, training, drop)]
+        return [f[0] for f in forks], [f[1] for f in forks]
     ok = (_ln_module_ok(mod, last_dim_only=True) and _ln_width_ok(shortcut, multiple=8, width=C, cap=(1024, 1536))
           and shortcut.dim() == 3 and 1 <= n <= L.MAX_TASKS + 1 and all(b.shape == shortcut.shape for b in branches) and torch.is_grad_enabled()
           and (shortcut.requires_grad or any(b.requires_grad for b in branches)))
@@ -1148,10 +1152,13 @@ def residual_layer_norm_multi(mod: torch.nn.Module, shortcut: torch.Tensor, bran
     return list(outs[:n]), list(outs[n:])
 
 
-def residual_layer_norm(mod: torch.nn.Module, shortcut: torch.Tensor, branch: torch.Tensor, drop_prob: float, training: bool):
+def residual_layer_norm(mod: torch.nn.Module, shortcut: torch.Tensor, branch: torch.Tensor, drop_prob: float, training: bool, drop=None):
     """(x_new, mod(x_new)) with x_new = shortcut + DropPath(branch): the fused kernel when it applies (nn.LayerNorm over
-    the last dim, branch already in the dtype the LayerNorm output takes), else residual_droppath + layer_norm_fork."""
+    the last dim, branch already in the dtype the LayerNorm output takes), else residual_droppath + layer_norm_fork.  ``drop``: a
+    pending activation dropout of the branch, as in ``residual_layer_norm_multi``."""
     C = shortcut.shape[-1]
+    if drop is not None:
+        return layer_norm_fork(mod, residual_droppath(shortcut, [branch], drop_prob, training, drop)[0])
     ok = (_ln_module_ok(mod, last_dim_only=True) and _ln_width_ok(shortcut, multiple=8, width=C)
           and branch.shape == shortcut.shape and shortcut.dim() == 3 and torch.is_grad_enabled() and (shortcut.requires_grad or branch.requires_grad))
     if ok:
@@ -1329,12 +1336,144 @@ class BatchNormReluFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------------------------
+# activation dropout (MODEL.DROP_RATE) generated inside the kernels: hidden / projection / Mlp output / position
+# ----------------------------------------------------------------------------------------------
+def act_dropout_stream(site: int, k: int) -> int:
+    """generator stream of tensor ``k`` of a call at ``site`` (``L.ACT_DROP_*``): 0 the shared tensor, 1 + i task i"""
+    return site + L.ACT_DROP_TENSOR_STRIDE * k
+
+
+def act_dropout_keep(seed: int, site: int, k: int, rows: int, cols: int, p: float, device="cpu") -> torch.Tensor:
+    """keep[m, c] (bool) of element (row m, channel c) of tensor ``k`` of a call at ``site``: the counter-based generator of
+    csrc/common.h (``mtl_dropout_keep``) in int64 torch arithmetic, on any device -- the definition the kernels implement."""
+    thr = min(int(p * 65536.0), 65535) if p > 0.0 else 0
+    if thr == 0:
+        return torch.ones(rows, cols, dtype=torch.bool, device=device)
+    M32 = 0xFFFFFFFF
+
+    def mix(x):  # x in [0, 2^32): int64 products wrap mod 2^64, the low 32 bits are exact
+        x = x ^ (x >> 16)
+        x = (x * 0x7FEB352D) & M32
+        x = x ^ (x >> 15)
+        x = (x * 0x846CA68B) & M32
+        return x ^ (x >> 16)
+
+    seed_lo, seed_hi = seed & M32, (seed >> 32) & M32
+    m = torch.arange(rows, dtype=torch.int64, device=device)[:, None]
+    c = torch.arange(cols, dtype=torch.int64, device=device)[None, :]
+    rh = mix((m * 0x9E3779B1 + seed_lo + act_dropout_stream(site, k) * 0x85EBCA77) & M32)
+    h = mix(rh ^ (((c >> 1) + seed_hi * 0x27D4EB2F) & M32))
+    bits = torch.where((c & 1) == 1, h >> 16, h & 0xFFFF)
+    return bits >= thr
+
+
+def _dropped(x: torch.Tensor, seed: int, site: int, k: int, p: float) -> torch.Tensor:
+    C = x.shape[-1]
+    keep = act_dropout_keep(seed, site, k, x.numel() // C, C, p, x.device).view(x.shape)
+    on = p > 0.0 and int(p * 65536.0) > 0
+    return torch.where(keep, x * (1.0 / (1.0 - p)) if on else x, torch.zeros((), dtype=x.dtype, device=x.device))
+
+
+def act_dropout_torch(hs, act: int, p: float, seed: int, site: int):
+    """portable definition of :class:`ActDropoutFn`: [keep_k * act(h_k) / (1 - p)] in plain torch (any device; ``seed`` is the
+    effective seed, any device-side offset already added)"""
+    return [_dropped(torch.nn.functional.gelu(h) if act == L.ACT_GELU else h, seed, site, k, p) for k, h in enumerate(hs)]
+
+
+def residual_droppath_drop_torch(res, ys, scale, p: float, seed: int, site: int):
+    """portable definition of ``residual_droppath(..., drop=(p, seed, site))``: [res_k + scale[k, sample] * keep_k * ys_k / (1 - p)];
+    ``res`` one shared tensor or a list, ``scale`` (n, B) or None, ``seed`` the effective seed"""
+    shared = not isinstance(res, (list, tuple))
+    out = []
+    for k, y in enumerate(ys):
+        y = _dropped(y, seed, site, k, p)
+        if scale is not None:
+            y = y * scale[k].view(-1, *([1] * (y.ndim - 1))).to(y.dtype)
+        out.append((res if shared else res[k]) + y)
+    return out
+
+
+def _effective_seed(seed: int) -> int:
+    """host value of ``seed`` + the device seed-offset word (a synchronising read: portable fallbacks only)"""
+    off = 0 if _seed_offset is None else int(_seed_offset.item())
+    return (seed + off) & 0xFFFFFFFFFFFFFFFF
+
+
+def _drop_arg(p: float, seed: int) -> "L.AttnDropout":
+    dr = L.AttnDropout()
+    dr.p, dr.seed, dr.seed_offset = p, seed, (0 if _seed_offset is None else _seed_offset.data_ptr())
+    return dr
+
+
+def act_dropout_ok(ts) -> bool:
+    """may the activation-dropout kernels take these tensors?  On the GPU, contiguous, one kernel dtype and shape, width % 8 == 0"""
+    t0 = ts[0]
+    return (1 <= len(ts) <= L.MAX_TASKS + 1 and t0.is_cuda and t0.dtype in _GLUE_DTYPES and t0.dim() >= 2 and t0.shape[-1] % 8 == 0
+            and t0.numel() // t0.shape[-1] < (1 << 32)
+            and all(t.is_cuda and t.dtype == t0.dtype and t.shape == t0.shape and t.is_contiguous() for t in ts))
+
+
+def pending_dropout(p: float, site: int):
+    """a dropout that the consumer applies (``residual_droppath(..., drop=...)``): draws the call site's seed NOW, in forward order"""
+    return (float(p), next_seed(), site)
+
+
+class ActDropoutFn(torch.autograd.Function):
+    """outs[k] = keep_k * act(hs[k]) / (1 - p) for the n tensors of a call site, one launch per direction; the backward reads the
+    gradient (and h for GELU) and regenerates keep_k.  ``act``: ``L.ACT_IDENTITY`` / ``L.ACT_GELU`` (exact erf form); ``seed`` (plus the
+    device word of :func:`set_seed_offset`) and the tensor's index select the mask (:func:`act_dropout_keep`).
+    args: site, act, p, seed, *hs"""
+
+    @staticmethod
+    def forward(ctx, site: int, act: int, p: float, seed: int, *hs):
+        L.require_gpu(*hs)
+        n, C = len(hs), hs[0].shape[-1]
+        M = hs[0].numel() // C
+        hc = [h.contiguous() for h in hs]
+        outs = [torch.empty_like(h) for h in hc]
+        dr = _drop_arg(float(p), int(seed))
+        st = L.lib().mtlora_act_dropout_fwd(n, L.ptr_array9(hc), L.ptr_array9(outs), ctypes.byref(dr), site, act, M, C,
+                                            L.dtype_code(hc[0]), L.stream_ptr())
+        L.check(st, "mtlora_act_dropout_fwd")
+        ctx.cfg = (site, act, n, M, C, hc[0].dtype, dr, _seed_offset)
+        if act != L.ACT_IDENTITY:
+            ctx.save_for_backward(*hc)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        site, act, n, M, C, dt, dr, _ = ctx.cfg
+        hc = ctx.saved_tensors
+        gs = [g.to(dt).contiguous() for g in grads]
+        dhs = [torch.empty_like(g) for g in gs]
+        st = L.lib().mtlora_act_dropout_bwd(n, L.ptr_array9(gs), L.ptr_array9(hc), L.ptr_array9(dhs), ctypes.byref(dr),
+                                            site, act, M, C, L._DT[dt], L.stream_ptr())
+        L.check(st, "mtlora_act_dropout_bwd")
+        return (None, None, None, None, *dhs)
+
+
+def apply_pending_dropout(ts, drop):
+    """a pending dropout (``pending_dropout``) applied as a launch of its own: the same mask the residual kernel would have used"""
+    return list(ActDropoutFn.apply(drop[2], L.ACT_IDENTITY, drop[0], drop[1], *ts))
+
+
+def act_dropout(ts, act: int, p: float, site: int):
+    """[drop(act(t))] for the tensors of one call site through :class:`ActDropoutFn` (one seed for the call), or None when the
+    kernels do not take them (the caller's nn.Dropout path then runs, and no seed has been drawn)"""
+    if not act_dropout_ok(ts):
+        return None
+    return list(ActDropoutFn.apply(site, act, float(p), next_seed(), *ts))
+
+
+# ----------------------------------------------------------------------------------------------
 # residual + DropPath over the 1+T tensors of a block half
 # ----------------------------------------------------------------------------------------------
 class ResidualDropPathFn(torch.autograd.Function):
     """outs[k] = res[k] + scale[k, sample] * ys[k].
     args: scale ((n, B) fp32 or None), shared (bool: every k adds the SAME residual tensor res[0]), n,
-          *res (1 tensor if shared else n), *ys (n)."""
+          *res (1 tensor if shared else n), *ys (n) [, p, seed, site].
+    Optional ``p, seed, site``: dropout on the branches (``proj_drop`` / the Mlp's output drop) generated inside the kernels --
+    outs[k] = res[k] + scale[k, sample] * keep[k] / (1 - p) * ys[k], keep[k] as :func:`act_dropout_keep` defines it for tensor k."""
 
     @staticmethod
     def forward(ctx, scale, shared: bool, n: int, *tensors):
@@ -1348,9 +1487,20 @@ class ResidualDropPathFn(torch.autograd.Function):
         ys_c = [y.contiguous() for y in ys]
         outs = [torch.empty_like(res_c[0]) for _ in range(n)]
         rlist = res_c * n if shared else res_c
-        st = L.lib().mtlora_residual_droppath_fwd(n, L.ptr_array9(rlist), L.ptr_array9(ys_c), L.ptr_array9(outs), L.ptr(scale),
-                                                  M, C, B, L.dtype_code(res_c[0]), L.dtype_code(ys_c[0]), L.stream_ptr())
-        L.check(st, "mtlora_residual_droppath_fwd")
+        drop = tensors[nres + n:]
+        if drop and float(drop[0]) > 0.0:  # dropout on the branches, generated in the kernel (row = row of the (M, C) matrix)
+            dr, site = _drop_arg(float(drop[0]), int(drop[1])), int(drop[2])
+            st = L.lib().mtlora_residual_droppath_drop_fwd(n, L.ptr_array9(rlist), L.ptr_array9(ys_c), L.ptr_array9(outs), L.ptr(scale),
+                                                           ctypes.byref(dr), site, M, C, B, L.dtype_code(res_c[0]),
+                                                           L.dtype_code(ys_c[0]), L.stream_ptr())
+            L.check(st, "mtlora_residual_droppath_drop_fwd")
+            ctx.drop = (dr, site, _seed_offset)
+        else:
+            st = L.lib().mtlora_residual_droppath_fwd(n, L.ptr_array9(rlist), L.ptr_array9(ys_c), L.ptr_array9(outs), L.ptr(scale),
+                                                      M, C, B, L.dtype_code(res_c[0]), L.dtype_code(ys_c[0]), L.stream_ptr())
+            L.check(st, "mtlora_residual_droppath_fwd")
+            ctx.drop = None
+        ctx.n_drop = len(drop)
         ctx.cfg = (shared, n, M, C, B, res_c[0].dtype, ys_c[0].dtype, res_c[0].shape)
         ctx.save_for_backward(scale)
         ctx.set_materialize_grads(False)
@@ -1361,22 +1511,29 @@ class ResidualDropPathFn(torch.autograd.Function):
         shared, n, M, C, B, rdt, ydt, shape = ctx.cfg
         (scale,) = ctx.saved_tensors
         if all(g is None for g in grads):
-            return (None,) * (3 + (1 if shared else n) + n)
+            return (None,) * (3 + (1 if shared else n) + n + ctx.n_drop)
         dev = next(g for g in grads if g is not None).device
         gs = [None if g is None else g.to(rdt).contiguous() for g in grads]
         dys = [None if g is None else torch.empty(shape, dtype=ydt, device=dev) for g in gs]
         dres = torch.empty(shape, dtype=rdt, device=dev) if shared else None
-        st = L.lib().mtlora_residual_droppath_bwd(n, L.ptr_array9(gs), L.ptr_array9(dys), L.ptr(dres), L.ptr(scale), M, C, B,
-                                                  L.dtype_code(gs[[g is not None for g in gs].index(True)]),
-                                                  L._DT.get(ydt, L.F32), L.stream_ptr())
-        L.check(st, "mtlora_residual_droppath_bwd")
+        rcode = L.dtype_code(gs[[g is not None for g in gs].index(True)])
+        if ctx.drop is not None:
+            st = L.lib().mtlora_residual_droppath_drop_bwd(n, L.ptr_array9(gs), L.ptr_array9(dys), L.ptr(dres), L.ptr(scale),
+                                                           ctypes.byref(ctx.drop[0]), ctx.drop[1], M, C, B, rcode, L._DT.get(ydt, L.F32),
+                                                           L.stream_ptr())
+            L.check(st, "mtlora_residual_droppath_drop_bwd")
+        else:
+            st = L.lib().mtlora_residual_droppath_bwd(n, L.ptr_array9(gs), L.ptr_array9(dys), L.ptr(dres), L.ptr(scale), M, C, B,
+                                                      rcode, L._DT.get(ydt, L.F32), L.stream_ptr())
+            L.check(st, "mtlora_residual_droppath_bwd")
         dres_out = [dres] if shared else gs          # separate residuals: identity (the incoming gradient itself)
-        return (None, None, None, *dres_out, *dys)
+        return (None, None, None, *dres_out, *dys) + (None,) * ctx.n_drop
 
 
-def residual_droppath(res, ys, drop_prob: float, training: bool):
+def residual_droppath(res, ys, drop_prob: float, training: bool, drop=None):
     """[res_k + DropPath(ys_k)] for k in range(len(ys)) with an independent per-sample mask per k (timm DropPath,
-    scale_by_keep).  ``res``: one tensor shared by all k, or a list of len(ys) tensors."""
+    scale_by_keep).  ``res``: one tensor shared by all k, or a list of len(ys) tensors.  ``drop``: a pending activation dropout
+    ``(p, seed, site)`` of the branches (``pending_dropout``), applied to ys_k before DropPath inside the same kernel."""
     shared = not isinstance(res, (list, tuple))
     rl = [res] if shared else list(res)
     n = len(ys)
@@ -1385,11 +1542,15 @@ def residual_droppath(res, ys, drop_prob: float, training: bool):
           and all(t.shape == rl[0].shape for t in list(ys) + rl))
     scale = _droppath_scale_for(n, rl[0].shape[0], drop_prob, training, rl[0].device)
     if not ok:
+        if drop is not None:
+            return residual_droppath_drop_torch(res, ys, scale, drop[0], _effective_seed(drop[1]), drop[2])
         out = []
         for k in range(n):
             y = ys[k] if scale is None else ys[k] * scale[k].view(-1, *([1] * (ys[k].ndim - 1))).to(ys[k].dtype)
             out.append((rl[0] if shared else rl[k]) + y)
         return out
+    if drop is not None:
+        return list(ResidualDropPathFn.apply(scale, shared, n, *rl, *ys, *drop))
     return list(ResidualDropPathFn.apply(scale, shared, n, *rl, *ys))
 
 

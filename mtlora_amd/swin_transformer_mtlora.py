@@ -31,6 +31,7 @@ from torch import Tensor
 import os
 import weakref
 
+from . import _lib as L
 from . import functional as Fn
 from .lora import MTLoRALinear
 from .window_process import WindowProcess, WindowProcessReverse
@@ -156,7 +157,37 @@ class Mlp(nn.Module):
         outs = Fn.MlpHidFn.apply(m1, m2, x, W1c, W1t, b1, W2c, W2t, b2, f1[0], f1[1], f2[0], f2[1], *xt, *f1[2], *f1[3], *f2[2], *f2[3])
         return outs[0], {t: outs[1 + i] for i, t in enumerate(tasks)}
 
-    def forward(self, x, x_tasks=None):
+    def _drop_forward(self, h, h_t, defer_drop: bool):
+        """training with ``drop.p > 0``: drop(act(h)) of the 1+T hidden tensors in one launch (``Fn.ActDropoutFn``), fc2, and the
+        dropout of fc2's outputs either applied here (one more launch) or, ``defer_drop``, handed to the caller as a pending
+        ``(p, seed, site)`` for its residual kernel.  None when the kernels do not take the tensors: the nn.Dropout path runs, and no
+        seed has been drawn for this call (the path is decided before each seed, as in ``_hid_forward``).  Seeds are drawn in forward
+        order: fc1's (already drawn), hidden, fc2's, output."""
+        p = self.drop.p
+        hs = [h] + ([h_t[t] for t in self.tasks] if h_t is not None else [])
+        gelu = type(self.act) is nn.GELU and getattr(self.act, "approximate", "none") == "none"
+        if not gelu:  # any other activation: the module's own, then dropout alone
+            hs = [self.act(v) for v in hs]
+        a = Fn.act_dropout(hs, L.ACT_GELU if gelu else L.ACT_IDENTITY, p, L.ACT_DROP_HIDDEN)
+        if a is None:
+            if gelu:
+                return None
+            a = [self.drop(v) for v in hs]
+        y, y_t = self.fc2(a[0], None if h_t is None else {t: a[1 + i] for i, t in enumerate(self.tasks)})
+        ys = [y] + ([y_t[t] for t in self.tasks] if y_t is not None else [])
+        if defer_drop and Fn.act_dropout_ok(ys):
+            return y, y_t, Fn.pending_dropout(p, L.ACT_DROP_MLP_OUT)
+        d = Fn.act_dropout(ys, L.ACT_IDENTITY, p, L.ACT_DROP_MLP_OUT)
+        if d is None:
+            d = [self.drop(v) for v in ys]
+        out = (d[0], None if y_t is None else {t: d[1 + i] for i, t in enumerate(self.tasks)})
+        return out + (None,) if defer_drop else out
+
+    def forward(self, x, x_tasks=None, defer_drop=False):
+        """defer_drop (the block's internal entry; only meaningful in training with ``drop.p > 0``): return ``(y, y_t, pending)`` where
+        a non-None ``pending`` is the output dropout the caller still has to apply (``Fn.residual_droppath(..., drop=pending)``)."""
+        if defer_drop and not (self.drop.training and self.drop.p > 0.0):
+            return self.forward(x, x_tasks) + (None,)
         if x_tasks is not None and self._fused_gelu(x):
             out = self._hid_forward(x, x_tasks)
             if out is not None:
@@ -169,6 +200,10 @@ class Mlp(nn.Module):
             a = Fn.GeluDeferredGradFn.apply(h)
             a_t = {t: Fn.GeluDeferredGradFn.apply(h_t[t]) for t in self.tasks} if h_t is not None else None
             return self.fc2(a, a_t, gelu_gate=(h, h_t))
+        if self.drop.training and self.drop.p > 0.0:
+            out = self._drop_forward(h, h_t, defer_drop)
+            if out is not None:
+                return out
         h = self.drop(self.act(h))
         if h_t is not None:
             h_t = {t: self.drop(self.act(h_t[t])) for t in self.tasks}
@@ -176,7 +211,7 @@ class Mlp(nn.Module):
         y = self.drop(y)
         if y_t is not None:
             y_t = {t: self.drop(y_t[t]) for t in self.tasks}
-        return y, y_t
+        return (y, y_t, None) if defer_drop else (y, y_t)
 
 
 def window_partition(x, window_size):
@@ -271,12 +306,22 @@ class WindowAttention(nn.Module):
             return Fn.WindowAttentionFn.apply(meta, qkv, self.dense_bias(), mask, mask_ids, self.attn_drop.p, Fn.next_seed())
         return Fn.WindowAttentionFn.apply(meta, qkv, self.dense_bias(), mask, mask_ids)
 
-    def _project(self, a: Tensor):
+    def _project(self, a: Tensor, defer_drop: bool = False):
+        """defer_drop (``forward_image`` for the block): ``(y, y_t, pending)`` -- a non-None ``pending`` is ``proj_drop`` left to the
+        caller's residual kernel (``Fn.pending_dropout``); the public entries return dropped outputs."""
         y, y_t = self.proj(a)
+        if self.proj_drop.training and self.proj_drop.p > 0.0:  # generated in the kernels; its seed is drawn after proj's, in forward order
+            ys = [y] + ([y_t[t] for t in self.tasks] if y_t is not None else [])
+            if defer_drop and Fn.act_dropout_ok(ys):
+                return y, y_t, Fn.pending_dropout(self.proj_drop.p, L.ACT_DROP_PROJ)
+            d = Fn.act_dropout(ys, L.ACT_IDENTITY, self.proj_drop.p, L.ACT_DROP_PROJ)
+            if d is not None:
+                out = (d[0], None if y_t is None else {t: d[1 + i] for i, t in enumerate(self.tasks)})
+                return out + (None,) if defer_drop else out
         y = self.proj_drop(y)
         if y_t is not None:
             y_t = {t: self.proj_drop(y_t[t]) for t in self.tasks}
-        return y, y_t
+        return (y, y_t, None) if defer_drop else (y, y_t)
 
     def forward(self, x, mask=None):
         """x: (num_windows*B, N, C) window-ordered tokens, mask: (nW, N, N) or None -- the reference API (:186-227)."""
@@ -288,14 +333,14 @@ class WindowAttention(nn.Module):
                            head_dim=C // self.num_heads, image_layout=False, scale=self.scale)
         return self._project(self._core(qkv, meta, mask, None))
 
-    def forward_image(self, x, H: int, W: int, shift: int, mask=None, mask_ids=None):
+    def forward_image(self, x, H: int, W: int, shift: int, mask=None, mask_ids=None, defer_drop=False):
         """x: (B, H*W, C) tokens in image order.  Equivalent to roll(-shift) -> partition -> forward ->
-        merge -> roll(+shift), with the permutations folded into the attention kernel's addressing."""
+        merge -> roll(+shift), with the permutations folded into the attention kernel's addressing.  defer_drop: see ``_project``."""
         B, L, C = x.shape
         qkv, _ = self.qkv(x)
         meta = Fn.AttnMeta(B=B, H=H, W=W, window_size=self.window_size[0], shift=shift, num_heads=self.num_heads,
                            head_dim=C // self.num_heads, image_layout=True, scale=self.scale)
-        return self._project(self._core(qkv, meta, mask, mask_ids))
+        return self._project(self._core(qkv, meta, mask, mask_ids), defer_drop)
 
     def extra_repr(self) -> str:
         return f"dim={self.dim}, window_size={self.window_size}, num_heads={self.num_heads}"
@@ -454,8 +499,13 @@ class SwinTransformerBlock(nn.Module):
             shortcut, xn = Fn.layer_norm_fork(self.norm1, x)
         else:
             shortcut, xn = x, normed
+        # activation dropout (training, drop > 0): proj_drop and the Mlp's output drop are applied by the residual kernels below
+        # (``pend_*``: a pending (p, seed, site)); the fused residual + LayerNorm forms have no dropout and stay off
+        pend_a = pend_m = None
         if self.attention_layout == "windows":
             a, a_t = self._attend_windows(xn, B, H, W, C)
+        elif self.attn.proj_drop.training and self.attn.proj_drop.p > 0.0:
+            a, a_t, pend_a = self.attn.forward_image(xn, H, W, self.shift_size, self.attn_mask, self._attn_mask_ids, defer_drop=True)
         else:
             a, a_t = self.attn.forward_image(xn, H, W, self.shift_size, self.attn_mask, self._attn_mask_ids)
         # residuals: an independent DropPath draw per tensor, like the reference (:389-392); all 1+T of them in one
@@ -464,25 +514,31 @@ class SwinTransformerBlock(nn.Module):
         x_t = None
         xn2_t = None
         if a_t is not None:  # shared shortcut, 1+T branches: residuals + DropPath + norm2 of every stream in one kernel
-            xs, xns = Fn.residual_layer_norm_multi(self.norm2, shortcut, [a] + [a_t[t] for t in self.tasks], p_dp, self.training)
+            xs, xns = Fn.residual_layer_norm_multi(self.norm2, shortcut, [a] + [a_t[t] for t in self.tasks], p_dp, self.training, pend_a)
             x, xn2 = xs[0], xns[0]
             x_t = {t: xs[1 + i] for i, t in enumerate(self.tasks)}
             xn2_t = {t: xns[1 + i] for i, t in enumerate(self.tasks)}
         else:  # single stream: residual + DropPath + norm2 in one kernel
-            x, xn2 = Fn.residual_layer_norm(self.norm2, shortcut, a, p_dp, self.training)
+            x, xn2 = Fn.residual_layer_norm(self.norm2, shortcut, a, p_dp, self.training, pend_a)
         # MLP half
-        m, m_t = self.mlp(xn2, xn2_t)
+        if self.mlp.drop.training and self.mlp.drop.p > 0.0:
+            m, m_t, pend_m = self.mlp(xn2, xn2_t, defer_drop=True)
+        else:
+            m, m_t = self.mlp(xn2, xn2_t)
         if m_t is None:
             if next_norm is not None:
-                x, nxt = Fn.residual_layer_norm(next_norm, x, m, p_dp, self.training)
+                x, nxt = Fn.residual_layer_norm(next_norm, x, m, p_dp, self.training, pend_m)
                 return x, None, nxt
-            return Fn.residual_droppath(x, [m], p_dp, self.training)[0], None
+            return Fn.residual_droppath(x, [m], p_dp, self.training, pend_m)[0], None
         if x_t is None:  # INTERMEDIATE_SPECIALIZATION-style: mlp specialises but attention did not (:401-403)
+            if pend_m is not None:  # (no residual kernel for the task outputs here: the pending dropout as a launch of its own)
+                d = Fn.apply_pending_dropout([m] + [m_t[t] for t in self.tasks], pend_m)
+                m, m_t = d[0], {t: d[1 + i] for i, t in enumerate(self.tasks)}
             out = Fn.residual_droppath(x, [m], p_dp, self.training)[0]
             return out, {t: self.drop_path(m_t[t]) for t in self.tasks}
         if defer_residual:  # the stage's PatchMerging applies x_k + DropPath(m_k) itself, inside its LayerNorm kernel
-            return None, None, None, ([x] + [x_t[t] for t in self.tasks], [m] + [m_t[t] for t in self.tasks], p_dp)
-        r = Fn.residual_droppath([x] + [x_t[t] for t in self.tasks], [m] + [m_t[t] for t in self.tasks], p_dp, self.training)
+            return None, None, None, ([x] + [x_t[t] for t in self.tasks], [m] + [m_t[t] for t in self.tasks], p_dp, pend_m)
+        r = Fn.residual_droppath([x] + [x_t[t] for t in self.tasks], [m] + [m_t[t] for t in self.tasks], p_dp, self.training, pend_m)
         return r[0], {t: r[1 + i] for i, t in enumerate(self.tasks)}
 
     def extra_repr(self) -> str:
@@ -517,13 +573,14 @@ class PatchMerging(nn.Module):
         y, _ = self.reduction(Fn.layer_norm_merge(self.norm, x, H, W))
         return y
 
-    def forward_residual_multi(self, res, branches, drop_prob, training):
+    def forward_residual_multi(self, res, branches, drop_prob, training, drop=None):
         """merging of (res_k + DropPath(branches_k)) for the shared + task streams: residual, 2x2 gather and LayerNorm in one
-        launch, one reduction GEMM; falls back to residual kernel + ``forward_multi``."""
+        launch, one reduction GEMM; falls back to residual kernel + ``forward_multi``.  ``drop``: a pending activation dropout of the
+        branches (``Fn.residual_droppath``): the residual kernel applies it, then ``forward_multi``."""
         H, W = self.input_resolution
-        stacked = Fn.residual_merge_norm_streams(self.norm, res, branches, H, W, drop_prob, training)
+        stacked = None if drop is not None else Fn.residual_merge_norm_streams(self.norm, res, branches, H, W, drop_prob, training)
         if stacked is None:
-            return self.forward_multi(Fn.residual_droppath(list(res), list(branches), drop_prob, training))
+            return self.forward_multi(Fn.residual_droppath(list(res), list(branches), drop_prob, training, drop))
         y, _ = self.reduction(stacked)
         return list(y.view(len(res), -1, *y.shape[1:]).unbind(0))
 
@@ -623,7 +680,7 @@ class BasicLayer(nn.Module):
             normed = out[2] if len(out) > 2 else None
             deferred = out[3] if len(out) > 3 else None
         if deferred is not None:
-            outs = self.downsample.forward_residual_multi(deferred[0], deferred[1], deferred[2], self.training)
+            outs = self.downsample.forward_residual_multi(deferred[0], deferred[1], deferred[2], self.training, deferred[3])
             return outs[0], {t: outs[1 + i] for i, t in enumerate(self.tasks)}
         if self.downsample is not None:
             if tasks_lora is not None and hasattr(self.downsample, "forward_multi"):
@@ -736,7 +793,10 @@ class SwinTransformerMTLoRA(nn.Module):
         x = self.patch_embed(x)
         if self.ape:
             x = x + self.absolute_pos_embed
-        x = self.pos_drop(x)
+        d = None
+        if self.pos_drop.training and self.pos_drop.p > 0.0:  # generated in the kernel (no stored mask); None: the nn.Dropout path
+            d = Fn.act_dropout([x], L.ACT_IDENTITY, self.pos_drop.p, L.ACT_DROP_POS)
+        x = self.pos_drop(x) if d is None else d[0]
         stages = []
         for layer in self.layers:
             x, tasks_lora = layer(x)
