@@ -166,6 +166,42 @@ int64_t mtlora_linear_pack_entry_bytes(void);
 int mtlora_linear_pack_entry(const mtlora_linear_desc* d, const float* A_s, const float* B_s, const float* const* A_t,
                              const float* const* B_t, void* packed, int64_t packed_bytes, void* entry_host);
 int mtlora_linear_pack_table(const void* table_dev, int n_entries, int dtype, void* stream);
+
+/* ---- scales that live on the device (TRAINABLE_SCALE_SHARED / TRAINABLE_SCALE_PER_TASK of the reference, config.py:307-326,
+ * lora.py:203-228: 1-element fp32 Parameters an optimizer moves every step).  Additive entries of ABI 12; the descriptor is
+ * unchanged.  The scales reach the kernels through the packed factors alone (the alpha row and the alpha-scaled projection rows),
+ * so a layer with such scales always runs with d->packed set, and the pack launch reads the scales when it RUNS: no host read of
+ * a Parameter, and a captured graph that contains the pack launch follows the Parameter on every replay.
+ *   scale_dev   HOST array of n_scale = 1 + d->T DEVICE pointers: [0] the shared scale, [1 + t] the scale of task t.  A null slot
+ *               means "constant": that segment takes d->scale_s / d->scale_t[t] as the by-value entries do.  A set slot makes
+ *               the kernel form  alpha = *scale_dev[o] * f  in fp32, f being the factor the host multiplies into a by-value
+ *               scale (1 / (1 - dropout_p) for the shared segment and for task segments without x_tasks, 1 for task segments
+ *               with x_tasks): a device scale holding the float s packs bit for bit what scale = s packs by value.
+ *   mtlora_linear_pack_dev         mtlora_linear_pack with device scales;
+ *   mtlora_linear_pack_entry_dev   mtlora_linear_pack_entry with device scales: one mtlora_linear_pack_table launch serves entries of
+ *                                  both kinds (mtlora_linear_pack_entry_bytes is the size of either).
+ * Rejected before any launch, after everything the by-value entry rejects: a null `scale_dev` array (MTLORA_ERR_NULL), n_scale !=
+ * 1 + d->T (MTLORA_ERR_SHAPE), a scale pointer off 4 bytes (MTLORA_ERR_ALIGN).
+ * d->scale_s / d->scale_t are read by the four packing entries and by a fwd that packs for itself (d->packed null), nowhere else: a
+ * call with d->packed set never reads them (a host on this path fills them with 1.0). */
+int mtlora_linear_pack_dev(const mtlora_linear_desc* d, const float* A_s, const float* B_s, const float* const* A_t,
+                           const float* const* B_t, const float* const* scale_dev, int n_scale, void* packed, int64_t packed_bytes,
+                           void* stream);
+int mtlora_linear_pack_entry_dev(const mtlora_linear_desc* d, const float* A_s, const float* B_s, const float* const* A_t,
+                                 const float* const* B_t, const float* const* scale_dev, int n_scale, void* packed,
+                                 int64_t packed_bytes, void* entry_host);
+/* d(loss)/d(scale) of the device scales of one layer in one call: d_scale[o] = <dB[o], B[o]> / *scale_dev[o] for o < n_scale =
+ * 1 + d->T (segment order as scale_dev), dB[o] the fp32 factor gradient (N, r_o) mtlora_linear_bwd has just written on the same
+ * stream, B[o] the fp32 master.  A segment whose scale_dev[o] or dB[o] is null (or whose rank is 0) is skipped: its d_scale word
+ * is not written.  *scale_dev[o] == 0 writes 0.  Reduction in a fixed order (per-workgroup fp32 partials in `scratch`, summed in
+ * double by a finishing launch behind it; no atomics): the same bits on every run.  d->M is ignored.  `d_scale`: 1 + d->T floats.
+ * Rejected before any launch: a null dB / B / d_scale / scratch / scale_dev array or a null B[o] of a live segment
+ * (MTLORA_ERR_NULL), n_scale != 1 + d->T (MTLORA_ERR_SHAPE), a pointer off 4 bytes (MTLORA_ERR_ALIGN), scratch_bytes below
+ * mtlora_linear_scale_grad_scratch_bytes (MTLORA_ERR_WORKSPACE). */
+int64_t mtlora_linear_scale_grad_scratch_bytes(void);
+int mtlora_linear_scale_grad(const mtlora_linear_desc* d, const float* const* dB, const float* const* B,
+                             const float* const* scale_dev, int n_scale, float* d_scale, void* scratch, int64_t scratch_bytes,
+                             void* stream);
 /* bytes of the backward scratch buffer. */
 int64_t mtlora_linear_bwd_scratch_bytes(const mtlora_linear_desc* d);
 

@@ -152,6 +152,14 @@ _SIGS = {
     "mtlora_linear_pack_entry": (c_int, [POINTER(LinearDesc), c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int64,
                                          c_void_p]),
     "mtlora_linear_pack_table": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    # device-resident (trainable) scales: scale_dev is a host array of 1 + T device pointers, null = the descriptor's constant
+    "mtlora_linear_pack_dev": (c_int, [POINTER(LinearDesc), c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                       c_int, c_void_p, c_int64, c_void_p]),
+    "mtlora_linear_pack_entry_dev": (c_int, [POINTER(LinearDesc), c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p),
+                                             POINTER(c_void_p), c_int, c_void_p, c_int64, c_void_p]),
+    "mtlora_linear_scale_grad_scratch_bytes": (c_int64, []),
+    "mtlora_linear_scale_grad": (c_int, [POINTER(LinearDesc), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p,
+                                         c_void_p, c_int64, c_void_p]),
     "mtlora_linear_fwd": (c_int, [POINTER(LinearDesc), c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p,
                                   POINTER(c_void_p), POINTER(c_void_p), c_void_p, POINTER(c_void_p), c_void_p, c_int64,
                                   c_void_p]),

@@ -900,8 +900,11 @@ static void launch_sp_tn(SpTnParams& q, int nb, hipStream_t s, double xb, double
     }
 }
 
+// scale_dev (nullable; 1 + T entries, each nullable): a set entry makes k_pack read that segment's scale from the device and
+// multiply it by the factor the host would have multiplied in; d->scale_* is read for the other segments only.  This is the ONLY
+// place the library reads d->scale_s / d->scale_t: a call with d->packed set never packs, so it never looks at them.
 static PackParams make_pack_params(const mtlora_linear_desc* d, const Segs& sg, const float* A_s, const float* B_s, const float* const* A_t,
-                                   const float* const* B_t) {
+                                   const float* const* B_t, const float* const* scale_dev = nullptr) {
     const float keep_scale = mtl_make_dropout(d->dropout_p, 0).enabled() ? 1.f / (1.f - d->dropout_p) : 1.f;
     PackParams pp;
     pp.s = sg;
@@ -911,6 +914,7 @@ static PackParams make_pack_params(const mtlora_linear_desc* d, const Segs& sg, 
         pp.A[o] = nullptr;
         pp.B[o] = nullptr;
         pp.alpha[o] = 0.f;
+        pp.alpha_dev[o] = nullptr;
     }
     pp.A[0] = A_s;
     pp.B[0] = B_s;
@@ -920,6 +924,11 @@ static PackParams make_pack_params(const mtlora_linear_desc* d, const Segs& sg, 
         pp.B[t + 1] = B_t[t];
         pp.alpha[t + 1] = d->scale_t[t] * (d->has_x_tasks ? 1.f : keep_scale);
     }
+    for (int o = 0; scale_dev && o <= d->T; ++o)
+        if (scale_dev[o]) {
+            pp.alpha_dev[o] = scale_dev[o];
+            pp.alpha[o] = (o == 0 || !d->has_x_tasks) ? keep_scale : 1.f;
+        }
     return pp;
 }
 static unsigned pack_blocks(const mtlora_linear_desc* d, const Segs& sg) {
@@ -930,8 +939,9 @@ static unsigned pack_blocks(const mtlora_linear_desc* d, const Segs& sg) {
 }
 template <typename T>
 static void launch_pack(const mtlora_linear_desc* d, const Segs& sg, const CtxLayout& L, unsigned char* pk, const float* A_s,
-                        const float* B_s, const float* const* A_t, const float* const* B_t, hipStream_t s) {
-    const PackParams pp = make_pack_params(d, sg, A_s, B_s, A_t, B_t);
+                        const float* B_s, const float* const* A_t, const float* const* B_t, hipStream_t s,
+                        const float* const* scale_dev = nullptr) {
+    const PackParams pp = make_pack_params(d, sg, A_s, B_s, A_t, B_t, scale_dev);
     MtlProfScope prof(PK_PACK, 0.0, s);
     hipLaunchKernelGGL(k_pack<T>, dim3(pack_blocks(d, sg)), dim3(256), 0, s, pp, reinterpret_cast<T*>(pk + L.a_cat),
                        reinterpret_cast<T*>(pk + L.b_cat), reinterpret_cast<T*>(pk + L.at_cat), reinterpret_cast<T*>(pk + L.bt_cat),
@@ -2017,37 +2027,110 @@ static int pack_check(const mtlora_linear_desc* d, const float* A_s, const float
     return MTLORA_OK;
 }
 
-int mtlora_linear_pack(const mtlora_linear_desc* d, const float* A_s, const float* B_s, const float* const* A_t,
-                       const float* const* B_t, void* packed, int64_t packed_bytes, void* stream) {
-    const int st = pack_check(d, A_s, B_s, A_t, B_t, packed, packed_bytes);
-    if (st != MTLORA_OK) return st;
+// the device-scale argument of the *_dev entries: the array is required and has one slot per segment (shared, then the tasks); a
+// null slot means "constant, the descriptor's value"; a scale is one aligned float
+static int scale_dev_check(const mtlora_linear_desc* d, const float* const* scale_dev, int n_scale) {
+    if (mtl_any_null({scale_dev})) return MTLORA_ERR_NULL;
+    if (n_scale != d->T + 1) return MTLORA_ERR_SHAPE;
+    if (mtl_any_misaligned({}, n_scale, {mtl_arr(scale_dev)}, 4)) return MTLORA_ERR_ALIGN;
+    return MTLORA_OK;
+}
+
+static int linear_pack(const mtlora_linear_desc* d, const float* A_s, const float* B_s, const float* const* A_t, const float* const* B_t,
+                       const float* const* scale_dev, void* packed, int64_t packed_bytes, void* stream) {
     const Segs sg = make_segs(d);
     if (sg.R == 0) return MTLORA_OK;
     const CtxLayout L = ctx_layout(d, sg);
     unsigned char* pk = reinterpret_cast<unsigned char*>(packed);
     hipStream_t s = (hipStream_t)stream;
-    mtl_dispatch_dtype(d->dtype, [&](auto t) { launch_pack<typename decltype(t)::type>(d, sg, L, pk, A_s, B_s, A_t, B_t, s); });
+    mtl_dispatch_dtype(d->dtype, [&](auto t) { launch_pack<typename decltype(t)::type>(d, sg, L, pk, A_s, B_s, A_t, B_t, s, scale_dev); });
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }
 
-int64_t mtlora_linear_pack_entry_bytes(void) { return (int64_t)sizeof(PackEntry); }
-
-int mtlora_linear_pack_entry(const mtlora_linear_desc* d, const float* A_s, const float* B_s, const float* const* A_t,
-                             const float* const* B_t, void* packed, int64_t packed_bytes, void* entry_host) {
+int mtlora_linear_pack(const mtlora_linear_desc* d, const float* A_s, const float* B_s, const float* const* A_t,
+                       const float* const* B_t, void* packed, int64_t packed_bytes, void* stream) {
     const int st = pack_check(d, A_s, B_s, A_t, B_t, packed, packed_bytes);
     if (st != MTLORA_OK) return st;
+    return linear_pack(d, A_s, B_s, A_t, B_t, nullptr, packed, packed_bytes, stream);
+}
+
+int mtlora_linear_pack_dev(const mtlora_linear_desc* d, const float* A_s, const float* B_s, const float* const* A_t,
+                           const float* const* B_t, const float* const* scale_dev, int n_scale, void* packed, int64_t packed_bytes,
+                           void* stream) {
+    int st = pack_check(d, A_s, B_s, A_t, B_t, packed, packed_bytes);
+    if (st == MTLORA_OK) st = scale_dev_check(d, scale_dev, n_scale);
+    if (st != MTLORA_OK) return st;
+    return linear_pack(d, A_s, B_s, A_t, B_t, scale_dev, packed, packed_bytes, stream);
+}
+
+int64_t mtlora_linear_pack_entry_bytes(void) { return (int64_t)sizeof(PackEntry); }
+
+static int linear_pack_entry(const mtlora_linear_desc* d, const float* A_s, const float* B_s, const float* const* A_t,
+                             const float* const* B_t, const float* const* scale_dev, void* packed, void* entry_host) {
     if (!entry_host) return MTLORA_ERR_NULL;
     const Segs sg = make_segs(d);
     if (sg.R == 0) return MTLORA_ERR_SHAPE;  // nothing to pack: such a layer does not belong in a table
     const CtxLayout L = ctx_layout(d, sg);
     PackEntry e;
     memset(&e, 0, sizeof(e));
-    e.pp = make_pack_params(d, sg, A_s, B_s, A_t, B_t);
+    e.pp = make_pack_params(d, sg, A_s, B_s, A_t, B_t, scale_dev);
     e.dst = reinterpret_cast<unsigned char*>(packed);
     const int64_t off[9] = {L.a_cat, L.b_cat, L.at_cat, L.bt_cat, L.alpha, L.a_proj, L.bt_proj, L.b_frag, L.at_frag};
     for (int i = 0; i < 9; ++i) e.off[i] = off[i];
     memcpy(entry_host, &e, sizeof(e));
+    return MTLORA_OK;
+}
+
+int mtlora_linear_pack_entry(const mtlora_linear_desc* d, const float* A_s, const float* B_s, const float* const* A_t,
+                             const float* const* B_t, void* packed, int64_t packed_bytes, void* entry_host) {
+    const int st = pack_check(d, A_s, B_s, A_t, B_t, packed, packed_bytes);
+    if (st != MTLORA_OK) return st;
+    return linear_pack_entry(d, A_s, B_s, A_t, B_t, nullptr, packed, entry_host);
+}
+
+int mtlora_linear_pack_entry_dev(const mtlora_linear_desc* d, const float* A_s, const float* B_s, const float* const* A_t,
+                                 const float* const* B_t, const float* const* scale_dev, int n_scale, void* packed,
+                                 int64_t packed_bytes, void* entry_host) {
+    int st = pack_check(d, A_s, B_s, A_t, B_t, packed, packed_bytes);
+    if (st == MTLORA_OK) st = scale_dev_check(d, scale_dev, n_scale);
+    if (st != MTLORA_OK) return st;
+    return linear_pack_entry(d, A_s, B_s, A_t, B_t, scale_dev, packed, entry_host);
+}
+
+int64_t mtlora_linear_scale_grad_scratch_bytes(void) { return (int64_t)(MAXO * SG_BLOCKS * sizeof(float)); }
+
+int mtlora_linear_scale_grad(const mtlora_linear_desc* d, const float* const* dB, const float* const* B, const float* const* scale_dev,
+                             int n_scale, float* d_scale, void* scratch, int64_t scratch_bytes, void* stream) {
+    int st = check_desc(d);
+    if (st != MTLORA_OK) return st;
+    if (mtl_any_null({dB, B, d_scale, scratch})) return MTLORA_ERR_NULL;
+    st = scale_dev_check(d, scale_dev, n_scale);
+    if (st != MTLORA_OK) return st;
+    if (mtl_any_misaligned({d_scale, scratch}, n_scale, {mtl_arr(dB), mtl_arr(B)}, 4)) return MTLORA_ERR_ALIGN;
+    if (scratch_bytes < mtlora_linear_scale_grad_scratch_bytes()) return MTLORA_ERR_WORKSPACE;
+    ScaleGradParams P;
+    memset(&P, 0, sizeof(P));
+    P.nseg = n_scale;
+    P.part = reinterpret_cast<float*>(scratch);
+    P.d_scale = d_scale;
+    bool any = false;
+    for (int o = 0; o < n_scale; ++o) {
+        const int64_t r = o == 0 ? d->r_s : d->r_t[o - 1];
+        if (!dB[o] || !scale_dev[o] || r <= 0) continue;  // nothing to form for this segment
+        if (!B[o]) return MTLORA_ERR_NULL;
+        P.dB[o] = dB[o];
+        P.B[o] = B[o];
+        P.scale[o] = scale_dev[o];
+        P.n[o] = d->N * r;
+        any = true;
+    }
+    if (!any) return MTLORA_OK;
+    hipStream_t s = (hipStream_t)stream;
+    MtlProfScope prof(PK_REDUCE, 0.0, s);
+    hipLaunchKernelGGL(k_scale_grad_part, dim3(SG_BLOCKS, (unsigned)n_scale), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_scale_grad_fin, dim3(1), dim3(64), 0, s, P);
+    MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }
 

@@ -40,9 +40,18 @@ struct PackParams {
     const float* A[MAXO];
     const float* B[MAXO];
     float alpha[MAXO];
+    const float* alpha_dev[MAXO];  // nullable: the segment's scale lives on the device (a trainable scale), alpha[o] then only holds
+                                   // the host's factor f (dropout keep scale or 1) and the packed value is *alpha_dev[o] * f
     Segs s;
     int K, N;
 };
+// alpha of segment o as packed: the by-value product of the host, or the same fp32 product formed here from the device scale (one
+// IEEE multiply either way: a device scale holding s packs bit for bit what scale = s packs by value)
+template <typename PP>
+__device__ __forceinline__ float pack_alpha(const PP& p, int o) {
+    const float* __restrict__ sd = p.alpha_dev[o];
+    return sd ? *sd * p.alpha[o] : p.alpha[o];
+}
 
 // The packing walks 64 x 64 TILES of the two concatenated factor matrices -- A_cat (R x K, rows = rank columns rr) and B_cat (N x R) -- one
 // tile per workgroup pass: the fp32 masters are read along their contiguous axis (K for A, the segment's rank for B), the same-orientation
@@ -85,7 +94,7 @@ __device__ __forceinline__ void pack_body(const PP& p, T* a_cat, T* b_cat, T* at
             for (int i = 0; i < PK_T / 4; ++i) {
                 const int rr = row0 + ty + 4 * i;  // (wave-uniform)
                 const int o = pack_seg_of(p, rr), lr = rr - p.s.off[o];
-                al[i] = p.alpha[o];
+                al[i] = pack_alpha(p, o);
                 v[i] = (rr < R && lr < p.s.r[o] && c < K && p.A[o]) ? p.A[o][(int64_t)lr * K + c] : 0.f;
             }
 #pragma unroll
@@ -97,7 +106,7 @@ __device__ __forceinline__ void pack_body(const PP& p, T* a_cat, T* b_cat, T* at
                     a_proj[(int64_t)rr * K + c] = mtl_from_f32<T>(v[i] * al[i]);
                 }
             }
-            if (col0 == 0 && threadIdx.x < PK_T && row0 + tx < R) alpha[row0 + tx] = p.alpha[pack_seg_of(p, row0 + tx)];
+            if (col0 == 0 && threadIdx.x < PK_T && row0 + tx < R) alpha[row0 + tx] = pack_alpha(p, pack_seg_of(p, row0 + tx));
         } else {
             const int rr = col0 + tx;
             const int o = pack_seg_of(p, rr), lr = rr - p.s.off[o], ro = p.s.r[o];
@@ -131,7 +140,7 @@ __device__ __forceinline__ void pack_body(const PP& p, T* a_cat, T* b_cat, T* at
                 if (rr < R && n < N) {
                     const float v = tile[tx][rl];
                     bt_cat[(int64_t)rr * N + n] = mtl_from_f32<T>(v);
-                    bt_proj[(int64_t)rr * N + n] = mtl_from_f32<T>(v * p.alpha[pack_seg_of(p, rr)]);
+                    bt_proj[(int64_t)rr * N + n] = mtl_from_f32<T>(v * pack_alpha(p, pack_seg_of(p, rr)));
                 }
             }
         }

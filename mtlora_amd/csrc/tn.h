@@ -291,6 +291,55 @@ __global__ __launch_bounds__(256) void k_sum(SumParams P, T* out) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_scale_grad : d(loss)/d(scale_o) = <dB_o, B_o> / scale_o for the 1 + T segments of a layer whose scales are trainable 1-element
+// Parameters (TRAINABLE_SCALE_*): y_o carries scale_o B_o (..), so dB_o = scale_o Z_o and d scale_o = <Z_o, B_o>.  dB_o (the fp32
+// factor gradient the backward has just written) and B_o (the fp32 master) are (N x r_o) contiguous; the scale is read from the
+// device.  Two steps in stream order, no atomics: blockIdx.y = segment, each of the SG_BLOCKS workgroups of a segment leaves one
+// fp32 partial (a thread walks its elements in ascending order, the workgroup sums in a fixed order), then k_scale_grad_fin adds a
+// segment's partials in ascending order in double and divides.  Same bits on every run.  Largest layer of the model family:
+// N x r_s = 3072 x 128 elements (Swin-B stage-3 fc1) = 48 elements per thread.
+// ------------------------------------------------------------------------------------------------
+constexpr int SG_BLOCKS = 32;
+struct ScaleGradParams {
+    const float* dB[MAXO];     // null: segment skipped (its d_scale word is not written)
+    const float* B[MAXO];
+    const float* scale[MAXO];  // null: segment skipped
+    int64_t n[MAXO];           // N * r_o
+    float* part;               // MAXO x SG_BLOCKS
+    float* d_scale;            // 1 + T
+    int nseg;
+};
+__global__ __launch_bounds__(256) void k_scale_grad_part(ScaleGradParams P) {
+    __shared__ float red[4];
+    const int o = blockIdx.y;
+    if (!P.dB[o] || !P.scale[o]) return;  // (uniform over the workgroup)
+    const float* __restrict__ g = P.dB[o];
+    const float* __restrict__ b = P.B[o];
+    const int64_t n = P.n[o], step = (int64_t)SG_BLOCKS * 256;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (; i + 3 * step < n; i += 4 * step) {  // four independent pairs of loads in flight
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] += g[i + u * step] * b[i + u * step];
+    }
+    for (; i < n; i += step) acc[0] += g[i] * b[i];
+    float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) s += __shfl_xor(s, w);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) P.part[o * SG_BLOCKS + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(64) void k_scale_grad_fin(ScaleGradParams P) {
+    const int o = threadIdx.x;
+    if (o >= P.nseg || !P.dB[o] || !P.scale[o]) return;
+    double t = 0.0;
+    for (int k = 0; k < SG_BLOCKS; ++k) t += (double)P.part[o * SG_BLOCKS + k];
+    const float s = *P.scale[o];
+    P.d_scale[o] = s == 0.f ? 0.f : (float)(t / (double)s);
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_rank_out : the task outputs of a dX launch,  dX_t = Q_t A_t  [.* gelu'(h_t)],  for SMALL task ranks (rp <= 16).
 // They share nothing with the base GEMM (no dY W term), and with r_t = 4 the "GEMM" is 8 multiply-adds per element: in the tiled
 // multi-output kernel each of them costs a full tile pass (rank k-tile staging, MFMA on a mostly-zero k-tile, LDS transposition) --

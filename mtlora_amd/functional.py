@@ -9,7 +9,7 @@ import ctypes
 import os
 import struct
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -297,8 +297,8 @@ class LinearMeta:
     N: int
     r_s: int
     r_t: Tuple[int, ...]
-    scale_s: float
-    scale_t: Tuple[float, ...]
+    scale_s: Union[float, torch.Tensor]               # a float, or the 1-element fp32 device tensor of a TRAINABLE scale (the Parameter):
+    scale_t: Tuple[Union[float, torch.Tensor], ...]   # such a segment is packed from device memory, the descriptor then carries 1.0
     mode: int                 # 0 matrix, 1 matrixv2
     has_x_tasks: bool
     dropout_p: float          # 0 in eval
@@ -314,6 +314,13 @@ class LinearMeta:
     def T(self) -> int:
         return len(self.r_t)
 
+    @property
+    def scale_dev(self):
+        """None when every scale is a constant, else the 1 + T list (shared, tasks) of the scale tensors, None where constant"""
+        if not (isinstance(self.scale_s, torch.Tensor) or any(isinstance(v, torch.Tensor) for v in self.scale_t)):
+            return None
+        return [v if isinstance(v, torch.Tensor) else None for v in (self.scale_s, *self.scale_t)]
+
     def desc(self, M: int) -> L.LinearDesc:
         d = L.LinearDesc()
         d.M, d.K, d.N = M, self.K, self.N
@@ -321,8 +328,9 @@ class LinearMeta:
         d.mode, d.T, d.r_s = self.mode, self.T, self.r_s
         for i, r in enumerate(self.r_t):
             d.r_t[i] = r
-            d.scale_t[i] = self.scale_t[i]
-        d.scale_s = self.scale_s
+            d.scale_t[i] = 1.0 if isinstance(self.scale_t[i], torch.Tensor) else self.scale_t[i]
+        # (a device scale only enters through the packed factors; a call with d.packed set never reads d.scale_*: include/mtlora_hip.h)
+        d.scale_s = 1.0 if isinstance(self.scale_s, torch.Tensor) else self.scale_s
         d.has_x_tasks = 1 if self.has_x_tasks else 0
         d.dropout_p = self.dropout_p
         d.seed = self.seed
@@ -404,8 +412,13 @@ class PackTable:
         for i, (meta, A_s, B_s, A_t, B_t, packed, *_owner) in enumerate(entries):
             d = meta.desc(1)
             d.packed = 0
-            st = lib.mtlora_linear_pack_entry(ctypes.byref(d), L.ptr(A_s), L.ptr(B_s), L.ptr_array(A_t), L.ptr_array(B_t), L.ptr(packed),
-                                              packed.numel(), ctypes.byref(host, i * eb))
+            sd = meta.scale_dev  # (trainable scales: the entry holds their addresses, the launch reads them when it runs)
+            if sd is None:
+                st = lib.mtlora_linear_pack_entry(ctypes.byref(d), L.ptr(A_s), L.ptr(B_s), L.ptr_array(A_t), L.ptr_array(B_t), L.ptr(packed),
+                                                  packed.numel(), ctypes.byref(host, i * eb))
+            else:
+                st = lib.mtlora_linear_pack_entry_dev(ctypes.byref(d), L.ptr(A_s), L.ptr(B_s), L.ptr_array(A_t), L.ptr_array(B_t),
+                                                      L.ptr_array9(sd), len(sd), L.ptr(packed), packed.numel(), ctypes.byref(host, i * eb))
             L.check(st, "mtlora_linear_pack_entry")
         self.n = len(entries)
         self.dtype_code = L._DT[dtype]
@@ -425,6 +438,40 @@ def packed_bytes(meta: "LinearMeta") -> int:
     return n
 
 
+def pack_dev(meta: "LinearMeta", A_s, B_s, A_t, B_t, buf: torch.Tensor) -> None:
+    """one launch that packs a layer's factors into ``buf`` (``packed_bytes(meta)`` bytes), the trainable scales of ``meta`` read from
+    device memory by the kernel (``mtlora_linear_pack_dev``): nothing is read back, and inside a capture every replay packs from the
+    Parameters' current values"""
+    sd = meta.scale_dev
+    A_s, B_s, A_t, B_t = _f32c(A_s), _f32c(B_s), [_f32c(a) for a in A_t], [_f32c(b) for b in B_t]
+    L.require_gpu(buf, A_s, B_s, *A_t, *B_t, *sd)
+    if any(v is not None and (v.dtype != torch.float32 or v.numel() != 1) for v in sd):
+        raise RuntimeError("mtlora_amd: a trainable LoRA scale must be a 1-element fp32 tensor")
+    d = meta.desc(1)
+    d.packed = 0
+    st = L.lib().mtlora_linear_pack_dev(ctypes.byref(d), L.ptr(A_s), L.ptr(B_s), L.ptr_array(A_t), L.ptr_array(B_t), L.ptr_array9(sd),
+                                        len(sd), L.ptr(buf), buf.numel(), L.stream_ptr())
+    L.check(st, "mtlora_linear_pack_dev")
+
+
+def scale_grad_torch(dB: torch.Tensor, B: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """portable definition of ``mtlora_linear_scale_grad`` for one segment: d(loss)/d(scale) = <dB, B> / scale (the output carries
+    scale * B (..), so dB = scale * Z and d scale = <Z, B>), summed in double; 0 where the scale is 0.  Returns a 1-element fp32 tensor."""
+    t = (dB.double() * B.double()).sum()
+    sv = s.detach().double().reshape(())
+    return torch.where(sv == 0, torch.zeros_like(t), t / torch.where(sv == 0, torch.ones_like(sv), sv)).float().reshape(1)
+
+
+_SG_BYTES = None
+
+
+def _scale_grad_bytes() -> int:
+    global _SG_BYTES
+    if _SG_BYTES is None:
+        _SG_BYTES = L.lib().mtlora_linear_scale_grad_scratch_bytes()
+    return _SG_BYTES
+
+
 class MTLoRALinearFn(torch.autograd.Function):
     """(y_s, y_t[0..T-1]) = f(x, x_t[0..T-1], A_s, B_s, A_t[..], B_t[..]); W (and bias) frozen by default.
 
@@ -432,8 +479,9 @@ class MTLoRALinearFn(torch.autograd.Function):
           *x_t(T or 0), *A_t(T), *B_t(T), *scale_t_params(T or 0), *gelu_gates(0 or 1 + len(x_t))
     W_c / Wt_c are the compute-dtype copies the module caches; W_master / bias_master are only used to
     route gradients when the pretrained weight is left trainable (MTLORA.FREEZE_PRETRAINED False);
-    scale_*_param are the 1-element Parameters of TRAINABLE_SCALE_* (None otherwise): the kernels take the
-    scales as scalars and d(loss)/d(scale) = <dB, B> / scale is formed from the factor gradient."""
+    scale_*_param are the 1-element Parameters of TRAINABLE_SCALE_* (None otherwise): the packing launch reads them on the
+    device (``meta.packed`` is always set for such a layer) and d(loss)/d(scale) = <dB, B> / scale is formed from the factor
+    gradient by ``mtlora_linear_scale_grad``, queued behind the factor gradients on whichever stream they run on."""
 
     @staticmethod
     def forward(ctx, meta: LinearMeta, x, W_c, Wt_c, bias_f32, W_master, bias_master, A_s, B_s, scale_s_param, *rest):
@@ -483,6 +531,10 @@ class MTLoRALinearFn(torch.autograd.Function):
         # (meta.packed keeps the packed-factor buffer alive until backward; a trainer overwrites it only after the step's backward)
         ctx.factor_params = (A_s, B_s, *A_t, *B_t)  # the Parameters themselves: backward looks at their .grad (side stream)
         ctx.has_scale_s = scale_s_param is not None
+        if ctx.has_scale_s or meta.n_scale_t:
+            if meta.packed is None or meta.scale_dev is None:
+                raise RuntimeError("mtlora_amd: a layer with trainable scales runs from factors packed with mtlora_linear_pack_dev")
+            ctx.factor_params += (scale_s_param, *rest[nx + 2 * T:nx + 2 * T + meta.n_scale_t])  # (their gradients: same stream)
         ctx.M = M
         return (ys, *yt, *acts)
 
@@ -517,12 +569,28 @@ class MTLoRALinearFn(torch.autograd.Function):
         # (a factor that takes no gradient -- the identity side of a rank-aware update, a frozen factor -- is not reduced at all: the
         # library skips the problems whose output pointer is null)
         nA, nB = 10 + nx, 10 + nx + T
+        # trainable scales: segment o needs d scale_o = <dB_o, B_o> / scale_o, so dB_o is formed whenever the SCALE needs a gradient, even
+        # where B itself is frozen (B then gets None)
+        nS = nB + T
+        if ctx.has_scale_s or meta.n_scale_t:
+            sg_need = [ctx.has_scale_s and need[9] and has_s] + [t < meta.n_scale_t and need[nS + t] and dy_t[t] is not None
+                                                                 for t in range(T)]
+        else:
+            sg_need = (False,) * (1 + T)
         dA_s = torch.empty((meta.r_s, meta.K), dtype=torch.float32, device=dev) if (has_s and need[7]) else None
-        dB_s = torch.empty((meta.N, meta.r_s), dtype=torch.float32, device=dev) if (has_s and need[8]) else None
+        dB_s = torch.empty((meta.N, meta.r_s), dtype=torch.float32, device=dev) if (has_s and (need[8] or sg_need[0])) else None
         dA_t = [torch.empty((meta.r_t[t], meta.K), dtype=torch.float32, device=dev) if (dy_t[t] is not None and need[nA + t]) else None
                 for t in range(T)]
-        dB_t = [torch.empty((meta.N, meta.r_t[t]), dtype=torch.float32, device=dev) if (dy_t[t] is not None and need[nB + t]) else None
-                for t in range(T)]
+        dB_t = [torch.empty((meta.N, meta.r_t[t]), dtype=torch.float32, device=dev)
+                if (dy_t[t] is not None and (need[nB + t] or sg_need[1 + t])) else None for t in range(T)]
+        d_sc = sg_scratch = None
+        if any(sg_need):
+            d_sc = torch.empty(1 + T, dtype=torch.float32, device=dev)
+            sg_scratch = torch.empty(_scale_grad_bytes(), dtype=torch.uint8, device=dev)
+            _, B_s_c, _, B_t_c = ctx.keep
+            sg_dB = [g if w else None for g, w in zip([dB_s, *dB_t], sg_need)]
+            sg_args = (L.ptr_array9(sg_dB), L.ptr_array9([B_s_c, *B_t_c]), L.ptr_array9(meta.scale_dev), 1 + T, L.ptr(d_sc),
+                       L.ptr(sg_scratch), sg_scratch.numel())
         if nx:  # a task input whose output got no gradient still needs a defined (zero) gradient
             for t in range(T):
                 if dy_t[t] is None:
@@ -542,10 +610,11 @@ class MTLoRALinearFn(torch.autograd.Function):
                                            L.ptr(dA_s), L.ptr(dB_s), L.ptr_array(dA_t), L.ptr_array(dB_t), L.ptr(scratch),
                                            scratch_bytes, stream_ptr)
                 L.check(st, "mtlora_linear_bwd")
+            if d_sc is not None and phase != 1:  # the scale gradients: queued behind the factor gradients, on their stream
+                L.check(lib.mtlora_linear_scale_grad(ctypes.byref(d), *sg_args, stream_ptr), "mtlora_linear_scale_grad")
 
-        fgrads = [t for t in [dA_s, dB_s, *dA_t, *dB_t] if t is not None]
-        # no side stream with a trainable scale: its gradient is formed from dB below, on this stream, inside backward
-        _run_factor_phases(ctx.factor_params, fgrads, M, dev, not ctx.has_scale_s and meta.n_scale_t == 0, launch,
+        fgrads = [t for t in [dA_s, dB_s, *dA_t, *dB_t, d_sc, sg_scratch] if t is not None]
+        _run_factor_phases(ctx.factor_params, fgrads, M, dev, True, launch,
                            lambda: [x2, ctxbuf, scratch, *xt2, *fgrads] + [g for g in g2 if g is not None])
         dW = dbias = None
         if need[5] or need[6]:
@@ -563,14 +632,11 @@ class MTLoRALinearFn(torch.autograd.Function):
                     dbias = G.sum(0)
         dxo = dx if ctx.in_dtypes[0] == meta.dtype else dx.to(ctx.in_dtypes[0])
         dxto = [dxt[t] if ctx.in_dtypes[1 + t] == meta.dtype else dxt[t].to(ctx.in_dtypes[1 + t]) for t in range(nx)]
-        _, B_s_c, _, B_t_c = ctx.keep
-        d_ss = None
-        if ctx.has_scale_s and dB_s is not None and meta.scale_s != 0.0:
-            d_ss = ((dB_s * B_s_c).sum() / meta.scale_s).reshape(1)
-        d_st = []
-        for t in range(meta.n_scale_t):
-            ok = dB_t[t] is not None and meta.scale_t[t] != 0.0
-            d_st.append(((dB_t[t] * B_t_c[t]).sum() / meta.scale_t[t]).reshape(1) if ok else None)
+        d_ss = d_sc[0:1] if (d_sc is not None and sg_need[0]) else None
+        d_st = [d_sc[1 + t:2 + t] if (d_sc is not None and sg_need[1 + t]) else None for t in range(meta.n_scale_t)]
+        if not need[8]:
+            dB_s = None  # (formed for the scale's gradient only)
+        dB_t = [g if need[nB + t] else None for t, g in enumerate(dB_t)]
         return (None, dxo, None, None, None, dW, dbias, dA_s, dB_s, d_ss, *dxto, *dA_t, *dB_t, *d_st, *([None] * meta.n_gate))
 
 

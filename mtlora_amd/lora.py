@@ -123,6 +123,25 @@ class MTLoRALinear(LoRALayer):
         self._packed: Optional[torch.Tensor] = None
         self._packed_sig = None
         self._call_sig = None
+        # trainable scales (1-element Parameters) never leave the device: such a layer always runs from packed factors, and when no
+        # FactorPacker buffer is current it packs inside the call (one launch that reads the scales, Fn.pack_dev) into a buffer of its
+        # own -- one per call signature, never freed or re-used: a captured HIP graph may hold its address (the _wcache policy)
+        self._own_packed: Dict[Any, torch.Tensor] = {}
+
+    def _scale_params(self):
+        """the layer's trainable scales (the shared one, then the tasks'); () where every scale is a constant.  Cached like
+        ``_factor_params``"""
+        ps = self.__dict__.get("_sp_cache")
+        if ps is None:
+            ts = getattr(self, "lora_task_scale", None)
+            cand = [getattr(self, "lora_shared_scale", None)] + ([ts[t] for t in self.tasks] if (ts is not None and self.tasks) else [])
+            ps = tuple(q for q in cand if isinstance(q, torch.Tensor))
+            self.__dict__["_sp_cache"] = ps
+        return ps
+
+    def _versions(self):
+        """what a packed copy of the factors was made from: ``_version`` of every factor and of every trainable scale"""
+        return tuple(q._version for q in self._factor_params()) + tuple(q._version for q in self._scale_params())
 
     def _factor_params(self):
         """the layer's low-rank factor Parameters (shared A, B, then the tasks' A..., B...); the tuple is built once -- Parameters are
@@ -141,6 +160,7 @@ class MTLoRALinear(LoRALayer):
     def __setattr__(self, name, value):
         if name.startswith("lora_"):  # a factor (container) is being (re)assigned: the cached tuple of _factor_params is stale
             self.__dict__.pop("_fp_cache", None)
+            self.__dict__.pop("_sp_cache", None)
         super().__setattr__(name, value)
 
     def reset_parameters(self):
@@ -232,7 +252,9 @@ class MTLoRALinear(LoRALayer):
     def _apply(self, fn, *a, **k):  # .to() / .cuda(): the copies live on the old device / dtype
         self._wcache = {}
         self._packed_sig = None
+        self._own_packed = {}
         self.__dict__.pop("_fp_cache", None)
+        self.__dict__.pop("_sp_cache", None)
         return super()._apply(fn, *a, **k)
 
     def _load_from_state_dict(self, state_dict, prefix, *a, **k):
@@ -285,7 +307,7 @@ class MTLoRALinear(LoRALayer):
                              has_x_tasks=False, dropout_p=p, seed=Fn.next_seed() if p > 0 else 0, dtype=dtype)
         sig = (dtype, meta.r_s, (), ss, (), 0, False, p, str(device))
         self._call_sig = sig
-        if self._packed is not None and self._packed_sig == (sig, tuple(q._version for q in self._factor_params())):
+        if self._packed is not None and self._packed_sig == (sig, self._versions()):
             meta.packed = self._packed
         return meta
 
@@ -310,7 +332,7 @@ class MTLoRALinear(LoRALayer):
                              scale_s=ss, scale_t=st, mode=0, has_x_tasks=True, dropout_p=p, seed=Fn.next_seed() if p > 0 else 0, dtype=dtype)
         sig = (dtype, meta.r_s, meta.r_t, meta.scale_s, meta.scale_t, meta.mode, True, p, str(device))  # (as forward: FactorPacker key)
         self._call_sig = sig
-        if self._packed is not None and self._packed_sig == (sig, tuple(q._version for q in self._factor_params())):
+        if self._packed is not None and self._packed_sig == (sig, self._versions()):
             meta.packed = self._packed
         factors = (self.lora_shared_A, self.lora_shared_B, [self.lora_tasks_A[t] for t in tasks], [self.lora_tasks_B[t] for t in tasks])
         return meta, self._weights(dtype), factors
@@ -328,7 +350,10 @@ class MTLoRALinear(LoRALayer):
         tasks = list(self.tasks) if (has_lora and self.tasks is not None) else []
         shared = has_lora and self.shared_mode in ("matrix", "matrixv2") and not self.merged
         p = self.dropout_p if (self.training and has_lora) else 0.0
-        val = lambda s: float(s.detach().item()) if isinstance(s, torch.Tensor) else float(s)
+        # a trainable scale (a 1-element Parameter) travels as the tensor it is: the packing launch reads it on the device, nothing
+        # here looks at its value (no host synchronisation, and a captured graph follows the Parameter)
+        val = lambda s: s if isinstance(s, torch.Tensor) else float(s)
+        con = lambda s: None if isinstance(s, torch.Tensor) else s
         par = lambda s: s if isinstance(s, nn.Parameter) else None
         ss = self.lora_shared_scale if shared else 0.0
         st = [self.lora_task_scale[t] for t in tasks]
@@ -358,14 +383,22 @@ class MTLoRALinear(LoRALayer):
             dtype=dtype, weight_requires_grad=self.linear.weight.requires_grad or (
                 self.linear.bias is not None and self.linear.bias.requires_grad),
             n_scale_t=len(tasks) if (tasks and isinstance(st[0], nn.Parameter)) else 0)
-        if has_lora and (ra_s or any(ra_t)):
-            self._call_sig = None  # (the effective factors are formed per call: nothing for a FactorPacker to pack ahead of time)
-        elif has_lora:
-            # (what the packed factors depend on besides the masters: the alpha-scaled copies carry the scales and the dropout scale)
-            sig = (dtype, meta.r_s, meta.r_t, meta.scale_s, meta.scale_t, meta.mode, meta.has_x_tasks, p, str(x.device))
-            self._call_sig = sig
-            if self._packed is not None and self._packed_sig == (sig, tuple(q._version for q in self._factor_params())):
-                meta.packed = self._packed
+        if has_lora:
+            # (what the packed factors depend on besides the masters: the alpha-scaled copies carry the scales and the dropout scale;
+            # a trainable scale enters as None -- its value is read by the packing launch, its _version is part of the freshness check)
+            sig = (dtype, meta.r_s, meta.r_t, con(vs), tuple(con(v) for v in vt), meta.mode, meta.has_x_tasks, p, str(x.device))
+            if ra_s or any(ra_t):
+                self._call_sig = None  # (the effective factors are formed per call: nothing for a FactorPacker to pack ahead of time)
+            else:
+                self._call_sig = sig
+                if self._packed is not None and self._packed_sig == (sig, self._versions()):
+                    meta.packed = self._packed
+            if meta.packed is None and meta.scale_dev is not None and meta.r_s + sum(meta.r_t) > 0:
+                buf = self._own_packed.get(sig)
+                if buf is None:
+                    buf = self._own_packed[sig] = torch.empty(Fn.packed_bytes(meta), dtype=torch.uint8, device=x.device)
+                Fn.pack_dev(meta, A_s, B_s, A_t, B_t, buf)
+                meta.packed = buf
         if gelu_out:
             if self.shared_mode == "addition":
                 raise RuntimeError("mtlora_amd: gelu_out is not available with shared_mode='addition'")
@@ -403,7 +436,8 @@ class FactorPacker:
     steps; a trainer calls ``refresh()`` once per step before the forward (``mtl_harness.train_step`` does).  A layer uses its packed
     buffer only while it is provably current: same call signature (dtype, ranks, scales, dropout p, x_tasks or not) and unchanged
     ``_version`` of every factor Parameter -- anything else (first step, eval, a state-dict load, hand edits) falls back to packing
-    inside the forward call.  Layers with trainable scales (1-element Parameters that move every step) are left out."""
+    inside the forward call.  Trainable scales (1-element Parameters that move every step) are read by the packing launch itself:
+    the table entry of such a layer holds the scale Parameters' addresses, and their ``_version`` is part of the freshness check."""
 
     def __init__(self, model: nn.Module):
         self.layers = [m for m in model.modules() if isinstance(m, MTLoRALinear) and m.r > 0]
@@ -417,20 +451,17 @@ class FactorPacker:
     def _eligible(self, m: "MTLoRALinear") -> bool:
         if m._call_sig is None or m.merged:
             return False
-        if isinstance(m.lora_shared_scale, torch.Tensor):
-            return False
-        if m.tasks is not None and isinstance(m.lora_task_scale, nn.ParameterDict):
-            return False
-        return all(q.dtype == torch.float32 and q.is_contiguous() and q.is_cuda for q in m._factor_params())
+        return all(q.dtype == torch.float32 and q.is_contiguous() and q.is_cuda for q in m._factor_params() + m._scale_params())
 
     def refresh(self) -> int:
         """(re)pack every eligible layer for the signature of its LAST forward call; returns the number of layers packed."""
         for m in self.layers:  # (an entry of a ParameterDict replaced behind the module's back is picked up here)
             m.__dict__.pop("_fp_cache", None)
+            m.__dict__.pop("_sp_cache", None)
         todo = [m for m in self.layers if self._eligible(m)]
         if not todo:
             return 0
-        key = tuple((id(m), m._call_sig) + tuple(q.data_ptr() for q in m._factor_params()) for m in todo)
+        key = tuple((id(m), m._call_sig) + tuple(q.data_ptr() for q in m._factor_params() + m._scale_params()) for m in todo)
         if key != self._table_key and key in self._tables:
             self._table = self._tables[key]
             self._table_key = key
@@ -441,6 +472,10 @@ class FactorPacker:
             by_dtype = {}
             for m in todo:
                 dtype, r_s, r_t, scale_s, scale_t, mode, has_xt, p, _dev = m._call_sig
+                tasks = list(m.tasks) if (m.tasks is not None and len(r_t) > 0) else []
+                if scale_s is None:  # (trainable: the entry holds the Parameter's address, ``meta`` in ``keep`` keeps it alive)
+                    scale_s = m.lora_shared_scale
+                scale_t = tuple(m.lora_task_scale[t] if v is None else v for t, v in zip(tasks, scale_t))
                 meta = Fn.LinearMeta(K=m.linear.in_features, N=m.linear.out_features, r_s=r_s, r_t=r_t, scale_s=scale_s, scale_t=scale_t,
                                      mode=mode, has_x_tasks=has_xt, dropout_p=p, seed=0, dtype=dtype)
                 dev = m._factor_params()[0].device
@@ -448,7 +483,6 @@ class FactorPacker:
                 # one buffer per (layer, signature), never freed or re-used for another signature (see __init__)
                 m._packed = torch.empty(need, dtype=torch.uint8, device=dev)
                 shared = r_s > 0
-                tasks = list(m.tasks) if (m.tasks is not None and len(r_t) > 0) else []
                 ent = (meta, m.lora_shared_A if shared else None, m.lora_shared_B if shared else None,
                        [m.lora_tasks_A[t] for t in tasks], [m.lora_tasks_B[t] for t in tasks], m._packed, m)
                 by_dtype.setdefault((dtype, str(dev)), []).append(ent)
@@ -458,7 +492,7 @@ class FactorPacker:
         for tb in self._table:
             tb.pack()
         for m in todo:
-            m._packed_sig = (m._call_sig, tuple(q._version for q in m._factor_params()))
+            m._packed_sig = (m._call_sig, m._versions())
         return len(todo)
 
 
