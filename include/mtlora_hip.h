@@ -554,6 +554,22 @@ int mtlora_upsample_predict(int kind, const void* low, void* out, int64_t B, int
  * ------------------------------------------------------------------------------------------ */
 int64_t mtlora_colsum_scratch_bytes(int64_t M, int64_t N);
 int mtlora_colsum(const void* x, int64_t M, int64_t N, int dtype, float* out, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Gradient of a trainable `linear.bias` of an MTLoRALinear whose W stays frozen (additive under ABI 12) -- MODEL.MTLORA.BIAS 'all':
+ * mark_only_lora_as_trainable(model, bias='all'), reference lora.py:606-624, sets requires_grad on every `*.bias`.  All 1 + T
+ * outputs of the layer add the same x W^T + b (lora.py:255-284, every shared mode), so
+ *   db[n] = sum_m ( dy_s[m][n] + sum_t dy_t[t][m][n] )     over the d->M rows
+ * dy_s, dy_t[t]: (M, N) row-major in d->dtype (fp32, bf16 or fp16), T = d->T; a NULL source is an output that got no gradient and
+ * is skipped (dy_t itself may be NULL when T == 0); with every source NULL, or M == 0, db is written as zeros.  db (N) fp32.
+ * Only M, N, dtype and T of the descriptor are read.  N a multiple of the 16-byte vector of d->dtype and <= 2^20, sources and
+ * scratch 16-byte aligned.  fp32 accumulation; every gradient element is read once, as 16-byte vectors, and no (M, N) intermediate
+ * exists.  Two launches on `stream` (the column walk of mtlora_colsum over all sources, then its fixed-order combine): no
+ * atomics, no memset, db fully overwritten, the same bits on every call with the same inputs.
+ * ------------------------------------------------------------------------------------------ */
+int64_t mtlora_linear_bias_grad_scratch_bytes(const mtlora_linear_desc* d);
+int mtlora_linear_bias_grad(const mtlora_linear_desc* d, const void* dy_s, const void* const* dy_t, float* db, void* scratch,
+                            int64_t scratch_bytes, void* stream);
 int64_t mtlora_label_stat_scratch_bytes(int64_t n);
 int mtlora_label_stat(const float* label, int64_t n, int kind, float ignore_index, float* out, void* scratch,
                       int64_t scratch_bytes, void* stream);
@@ -591,7 +607,9 @@ int mtlora_upsample_cl_bwd(const void* grad_fine, void* grad_coarse, int64_t B, 
  *   tmp: scratch of mtlora_block_fwd_tmp_bytes(), dead when fwd returns (stream-ordered).
  * bwd: g_x_out (M,C) x_dtype and g_normed_out (M,C) dtype are the gradients of the two outputs (g_x_out may be NULL);
  *   it writes g_x (x_dtype) and, when has_norm1 == 0, g_normed (dtype), the LayerNorm gradients, the eight factor gradients
- *   (fp32, shapes of the masters) and dbias (num_heads, N, N) fp32.  phase as mtlora_linear_desc.bwd_phase: 0 everything on
+ *   (fp32, shapes of the masters), dbias (num_heads, N, N) fp32 and, where asked for, the gradients of the four linears'
+ *   biases: one mtlora_linear_bias_grad each on the buffer that linear's backward reads as dy, issued with the factor gradients
+ *   (phases 0 and 2) and bit identical to the stand-alone call.  phase as mtlora_linear_desc.bwd_phase: 0 everything on
  *   `stream`; 1 everything but the factor gradients; 2 the factor gradients only (same arguments, a second stream ordered
  *   behind phase 1).  scratch: mtlora_block_bwd_scratch_bytes(), must stay valid until phase 2 has run.
  * ------------------------------------------------------------------------------------------ */
@@ -630,6 +648,8 @@ typedef struct mtlora_block_grads {    /* outputs of bwd, fp32 unless noted, all
     float* dA[4];
     float* dB[4];
     float* dbias;                      /* (num_heads, N, N) */
+    float* dlin_bias[4];               /* (N) gradient of the bias of qkv, proj, fc1, fc2; NULL = not wanted.  Appended under ABI 12: a library
+                                          from before it lacks mtlora_linear_bias_grad, which the binding looks up when it loads */
 } mtlora_block_grads;
 
 int64_t mtlora_block_save_bytes(const mtlora_block_desc* d);

@@ -70,7 +70,7 @@ class BlockParams(Structure):
 class BlockGrads(Structure):
     _fields_ = [("g_x", c_void_p), ("g_normed", c_void_p), ("d_norm1_g", c_void_p), ("d_norm1_b", c_void_p), ("d_norm2_g", c_void_p),
                 ("d_norm2_b", c_void_p), ("d_next_g", c_void_p), ("d_next_b", c_void_p), ("dA", c_void_p * 4), ("dB", c_void_p * 4),
-                ("dbias", c_void_p)]
+                ("dbias", c_void_p), ("dlin_bias", c_void_p * 4)]
 
 
 class AdamwGroup(Structure):
@@ -241,6 +241,8 @@ _SIGS = {
     "mtlora_upsample_loss_partials": (c_int64, [c_int64, c_int, c_int, c_int]),
     "mtlora_colsum_scratch_bytes": (c_int64, [c_int64, c_int64]),
     "mtlora_colsum": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mtlora_linear_bias_grad_scratch_bytes": (c_int64, [POINTER(LinearDesc)]),
+    "mtlora_linear_bias_grad": (c_int, [POINTER(LinearDesc), c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_int64, c_void_p]),
     "mtlora_label_stat_scratch_bytes": (c_int64, [c_int64]),
     "mtlora_label_stat": (c_int, [c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
     "mtlora_upsample_loss": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,

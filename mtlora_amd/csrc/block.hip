@@ -33,6 +33,8 @@ struct BwdLayout {
     int64_t d_m, d_h, d_xn2, d_x1, d_y, d_a, d_qkv, d_xn, d_skip;  // activation gradients along the chain
     int64_t ln[3], attn, lin[4];                             // LayerNorm partials (next / norm2 / norm1: kept until phase 2 reduces them), attention, the linears' scratch (Q)
     int64_t ln_bytes, attn_bytes, lin_bytes[4];
+    int64_t db, db_bytes;  // partials of the linears' bias gradients: ONE region for the four reductions (they run one after the other
+                           // on the factor gradients' stream), sized for the largest
     int64_t total;
 };
 
@@ -119,6 +121,13 @@ int bwd_layout(const mtlora_block_desc* d, BwdLayout& L) {
         if (L.lin_bytes[i] < 0) return MTLORA_ERR_SHAPE;
         L.lin[i] = take(L.lin_bytes[i] > 16 ? L.lin_bytes[i] : 16);
     }
+    L.db_bytes = 0;
+    for (int i = 0; i < 4; ++i) {
+        const int64_t b = mtlora_linear_bias_grad_scratch_bytes(&d->lin[i]);
+        if (b < 0) return MTLORA_ERR_SHAPE;
+        if (b > L.db_bytes) L.db_bytes = b;
+    }
+    L.db = take(L.db_bytes);
     L.total = o;
     return MTLORA_OK;
 }
@@ -219,13 +228,22 @@ int mtlora_block_bwd(const mtlora_block_desc* d, const mtlora_block_params* p, c
     const void* lin_dy[4] = {at(scratch, S.d_qkv), at(scratch, S.d_y), at(scratch, S.d_h), at(scratch, S.d_m)};
     void* lin_dx[4] = {d->has_norm1 ? (void*)at(scratch, S.d_xn) : g->g_normed, at(scratch, S.d_a), at(scratch, S.d_xn2),
                        at(scratch, S.d_h)};
+    // a trainable bias (MTLORA.BIAS 'all'): the column sum of the gradient linear i's backward reads as dy.  d_m, d_h, d_y and d_qkv are
+    // regions of their own in BwdLayout, each written once (by ln_next, fc2's dX, ln_2 and the attention backward, all in the chain of
+    // phase 0 / 1) and only read afterwards, so in phase 2 they still hold what the factor gradients read there as well
+    auto bias_grad = [&](int i) -> int {
+        if (!g->dlin_bias[i] || phase == 1) return MTLORA_OK;
+        return mtlora_linear_bias_grad(&ld[i], lin_dy[i], kNoIn, g->dlin_bias[i], at(scratch, S.db), S.db_bytes, stream);
+    };
     auto linear_bwd = [&](int i) -> int {
         if (i == 3)  // fc2 reads a = gelu(h): its dX epilogue applies gelu'(h) and hands back the gradient w.r.t. h
-            return mtlora_linear_bwd_gelu(&ld[3], lin_x[3], kNoIn, p->Wt[3], lin_dy[3], kNoIn, at(save, L.ctx[3]), L.ctx_bytes[3],
-                                          lin_dx[3], kNoOut, g->dA[3], g->dB[3], kNoG, kNoG, at(scratch, S.lin[3]), S.lin_bytes[3],
-                                          at(save, L.h), kNoIn, stream);
-        return mtlora_linear_bwd(&ld[i], lin_x[i], kNoIn, p->Wt[i], lin_dy[i], kNoIn, at(save, L.ctx[i]), L.ctx_bytes[i], lin_dx[i],
-                                 kNoOut, g->dA[i], g->dB[i], kNoG, kNoG, at(scratch, S.lin[i]), S.lin_bytes[i], stream);
+            BLK_TRY(mtlora_linear_bwd_gelu(&ld[3], lin_x[3], kNoIn, p->Wt[3], lin_dy[3], kNoIn, at(save, L.ctx[3]), L.ctx_bytes[3],
+                                           lin_dx[3], kNoOut, g->dA[3], g->dB[3], kNoG, kNoG, at(scratch, S.lin[3]), S.lin_bytes[3],
+                                           at(save, L.h), kNoIn, stream));
+        else
+            BLK_TRY(mtlora_linear_bwd(&ld[i], lin_x[i], kNoIn, p->Wt[i], lin_dy[i], kNoIn, at(save, L.ctx[i]), L.ctx_bytes[i], lin_dx[i],
+                                      kNoOut, g->dA[i], g->dB[i], kNoG, kNoG, at(scratch, S.lin[i]), S.lin_bytes[i], stream));
+        return bias_grad(i);
     };
     const mtlora_attn_desc ad = attn_desc(d);
     auto ln_next = [&](int ph) -> int {      // next block's norm1 + the MLP residual: d_x1 = g_x_out + LN'(g_normed_out), d_m = scale2 * d_x1

@@ -6,6 +6,9 @@
 //
 //   mtlora_colsum       out[n] = sum_m x[m][n]                     bias gradient of the heads' big-M 1x1 convolutions
 //                                                                  (dL/db of reference models/seg_hrnet.py:498-526 layers)
+//   mtlora_linear_bias_grad  db[n] = sum_m (dy_s[m][n] + sum_t dy_t[t][m][n])   gradient of a trainable `linear.bias` of an MTLoRALinear
+//                                                                  (MTLORA.BIAS 'all', reference lora.py:606-624): the same walk over
+//                                                                  up to 1 + T sources, no (M, N) intermediate
 //   mtlora_label_stat   kind 0: #{ lab != ignore }                 valid-pixel count / mask sum of mtl_loss_schemes.py:22-39,
 //                       kind 1: mean(1 - (lab >= 0.5))             :162-220; class balance w of :42-89
 #include "dispatch.h"
@@ -14,9 +17,16 @@ namespace {
 
 constexpr int RD_MAXBLK = 1024;
 
-// stage 1: block b sums rows b, b + G, ... (256 / nvec rows per sweep) of the 16-byte column vectors -> part[b][N]
+// stage 1: block b sums rows b, b + G, ... (256 / nvec rows per sweep) of the 16-byte column vectors of EVERY source -> part[b][N].
+// The sources travel by value (SumParams of tn.h is the pattern); a row batch issues its four loads per source before the adds,
+// which keep the order row-major then source-major: one source gives the bits of the single-pointer kernel this one replaced.
+constexpr int CS_MAXSRC = 1 + MTLORA_MAX_TASKS;
+struct ColsumParams {
+    const void* src[CS_MAXSRC];
+    int n;
+};
 template <typename T>
-__global__ __launch_bounds__(256) void k_colsum_part(const T* x, int64_t M, int N, float* part) {
+__global__ __launch_bounds__(256) void k_colsum_part(ColsumParams P, int64_t M, int N, float* part) {
     constexpr int VE = ET<T>::VEC;
     __shared__ float sm[256][VE + 1];
     const int nvec = N / VE;
@@ -29,11 +39,26 @@ __global__ __launch_bounds__(256) void k_colsum_part(const T* x, int64_t M, int 
 #pragma unroll
         for (int e = 0; e < VE; ++e) acc[e] = 0.f;
         if (r < rps) {
-            for (int64_t m = (int64_t)blockIdx.x * rps + r; m < M; m += (int64_t)gridDim.x * rps) {
-                const Vec16<T> q = mtl_ld16<T>(x + m * N + (int64_t)(v0 + v) * VE);
+            const int64_t step = (int64_t)gridDim.x * rps, col = (int64_t)(v0 + v) * VE;
+            int64_t m = (int64_t)blockIdx.x * rps + r;
+            for (; m + 3 * step < M; m += 4 * step) {  // four rows in flight per source
+                for (int s = 0; s < P.n; ++s) {
+                    const T* x = reinterpret_cast<const T*>(P.src[s]) + col;
+                    Vec16<T> q[4];
 #pragma unroll
-                for (int e = 0; e < VE; ++e) acc[e] += mtl_to_f32(q.e[e]);
+                    for (int j = 0; j < 4; ++j) q[j] = mtl_ld16<T>(x + (m + j * step) * N);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int e = 0; e < VE; ++e) acc[e] += mtl_to_f32(q[j].e[e]);
+                }
             }
+            for (; m < M; m += step)
+                for (int s = 0; s < P.n; ++s) {
+                    const Vec16<T> q = mtl_ld16<T>(reinterpret_cast<const T*>(P.src[s]) + col + m * N);
+#pragma unroll
+                    for (int e = 0; e < VE; ++e) acc[e] += mtl_to_f32(q.e[e]);
+                }
         }
 #pragma unroll
         for (int e = 0; e < VE; ++e) sm[tid][e] = (r < rps) ? acc[e] : 0.f;
@@ -123,6 +148,30 @@ int rd_blocks(int64_t work_items) {
     return (int)(g < 1 ? 1 : g);
 }
 
+bool colsum_shape_ok(int64_t M, int64_t N, int dtype) { return M >= 0 && N > 0 && N % mtl_vec_elems(dtype) == 0 && N <= (1 << 20); }
+
+// >= 8 sweeps per block, at most RD_MAXBLK blocks
+int colsum_blocks(int64_t M, int64_t N, int dtype) {
+    const int nvec = (int)(N / mtl_vec_elems(dtype));
+    const int rps = nvec >= 256 ? 1 : 256 / nvec;
+    int64_t g = mtl_ceil_div(M, (int64_t)rps * 8);
+    if (g > RD_MAXBLK) g = RD_MAXBLK;
+    return (int)(g < 1 ? 1 : g);
+}
+
+// the two launches of a column sum over P's sources; `part` holds colsum_blocks() x N floats
+int colsum_launch(const ColsumParams& P, int64_t M, int64_t N, int dtype, float* out, float* part, hipStream_t s) {
+    const int g = colsum_blocks(M, N, dtype);
+    mtl_dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(k_colsum_part<T>, dim3((unsigned)g), dim3(256), 0, s, P, M, (int)N, part);
+    });
+    hipLaunchKernelGGL(k_colsum_combine, dim3((unsigned)mtl_ceil_div(N, 64)), dim3(64 * RD_RW), 0, s, (const float*)part, out, g, (int)N,
+                       1.f);
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -134,26 +183,33 @@ int64_t mtlora_colsum_scratch_bytes(int64_t M, int64_t N) {
 
 int mtlora_colsum(const void* x, int64_t M, int64_t N, int dtype, float* out, void* scratch, int64_t scratch_bytes, void* stream) {
     if (!mtl_dtype_in(dtype, MTL_DT_F32_BF16)) return MTLORA_ERR_DTYPE;
-    const int ve = mtl_vec_elems(dtype);
-    if (M < 0 || N <= 0 || N % ve || N > (1 << 20)) return MTLORA_ERR_SHAPE;
+    if (!colsum_shape_ok(M, N, dtype)) return MTLORA_ERR_SHAPE;
     if (mtl_any_null({x, out, scratch})) return MTLORA_ERR_NULL;
     if (mtl_any_misaligned({x, scratch})) return MTLORA_ERR_ALIGN;
     if (scratch_bytes < mtlora_colsum_scratch_bytes(M, N)) return MTLORA_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int nvec = (int)(N / ve);
-    const int rps = nvec >= 256 ? 1 : 256 / nvec;
-    int64_t g = mtl_ceil_div(M, (int64_t)rps * 8);  // >= 8 sweeps per block
-    if (g > RD_MAXBLK) g = RD_MAXBLK;
-    if (g < 1) g = 1;
-    float* part = reinterpret_cast<float*>(scratch);
-    mtl_dispatch_f32_bf16(dtype, [&](auto t) {
-        using T = typename decltype(t)::type;
-        hipLaunchKernelGGL(k_colsum_part<T>, dim3((unsigned)g), dim3(256), 0, s, reinterpret_cast<const T*>(x), M, (int)N, part);
-    });
-    hipLaunchKernelGGL(k_colsum_combine, dim3((unsigned)mtl_ceil_div(N, 64)), dim3(64 * RD_RW), 0, s, (const float*)part, out, (int)g,
-                       (int)N, 1.f);
-    MTL_CHECK_LAUNCH();
-    return MTLORA_OK;
+    ColsumParams P = {};
+    P.src[P.n++] = x;
+    return colsum_launch(P, M, N, dtype, out, reinterpret_cast<float*>(scratch), (hipStream_t)stream);
+}
+
+int64_t mtlora_linear_bias_grad_scratch_bytes(const mtlora_linear_desc* d) {
+    if (!d || !mtl_dtype_in(d->dtype, MTL_DT_ALL) || d->T < 0 || d->T > MTLORA_MAX_TASKS || !colsum_shape_ok(d->M, d->N, d->dtype)) return -1;
+    return (int64_t)colsum_blocks(d->M, d->N, d->dtype) * d->N * 4 + 256;
+}
+
+int mtlora_linear_bias_grad(const mtlora_linear_desc* d, const void* dy_s, const void* const* dy_t, float* db, void* scratch,
+                            int64_t scratch_bytes, void* stream) {
+    if (!d) return MTLORA_ERR_NULL;
+    if (!mtl_dtype_in(d->dtype, MTL_DT_ALL)) return MTLORA_ERR_DTYPE;
+    if (d->T < 0 || d->T > MTLORA_MAX_TASKS || !colsum_shape_ok(d->M, d->N, d->dtype)) return MTLORA_ERR_SHAPE;
+    if (mtl_any_null({db, scratch}) || (d->T > 0 && !dy_t)) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({dy_s, scratch}, d->T, {dy_t}) || ((uintptr_t)db & 3)) return MTLORA_ERR_ALIGN;
+    if (scratch_bytes < mtlora_linear_bias_grad_scratch_bytes(d)) return MTLORA_ERR_WORKSPACE;
+    ColsumParams P = {};  // an output that got no gradient (NULL) is skipped; no source at all: the kernels write zeros
+    if (dy_s) P.src[P.n++] = dy_s;
+    for (int t = 0; t < d->T; ++t)
+        if (dy_t[t]) P.src[P.n++] = dy_t[t];
+    return colsum_launch(P, d->M, d->N, d->dtype, db, reinterpret_cast<float*>(scratch), (hipStream_t)stream);
 }
 
 int64_t mtlora_label_stat_scratch_bytes(int64_t n) {

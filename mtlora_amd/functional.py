@@ -535,6 +535,7 @@ class MTLoRALinearFn(torch.autograd.Function):
             if meta.packed is None or meta.scale_dev is None:
                 raise RuntimeError("mtlora_amd: a layer with trainable scales runs from factors packed with mtlora_linear_pack_dev")
             ctx.factor_params += (scale_s_param, *rest[nx + 2 * T:nx + 2 * T + meta.n_scale_t])  # (their gradients: same stream)
+        ctx.bias_param = bias_master  # (a trainable bias with W frozen: its gradient runs with the factor gradients, see backward)
         ctx.M = M
         return (ys, *yt, *acts)
 
@@ -595,6 +596,17 @@ class MTLoRALinearFn(torch.autograd.Function):
             for t in range(T):
                 if dy_t[t] is None:
                     dxt[t].zero_()
+        # `linear.bias` trains while W stays frozen (mark_only_lora_as_trainable bias='all', reference lora.py:606-624): every output adds
+        # the same x W^T + b, so db is the column sum of the output gradients in hand -- one mtlora_linear_bias_grad over the 1 + T
+        # sources, queued with the factor gradients.  A shape the entry refuses (N off the 16-byte vector grid) keeps the ATen form below
+        db = db_scratch = None
+        db_bytes = -1
+        if need[6] and not need[5]:
+            db_bytes = _size_query("bias_grad", lib.mtlora_linear_bias_grad_scratch_bytes, d)
+        if db_bytes >= 0:
+            db = torch.empty(meta.N, dtype=torch.float32, device=dev)
+            db_scratch = torch.empty(db_bytes, dtype=torch.uint8, device=dev)
+        db_cast = db is not None and ctx.bias_param.dtype != torch.float32  # (the cast reads db on THIS stream)
 
         def launch(phase, stream_ptr):
             d.bwd_phase = phase
@@ -612,12 +624,17 @@ class MTLoRALinearFn(torch.autograd.Function):
                 L.check(st, "mtlora_linear_bwd")
             if d_sc is not None and phase != 1:  # the scale gradients: queued behind the factor gradients, on their stream
                 L.check(lib.mtlora_linear_scale_grad(ctypes.byref(d), *sg_args, stream_ptr), "mtlora_linear_scale_grad")
+            if db is not None and phase != 1:
+                L.check(lib.mtlora_linear_bias_grad(ctypes.byref(d), L.ptr(dy_s), L.ptr_array(dy_t), L.ptr(db), L.ptr(db_scratch), db_bytes,
+                                                    stream_ptr), "mtlora_linear_bias_grad")
 
-        fgrads = [t for t in [dA_s, dB_s, *dA_t, *dB_t, d_sc, sg_scratch] if t is not None]
-        _run_factor_phases(ctx.factor_params, fgrads, M, dev, True, launch,
+        fgrads = [t for t in [dA_s, dB_s, *dA_t, *dB_t, d_sc, sg_scratch, db, db_scratch] if t is not None]
+        _run_factor_phases(ctx.factor_params if db is None else ctx.factor_params + (ctx.bias_param,), fgrads, M, dev, not db_cast, launch,
                            lambda: [x2, ctxbuf, scratch, *xt2, *fgrads] + [g for g in g2 if g is not None])
         dW = dbias = None
-        if need[5] or need[6]:
+        if db is not None:
+            dbias = db.to(ctx.bias_param.dtype) if db_cast else db
+        elif need[5] or need[6]:
             # pretrained weight and / or bias left trainable (MTLORA.FREEZE_PRETRAINED False; mark_only_lora_as_trainable
             # bias='all' trains `linear.bias` with W frozen, reference lora.py:606-617): dense gradients outside the frozen-W
             # hot path.  Every output adds the same base  x W^T + b, so both see G = sum of the output gradients.
@@ -2147,7 +2164,7 @@ class BlockCall:
     """what one block of a ``SwinBlockRunFn`` call needs besides its tensors: the four linears' metas (seeds drawn, packed factors
     looked up), their frozen-weight copies, the attention geometry.  Built per call by ``SwinTransformerBlock._block_call``."""
     __slots__ = ("has_norm1", "metas", "weights", "mask", "mask_ids", "H", "W", "num_heads", "window_size", "shift", "hidden",
-                 "eps", "attn_scale", "mask_value", "factor_params", "norm_params", "desc", "params", "n_flat")
+                 "eps", "attn_scale", "mask_value", "factor_params", "norm_params", "desc", "params", "n_flat", "flat_at", "bias_params")
 
     def __init__(self, has_norm1, metas, weights, mask, mask_ids, H, W, num_heads, window_size, shift, hidden, eps, attn_scale,
                  factor_params, norm_params=(), mask_value=-100.0):
@@ -2156,7 +2173,7 @@ class BlockCall:
         self.eps, self.attn_scale, self.mask_value, self.factor_params = eps, attn_scale, mask_value, factor_params
         self.norm_params = tuple(norm_params)
         self.desc = self.params = None
-        self.n_flat = 17 if has_norm1 else 15
+        self.n_flat = 21 if has_norm1 else 19
 
     def build_desc(self, B: int, C: int, cdtype: torch.dtype, x_dtype: torch.dtype) -> "L.BlockDesc":
         d = L.BlockDesc()
@@ -2198,7 +2215,9 @@ class SwinBlockRunFn(torch.autograd.Function):
     args: calls (list of BlockCall), x (B, L, C) residual stream, normed (norm1(x) of the first block, or None when that block
     applies it itself), then per block
         bias (nH, N, N) fp32, scale1, scale2 ((B) fp32 DropPath factors or None), [norm1.weight, norm1.bias when has_norm1],
-        norm2.weight, norm2.bias, next_norm.weight, next_norm.bias, A_qkv, B_qkv, A_proj, B_proj, A_fc1, B_fc1, A_fc2, B_fc2"""
+        norm2.weight, norm2.bias, next_norm.weight, next_norm.bias, A_qkv, B_qkv, A_proj, B_proj, A_fc1, B_fc1, A_fc2, B_fc2,
+        then the four `linear.bias` masters that train with W frozen (None where the bias is frozen or absent): the block call reads
+        them as its bias operands and returns their gradients (``mtlora_block_grads.dlin_bias``)"""
 
     @staticmethod
     def forward(ctx, calls, x, normed, *flat):
@@ -2216,6 +2235,8 @@ class SwinBlockRunFn(torch.autograd.Function):
         xs, ns, saves = [x], [normed], []
         for c in calls:
             t = flat[at:at + c.n_flat]
+            c.flat_at = at
+            c.bias_params = tuple(q for q in t[c.n_flat - 4:] if q is not None)
             at += c.n_flat
             # every tensor whose raw address goes into BlockParams: on x's device, contiguous, in the dtype the kernels read it as
             # (the per-layer Functions report a mismatch as an error; here it would be an illegal access)
@@ -2243,6 +2264,10 @@ class SwinBlockRunFn(torch.autograd.Function):
                 wc, wt, bf = c.weights[i]
                 p.W[i], p.Wt[i], p.bias[i] = wc.data_ptr(), wt.data_ptr(), (0 if bf is None else bf.data_ptr())
                 p.A[i], p.Bf[i] = t[k + 4 + 2 * i].data_ptr(), t[k + 5 + 2 * i].data_ptr()
+                if t[k + 12 + i] is not None:  # a trainable bias: the operand is the master itself
+                    if t[k + 12 + i].numel() != c.metas[i].N:
+                        raise RuntimeError("mtlora_amd: SwinBlockRunFn got a bias master that does not match its linear")
+                    p.bias[i] = t[k + 12 + i].data_ptr()
             p.mask_ids = 0 if c.mask_ids is None else c.mask_ids.data_ptr()
             p.mask = 0 if (c.mask is None or c.mask_ids is not None) else c.mask.data_ptr()
             c.params = p
@@ -2300,20 +2325,25 @@ class SwinBlockRunFn(torch.autograd.Function):
             g.g_x, g.g_normed = gx.data_ptr(), (0 if gn is None else gn.data_ptr())
             g.d_norm1_g, g.d_norm1_b, g.d_norm2_g, g.d_norm2_b = lnw[0].data_ptr(), lnw[1].data_ptr(), lnw[2].data_ptr(), lnw[3].data_ptr()
             g.d_next_g, g.d_next_b, g.dbias = lnw[4].data_ptr(), lnw[5].data_ptr(), dbias.data_ptr()
+            at_b = 3 + c.flat_at + c.n_flat - 4  # (the bias masters close this block's flat arguments: see the class docstring)
+            need_b = ctx.needs_input_grad[at_b:at_b + 4]
+            db = [torch.empty(m.N, dtype=torch.float32, device=dev) if need_b[i] else None for i, m in enumerate(c.metas)]
             for i in range(4):
                 g.dA[i], g.dB[i] = fg[2 * i].data_ptr(), fg[2 * i + 1].data_ptr()
+                g.dlin_bias[i] = 0 if db[i] is None else db[i].data_ptr()
+            fg_all = fg + [t for t in db if t is not None]
             # everything phase 2 writes on the side stream: the eight factor gradients and the LayerNorm dgamma / dbeta (their
             # second-stage reduces ride along, csrc/internal.h) -- none of their Parameters may have a .grad to accumulate into
             args = (ctypes.byref(d), ctypes.byref(p), xs[bi].data_ptr(), 0 if ns[bi] is None else ns[bi].data_ptr(),
                     xs[bi + 1].data_ptr(), g_x.data_ptr(), g_n.data_ptr(), saves[bi].data_ptr(), saves[bi].numel(), ctypes.byref(g),
                     scratch.data_ptr(), scb)
-            _run_factor_phases(c.factor_params + c.norm_params, fg, M, dev, True,
+            _run_factor_phases(c.factor_params + c.norm_params + c.bias_params, fg_all, M, dev, True,
                                lambda phase, sp: L.check(lib.mtlora_block_bwd(*args, phase, sp), "mtlora_block_bwd"),
-                               lambda: (xs[bi], xs[bi + 1], saves[bi], scratch, lnw, g_n, *fg) + (() if ns[bi] is None else (ns[bi],)))
+                               lambda: (xs[bi], xs[bi + 1], saves[bi], scratch, lnw, g_n, *fg_all) + (() if ns[bi] is None else (ns[bi],)))
             blk = [dbias, None, None]
             if c.has_norm1:
                 blk += [lnw[0], lnw[1]]
-            blk += [lnw[2], lnw[3], lnw[4], lnw[5], *fg]
+            blk += [lnw[2], lnw[3], lnw[4], lnw[5], *fg, *db]
             grads_flat = blk + grads_flat
             g_x, g_n = gx, gn
         return (None, g_x, g_n if ctx.has_normed else None, *grads_flat)

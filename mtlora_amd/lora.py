@@ -213,9 +213,18 @@ class MTLoRALinear(LoRALayer):
     def _weights(self, dtype: torch.dtype):
         w, b = self.linear.weight, self.linear.bias
         key = (dtype, w.device)
-        ver = (w._version, w.data_ptr(), None if b is None else (b._version, b.data_ptr()))
+        # only the bias trains (MTLORA.BIAS 'all' with W frozen): the W / W^T copies stay cached as for a frozen layer and just the fp32
+        # bias operand follows the master -- the master itself where the kernels can read it (its address is the Parameter's, stable
+        # for a captured graph), else the cached buffer, refreshed in place on every call
+        b_train = b is not None and b.requires_grad and not w.requires_grad
+        b_master = b_train and b.dtype == torch.float32 and b.is_contiguous() and b.device == w.device
+        if b_train:
+            bver = ("master" if b_master else "follow", b.data_ptr())
+        else:
+            bver = None if b is None else (b._version, b.data_ptr())
+        ver = (w._version, w.data_ptr(), bver)
         hit = self._wcache.get(key)
-        if w.requires_grad or (b is not None and b.requires_grad):
+        if w.requires_grad:
             hit = None  # trained by an optimizer every step: never serve a cached copy
         if hit is not None and hit[1].is_inference() and not torch.is_inference_mode_enabled():
             hit = None  # copies made under torch.inference_mode() (an eval pass) cannot be saved for backward or refreshed in place
@@ -226,16 +235,21 @@ class MTLoRALinear(LoRALayer):
                     wc, wt, bf = hit[1], hit[2], hit[3]
                     wc.copy_(w.detach())
                     wt.copy_(w.detach().t())
-                    if bf is not None:
+                    if b_master:
+                        bf = b.detach()
+                    elif bf is not None:
                         bf.copy_(b.detach())
                 else:
                     wc = w.detach().to(dtype).contiguous()
                     wt = w.detach().t().to(dtype).contiguous()
-                    bf = None if b is None else b.detach().float().contiguous()
+                    bf = None if b is None else (b.detach() if b_master else b.detach().float().contiguous())
             hit = (ver, wc, wt, bf)
             # one entry per (dtype, device), none evicted: an fp32 eval between bf16 graphed steps must not free the copies whose
             # addresses a captured HIP graph holds (52 MB per extra dtype at C2: irrelevant against 288 GB)
             self._wcache[key] = hit
+        elif b_train and not b_master:
+            with torch.no_grad():
+                hit[3].copy_(b.detach())
         return hit[1], hit[2], hit[3]
 
     def invalidate_weight_cache(self) -> None:

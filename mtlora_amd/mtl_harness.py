@@ -85,6 +85,7 @@ def config(name: str) -> dict:
 
 
 def build_config_model(name: str, seed: int = 0, **over) -> "MultiTaskSwin":
+    """the model of a named configuration; ``over`` replaces its entries or adds ``build_model`` arguments (``bias="all"``)"""
     c = config(name)
     c.update(over)
     return build_model(img_size=c["img_size"], tasks=c["tasks"], embed_dim=c["embed_dim"], depths=c["depths"],
@@ -228,6 +229,7 @@ class MultiTaskSwin(nn.Module):
         self.tasks = list(tasks)
         res = backbone.patch_embed.patches_resolution
         n = backbone.num_layers
+        decoder_channels = tuple(decoder_channels)[:n]  # (a backbone with fewer stages, as the small test models: one map per stage)
         self.dims = [int(backbone.embed_dim * 2 ** ((i + 1) if i < n - 1 else i)) for i in range(n)]
         self.input_res = [res[0] // (2 ** ((i + 1) if i < n - 1 else i)) for i in range(n)]
         self.img_size = backbone.patch_embed.img_size
@@ -349,11 +351,12 @@ class MultiTaskLoss(nn.Module):
 # --------------------------------------------------------------------------------------------------
 def build_model(img_size=448, tasks=("semseg", "normals", "sal", "human_parts"), embed_dim=96, depths=(2, 2, 6, 2),
                 num_heads=(3, 6, 12, 24), r_shared=64, r_task=4, drop_path_rate=0.2, lora_b_std=0.02, seed=0,
-                freeze=True, num_outputs: Optional[Mapping[str, int]] = None, **mt_over) -> MultiTaskSwin:
+                freeze=True, num_outputs: Optional[Mapping[str, int]] = None, bias: str = "none", **mt_over) -> MultiTaskSwin:
     """random-init model of the BASELINE configs: trunc_normal(.02) weights (reference :717-724),
     lora_*_B ~ N(0, lora_b_std) so that the LoRA paths are numerically live, and the reference's
     trainable set (mark_only_lora_as_trainable with every freeze flag False, main.py:257-262).
-    ``num_outputs`` overrides the channel count of named tasks (NYUD: ``{"semseg": 40}``)."""
+    ``num_outputs`` overrides the channel count of named tasks (NYUD: ``{"semseg": 40}``).  ``bias`` is MODEL.MTLORA.BIAS
+    (reference config.py:309): 'all' also trains every ``*.bias`` of the backbone, the frozen linears' among them."""
     torch.manual_seed(seed)
     mt = mtlora_namespace(tasks, r_shared, r_task, n_stages=len(depths), **mt_over)
     bb = SwinTransformerMTLoRA(img_size=img_size, patch_size=4, in_chans=3, num_classes=0, embed_dim=embed_dim,
@@ -367,7 +370,7 @@ def build_model(img_size=448, tasks=("semseg", "normals", "sal", "human_parts"),
                 if "lora_" in n and "_B" in n:
                     p.normal_(0.0, lora_b_std)
     if freeze:
-        mark_only_lora_as_trainable(model.backbone, bias="none")
+        mark_only_lora_as_trainable(model.backbone, bias=bias)
     return model
 
 

@@ -442,8 +442,10 @@ class SwinTransformerBlock(nn.Module):
                 if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
                     return None
         for m in lin:
-            if (m.merged or isinstance(m.lora_shared_scale, torch.Tensor) or m.rank_aware_shared() or m.linear.weight.requires_grad
-                    or (m.linear.bias is not None and m.linear.bias.requires_grad)):
+            if m.merged or isinstance(m.lora_shared_scale, torch.Tensor) or m.rank_aware_shared() or m.linear.weight.requires_grad:
+                return None
+            b = m.linear.bias  # trainable with W frozen (MTLORA.BIAS 'all'): the call reads the master and hands back its gradient
+            if b is not None and b.requires_grad and (b.dtype != torch.float32 or b.device != dev or not b.is_contiguous()):
                 return None
             for t in (m.lora_shared_A, m.lora_shared_B):
                 if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
@@ -475,6 +477,7 @@ class SwinTransformerBlock(nn.Module):
         flat += [self.norm2.weight, self.norm2.bias, next_norm.weight, next_norm.bias]
         call.norm_params = tuple(flat[3:])
         flat += fparams
+        flat += [m.linear.bias if (m.linear.bias is not None and m.linear.bias.requires_grad) else None for m in lin]
         return call, flat
 
     # -- attention half ------------------------------------------------------------------------------
