@@ -575,6 +575,31 @@ int mtlora_label_stat(const float* label, int64_t n, int kind, float ignore_inde
                       int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Full fine-tuning (additive under ABI 12) -- MODEL.MTLORA.FREEZE_PRETRAINED False (reference config.py:317): main.py:254-262 then
+ * skips mark_only_lora_as_trainable, so every `linear.weight` of the MTLoRALinear layers trains next to the LoRA factors.
+ *
+ * mtlora_linear_weight_grad: the dense gradient of `linear.weight`.  All 1 + T outputs of the layer add the same x W^T + b, and the
+ * task inputs and the dropout mask touch only the low-rank branches (lora.py:255-284, every shared mode), so
+ *   dW[n][k] = sum_m ( dy_s[m][n] + sum_t dy_t[t][m][n] ) * x[m][k]          (N x K) fp32 row-major, the master's layout
+ * x (M, K): the shared input the forward's dense product read (un-dropped; gelu(h) for a layer fed through a GELU gate);
+ * dy_s, dy_t[t] (M, N); all row-major in d->dtype (fp32, bf16 or fp16), T = d->T.  Only M, K, N, dtype and T of the descriptor are
+ * read.  A NULL source is an output that got no gradient and is skipped (dy_t itself may be NULL when T == 0); with every source
+ * NULL, or M == 0, dW is written as zeros.  dW is fully overwritten on every call.  N and K multiples of the 16-byte vector of
+ * d->dtype, N x K at most 65535 tiles of 128 x 128, every pointer 16-byte aligned; the size query answers -1 for a refused shape.
+ * fp32 accumulation on the matrix pipe (MFMA for all three types); the sources extend the reduction dimension (sum_o dy_o^T x), so
+ * no (M, N) intermediate exists.  One launch over 128 x 128 tiles x splits of M, then (when M is split) the fixed-order combine of
+ * the partial tiles: no atomics, no memset, the same bits on every call with the same inputs.
+ *
+ * mtlora_linear_weight_cast: the per-step refresh of the compute-dtype copies of a trainable fp32 master W (N, K), one launch that
+ * reads W once and writes Wc (N, K) and Wt (K, N) = Wc^T in `dtype` (rounding of W.to(dtype): to nearest even; fp32: a copy and a
+ * transpose) -- the two operands MTLoRALinear's forward and backward read (lora.py:255, F.linear(x, self.linear.weight)).
+ * ------------------------------------------------------------------------------------------ */
+int64_t mtlora_linear_weight_grad_scratch_bytes(const mtlora_linear_desc* d);
+int mtlora_linear_weight_grad(const mtlora_linear_desc* d, const void* x, const void* dy_s, const void* const* dy_t, float* dW,
+                              void* scratch, int64_t scratch_bytes, void* stream);
+int mtlora_linear_weight_cast(const float* W, int N, int K, int dtype, void* Wc, void* Wt, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Channels-last bilinear upsampling by an integer factor (align_corners=False) for the HRNet head of the callers
  * (models/seg_hrnet.py:498-526: F.interpolate of the coarse maps + torch.cat).  coarse (B,h,w,C) contiguous; the fine
  * tensor (B, scale*h, scale*w, .) is addressed with `ld_fine` elements per pixel, its pointer already offset to the

@@ -243,6 +243,10 @@ _SIGS = {
     "mtlora_colsum": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "mtlora_linear_bias_grad_scratch_bytes": (c_int64, [POINTER(LinearDesc)]),
     "mtlora_linear_bias_grad": (c_int, [POINTER(LinearDesc), c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_int64, c_void_p]),
+    "mtlora_linear_weight_grad_scratch_bytes": (c_int64, [POINTER(LinearDesc)]),
+    "mtlora_linear_weight_grad": (c_int, [POINTER(LinearDesc), c_void_p, c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_int64,
+                                          c_void_p]),
+    "mtlora_linear_weight_cast": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mtlora_label_stat_scratch_bytes": (c_int64, [c_int64]),
     "mtlora_label_stat": (c_int, [c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
     "mtlora_upsample_loss": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,

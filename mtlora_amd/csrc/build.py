@@ -11,7 +11,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["window_process.hip", "linear.hip", "attention.hip", "glue.hip", "act_dropout.hip", "layernorm.hip", "loss.hip", "metrics.hip", "predict.hip", "upsample.hip", "reduce.hip", "selftest.hip", "block.hip", "hid.hip", "optim.hip", "ingest.hip", "augment.hip", "meter.hip", "snapshot.hip"]
+SOURCES = ["window_process.hip", "linear.hip", "attention.hip", "glue.hip", "act_dropout.hip", "layernorm.hip", "loss.hip", "metrics.hip", "predict.hip", "upsample.hip", "reduce.hip", "weight_grad.hip", "selftest.hip", "block.hip", "hid.hip", "optim.hip", "ingest.hip", "augment.hip", "meter.hip", "snapshot.hip"]
 LIB = os.path.join(HERE, "libmtlora_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
 

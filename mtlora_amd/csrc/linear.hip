@@ -1641,7 +1641,7 @@ static void bwd_factors(Bwd<T>& b) {
                                dim3(256), 0, s, tp);
         }
         MtlProfScope prof(PK_REDUCE, 0.0, s);
-        hipLaunchKernelGGL(k_tn_reduce, dim3(TN_TILE / 1024, (unsigned)max_tiles, (unsigned)tp.n_prob), dim3(256 * TN_RG), 0, s, tp);
+        hipLaunchKernelGGL(k_tn_reduce<>, dim3(TN_TILE / 1024, (unsigned)max_tiles, (unsigned)tp.n_prob), dim3(256 * TN_RG), 0, s, tp);
     }
 }
 
@@ -2333,7 +2333,7 @@ int mtlora_gemm_tn(const void* a, const void* b, float* out, int64_t M, int Na, 
         });
     }
     MtlProfScope prof(PK_REDUCE, 0.0, s);
-    hipLaunchKernelGGL(k_tn_reduce, dim3(TN_TILE / 1024, (unsigned)(ta * tb), 1), dim3(256 * TN_RG), 0, s, tp);
+    hipLaunchKernelGGL(k_tn_reduce<>, dim3(TN_TILE / 1024, (unsigned)(ta * tb), 1), dim3(256 * TN_RG), 0, s, tp);
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }

@@ -224,6 +224,7 @@ __global__ __launch_bounds__(256, 2) void k_tn(const TnParams P) {
 }
 
 constexpr int TN_RG = 4;  // thread groups that share the splits of a 1024-element block
+template <int TA = TN_A, int TB = TN_B>  // the partial tiles' shape: k_tn's 64 x 256, or the 128 x 128 of k_wgrad (weight_grad.hip)
 __global__ __launch_bounds__(256 * TN_RG) void k_tn_reduce(const TnParams P) {
     // one workgroup per (problem, tile, 1024-element block): 4 outputs per thread (one 16-byte load per split, coalesced
     // across the wave); the splits are dealt round-robin to TN_RG groups of 256 threads, each summing its share in a
@@ -234,16 +235,16 @@ __global__ __launch_bounds__(256 * TN_RG) void k_tn_reduce(const TnParams P) {
     const int tile = blockIdx.y;
     if (tile >= ntile) return;
     const int t = threadIdx.x & 255, grp = threadIdx.x >> 8;
-    const int e0 = blockIdx.x * 1024 + t * 4;  // element inside the 64x256 tile
+    const int e0 = blockIdx.x * 1024 + t * 4;  // element inside the TA x TB tile
     const int ta = tile / pr.tiles_b, tb = tile % pr.tiles_b;
-    const int a = ta * TN_A + e0 / TN_B, b0 = tb * TN_B + e0 % TN_B;
+    const int a = ta * TA + e0 / TB, b0 = tb * TB + e0 % TB;
     const bool live = a < pr.out_a && b0 < pr.out_b;
     f32x4 acc[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (live) {
-        const float* src = pr.part + (int64_t)tile * TN_TILE + e0;
-        const int64_t stride = (int64_t)ntile * TN_TILE;
+        const float* src = pr.part + (int64_t)tile * (TA * TB) + e0;
+        const int64_t stride = (int64_t)ntile * (TA * TB);
         int sp = grp;
         for (; sp + 3 * TN_RG < P.nsplit; sp += 4 * TN_RG) {
 #pragma unroll

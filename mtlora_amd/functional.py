@@ -462,6 +462,34 @@ def scale_grad_torch(dB: torch.Tensor, B: torch.Tensor, s: torch.Tensor) -> torc
     return torch.where(sv == 0, torch.zeros_like(t), t / torch.where(sv == 0, torch.ones_like(sv), sv)).float().reshape(1)
 
 
+def weight_cast(w: torch.Tensor, wc: torch.Tensor, wt: torch.Tensor) -> None:
+    """refill ``wc`` (N, K) and ``wt`` (K, N), contiguous and of one dtype, from the contiguous fp32 master ``w`` (N, K) in one launch
+    (``mtlora_linear_weight_cast``): bit-equal to ``w.to(dtype)`` and its transpose.  A raw-pointer write: no version counter moves,
+    so a buffer that an earlier call saved for backward stays usable, and a captured graph re-reads the master on every replay."""
+    L.require_gpu(w, wc, wt)
+    N, K = w.shape
+    if (w.dtype != torch.float32 or not w.is_contiguous() or wc.dtype != wt.dtype or wc.shape != (N, K) or wt.shape != (K, N)
+            or not wc.is_contiguous() or not wt.is_contiguous()):
+        raise RuntimeError("mtlora_amd: weight_cast takes a contiguous fp32 (N, K) master and contiguous (N, K), (K, N) copies of one dtype")
+    L.check(L.lib().mtlora_linear_weight_cast(L.ptr(w), N, K, L.dtype_code(wc), L.ptr(wc), L.ptr(wt), L.stream_ptr()),
+            "mtlora_linear_weight_cast")
+
+
+def weight_grad_torch(x: torch.Tensor, dys) -> torch.Tensor:
+    """portable definition of ``mtlora_linear_weight_grad``: dW (N, K) = (sum of the output gradients)^T x for the shared input ``x``
+    (..., K) of the dense product and the gradients ``dys`` (each (..., N), or None for an output that got none) of the 1 + T outputs,
+    which all add the same x W^T + b (reference lora.py:255-284).  Computed in the dtype of ``x``; at least one gradient must be given."""
+    x2 = x.reshape(-1, x.shape[-1])
+    G = None
+    for g in dys:
+        if g is not None:
+            g2 = g.reshape(x2.shape[0], -1).to(x2.dtype)
+            G = g2 if G is None else G + g2
+    if G is None:
+        raise ValueError("weight_grad_torch: every output gradient is None")
+    return G.t() @ x2
+
+
 _SG_BYTES = None
 
 
@@ -535,7 +563,7 @@ class MTLoRALinearFn(torch.autograd.Function):
             if meta.packed is None or meta.scale_dev is None:
                 raise RuntimeError("mtlora_amd: a layer with trainable scales runs from factors packed with mtlora_linear_pack_dev")
             ctx.factor_params += (scale_s_param, *rest[nx + 2 * T:nx + 2 * T + meta.n_scale_t])  # (their gradients: same stream)
-        ctx.bias_param = bias_master  # (a trainable bias with W frozen: its gradient runs with the factor gradients, see backward)
+        ctx.bias_param, ctx.weight_param = bias_master, W_master  # (trainable: their gradients run with the factor gradients, see backward)
         ctx.M = M
         return (ys, *yt, *acts)
 
@@ -596,17 +624,28 @@ class MTLoRALinearFn(torch.autograd.Function):
             for t in range(T):
                 if dy_t[t] is None:
                     dxt[t].zero_()
-        # `linear.bias` trains while W stays frozen (mark_only_lora_as_trainable bias='all', reference lora.py:606-624): every output adds
-        # the same x W^T + b, so db is the column sum of the output gradients in hand -- one mtlora_linear_bias_grad over the 1 + T
+        # `linear.bias` trains (mark_only_lora_as_trainable bias='all', reference lora.py:606-624; or FREEZE_PRETRAINED False): every output
+        # adds the same x W^T + b, so db is the column sum of the output gradients in hand -- one mtlora_linear_bias_grad over the 1 + T
         # sources, queued with the factor gradients.  A shape the entry refuses (N off the 16-byte vector grid) keeps the ATen form below
         db = db_scratch = None
         db_bytes = -1
-        if need[6] and not need[5]:
+        if need[6]:
             db_bytes = _size_query("bias_grad", lib.mtlora_linear_bias_grad_scratch_bytes, d)
         if db_bytes >= 0:
             db = torch.empty(meta.N, dtype=torch.float32, device=dev)
             db_scratch = torch.empty(db_bytes, dtype=torch.uint8, device=dev)
         db_cast = db is not None and ctx.bias_param.dtype != torch.float32  # (the cast reads db on THIS stream)
+        # `linear.weight` trains (MODEL.MTLORA.FREEZE_PRETRAINED False, reference main.py:254-262): dW = (sum of the output gradients)^T x
+        # with x the shared input the dense product read (x2: un-dropped, gelu(gate) behind a GELU gate) -- one
+        # mtlora_linear_weight_grad over the same sources, no (M, N) sum, queued with the factor gradients as well
+        dWn = dw_scratch = None
+        dw_bytes = -1
+        if need[5]:
+            dw_bytes = _size_query("weight_grad", lib.mtlora_linear_weight_grad_scratch_bytes, d)
+        if dw_bytes >= 0:
+            dWn = torch.empty((meta.N, meta.K), dtype=torch.float32, device=dev)
+            dw_scratch = torch.empty(dw_bytes, dtype=torch.uint8, device=dev)
+        dw_cast = dWn is not None and ctx.weight_param.dtype != torch.float32
 
         def launch(phase, stream_ptr):
             d.bwd_phase = phase
@@ -627,14 +666,24 @@ class MTLoRALinearFn(torch.autograd.Function):
             if db is not None and phase != 1:
                 L.check(lib.mtlora_linear_bias_grad(ctypes.byref(d), L.ptr(dy_s), L.ptr_array(dy_t), L.ptr(db), L.ptr(db_scratch), db_bytes,
                                                     stream_ptr), "mtlora_linear_bias_grad")
+            if dWn is not None and phase != 1:
+                L.check(lib.mtlora_linear_weight_grad(ctypes.byref(d), L.ptr(x2), L.ptr(dy_s), L.ptr_array(dy_t), L.ptr(dWn),
+                                                      L.ptr(dw_scratch), dw_bytes, stream_ptr), "mtlora_linear_weight_grad")
 
-        fgrads = [t for t in [dA_s, dB_s, *dA_t, *dB_t, d_sc, sg_scratch, db, db_scratch] if t is not None]
-        _run_factor_phases(ctx.factor_params if db is None else ctx.factor_params + (ctx.bias_param,), fgrads, M, dev, not db_cast, launch,
+        fgrads = [t for t in [dA_s, dB_s, *dA_t, *dB_t, d_sc, sg_scratch, db, db_scratch, dWn, dw_scratch] if t is not None]
+        side_params = ctx.factor_params
+        if db is not None:
+            side_params += (ctx.bias_param,)
+        if dWn is not None:
+            side_params += (ctx.weight_param,)
+        _run_factor_phases(side_params, fgrads, M, dev, not (db_cast or dw_cast), launch,
                            lambda: [x2, ctxbuf, scratch, *xt2, *fgrads] + [g for g in g2 if g is not None])
         dW = dbias = None
         if db is not None:
             dbias = db.to(ctx.bias_param.dtype) if db_cast else db
-        elif need[5] or need[6]:
+        if dWn is not None:
+            dW = dWn.to(ctx.weight_param.dtype) if dw_cast else dWn
+        if (need[5] and dWn is None) or (need[6] and db is None):
             # pretrained weight and / or bias left trainable (MTLORA.FREEZE_PRETRAINED False; mark_only_lora_as_trainable
             # bias='all' trains `linear.bias` with W frozen, reference lora.py:606-617): dense gradients outside the frozen-W
             # hot path.  Every output adds the same base  x W^T + b, so both see G = sum of the output gradients.
@@ -643,9 +692,9 @@ class MTLoRALinearFn(torch.autograd.Function):
                 if g is not None:
                     G = g.reshape(M, meta.N).float() if G is None else G + g.reshape(M, meta.N).float()
             if G is not None:
-                if need[5]:
+                if need[5] and dWn is None:
                     dW = G.t() @ x2.reshape(M, meta.K).float()
-                if need[6]:
+                if need[6] and db is None:
                     dbias = G.sum(0)
         dxo = dx if ctx.in_dtypes[0] == meta.dtype else dx.to(ctx.in_dtypes[0])
         dxto = [dxt[t] if ctx.in_dtypes[1 + t] == meta.dtype else dxt[t].to(ctx.in_dtypes[1 + t]) for t in range(nx)]

@@ -213,6 +213,8 @@ class MTLoRALinear(LoRALayer):
     def _weights(self, dtype: torch.dtype):
         w, b = self.linear.weight, self.linear.bias
         key = (dtype, w.device)
+        if w.requires_grad and w.dtype == torch.float32 and w.is_contiguous() and w.is_cuda:
+            return self._weights_trained(key)
         # only the bias trains (MTLORA.BIAS 'all' with W frozen): the W / W^T copies stay cached as for a frozen layer and just the fp32
         # bias operand follows the master -- the master itself where the kernels can read it (its address is the Parameter's, stable
         # for a captured graph), else the cached buffer, refreshed in place on every call
@@ -251,6 +253,28 @@ class MTLoRALinear(LoRALayer):
             with torch.no_grad():
                 hit[3].copy_(b.detach())
         return hit[1], hit[2], hit[3]
+
+    def _weights_trained(self, key):
+        """the copies of a TRAINABLE fp32 master on the device (MODEL.MTLORA.FREEZE_PRETRAINED False): one pair of buffers per
+        (dtype, device), as for a frozen weight, refilled from the master on EVERY call by one ``mtlora_linear_weight_cast`` launch.  No
+        version key decides here: FusedAdamW writes parameters through raw pointers and moves no ``_version``.  The addresses are
+        stable, so a captured graph follows the optimizer; the refill is a raw-pointer write as well, so a buffer that an earlier
+        call of the same step saved for backward keeps its version."""
+        w, b = self.linear.weight, self.linear.bias
+        hit = self._wcache.get(key)
+        if hit is not None and (hit[1].shape != w.shape or (hit[1].is_inference() and not torch.is_inference_mode_enabled())):
+            hit = None
+        with torch.no_grad():
+            if hit is None:
+                N, K = w.shape
+                wc = torch.empty((N, K), dtype=key[0], device=w.device)
+                wt = torch.empty((K, N), dtype=key[0], device=w.device)
+            else:
+                wc, wt = hit[1], hit[2]
+            Fn.weight_cast(w.detach(), wc, wt)
+            bf = None if b is None else b.detach().float().contiguous()
+        self._wcache[key] = (("trained", w.data_ptr()), wc, wt, bf)
+        return wc, wt, bf
 
     def invalidate_weight_cache(self) -> None:
         """mark the cached compute-dtype copies of ``linear.weight`` / ``linear.bias`` stale: the next forward re-fills the SAME

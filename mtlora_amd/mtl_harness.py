@@ -356,7 +356,10 @@ def build_model(img_size=448, tasks=("semseg", "normals", "sal", "human_parts"),
     lora_*_B ~ N(0, lora_b_std) so that the LoRA paths are numerically live, and the reference's
     trainable set (mark_only_lora_as_trainable with every freeze flag False, main.py:257-262).
     ``num_outputs`` overrides the channel count of named tasks (NYUD: ``{"semseg": 40}``).  ``bias`` is MODEL.MTLORA.BIAS
-    (reference config.py:309): 'all' also trains every ``*.bias`` of the backbone, the frozen linears' among them."""
+    (reference config.py:309): 'all' also trains every ``*.bias`` of the backbone, the frozen linears' among them.
+    ``freeze=False`` is the MODEL.MTLORA.FREEZE_PRETRAINED False model (reference config.py:317, main.py:254-262: nothing is marked, every
+    parameter trains -- the full-fine-tuning baseline); the ``linear.weight`` of its MTLoRALinear layers gets its gradient from
+    ``mtlora_linear_weight_grad`` and its compute-dtype copies from ``mtlora_linear_weight_cast``."""
     torch.manual_seed(seed)
     mt = mtlora_namespace(tasks, r_shared, r_task, n_stages=len(depths), **mt_over)
     bb = SwinTransformerMTLoRA(img_size=img_size, patch_size=4, in_chans=3, num_classes=0, embed_dim=embed_dim,
