@@ -88,6 +88,23 @@ __device__ __forceinline__ void hid_row_vals(const T* p, float (&f)[RR]) {
 __device__ __forceinline__ float hid_sel(uint32_t m, float a, float b) {
     return __builtin_bit_cast(float, (__builtin_bit_cast(uint32_t, a) & m) | (__builtin_bit_cast(uint32_t, b) & ~m));
 }
+// Non-finite values stay inside their task.  The four tasks of a group share MFMA operands and accumulators, each
+// product seeing "its" task through zeros in the OTHER operand -- and 0 * NaN = NaN.  So the operand that carries activations is cut
+// down to task t by a select (hid_task_cols), and a product whose activation operand cannot be cut (every output column reads it) runs on
+// a copy of the shared accumulator from which only the lanes of task t are taken back (hid_take).
+// the 8 rank columns 8 kg .. 8 kg + 7 of a P1 / Q2 image row (tasks 2 kg and 2 kg + 1, two words each): task t's words, zeros elsewhere
+template <int t>
+__device__ __forceinline__ u32x4 hid_task_cols(const u32x4& f, int kg) {
+    const bool mine = kg == (t >> 1);
+    if constexpr ((t & 1) == 0)
+        return u32x4{mine ? f[0] : 0u, mine ? f[1] : 0u, 0u, 0u};
+    else
+        return u32x4{0u, 0u, mine ? f[2] : 0u, mine ? f[3] : 0u};
+}
+__device__ __forceinline__ void hid_take(f32x16& acc, const f32x16& upd, bool mine) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = mine ? upd[e] : acc[e];
+}
 template <int NV>
 __device__ __forceinline__ float hid_wave_reduce(float (&v)[NV], int lane, int& idx) {
     static_assert(NV == 1 || NV == 2 || NV == 4 || NV == 8 || NV == 16, "power of two");
@@ -390,7 +407,7 @@ __global__ __launch_bounds__(HC * 2, HC == 384 ? 3 : (HC == 128 ? 4 : 2)) void k
             constexpr int t = decltype(tc)::value;
             const u32x2 tb = *reinterpret_cast<const u32x2*>(tabH + ((size_t)t * HC + cw + c) * 8);
             f32x16 h = hbD;
-            sp_mma1<T>(fp, hid_place<t>(tb, kg), h);
+            sp_mma1<T>(hid_task_cols<t>(fp, kg), hid_place<t>(tb, kg), h);
             u32x4 a0, a1;
 #pragma unroll
             for (int i4 = 0; i4 < 2; ++i4) {  // four pairs at a time (independent Horner chains)
@@ -414,8 +431,10 @@ __global__ __launch_bounds__(HC * 2, HC == 384 ? 3 : (HC == 128 ? 4 : 2)) void k
             hid_tr_frag(wimg, lane, f0, f1);
             const u32x4 fb0 = *reinterpret_cast<const u32x4*>(bq + brow[t] + (cw + 8 * hh) * 2);
             const u32x4 fb1 = *reinterpret_cast<const u32x4*>(bq + brow[t] + (cw + 16 + 8 * hh) * 2);
-            sp_mma1<T>(f0, fb0, accP);
-            sp_mma1<T>(f1, fb1, accP);
+            f32x16 upd = accP;
+            sp_mma1<T>(f0, fb0, upd);
+            sp_mma1<T>(f1, fb1, upd);
+            hid_take(accP, upd, (n >> 2) == t);
             __builtin_amdgcn_wave_barrier();
         };
         task(std::integral_constant<int, 0>{});
@@ -534,8 +553,8 @@ __global__ __launch_bounds__(HC * 2, HC == 384 ? 3 : (HC == 128 ? 3 : 2)) void k
             {   // (the row block's P1 / Q2 values as A operands: re-read per task, 16 bytes each, instead of 8 registers held across the block)
                 const u32x4 fp = *reinterpret_cast<const u32x4*>(pimg + hid_off16(m, kg));
                 const u32x4 fq = *reinterpret_cast<const u32x4*>(pimg + hid_off16(m, 2 + kg));
-                sp_mma1<T>(fp, hid_place<t>(tbh, kg), h);
-                sp_mma1<T>(fq, hid_place<t>(tbu, kg), u);
+                sp_mma1<T>(hid_task_cols<t>(fp, kg), hid_place<t>(tbh, kg), h);
+                sp_mma1<T>(hid_task_cols<t>(fq, kg), hid_place<t>(tbu, kg), u);
             }
             u32x4 d0, d1, x0, x1;
 #pragma unroll
@@ -572,15 +591,17 @@ __global__ __launch_bounds__(HC * 2, HC == 384 ? 3 : (HC == 128 ? 3 : 2)) void k
                     bP[i] = pq0[i] & tmP;
                     bQ[i] = pq0[i] & tmQ;
                 }
-                sp_mma1<T>(d0, bP, accF);
-                sp_mma1<T>(x0, bQ, accF);
+                f32x16 upd = accF;
+                sp_mma1<T>(d0, bP, upd);
+                sp_mma1<T>(x0, bQ, upd);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     bP[i] = pq1[i] & tmP;
                     bQ[i] = pq1[i] & tmQ;
                 }
-                sp_mma1<T>(d1, bP, accF);
-                sp_mma1<T>(x1, bQ, accF);
+                sp_mma1<T>(d1, bP, upd);
+                sp_mma1<T>(x1, bQ, upd);
+                hid_take(accF, upd, (tmP | tmQ) != 0u);
             }
             __builtin_amdgcn_sched_barrier(0);
             // column reduction Q1 += dH_t B1_t^T: rows along lanes through the wave's image
@@ -592,8 +613,10 @@ __global__ __launch_bounds__(HC * 2, HC == 384 ? 3 : (HC == 128 ? 3 : 2)) void k
             const int br = ((n >> 2) == t ? n : 16) * bs;
             const u32x4 fb0 = *reinterpret_cast<const u32x4*>(bq + br + (cw + 8 * hh) * 2);
             const u32x4 fb1 = *reinterpret_cast<const u32x4*>(bq + br + (cw + 16 + 8 * hh) * 2);
-            sp_mma1<T>(f0, fb0, accQ);
-            sp_mma1<T>(f1, fb1, accQ);
+            f32x16 upd = accQ;
+            sp_mma1<T>(f0, fb0, upd);
+            sp_mma1<T>(f1, fb1, upd);
+            hid_take(accQ, upd, (n >> 2) == t);
             __builtin_amdgcn_wave_barrier();
         };
         task(std::integral_constant<int, 0>{});

@@ -867,8 +867,8 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_ares(const S
 // kernel, and the Q pass); with G written next to Q the dX launch becomes single-source (dX = G W + keep .* (Q_s A_s), dX_t =
 // Q_t A_t) and k_sum disappears.  Work item = slab of 32 rows; per reduction chunk the wave walks the sources (one DMA chunk
 // each, same slot ring as k_sp_proj), adds the fragments into the chunk's fp32 sum and feeds that source's projection blocks
-// (shared: <= 2 blocks of 32 rank rows; the task segments lie in <= 4 blocks, the tasks of one block sharing its accumulator through
-// row-masked projection fragments).  Any number of task outputs up to MTLORA_MAX_TASKS.
+// (shared: <= 2 blocks of 32 rank rows; the task segments lie in <= 4 blocks, the tasks of one block sharing its accumulator, each
+// taking back its own rank rows by a select).  Any number of task outputs up to MTLORA_MAX_TASKS.
 // ------------------------------------------------------------------------------------------------
 constexpr int SP_PS_MAXT = 4;  // 32-row blocks the task segments may span (the tasks of a block share one accumulator)
 template <typename T, int CH, int NS>
@@ -987,18 +987,27 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 4) void k_sp_projsum(cons
                             if (nb > 1) sp_mma1<T>(*reinterpret_cast<const u32x4*>(wb + ((size_t)KST + ks) * 1024), xf[ks], accS[1]);
                         }
                     } else {
-                        // the tasks of one 32-row block share ONE accumulator: this task's projection rows only (the other rows of
-                        // the fragment are zeroed), so its product lands in its own rank rows and nowhere else
+                        // the tasks of one 32-row block share ONE accumulator.  The product runs on a COPY of it and only this task's
+                        // rank rows are taken back, by a select: a non-finite gradient of this task stays out of the other tasks' rows
+                        // (zeroed projection rows would not do: 0 * NaN = NaN).  Own rows accumulate in the same order as ever.
                         const int tb = blk_lo - tblk0;
-                        const bool mine = blk_lo * 32 + rl >= P->src[s].col_lo && blk_lo * 32 + rl < P->src[s].col_hi;
+                        const int c_lo = P->src[s].col_lo - blk_lo * 32 - 4 * h, c_hi = P->src[s].col_hi - blk_lo * 32 - 4 * h;
+                        f32x16 tmp;
 #pragma unroll
-                        for (int ks = 0; ks < G::KS; ++ks) {
-                            u32x4 wf = *reinterpret_cast<const u32x4*>(wb + (size_t)ks * 1024);
-                            wf = mine ? wf : u32x4{0u, 0u, 0u, 0u};
+                        for (int b = 0; b < SP_PS_MAXT; ++b)
+                            if (b == tb) tmp = accT[b];
 #pragma unroll
-                            for (int b = 0; b < SP_PS_MAXT; ++b)
-                                if (b == tb) sp_mma1<T>(wf, xf[ks], accT[b]);
-                        }
+                        for (int ks = 0; ks < G::KS; ++ks)
+                            sp_mma1<T>(*reinterpret_cast<const u32x4*>(wb + (size_t)ks * 1024), xf[ks], tmp);
+#pragma unroll
+                        for (int b = 0; b < SP_PS_MAXT; ++b)
+                            if (b == tb) {
+#pragma unroll
+                                for (int r = 0; r < 16; ++r) {  // (register r of lane (m, h): rank row (r & 3) + 8 (r >> 2) + 4 h)
+                                    const int row = (r & 3) + 8 * (r >> 2);
+                                    accT[b][r] = (row >= c_lo && row < c_hi) ? tmp[r] : accT[b][r];
+                                }
+                            }
                     }
                 }
             }
