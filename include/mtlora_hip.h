@@ -411,6 +411,26 @@ int mtlora_residual_layernorm_multi_bwd(int n, const void* const* dy, const void
                                         int64_t B, int64_t M, int64_t C, int x_dtype, int dy_dtype, void* scratch,
                                         int64_t scratch_bytes, void* stream);
 
+/* SHARED_MODE "addition" (reference lora.py:275-284): the LayerNorm of the SUM of the n task outputs of a linear layer, added to
+ * its pretrained output, one launch:
+ *   tot = sum_k y_t[k]  (fp32, in index order; never stored);  out = y + gamma (tot - mean) rstd + beta,  rounded to `dtype` once.
+ * y_t[k], y, out: (M, N) of `dtype` (fp32 / bf16 / fp16), contiguous, 16-byte aligned; out may be y.  mean / rstd: (M) fp32, saved
+ * for the backward.  n in 1 .. MTLORA_MAX_TASKS; N a multiple of 8 (16-bit) or 4 (fp32), up to 4096; M >= 0, and M == 0 returns
+ * MTLORA_OK without a launch and without looking at the pointers.  A non-finite value in a row of any y_t makes that row of out non-finite and no other. */
+int mtlora_sum_ln_add_fwd(int n, const void* const* y_t, const void* y, const float* gamma, const float* beta,
+                                 void* out, float* mean, float* rstd, int64_t M, int64_t N, float eps, int dtype, void* stream);
+/* Backward of mtlora_sum_ln_add_fwd (reference lora.py:275-284).  The gradient of y is dout itself: the caller passes it
+ * through, nothing is written for it.  d_tot = LayerNorm-backward(dout) with tot formed again from y_t, and
+ *   dy_t[k] = dy_t_addend[k] + d_tot
+ * where dy_t_addend[k] (the array or any entry may be NULL) is the gradient that reached y_t[k] from downstream, as dx_addend of
+ * mtlora_layernorm_bwd; dy_t[k] may be its addend.  dgamma / dbeta: (N) fp32, overwritten, deterministic (per-workgroup partials
+ * in `scratch`, summed in a fixed order: no atomics, no memset); M == 0 zero-fills them; both NULL (a frozen norm): not computed.  scratch: at least
+ * mtlora_sum_ln_add_bwd_scratch_bytes (-1: arguments outside the limits above). */
+int64_t mtlora_sum_ln_add_bwd_scratch_bytes(int n, int64_t M, int64_t N, int dtype);
+int mtlora_sum_ln_add_bwd(int n, const void* dout, const void* const* y_t, const float* gamma, const float* mean,
+                                 const float* rstd, const void* const* dy_t_addend, void* const* dy_t, float* dgamma,
+                                 float* dbeta, int64_t M, int64_t N, int dtype, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Training-mode BatchNorm + optional ReLU over a channels-last (R rows, C channels) matrix -- the decoder heads'
  * conv1x1 -> BatchNorm2d -> ReLU (seg_hrnet.py:498-526) on the (pixels, channels) matrix; replaces

@@ -220,6 +220,13 @@ _SIGS = {
                                               c_void_p, c_void_p]),
     "mtlora_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p]),
+    # SHARED_MODE "addition": out = y + LayerNorm(sum_k y_t[k])
+    "mtlora_sum_ln_add_fwd": (c_int, [c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_int64, c_int64, c_float, c_int, c_void_p]),
+    "mtlora_sum_ln_add_bwd_scratch_bytes": (c_int64, [c_int, c_int64, c_int64, c_int]),
+    "mtlora_sum_ln_add_bwd": (c_int, [c_int, c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_void_p, POINTER(c_void_p),
+                                             POINTER(c_void_p), c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64,
+                                             c_void_p]),
     "mtlora_bn_scratch_bytes": (c_int64, [c_int64, c_int64, c_int]),
     "mtlora_bn_relu_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64,

@@ -429,6 +429,8 @@ enum MtlProfKind {
     PK_NT_PLAIN_DX = 18,   // k_nt at rank 0: dX = dY W of the same
     PK_TN_PLAIN = 19,      // k_tn through mtlora_gemm_tn: narrow-output weight gradients of the callers
     PK_ACT_DROP = 20,      // k_act_dropout: drop(act(h)) over 1+T tensors, one direction     2 (fwd) or 3 (bwd) tensors of M*C
+    PK_SUM_LN_ADD_FWD = 21,  // k_sum_ln_add_fwd: n task outputs + y in, out                        (n + 2) tensors of M*N
+    PK_SUM_LN_ADD_BWD = 22,  // k_sum_ln_add_bwd (+ k_ln_reduce): dout, n y_t, addends in, n dy_t out
     PK_COUNT = 24
 };
 int mtl_prof_start(int kind, double alg_bytes, hipStream_t s, double s8d_bytes = 0.0, double flops = 0.0);

@@ -1,5 +1,5 @@
 // layernorm.hip -- host side of the LayerNorm family (kernels: ln.h): the ten mtlora_*layernorm* entries, the two scratch-size
-// queries and the two phased mtli_* entries of internal.h.
+// queries and the two phased mtli_* entries of internal.h; and the three mtlora_sum_ln_add_* entries (kernels: sum_ln_add.h).
 //
 // Every entry is  validate -> fill LnParams -> plan -> launch:
 //   validate   one helper per concern, always in this order (first failure wins):  ln_check status (dtypes, C) -> n range -> null
@@ -9,6 +9,7 @@
 //   launch     ln_run_fwd / ln_run_bwd through ln_dispatch, the one dtype x LPR x MAXV ladder
 #include "dispatch.h"
 #include "ln.h"
+#include "sum_ln_add.h"
 
 namespace {
 
@@ -315,9 +316,133 @@ int ln_streams_bwd(int n, const void* const* dy, const void* const* x, const flo
                       s);
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// SHARED_MODE "addition" (kernels: sum_ln_add.h): one tensor dtype, rows up to SNA_MAXV vectors per lane
+// ------------------------------------------------------------------------------------------------
+int sna_check(int n, int64_t M, int64_t N, int dtype) {
+    if (!mtl_dtype_in(dtype, MTL_DT_ALL)) return MTLORA_ERR_DTYPE;
+    const int ve = mtl_vec_elems(dtype);
+    if (M < 0 || N <= 0 || N % ve) return MTLORA_ERR_SHAPE;
+    if (mtl_ceil_div(N / ve, 64) > (dtype == MTLORA_F32 ? SNA_MAXV : LN_MAXV)) return MTLORA_ERR_UNSUPPORTED;
+    if (n < 1 || n > MTLORA_MAX_TASKS) return MTLORA_ERR_SHAPE;
+    return MTLORA_OK;
+}
+
+// f(MtlTag<T>, MtlInt<LPR>, MtlInt<MAXV>): MAXV 3 for the four LPR; 8, and 16 for fp32, at LPR 64 (pick_lpr leaves more than three
+// vectors per lane only there)
+template <typename F>
+void sna_dispatch(int dtype, const LnPlan& pl, F&& f) {
+    mtl_dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (pl.vpl > 3) {
+            if constexpr (sizeof(T) == 4) {
+                if (pl.vpl > LN_MAXV) {
+                    f(t, MtlInt<64>{}, MtlInt<SNA_MAXV>{});
+                    return;
+                }
+            }
+            f(t, MtlInt<64>{}, MtlInt<LN_MAXV>{});
+            return;
+        }
+        switch (pl.lpr) {
+            case 8: f(t, MtlInt<8>{}, MtlInt<3>{}); break;
+            case 16: f(t, MtlInt<16>{}, MtlInt<3>{}); break;
+            case 32: f(t, MtlInt<32>{}, MtlInt<3>{}); break;
+            default: f(t, MtlInt<64>{}, MtlInt<3>{}); break;
+        }
+    });
+}
+
+// workgroups of the backward launch = dgamma / dbeta partials; the forward takes up to twice as many
+int sna_grid_bwd(int64_t M, int64_t N, int dtype) { return ln_grid(M, ln_plan_row(N, dtype).lpr); }
+int64_t sna_part_bytes(int64_t M, int64_t N, int dtype) { return (int64_t)sna_grid_bwd(M, N, dtype) * 2 * N * 4; }
+
 }  // namespace
 
 extern "C" {
+
+/* SHARED_MODE "addition" (reference lora.py:275-284): out = y + LayerNorm(sum_k y_t[k]) in one launch, tot never stored. */
+int mtlora_sum_ln_add_fwd(int n, const void* const* y_t, const void* y, const float* gamma, const float* beta, void* out,
+                                 float* mean, float* rstd, int64_t M, int64_t N, float eps, int dtype, void* stream) {
+    int st = sna_check(n, M, N, dtype);
+    if (st != MTLORA_OK) return st;
+    if (M == 0) return MTLORA_OK;  // (before the pointers: tensors without rows have no address)
+    if (mtl_any_null({y, gamma, beta, out, mean, rstd}, n, {y_t})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({y, out, gamma, beta}, n, {y_t})) return MTLORA_ERR_ALIGN;
+    SnaParams p = {};
+    for (int k = 0; k < n; ++k) p.yt[k] = y_t[k];
+    p.y = y;
+    p.out = out;
+    p.gamma = gamma;
+    p.beta = beta;
+    p.mean = mean;
+    p.rstd = rstd;
+    p.M = M;
+    p.C = (int)N;
+    p.n = n;
+    p.eps = eps;
+    const LnPlan pl = ln_plan_row(N, dtype);
+    const int grid = ln_grid(M, pl.lpr, 256 * 8);
+    hipStream_t s = (hipStream_t)stream;
+    mtl_prof_tag("M%lld N%lld dt%d n%d", (long long)M, (long long)N, dtype, n);
+    MtlProfScope prof(PK_SUM_LN_ADD_FWD, (double)M * N * mtl_elem_size(dtype) * (n + 2), s);
+    sna_dispatch(dtype, pl, [&](auto t, auto lpr, auto maxv) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((k_sum_ln_add_fwd<T, decltype(lpr)::value, decltype(maxv)::value>), dim3((unsigned)grid), dim3(256), 0, s, p);
+    });
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
+int64_t mtlora_sum_ln_add_bwd_scratch_bytes(int n, int64_t M, int64_t N, int dtype) {
+    if (sna_check(n, M, N, dtype) != MTLORA_OK) return -1;
+    return sna_part_bytes(M, N, dtype) + 256;
+}
+
+/* backward of mtlora_sum_ln_add_fwd (reference lora.py:275-284): dy_t[k] = dy_t_addend[k] + LN-backward(dout) with tot formed
+ * again from y_t; the gradient of y is dout itself and is not written here.  dgamma / dbeta: partials in scratch, fixed-order reduce. */
+int mtlora_sum_ln_add_bwd(int n, const void* dout, const void* const* y_t, const float* gamma, const float* mean,
+                                 const float* rstd, const void* const* dy_t_addend, void* const* dy_t, float* dgamma, float* dbeta,
+                                 int64_t M, int64_t N, int dtype, void* scratch, int64_t scratch_bytes, void* stream) {
+    int st = sna_check(n, M, N, dtype);
+    if (st != MTLORA_OK) return st;
+    if ((dgamma == nullptr) != (dbeta == nullptr)) return MTLORA_ERR_NULL;  // both, or neither (a frozen lora_norm: no reduce)
+    hipStream_t s = (hipStream_t)stream;
+    if (M == 0) return dgamma ? ln_bwd_empty(dgamma, dbeta, N, s) : MTLORA_OK;  // (before the row tensors' pointers, as the forward)
+    if (mtl_any_null({dout, gamma, mean, rstd, scratch}, n, {y_t, mtl_arr(dy_t)})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({dout, gamma, scratch}, n, {y_t, dy_t_addend, mtl_arr(dy_t)})) return MTLORA_ERR_ALIGN;
+    if (scratch_bytes < sna_part_bytes(M, N, dtype)) return MTLORA_ERR_WORKSPACE;
+    SnaParams p = {};
+    int n_add = 0;
+    for (int k = 0; k < n; ++k) {
+        p.yt[k] = y_t[k];
+        p.add[k] = dy_t_addend ? dy_t_addend[k] : nullptr;
+        p.dyt[k] = dy_t[k];
+        n_add += p.add[k] ? 1 : 0;
+    }
+    p.y = dout;
+    p.gamma = gamma;
+    p.mean = const_cast<float*>(mean);
+    p.rstd = const_cast<float*>(rstd);
+    p.part = reinterpret_cast<float*>(scratch);
+    p.M = M;
+    p.C = (int)N;
+    p.n = n;
+    const LnPlan pl = ln_plan_row(N, dtype);
+    const int grid = sna_grid_bwd(M, N, dtype);
+    mtl_prof_tag("M%lld N%lld dt%d n%d add%d", (long long)M, (long long)N, dtype, n, n_add);
+    MtlProfScope prof(PK_SUM_LN_ADD_BWD, (double)M * N * mtl_elem_size(dtype) * (2 * n + 1 + n_add), s);
+    sna_dispatch(dtype, pl, [&](auto t, auto lpr, auto maxv) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((k_sum_ln_add_bwd<T, decltype(lpr)::value, decltype(maxv)::value>), dim3((unsigned)grid), dim3(256), 0, s, p);
+    });
+    if (dgamma)
+        hipLaunchKernelGGL(k_ln_reduce, dim3((unsigned)mtl_ceil_div(2 * N, 64)), dim3(64 * LN_RW), 0, s, (const float*)p.part, dgamma,
+                           dbeta, grid, (int)N);
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
 
 int64_t mtlora_layernorm_bwd_scratch_bytes(int64_t M, int64_t C, int x_dtype) {
     if (ln_check(M, C, x_dtype, MTLORA_F32) != MTLORA_OK) return -1;

@@ -187,6 +187,8 @@ extern "C" const char* mtlora_prof_kind_name(int kind) {
         case PK_NT_PLAIN_DX: return "k_nt:plain_dX";
         case PK_TN_PLAIN: return "k_tn:plain_dW";
         case PK_ACT_DROP: return "k_act_dropout";
+        case PK_SUM_LN_ADD_FWD: return "k_sum_ln_add_fwd";
+        case PK_SUM_LN_ADD_BWD: return "k_sum_ln_add_bwd";
         default: return "";
     }
 }

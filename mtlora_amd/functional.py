@@ -1427,6 +1427,77 @@ def layer_norm(mod: torch.nn.Module, x: torch.Tensor, feeds_linear: bool = True,
 
 
 # ----------------------------------------------------------------------------------------------
+# SHARED_MODE "addition" (reference lora.py:275-284): y + LayerNorm(sum of the task outputs), one kernel each way
+# ----------------------------------------------------------------------------------------------
+def sum_norm_add_torch(y: torch.Tensor, y_t, weight: torch.Tensor, bias: torch.Tensor, eps: float) -> torch.Tensor:
+    """The portable definition of ``mtlora_sum_ln_add_fwd``: ``y + LayerNorm(sum_k y_t[k])`` over the last dim, the sum taken
+    in index order, everything carried in fp32 (in fp64 for fp64 inputs) and rounded to ``y.dtype`` once.  Plain torch, any device,
+    differentiable."""
+    acc = torch.promote_types(y.dtype, torch.float32)
+    tot = y_t[0].to(acc)
+    for t in y_t[1:]:
+        tot = tot + t.to(acc)
+    mean = tot.mean(-1, keepdim=True)
+    d = tot - mean
+    rstd = torch.rsqrt((d * d).mean(-1, keepdim=True) + eps)
+    return (y.to(acc) + (d * rstd * weight.to(acc) + bias.to(acc))).to(y.dtype)
+
+
+def sum_norm_add_ok(mod: torch.nn.Module, y: torch.Tensor, y_t) -> bool:
+    """may ``SumNormAddFn`` take this call?  An affine ``nn.LayerNorm`` over the last dim, 1 .. MAX_TASKS task outputs, everything
+    on the device, contiguous, of one kernel dtype and shape, the width a multiple of a 16-byte vector and at most 4096"""
+    return (_ln_module_ok(mod, last_dim_only=True) and 1 <= len(y_t) <= L.MAX_TASKS and y.dim() >= 1 and y.is_contiguous()
+            and _ln_width_ok(y, multiple=_ln_vec(y), width=y.shape[-1], cap=(4096, 4096)) and mod.weight.is_cuda
+            and all(t.is_cuda and t.dtype == y.dtype and t.shape == y.shape and t.is_contiguous() for t in y_t))
+
+
+class SumNormAddFn(torch.autograd.Function):
+    """(out, y_t_0 .. y_t_n-1) = (y + LayerNorm(sum_k y_t_k), the task outputs passed through).  The task outputs leave the node
+    again because they feed the LayerNorm AND whatever consumes them downstream (a fork, as ``LayerNormFn(fork=True)``): the
+    backward kernel then forms  d y_t_k = g_k + LN-backward(g_out)  itself (``dy_t_addend``) instead of autograd's n full-size
+    gradient adds.  The gradient of ``y`` is ``g_out``, passed through.  Saves y_t, mean and rstd; ``tot`` is formed again.
+    args: y, weight, bias, eps, *y_t"""
+
+    @staticmethod
+    def forward(ctx, y, weight, bias, eps: float, *y_t):
+        L.require_gpu(y, weight, bias, *y_t)
+        n, N = len(y_t), y.shape[-1]
+        M = y.numel() // N
+        w, b = _ln_affine(weight, bias)
+        out = torch.empty_like(y)
+        mean, rstd = _ln_row_stats(M, y.device)
+        st = L.lib().mtlora_sum_ln_add_fwd(n, L.ptr_array(y_t), L.ptr(y), L.ptr(w), L.ptr(b), L.ptr(out), L.ptr(mean),
+                                                  L.ptr(rstd), M, N, float(eps), L.dtype_code(y), L.stream_ptr())
+        L.check(st, "mtlora_sum_ln_add_fwd")
+        ctx.save_for_backward(w, mean, rstd, *y_t)
+        ctx.MN = (M, N)
+        ctx.set_materialize_grads(False)
+        return (out,) + tuple(t.view_as(t) for t in y_t)
+
+    @staticmethod
+    def backward(ctx, g_out, *g_t):
+        w, mean, rstd, *y_t = ctx.saved_tensors
+        M, N = ctx.MN
+        n = len(y_t)
+        if g_out is None:  # the sum was not used: the task outputs' own gradients pass through
+            return (None, None, None, None) + tuple(g_t)
+        dt, shape = y_t[0].dtype, y_t[0].shape
+        dout = _canon_grad(g_out, shape, dt)
+        adds = [_canon_grad(g, shape, dt) for g in g_t]
+        want_affine = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        lib, code = L.lib(), L.dtype_code(dout)
+        sb = lib.mtlora_sum_ln_add_bwd_scratch_bytes(n, M, N, code)
+        scratch = _scratch(sb, dout.device, "sum + LayerNorm + add backward shape (n, M, N)", n, M, N)
+        dg = torch.empty(N, dtype=torch.float32, device=dout.device) if want_affine else None
+        db = torch.empty(N, dtype=torch.float32, device=dout.device) if want_affine else None
+        dys = [torch.empty(shape, dtype=dt, device=dout.device) for _ in range(n)]
+        st = lib.mtlora_sum_ln_add_bwd(n, L.ptr(dout), L.ptr_array(y_t), L.ptr(w), L.ptr(mean), L.ptr(rstd), L.ptr_array(adds),
+                                              L.ptr_array(dys), L.ptr(dg), L.ptr(db), M, N, code, L.ptr(scratch), sb, L.stream_ptr())
+        L.check(st, "mtlora_sum_ln_add_bwd")
+        return (g_out, dg if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None) + tuple(dys)
+
+
+# ----------------------------------------------------------------------------------------------
 # training-mode BatchNorm (+ReLU) over a channels-last (rows, C) matrix (decoder heads)
 # ----------------------------------------------------------------------------------------------
 class BatchNormReluFn(torch.autograd.Function):

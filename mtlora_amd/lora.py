@@ -462,7 +462,11 @@ class MTLoRALinear(LoRALayer):
             return y, None
         y_tasks = {t: outs[1 + i] for i, t in enumerate(tasks)} if tasks else None
         if self.shared_mode == "addition":  # lora.py:275-282: LayerNorm(sum_t y_t) added to the pretrained output
-            tot = torch.stack(list(y_tasks.values()), 0).sum(0).float()
+            ys = list(y_tasks.values())
+            if Fn.sum_norm_add_ok(self.lora_norm, y, ys):  # one kernel each way; no host read: graph-capturable
+                outs = Fn.SumNormAddFn.apply(y, self.lora_norm.weight, self.lora_norm.bias, self.lora_norm.eps, *ys)
+                return outs[0], {t: outs[1 + i] for i, t in enumerate(tasks)}
+            tot =torch.stack(list(y_tasks.values()), 0).sum(0).float()
             y = y + nn.functional.layer_norm(tot, (tot.shape[-1],), self.lora_norm.weight.float(),
                                              self.lora_norm.bias.float(), self.lora_norm.eps).to(y.dtype)
         return y, y_tasks
