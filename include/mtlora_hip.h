@@ -513,6 +513,24 @@ int mtlora_upsample_loss(int kind, const void* low, const float* label, const fl
                          int64_t B, int h, int w, int C, int scale, int dtype, float ignore_index, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Partially labelled batches (additive under ABI 12): the same launch with a per-sample validity flag.  `valid` is a device
+ * array of B bytes, non-zero = sample b carries a label for this task; V = the labelled samples.  The loss is the criterion
+ * above applied to the sub-batch (up[V], label[V]):
+ *   stat[0]  the statistic of mtlora_upsample_loss over the samples of V only (kind 2 with a constant weight: pos_weight)
+ *   stat[1]  |V| as a float -- kind 2 normalises by |V| H W; both words are what mtlora_label_stat_valid writes
+ * A tile of an unlabelled sample writes +0.0 to the elements of dlow it owns and 0 to its partial before it loads anything:
+ * neither low[b] nor label[b] of such a sample is read (any bits, NaN and Inf included, may stand there), every element of
+ * dlow is still written exactly once and the partial count is mtlora_upsample_loss_partials as before.  With V empty the
+ * partials sum to +0.0 and dlow is all zero bytes.  With every sample labelled, loss partials and dlow have the bits of
+ * mtlora_upsample_loss fed by mtlora_label_stat.  `valid` is read by the kernel, at launch or replay time: a captured launch
+ * follows the buffer's content.  Checks and return codes as mtlora_upsample_loss; valid == NULL with B > 0 is
+ * MTLORA_ERR_NULL.
+ * ------------------------------------------------------------------------------------------ */
+int mtlora_upsample_loss_valid(int kind, const void* low, const float* label, const unsigned char* valid, const float* stat,
+                               void* dlow, float* partials, int64_t B, int h, int w, int C, int scale, int dtype,
+                               float ignore_index, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Validation end of an epoch, fused (ABI v9): replaces, for one task and one batch, the final
  * F.interpolate(pred, img_size, mode="bilinear") of models/swin_mtl.py:245 TOGETHER WITH get_output
  * (evaluation/evaluate_utils.py:20-38), the task's meter update and the task's loss of main.py:439-528 validate().
@@ -593,6 +611,23 @@ int mtlora_linear_bias_grad(const mtlora_linear_desc* d, const void* dy_s, const
 int64_t mtlora_label_stat_scratch_bytes(int64_t n);
 int mtlora_label_stat(const float* label, int64_t n, int kind, float ignore_index, float* out, void* scratch,
                       int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * mtlora_label_stat over the labelled samples of a batch (additive under ABI 12; `stat` of mtlora_upsample_loss_valid).
+ * label: B samples of n_per_sample fp32 values each, contiguous; valid: B device bytes, non-zero = labelled, NULL = all.
+ *   out[0]  kind 0: number of elements != ignore_index among the labelled samples; kind 1: mean(1 - (label >= 0.5)) over
+ *           them; kind 2: 0 -- only the count below is wanted (a constant pos_weight), `label` is not read and may be NULL.
+ *           0 when no sample is labelled.  With valid == NULL or all non-zero: the bits of mtlora_label_stat(label, B * n_per_sample).
+ *   out[1]  the number of labelled samples, as a float
+ * Two launches (kind 2: the second only): per-sample, per-block counts, then a fixed-order combine that skips the partials
+ * of unlabelled samples; the labels of an unlabelled sample are never read.  No atomics, no memset; `valid` is read on the
+ * device.  out: 2 floats, 4-byte aligned.  MTLORA_ERR_UNSUPPORTED: kind outside 0..2; SHAPE: B <= 0, n_per_sample <= 0 or
+ * >= 2^31, B >= 2^21; NULL: out, scratch, or label with kind != 2; ALIGN: label or scratch not 16-byte aligned; WORKSPACE:
+ * scratch_bytes below mtlora_label_stat_valid_scratch_bytes(B, n_per_sample) (-1 for a shape the entry rejects).
+ * ------------------------------------------------------------------------------------------ */
+int64_t mtlora_label_stat_valid_scratch_bytes(int64_t B, int64_t n_per_sample);
+int mtlora_label_stat_valid(const float* label, const unsigned char* valid, int64_t B, int64_t n_per_sample, int kind,
+                            float ignore_index, float* out, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Full fine-tuning (additive under ABI 12) -- MODEL.MTLORA.FREEZE_PRETRAINED False (reference config.py:317): main.py:254-262 then

@@ -258,6 +258,10 @@ _SIGS = {
     "mtlora_label_stat": (c_int, [c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
     "mtlora_upsample_loss": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                      c_int, c_int, ctypes.c_float, c_void_p]),
+    "mtlora_label_stat_valid_scratch_bytes": (c_int64, [c_int64, c_int64]),
+    "mtlora_label_stat_valid": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mtlora_upsample_loss_valid": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                           c_int, c_int, c_int, ctypes.c_float, c_void_p]),
     "mtlora_upsample_metrics_sizes": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "mtlora_upsample_metrics": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                         c_int, c_int, ctypes.c_float, c_void_p]),

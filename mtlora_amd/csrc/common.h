@@ -431,6 +431,7 @@ enum MtlProfKind {
     PK_ACT_DROP = 20,      // k_act_dropout: drop(act(h)) over 1+T tensors, one direction     2 (fwd) or 3 (bwd) tensors of M*C
     PK_SUM_LN_ADD_FWD = 21,  // k_sum_ln_add_fwd: n task outputs + y in, out                        (n + 2) tensors of M*N
     PK_SUM_LN_ADD_BWD = 22,  // k_sum_ln_add_bwd (+ k_ln_reduce): dout, n y_t, addends in, n dy_t out
+    PK_LABEL_STAT_VALID = 23,  // k_label_stat_valid_part / _combine: label statistic over the labelled samples of a batch
     PK_COUNT = 24
 };
 int mtl_prof_start(int kind, double alg_bytes, hipStream_t s, double s8d_bytes = 0.0, double flops = 0.0);

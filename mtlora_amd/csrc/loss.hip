@@ -31,6 +31,9 @@
 //   kind 3  DepthLoss l1           (:132-148)                   |up - label| over label != ignore, mean over valid pixels
 // (the per-pixel formulas live in up_pixel.h, shared with metrics.hip)
 // Label-only statistics (valid count, mask sum, w) come from the caller (they do not depend on the prediction).
+// Partially labelled batches (mtlora_upsample_loss_valid): a byte per sample says whether it carries a label.  A tile belongs
+// to one sample, so the decision is wave-uniform: a tile of an unlabelled sample zeroes the part of dlow it owns and leaves before
+// it loads anything of that sample; the statistics (reduce.hip, mtlora_label_stat_valid) run over the labelled samples only.
 #include "dispatch.h"
 #include "up_pixel.h"
 
@@ -42,6 +45,7 @@ struct UpLossParams {
     const float* stat;   // device scalars, see above
     void* dlow;          // (B, h, w, C)  d loss / d low  (same dtype as low)
     float* part;         // [gridDim.x]   per-workgroup share of the (already normalised) loss value
+    const unsigned char* valid;  // (B) non-zero: the sample has a label; NULL: all have (mtlora_upsample_loss)
     int B, h, w, C, S;
     float ignore;
 };
@@ -83,6 +87,19 @@ __global__ __launch_bounds__(64) void k_up_loss(const UpLossParams p) {
     const T* low = reinterpret_cast<const T*>(p.low);
     const float rs = (float)p.h / (float)H;  // in / out, exactly 1/S
 
+    // a sample without a label (wave-uniform: b comes from blockIdx): the tile writes +0 to the region of dlow it owns -- the
+    // rows and columns emit() stores below -- and 0 to its partial; neither low[b] nor label[b] is loaded
+    if (p.valid != nullptr && __builtin_amdgcn_readfirstlane((int)p.valid[b]) == 0) {
+        T* dz = reinterpret_cast<T*>(p.dlow);
+        for (int it = lane; it < TR * TQ * C; it += 64) {
+            const int r = it / (TQ * C), rem = it - r * (TQ * C);
+            const int ql = rem / C, c = rem - ql * C;
+            if (qy0 + r < p.h && qx0 + ql < p.w) dz[(((int64_t)b * p.h + qy0 + r) * p.w + qx0 + ql) * C + c] = mtl_from_f32<T>(0.f);
+        }
+        if (lane == 0) p.part[blockIdx.x] = 0.f;
+        return;
+    }
+
     for (int i = lane; i < (TR + 2) * (TQ + 2) * C; i += 64) {
         const int pix = i / C, c = i - pix * C;
         const int py = pix / (TQ + 2), px = pix - py * (TQ + 2);
@@ -97,15 +114,18 @@ __global__ __launch_bounds__(64) void k_up_loss(const UpLossParams p) {
         const int ox = S * (qx0 + ql) - hs + k;
         wxt[i] = (ox >= 0 && ox < W && qx0 + ql < p.w) ? up_weight(ox, qx0 + ql, rs, p.w) : 0.f;
     }
-    float norm;  // 1 / normaliser of the mean
+    // 1 / normaliser of the mean.  With `valid`, stat = {statistic over the labelled samples, their number |V|}: kind 2 takes |V|
+    // where it took B (the same expression: all labelled gives the same bits), and kind 0 guards a count of 0 (a valid pixel,
+    // the only user of norm, implies a count > 0; kinds 1 and 3 are guarded already)
+    float norm;
     if (KIND == 0)
-        norm = 1.f / p.stat[0];
+        norm = (p.valid != nullptr && p.stat[0] == 0.f) ? 0.f : 1.f / p.stat[0];
     else if (KIND == 1)
         norm = 1.f / fmaxf(p.stat[0], 1e-6f);
     else if (KIND == 3)
         norm = 1.f / fmaxf(p.stat[0], 1.f);
     else
-        norm = 1.f / ((float)p.B * (float)H * (float)W);
+        norm = 1.f / ((p.valid != nullptr ? p.stat[1] : (float)p.B) * (float)H * (float)W);
     const float wneg = KIND == 2 ? p.stat[0] : 0.f;
 
     // this lane's output column
@@ -295,12 +315,14 @@ int64_t mtlora_upsample_loss_partials(int64_t B, int h, int w, int scale) {
     return B * (int64_t)t.tiles_y * t.tiles_x;
 }
 
-int mtlora_upsample_loss(int kind, const void* low, const float* label, const float* stat, void* dlow, float* partials,
-                         int64_t B, int h, int w, int C, int scale, int dtype, float ignore_index, void* stream) {
+// the launch behind both entries: mtlora_upsample_loss hands in valid == NULL (need_valid false), the kernel's all-labelled path
+static int up_loss_launch(int kind, const void* low, const float* label, const unsigned char* valid, bool need_valid,
+                          const float* stat, void* dlow, float* partials, int64_t B, int h, int w, int C, int scale, int dtype,
+                          float ignore_index, void* stream) {
     if (B < 0 || h <= 0 || w <= 0 || C <= 0 || scale <= 0) return MTLORA_ERR_SHAPE;
     if (!mtl_dtype_in(dtype, MTL_DT_F32_BF16)) return MTLORA_ERR_DTYPE;
     if (B == 0) return MTLORA_OK;
-    if (mtl_any_null({low, label, stat, dlow, partials})) return MTLORA_ERR_NULL;
+    if (mtl_any_null({low, label, stat, dlow, partials}) || (need_valid && !valid)) return MTLORA_ERR_NULL;
     if (scale > 32) return MTLORA_ERR_UNSUPPORTED;
     const int64_t blocks = mtlora_upsample_loss_partials(B, h, w, scale);
     if (blocks >= ((int64_t)1 << 31) || (int64_t)h * scale * (int64_t)w * scale >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
@@ -310,6 +332,7 @@ int mtlora_upsample_loss(int kind, const void* low, const float* label, const fl
     p.stat = stat;
     p.dlow = dlow;
     p.part = partials;
+    p.valid = valid;
     p.B = (int)B;
     p.h = h;
     p.w = w;
@@ -317,12 +340,24 @@ int mtlora_upsample_loss(int kind, const void* low, const float* label, const fl
     p.S = scale;
     p.ignore = ignore_index;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (valid) mtl_prof_tag("valid k%d B%lld h%d w%d C%d S%d", kind, (long long)B, h, w, C, scale);
     MtlProfScope prof(PK_LOSS, (double)B * h * w * C * 2.0 * mtl_elem_size(dtype) +
                                    (double)B * h * scale * w * scale * 4.0 * (kind == 1 ? C : 1), s);
     const int rc = mtl_dispatch_f32_bf16(dtype, [&](auto t) { return dispatch_up<typename decltype(t)::type>(kind, p, blocks, s); });
     if (rc != MTLORA_OK) return rc;
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
+}
+
+int mtlora_upsample_loss(int kind, const void* low, const float* label, const float* stat, void* dlow, float* partials,
+                         int64_t B, int h, int w, int C, int scale, int dtype, float ignore_index, void* stream) {
+    return up_loss_launch(kind, low, label, nullptr, false, stat, dlow, partials, B, h, w, C, scale, dtype, ignore_index, stream);
+}
+
+int mtlora_upsample_loss_valid(int kind, const void* low, const float* label, const unsigned char* valid, const float* stat,
+                               void* dlow, float* partials, int64_t B, int h, int w, int C, int scale, int dtype,
+                               float ignore_index, void* stream) {
+    return up_loss_launch(kind, low, label, valid, true, stat, dlow, partials, B, h, w, C, scale, dtype, ignore_index, stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,8 @@
 //                                                                  up to 1 + T sources, no (M, N) intermediate
 //   mtlora_label_stat   kind 0: #{ lab != ignore }                 valid-pixel count / mask sum of mtl_loss_schemes.py:22-39,
 //                       kind 1: mean(1 - (lab >= 0.5))             :162-220; class balance w of :42-89
+//   mtlora_label_stat_valid  the same over the labelled samples of a batch (a byte per sample), plus their number: the `stat`
+//                       of mtlora_upsample_loss_valid; an unlabelled sample's labels are not read
 #include "dispatch.h"
 
 namespace {
@@ -142,6 +144,69 @@ __global__ __launch_bounds__(256) void k_label_stat_combine(const float* part, f
     if (threadIdx.x == 0) out[0] = (float)(sm[0] * scale);
 }
 
+// label statistics over the LABELLED samples of a batch (valid[b] != 0; NULL: all), stage 1: block (b, j) = blockIdx.x / g,
+// blockIdx.x % g counts its share of sample b into part[b * g + j].  A block of an unlabelled sample returns before it reads
+// anything of that sample and leaves its partial unwritten: stage 2 does not read it.  Samples whose first element is not
+// 16-byte aligned (n_per_sample % 4 != 0) are walked element by element; counts are integers, so the walk does not matter.
+__global__ __launch_bounds__(256) void k_label_stat_valid_part(const float* lab, const unsigned char* valid, int64_t nps, int g, int kind,
+                                                               float ignore, float* part) {
+    __shared__ float sm[256];
+    const int b = blockIdx.x / g, j = blockIdx.x - b * g;
+    if (valid != nullptr && valid[b] == 0) return;  // (block-uniform)
+    const float* x = lab + (int64_t)b * nps;
+    float c = 0.f;
+    if ((nps & 3) == 0) {
+        const int64_t nv = nps >> 2;
+        for (int64_t i = (int64_t)j * 256 + threadIdx.x; i < nv; i += (int64_t)g * 256) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(x + i * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) c += kind == 0 ? (v[e] != ignore ? 1.f : 0.f) : (v[e] >= 0.5f ? 0.f : 1.f);
+        }
+    } else {
+        for (int64_t i = (int64_t)j * 256 + threadIdx.x; i < nps; i += (int64_t)g * 256) {
+            const float v = x[i];
+            c += kind == 0 ? (v != ignore ? 1.f : 0.f) : (v >= 0.5f ? 0.f : 1.f);
+        }
+    }
+    sm[threadIdx.x] = c;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = sm[0];
+}
+
+// stage 2: the labelled samples' partials (exact integers) in double, in a fixed order, and their number |V|:
+// out[0] = kind 0: the count; kind 1: count / (|V| n_per_sample), the mean, formed as k_label_stat_combine forms count / n
+// (all labelled: the same bits); kind 2: 0 (nothing was counted).  0 when no sample is labelled.  out[1] = |V|.
+__global__ __launch_bounds__(256) void k_label_stat_valid_combine(const float* part, const unsigned char* valid, float* out, int B, int g,
+                                                                  int64_t nps, int kind) {
+    __shared__ double sm[256];
+    __shared__ int sv[256];
+    double t = 0.0;
+    int nv = 0;
+    if (kind != 2)
+        for (int i = threadIdx.x; i < B * g; i += 256)
+            if (valid == nullptr || valid[i / g] != 0) t += (double)part[i];
+    for (int b = threadIdx.x; b < B; b += 256) nv += (valid == nullptr || valid[b] != 0) ? 1 : 0;
+    sm[threadIdx.x] = t;
+    sv[threadIdx.x] = nv;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+            sm[threadIdx.x] += sm[threadIdx.x + s];
+            sv[threadIdx.x] += sv[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double scale = kind == 0 ? 1.0 : (sv[0] > 0 ? 1.0 / (double)((int64_t)sv[0] * nps) : 0.0);
+        out[0] = (float)(sm[0] * scale);
+        out[1] = (float)sv[0];
+    }
+}
+
 int rd_blocks(int64_t work_items) {
     int64_t g = mtl_ceil_div(work_items, 256 * 8);
     if (g > RD_MAXBLK) g = RD_MAXBLK;
@@ -229,6 +294,44 @@ int mtlora_label_stat(const float* label, int64_t n, int kind, float ignore_inde
     float* part = reinterpret_cast<float*>(scratch);
     hipLaunchKernelGGL(k_label_stat_part, dim3((unsigned)g), dim3(256), 0, s, label, n, kind, ignore_index, part);
     hipLaunchKernelGGL(k_label_stat_combine, dim3(1), dim3(256), 0, s, (const float*)part, out, g, kind == 0 ? 1.0 : 1.0 / (double)n);
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
+// blocks per sample of mtlora_label_stat_valid (a block sees < 2^24 elements: n_per_sample < 2^31)
+static int label_stat_valid_blocks(int64_t n_per_sample) { return rd_blocks(n_per_sample / 4 + 1); }
+
+static bool label_stat_valid_shape_ok(int64_t B, int64_t n_per_sample) {
+    return B > 0 && n_per_sample > 0 && n_per_sample < ((int64_t)1 << 31) && B * (int64_t)RD_MAXBLK < ((int64_t)1 << 31);
+}
+
+int64_t mtlora_label_stat_valid_scratch_bytes(int64_t B, int64_t n_per_sample) {
+    if (!label_stat_valid_shape_ok(B, n_per_sample)) return -1;
+    return B * (int64_t)label_stat_valid_blocks(n_per_sample) * 4 + 256;
+}
+
+int mtlora_label_stat_valid(const float* label, const unsigned char* valid, int64_t B, int64_t n_per_sample, int kind,
+                            float ignore_index, float* out, void* scratch, int64_t scratch_bytes, void* stream) {
+    if (kind != 0 && kind != 1 && kind != 2) return MTLORA_ERR_UNSUPPORTED;
+    if (!label_stat_valid_shape_ok(B, n_per_sample)) return MTLORA_ERR_SHAPE;
+    if (mtl_any_null({out, scratch}) || (kind != 2 && !label)) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({label, scratch}) || ((uintptr_t)out & 3)) return MTLORA_ERR_ALIGN;
+    if (scratch_bytes < mtlora_label_stat_valid_scratch_bytes(B, n_per_sample)) return MTLORA_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int g = label_stat_valid_blocks(n_per_sample);
+    float* part = reinterpret_cast<float*>(scratch);
+    mtl_prof_tag("part B%lld n%lld k%d g%d", (long long)B, (long long)n_per_sample, kind, g);
+    if (kind != 2) {
+        MtlProfScope prof(PK_LABEL_STAT_VALID, (double)B * n_per_sample * 4.0, s);
+        hipLaunchKernelGGL(k_label_stat_valid_part, dim3((unsigned)(B * g)), dim3(256), 0, s, label, valid, n_per_sample, g, kind,
+                           ignore_index, part);
+    }
+    {
+        mtl_prof_tag("combine B%lld k%d g%d", (long long)B, kind, g);
+        MtlProfScope prof(PK_LABEL_STAT_VALID, (double)B * g * 4.0, s);
+        hipLaunchKernelGGL(k_label_stat_valid_combine, dim3(1), dim3(256), 0, s, (const float*)part, valid, out, (int)B, g, n_per_sample,
+                           kind);
+    }
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
 }

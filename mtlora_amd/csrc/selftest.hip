@@ -189,6 +189,7 @@ extern "C" const char* mtlora_prof_kind_name(int kind) {
         case PK_ACT_DROP: return "k_act_dropout";
         case PK_SUM_LN_ADD_FWD: return "k_sum_ln_add_fwd";
         case PK_SUM_LN_ADD_BWD: return "k_sum_ln_add_bwd";
+        case PK_LABEL_STAT_VALID: return "k_label_stat_valid";
         default: return "";
     }
 }

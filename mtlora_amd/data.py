@@ -16,6 +16,8 @@ Wire format.  A host batch is a dict of contiguous CPU tensors (or numpy arrays)
     ``normals``                          fp32 or fp16 (B, H, W, 3)    after ``FixedResize``'s renormalisation
     ``depth``                            fp32 (B, H, W)
     ``flip`` (optional)                  uint8 (B,)                   1 = mirror this sample
+    ``valid`` (optional)                 {task: uint8 (B,)}           non-zero = the sample carries a label for that task; a task
+                                                                      without an entry is labelled everywhere
 
 The synthetic tasks ``t0`` .. ``t7`` (mtl_harness.task_kind) use the normals format.  Semantics, per sample, in
 this order -- ``prepare_batch_torch`` below is the definition, ``prepare_batch`` (csrc/ingest.hip) the implementation:
@@ -26,6 +28,12 @@ this order -- ``prepare_batch_torch`` below is the definition, ``prepare_batch``
   3. ToTensor: image (B, 3, H, W) fp32 ``u8 / 255``; labels (B, C, H, W) fp32 (the reference: float64; every value here
      is an fp32 or narrower number, so fp32 holds it exactly -- the dtype train_step / validate_step take).
   4. Normalize: ``(x - mean[c]) / std[c]`` in fp32.
+
+Partially labelled batches.  With ``valid``, the label plane of a sample flagged 0 still travels and is still ingested (the
+kernels walk whole tensors), but its content is undefined, on the wire and after the ingest: the fused losses never read it
+(``functional.UpsampleLossFn``).  ``prepare_batch`` / ``prepare_batch_torch`` / ``DeviceLoader`` hand the flags through as a third
+value, ``(images, targets, valid)``, only when the batch carries them.  ``merge_wire_batches`` builds such a batch from two
+datasets with different task sets (PASCAL-Context + NYUD).  The flip does not touch the flags (they are per sample).
 
 Resampling (ScaleNRotate, FixedResize) runs on the device as well, in front of the ingest: the loader workers ship the
 decoded, un-resampled sample and the GPU produces the wire-format batch above.
@@ -91,6 +99,20 @@ def image_table(mean: Sequence[float] = IMAGENET_MEAN, std: Sequence[float] = IM
     return ((v - m) / s).contiguous()
 
 
+def _check_valid(batch: Mapping, tasks: Sequence[str], B: int, what: str) -> None:
+    v = batch.get("valid")
+    if v is None:
+        return
+    if not isinstance(v, Mapping):
+        raise ValueError(f"{what}: valid must be a dict {{task: uint8 (B,)}}, got {type(v).__name__}")
+    for t, x in v.items():
+        if t not in tasks:
+            raise ValueError(f"{what}: valid names {t!r}, which is not one of the tasks {list(tasks)}")
+        x = _as_tensor(x)
+        if x.dtype != torch.uint8 or tuple(x.shape) != (B,):
+            raise ValueError(f"{what}: valid[{t!r}] must be uint8 (B,) with B = {B}, got {x.dtype} {tuple(x.shape)}")
+
+
 def check_wire_batch(batch: Mapping, tasks: Sequence[str]) -> Tuple[int, int, int]:
     """shapes and dtypes of a wire-format batch (see the module docstring); returns (B, H, W)"""
     if "image" not in batch:
@@ -121,6 +143,7 @@ def check_wire_batch(batch: Mapping, tasks: Sequence[str]) -> Tuple[int, int, in
         f = _as_tensor(f)
         if f.dtype != torch.uint8 or tuple(f.shape) != (B,):
             raise ValueError(f"wire batch: flip must be uint8 (B,), got {f.dtype} {tuple(f.shape)}")
+    _check_valid(batch, tasks, B, "wire batch")
     return B, H, W
 
 
@@ -128,7 +151,8 @@ def prepare_batch_torch(batch: Mapping, tasks: Sequence[str], mean: Sequence[flo
                         std: Sequence[float] = IMAGENET_STD):
     """The semantics of the ingest, in plain torch on whatever device the batch lives on: ``(images, targets)`` as
     ``RandomHorizontalFlip`` (for the samples ``batch["flip"]`` flags), ``AddIgnoreRegions``, ``ToTensor`` and ``Normalize``
-    give them, labels in fp32.  The documented definition and the tests' oracle; inputs are not modified."""
+    give them, labels in fp32.  The documented definition and the tests' oracle; inputs are not modified.  A batch with
+    ``valid`` returns ``(images, targets, valid)``, the flags as uint8 tensors on the batch's device."""
     B, H, W = check_wire_batch(batch, tasks)
     img = _as_tensor(batch["image"])
     dev = img.device
@@ -163,6 +187,8 @@ def prepare_batch_torch(batch: Mapping, tasks: Sequence[str], mean: Sequence[flo
                 lab = torch.where(empty, torch.full_like(lab, 255.0), lab)
             lab = lab.unsqueeze(1)
         targets[t] = lab.contiguous()
+    if batch.get("valid") is not None:
+        return images, targets, {t: _as_tensor(v).to(dev) for t, v in batch["valid"].items()}
     return images, targets
 
 
@@ -184,7 +210,8 @@ def prepare_batch(batch: Mapping, tasks: Sequence[str], flip: Optional[torch.Ten
                   mean: Sequence[float] = IMAGENET_MEAN, std: Sequence[float] = IMAGENET_STD):
     """``prepare_batch_torch`` of a wire-format batch that already lives on the GPU, as ONE library call on the current stream
     (csrc/ingest.hip: at most three launches, no host sync).  ``flip``: uint8 (B,) on the device (default: ``batch["flip"]``
-    if present, else no flips).  Returns ``(images, targets)``; GPU only, there is no CPU fallback."""
+    if present, else no flips).  Returns ``(images, targets)`` -- ``(images, targets, valid)`` for a batch with ``valid``, the flags as
+    uint8 tensors on the device --; GPU only, there is no CPU fallback."""
     from . import functional as Fn
     B, H, W = check_wire_batch(batch, tasks)
     img = batch["image"]
@@ -197,14 +224,57 @@ def prepare_batch(batch: Mapping, tasks: Sequence[str], flip: Optional[torch.Ten
         raise RuntimeError(f"mtlora_amd: prepare_batch takes at most {L.INGEST_MAX_JOBS - 1} tasks per call")
     jobs = [("image", img)] + [(_JOB_KIND[task_kind(t)], batch[t]) for t in tasks]
     outs = Fn.ingest_batch(jobs, flip=flip, lut=_device_table(mean, std, img.device))
+    if batch.get("valid") is not None:
+        return outs[0], dict(zip(tasks, outs[1:])), {t: _as_tensor(v).to(img.device) for t, v in batch["valid"].items()}
     return outs[0], dict(zip(tasks, outs[1:]))
 
 
+def merge_wire_batches(a: Mapping, tasks_a: Sequence[str], b: Mapping, tasks_b: Sequence[str]):
+    """One wire batch over the union of two task sets from two wire batches of the same image size (a PASCAL-Context batch and
+    an NYUD batch): the samples of ``a`` first, then those of ``b``.  A task that only one side has gets a label plane for the
+    other side's samples that is allocated and NOT defined (``torch.empty``), and ``valid[task]`` flags those samples 0; a task
+    both sides have is labelled everywhere (flags given by either side are kept).  ``flip`` is concatenated when either side has
+    one (0 for the other).  Returns ``(batch, tasks)``, the union in the order of ``tasks_a``, then the new ones of ``tasks_b``.
+    Host or device tensors, both batches on the same device."""
+    Ba, H, W = check_wire_batch(a, tasks_a)
+    Bb, Hb, Wb = check_wire_batch(b, tasks_b)
+    if (H, W) != (Hb, Wb):
+        raise ValueError(f"merge_wire_batches: image sizes differ, {(H, W)} and {(Hb, Wb)}")
+    tasks = list(tasks_a) + [t for t in tasks_b if t not in tasks_a]
+    ia, ib = _as_tensor(a["image"]), _as_tensor(b["image"])
+    out = {"image": torch.cat([ia, ib], 0)}
+    dev = ia.device
+    va, vb = a.get("valid") or {}, b.get("valid") or {}
+    valid = {}
+    for t in tasks:
+        xa = _as_tensor(a[t]) if t in tasks_a else None
+        xb = _as_tensor(b[t]) if t in tasks_b else None
+        if xa is not None and xb is not None and xa.dtype != xb.dtype:  # (normals: fp32 on one side, fp16 on the other)
+            xa, xb = xa.to(torch.float32), xb.to(torch.float32)
+        if xa is None:
+            xa = torch.empty((Ba,) + tuple(xb.shape[1:]), dtype=xb.dtype, device=dev)
+        if xb is None:
+            xb = torch.empty((Bb,) + tuple(xa.shape[1:]), dtype=xa.dtype, device=dev)
+        out[t] = torch.cat([xa, xb], 0)
+        fa = _as_tensor(va[t]).to(dev) if t in va else torch.full((Ba,), int(t in tasks_a), dtype=torch.uint8, device=dev)
+        fb = _as_tensor(vb[t]).to(dev) if t in vb else torch.full((Bb,), int(t in tasks_b), dtype=torch.uint8, device=dev)
+        valid[t] = torch.cat([fa, fb], 0)
+    out["valid"] = valid
+    if a.get("flip") is not None or b.get("flip") is not None:
+        fl = [(_as_tensor(x["flip"]).to(dev) if x.get("flip") is not None else torch.zeros(n, dtype=torch.uint8, device=dev))
+              for x, n in ((a, Ba), (b, Bb))]
+        out["flip"] = torch.cat(fl, 0)
+    return out, tasks
+
+
 def synthetic_wire_batch(B: int, S: int, tasks: Sequence[str], seed: int, num_outputs: Optional[Mapping[str, int]] = None,
-                         normals_dtype: torch.dtype = torch.float32) -> Dict[str, torch.Tensor]:
+                         normals_dtype: torch.dtype = torch.float32,
+                         valid: Optional[Mapping[str, Sequence[int]]] = None) -> Dict[str, torch.Tensor]:
     """a host batch in wire format with the label distributions of ``mtl_harness.synthetic_batch`` (class ids with 5 % 255, sal
     Bernoulli(.3), unit normals with 5 % ignored pixels, depth uniform in [0, 10), edge Bernoulli(.1)) and a uniform uint8
-    image.  Ignored normals travel as (0, 0, 0), the value ``AddIgnoreRegions`` turns into 255."""
+    image.  Ignored normals travel as (0, 0, 0), the value ``AddIgnoreRegions`` turns into 255.  ``valid`` (``{task: B flags}``):
+    the batch carries these flags, and the label planes of the samples flagged 0 are overwritten with garbage (NaN for normals
+    and depth, 0xFF bytes for the uint8 maps); the labelled samples and the random draws are those of the call without it."""
     g = torch.Generator(device="cpu").manual_seed(seed)
     out = {"image": torch.randint(0, 256, (B, S, S, 3), generator=g, dtype=torch.uint8)}
     for t in tasks:
@@ -224,7 +294,11 @@ def synthetic_wire_batch(B: int, S: int, tasks: Sequence[str], seed: int, num_ou
             lab = (torch.rand(B, S, S, generator=g) < 0.1).to(torch.uint8)
         else:
             raise NotImplementedError(t)
+        if valid is not None and t in valid:
+            lab[torch.as_tensor(valid[t]).reshape(B) == 0] = 255 if lab.dtype == torch.uint8 else float("nan")
         out[t] = lab.contiguous()
+    if valid is not None:
+        out["valid"] = {t: torch.as_tensor(v).reshape(B).ne(0).to(torch.uint8) for t, v in valid.items()}
     return out
 
 
@@ -523,7 +597,9 @@ def synthetic_raw_batch(B: int, Hc: int, Wc: int, tasks: Sequence[str], seed: in
 
 class DeviceLoader:
     """Wraps any iterable of wire-format host batches and yields ``(images, targets)`` on ``device``, ready for
-    ``train_step``, ``validate_step`` and ``predict``.
+    ``train_step``, ``validate_step`` and ``predict``.  A host batch that carries ``valid`` (a partially labelled batch, see the
+    module docstring) yields ``(images, targets, valid)``: the flags travel through the ring with the tensors and arrive as
+    fresh uint8 tensors on ``device``, what ``train_step(valid=)`` takes.
 
     A ring of ``depth`` pinned staging sets (host and device side) is filled ahead of the consumer: the host-to-device
     copies and ``prepare_batch`` of the next batches run on a side stream while the consumer works on the current one; an
@@ -645,6 +721,8 @@ class DeviceLoader:
         keys = ["image"] + self.tasks
         raw = self.out_size is not None
         B = (check_raw_batch if raw else check_wire_batch)(host, self.tasks)[0]
+        if raw:
+            _check_valid(host, self.tasks, B, "raw batch")
         if host.get("flip") is not None:
             flip = _as_tensor(host["flip"])
         elif self.flip_p > 0.0:
@@ -653,6 +731,7 @@ class DeviceLoader:
             flip = None
         geom = self._draw_geometry(host, B, gen) if raw else None
         extra = {"flip": flip} if flip is not None else {}
+        extra.update({"valid:" + t: _as_tensor(v) for t, v in (host.get("valid") or {}).items()})
         if raw:
             extra.update(size=_as_tensor(host["size"]), coef=geom.coef, side=geom.side)
         entry = self._ring[slot]
@@ -671,9 +750,13 @@ class DeviceLoader:
                     pinned.copy_(src)
                 on_dev.copy_(src if direct else pinned, non_blocking=True)
                 dev_batch[k] = on_dev
+            # (the yielded flags are copies: the ring's buffers are overwritten by a later batch)
+            valid = {k[6:]: dev_batch.pop(k).clone() for k in list(dev_batch) if k.startswith("valid:")}
             if raw:  # the wire-format intermediate is an allocation of the side stream, consumed on it right away
                 dev_batch = augment_batch(dev_batch, self.tasks, Geometry(dev_batch.pop("coef"), dev_batch.pop("side")), self.out_size)
             out = prepare_batch(dev_batch, self.tasks, mean=self.mean, std=self.std)
+            if valid:
+                out = (out[0], out[1], valid)
             entry["done"] = torch.cuda.Event()
             entry["done"].record(self._stream)
         return out, entry["done"], flip, geom
@@ -699,11 +782,11 @@ class DeviceLoader:
                 slot = (slot + 1) % self.depth
             if not pending:
                 return
-            (images, targets), done, flip, geom = pending.pop(0)
+            out, done, flip, geom = pending.pop(0)
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(done)
-            for t in [images] + list(targets.values()):
+            for t in [out[0]] + [x for d in out[1:] for x in d.values()]:
                 t.record_stream(cur)
             self.last_flips.append(flip)
             self.last_geoms.append(geom)
-            yield images, targets
+            yield out

@@ -12,6 +12,7 @@ from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
+import torch.nn.functional as F
 
 from . import _lib as L
 
@@ -1786,20 +1787,99 @@ def label_stat(lab: torch.Tensor, kind: int, ignore_index: float) -> torch.Tenso
     return out
 
 
+def _valid_flags(valid, B: int, device) -> torch.Tensor:
+    """``valid`` checked as the contiguous uint8 (B,) device tensor the kernels read; it passes through as it is, never as a
+    copy: a static buffer stays the buffer a captured launch reads"""
+    if not isinstance(valid, torch.Tensor) or valid.dtype != torch.uint8 or tuple(valid.shape) != (B,):
+        raise RuntimeError(f"mtlora_amd: valid must be a uint8 tensor of shape ({B},), got "
+                           f"{getattr(valid, 'dtype', type(valid))} {tuple(getattr(valid, 'shape', ()))}")
+    if valid.device != device:
+        raise RuntimeError(f"mtlora_amd: valid lives on {valid.device}, the prediction on {device}")
+    if not valid.is_contiguous():  # (a copy would be what a captured launch reads from then on, not the caller's buffer)
+        raise RuntimeError("mtlora_amd: valid must be contiguous (the kernels read the tensor itself, also at replay time)")
+    return valid
+
+
+def label_stat_valid(lab: torch.Tensor, valid: Optional[torch.Tensor], kind: int, ignore_index: float) -> torch.Tensor:
+    """``label_stat`` over the labelled samples of a batch, as a 2-element fp32 tensor ``[statistic, |V|]`` through
+    ``mtlora_label_stat_valid``: ``lab`` (B, ...) contiguous fp32, ``valid`` uint8 (B,) on the same device (non-zero: the sample
+    has a label; ``None``: all have).  ``kind`` 0 / 1 as ``label_stat``, 2: only ``|V|`` (the statistic is 0, the labels are not
+    read).  The labels of an unlabelled sample are never read; nothing comes back to the host."""
+    B = lab.shape[0]
+    nps = lab.numel() // max(B, 1)
+    lib = L.lib()
+    sb = lib.mtlora_label_stat_valid_scratch_bytes(B, nps)
+    scratch = _scratch(sb, lab.device, "label count per sample", B, nps)
+    out = torch.empty(2, dtype=torch.float32, device=lab.device)
+    v = None if valid is None else _valid_flags(valid, B, lab.device)
+    L.check(lib.mtlora_label_stat_valid(L.ptr(lab), None if v is None else L.ptr(v), B, nps, kind, float(ignore_index), L.ptr(out),
+                                        L.ptr(scratch), sb, L.stream_ptr()), "mtlora_label_stat_valid")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # loss end of the train step: bilinear upsample (integer scale, align_corners=False) + per-task loss, fused
 # ----------------------------------------------------------------------------------------------
 LOSS_KINDS = {"softmax": 0, "normals": 1, "balanced_bce": 2, "l1_masked": 3}
 
 
+def loss_of_kind(kind: str, up: torch.Tensor, label: torch.Tensor, ignore_index: float = 255.0, pos_weight: Optional[float] = None):
+    """the four criteria behind ``LOSS_KINDS`` on a full-resolution prediction ``up`` (B, C, H, W), in the dtype of ``up`` (fp64
+    for an oracle), sync-free restatements of mtl_loss_schemes.py: same value, no .item() / masked_select host round trip.
+    The one copy of the formulas: ``mtl_harness.task_loss`` applies them to the fp32 prediction."""
+    if kind == "softmax":                           # SoftMaxwithLoss (:22-39)
+        return F.nll_loss(F.log_softmax(up, 1), label[:, 0].long(), ignore_index=int(ignore_index))
+    if kind == "normals":                           # NormalsLoss(normalize=True, L1, size_average) (:162-220)
+        mask = (label != ignore_index).to(up.dtype)
+        on = up / (torch.norm(up, p=2, dim=1, keepdim=True) + 1e-12)
+        return ((on - label).abs() * mask).sum() / mask.sum().clamp_min(1e-6)
+    if kind == "balanced_bce":                      # BalancedCrossEntropyLoss(size_average[, pos_weight]) (:42-89, :243-245)
+        labels = (label >= 0.5).to(up.dtype)
+        w = (1.0 - labels).sum() / labels.numel() if pos_weight is None else float(pos_weight)
+        gz = (up >= 0).to(up.dtype)
+        lv = up * (labels - gz) - torch.log(1 + torch.exp(up - 2 * up * gz))
+        return (w * (-(labels * lv)).sum() + (1 - w) * (-((1.0 - labels) * lv)).sum()) / labels.numel()
+    if kind == "l1_masked":                         # DepthLoss l1 (:132-148)
+        mask = (label != ignore_index).to(up.dtype)
+        return ((up - label).abs() * mask).sum() / mask.sum().clamp_min(1.0)
+    raise RuntimeError(f"mtlora_amd: unknown fused loss kind {kind!r}")
+
+
+def upsample_loss_valid_torch(kind: str, low, label, scale: int, valid=None, ignore_index: float = 255.0,
+                              pos_weight: Optional[float] = None):
+    """The semantics of ``UpsampleLossFn.apply(..., valid=valid)`` in plain torch, on any device and in the dtype of ``low`` (fp64
+    for an oracle): the samples with ``valid[b] != 0`` are index-selected, their low-resolution prediction is upsampled
+    (bilinear, align_corners=False) and the criterion of ``kind`` is applied to that sub-batch -- what the reference's
+    ``criterion(pred[V], gt[V])`` computes.  No labelled sample: ``+0.0`` with a zero gradient (the reference would divide by
+    zero).  Unlabelled samples' ``low`` and ``label`` are never touched, so they may hold anything.  ``valid=None``: all labelled.
+    The documented definition and the tests' oracle; it reads ``valid`` on the host."""
+    B = low.shape[0]
+    if valid is None:
+        idx = torch.arange(B, device=low.device)
+    else:
+        idx = torch.nonzero(torch.as_tensor(valid).reshape(-1) != 0).reshape(-1).to(low.device)
+    if idx.numel() == 0:
+        return low.reshape(-1)[:0].sum()  # +0.0, differentiable: d / d low = 0
+    lo = low.index_select(0, idx)
+    up = F.interpolate(lo.permute(0, 3, 1, 2), scale_factor=int(scale), mode="bilinear", align_corners=False)
+    return loss_of_kind(kind, up, label.index_select(0, idx.to(label.device)), ignore_index, pos_weight)
+
+
 class UpsampleLossFn(torch.autograd.Function):
     """loss_kind( F.interpolate(low.permute(0,3,1,2), scale_factor=scale, mode="bilinear"), label ) as ONE kernel that also
     produces d loss / d low (csrc/loss.hip); the upsampled prediction never exists.  ``low`` is (B, h, w, C)
     channels-last (fp32 / bf16), ``label`` (B, 1 | C, scale*h, scale*w).  ``pos_weight`` (``balanced_bce`` only): the constant
-    weight of BalancedCrossEntropyLoss(pos_weight=...) instead of the label statistic (edge: 0.95)."""
+    weight of BalancedCrossEntropyLoss(pos_weight=...) instead of the label statistic (edge: 0.95).
+
+    ``valid`` (uint8 (B,) on the device, non-zero: the sample carries a label for this task): the loss of the labelled
+    sub-batch, ``upsample_loss_valid_torch``; the same launch (``mtlora_upsample_loss_valid``) fed by ``label_stat_valid``.  The
+    kernels read the flags on the device -- a captured call follows the tensor's content at replay time -- and never read the
+    prediction or the label of an unlabelled sample; its rows of d loss / d low are +0.0, and with no labelled sample the loss
+    is +0.0.  ``None``: today's launch, bit for bit."""
 
     @staticmethod
-    def forward(ctx, kind: str, low, label, scale: int, ignore_index: float = 255.0, pos_weight: Optional[float] = None):
+    def forward(ctx, kind: str, low, label, scale: int, ignore_index: float = 255.0, pos_weight: Optional[float] = None,
+                valid=None):
         L.require_gpu(low, label)
         B, h, w, C = low.shape
         H, W = h * scale, w * scale
@@ -1810,18 +1890,25 @@ class UpsampleLossFn(torch.autograd.Function):
         lo = low.detach().contiguous()
         if lo.dtype not in (torch.float32, torch.bfloat16):
             lo = lo.float()
+        if kind not in LOSS_KINDS:
+            raise RuntimeError(f"mtlora_amd: unknown fused loss kind {kind!r}")
+        vflags = None if valid is None else _valid_flags(valid, B, lo.device)
         # label-only statistics (independent of the prediction)
-        if kind == "softmax":
+        if vflags is not None:  # [statistic over the labelled samples, their number]
+            if kind == "balanced_bce" and pos_weight is not None:
+                stat = torch.cat([torch.full((1,), float(pos_weight), dtype=torch.float32, device=lab.device),
+                                  label_stat_valid(lab, vflags, 2, ignore_index)[1:]])
+            else:
+                stat = label_stat_valid(lab, vflags, 1 if kind == "balanced_bce" else 0, ignore_index)
+        elif kind == "softmax":
             stat = label_stat(lab, 0, ignore_index)
         elif kind == "normals":
             stat = label_stat(lab, 0, ignore_index)
         elif kind == "balanced_bce":
             stat = (label_stat(lab, 1, ignore_index) if pos_weight is None
                     else torch.full((1,), float(pos_weight), dtype=torch.float32, device=lab.device))
-        elif kind == "l1_masked":
-            stat = label_stat(lab, 0, ignore_index)
         else:
-            raise RuntimeError(f"mtlora_amd: unknown fused loss kind {kind!r}")
+            stat = label_stat(lab, 0, ignore_index)
         if pos_weight is not None and kind != "balanced_bce":
             raise RuntimeError(f"mtlora_amd: pos_weight applies to 'balanced_bce', not {kind!r}")
         lib = L.lib()
@@ -1830,9 +1917,15 @@ class UpsampleLossFn(torch.autograd.Function):
             raise RuntimeError(f"mtlora_amd: fused upsample + loss supports scales 1..32, got {scale}")
         part = torch.empty(max(n, 1), dtype=torch.float32, device=lo.device)
         dlow = torch.empty_like(lo)
-        st = lib.mtlora_upsample_loss(LOSS_KINDS[kind], L.ptr(lo), L.ptr(lab), L.ptr(stat), L.ptr(dlow), L.ptr(part), B, h, w,
-                                      C, int(scale), L.dtype_code(lo), float(ignore_index), L.stream_ptr())
-        L.check(st, "mtlora_upsample_loss")
+        if vflags is None:
+            st = lib.mtlora_upsample_loss(LOSS_KINDS[kind], L.ptr(lo), L.ptr(lab), L.ptr(stat), L.ptr(dlow), L.ptr(part), B, h, w,
+                                          C, int(scale), L.dtype_code(lo), float(ignore_index), L.stream_ptr())
+            L.check(st, "mtlora_upsample_loss")
+        else:
+            st = lib.mtlora_upsample_loss_valid(LOSS_KINDS[kind], L.ptr(lo), L.ptr(lab), L.ptr(vflags), L.ptr(stat), L.ptr(dlow),
+                                                L.ptr(part), B, h, w, C, int(scale), L.dtype_code(lo), float(ignore_index),
+                                                L.stream_ptr())
+            L.check(st, "mtlora_upsample_loss_valid")
         ctx.save_for_backward(dlow)
         ctx.in_dtype = low.dtype
         return part[:n].sum() if n > 0 else part.sum() * 0
@@ -1840,7 +1933,7 @@ class UpsampleLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (dlow,) = ctx.saved_tensors
-        return None, (dlow * g.to(dlow.dtype)).to(ctx.in_dtype), None, None, None, None
+        return None, (dlow * g.to(dlow.dtype)).to(ctx.in_dtype), None, None, None, None, None
 
 
 # validation end: bilinear upsample + get_output + meter update + loss, fused and forward-only (csrc/metrics.hip)

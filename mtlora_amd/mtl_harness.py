@@ -281,30 +281,19 @@ class MultiTaskSwin(nn.Module):
 # --------------------------------------------------------------------------------------------------
 # losses (mtl_loss_schemes.py), sync-free restatements: same value, no .item() / masked_select host round trip
 # --------------------------------------------------------------------------------------------------
-def task_loss(task: str, out: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
-    out = out.float()
-    task = task_kind(task)
-    if task in ("semseg", "human_parts"):          # SoftMaxwithLoss (:22-39)
-        return F.nll_loss(F.log_softmax(out, 1), label[:, 0].long(), ignore_index=255)
-    if task == "normals":                           # NormalsLoss(normalize=True, L1, size_average) (:162-220)
-        mask = (label != 255).to(out.dtype)
-        on = out / (torch.norm(out, p=2, dim=1, keepdim=True) + 1e-12)
-        return ((on - label).abs() * mask).sum() / mask.sum().clamp_min(1e-6)
-    if task == "sal":                               # BalancedCrossEntropyLoss(size_average) (:42-89)
-        labels = (label >= 0.5).to(out.dtype)
-        w = (1.0 - labels).sum() / labels.numel()
-        gz = (out >= 0).to(out.dtype)
-        lv = out * (labels - gz) - torch.log(1 + torch.exp(out - 2 * out * gz))
-        return (w * (-(labels * lv)).sum() + (1 - w) * (-((1.0 - labels) * lv)).sum()) / labels.numel()
-    if task == "depth":                             # DepthLoss l1 (:132-148)
-        mask = (label != 255).to(out.dtype)
-        return ((out - label).abs() * mask).sum() / mask.sum().clamp_min(1.0)
-    if task == "edge":                              # BalancedCrossEntropyLoss(size_average, pos_weight=0.95) (:243-245)
-        labels = (label >= 0.5).to(out.dtype)
-        gz = (out >= 0).to(out.dtype)
-        lv = out * (labels - gz) - torch.log(1 + torch.exp(out - 2 * out * gz))
-        return (EDGE_POS_WEIGHT * (-(labels * lv)).sum() + (1 - EDGE_POS_WEIGHT) * (-((1.0 - labels) * lv)).sum()) / labels.numel()
-    raise NotImplementedError(task)
+def task_loss(task: str, out: torch.Tensor, label: torch.Tensor, valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``valid`` (uint8 (B,), non-zero: the sample has a label for ``task``): the criterion on the index-selected sub-batch
+    ``(out[V], label[V])``, as the reference's ``criterion(pred[V], gt[V])``; with no labelled sample +0.0 and a zero gradient
+    (the reference would divide by zero).  The selection reads ``valid`` on the host: this is the plain path."""
+    if valid is not None:
+        idx = torch.nonzero(valid.reshape(-1) != 0).reshape(-1)
+        if idx.numel() == 0:
+            return out.float().reshape(-1)[:0].sum()
+        return task_loss(task, out.index_select(0, idx.to(out.device)), label.index_select(0, idx.to(label.device)))
+    kind = MultiTaskLoss.FUSED_KIND.get(task_kind(task))  # the formulas live in functional.loss_of_kind, dtype-generic
+    if kind is None:
+        raise NotImplementedError(task)
+    return Fn.loss_of_kind(kind, out.float(), label, 255.0, EDGE_POS_WEIGHT if task_kind(task) == "edge" else None)
 
 
 class MultiTaskLoss(nn.Module):
@@ -315,8 +304,10 @@ class MultiTaskLoss(nn.Module):
         self.tasks = list(tasks)
         self.loss_weights = dict(loss_weights or {t: loss_weight(t) for t in tasks})
 
-    def forward(self, pred, gt):
-        per = {t: task_loss(t, pred[t], gt[t]) for t in self.tasks}
+    def forward(self, pred, gt, valid: Optional[Mapping[str, torch.Tensor]] = None):
+        """``valid``: ``{task: uint8 (B,)}``, non-zero where the sample carries a label for that task (partially labelled
+        batches: ``task_loss``); a task without an entry is labelled everywhere"""
+        per = {t: task_loss(t, pred[t], gt[t], (valid or {}).get(t)) for t in self.tasks}
         total = torch.stack([self.loss_weights[t] * per[t] for t in self.tasks]).sum()
         per["total"] = total
         return total, per
@@ -324,15 +315,29 @@ class MultiTaskLoss(nn.Module):
     FUSED_KIND = {"semseg": "softmax", "human_parts": "softmax", "normals": "normals", "sal": "balanced_bce",
                   "depth": "l1_masked", "edge": "balanced_bce"}
 
-    def task_low(self, t, lo, lab):
-        """loss of task t from its LOW-resolution (B, h, w, C) prediction (fused upsample + loss + backward where it applies)"""
+    def task_low(self, t, lo, lab, valid: Optional[torch.Tensor] = None):
+        """loss of task t from its LOW-resolution (B, h, w, C) prediction (fused upsample + loss + backward where it applies).
+        ``valid`` (uint8 (B,) on the device of ``lo``): the samples that carry a label for t; the fused kernels read it on the
+        device, so a captured call follows its content (``UpsampleLossFn``)."""
         h, w = lo.shape[1:3]
         H, W = lab.shape[-2:]
         kind = self.FUSED_KIND.get(task_kind(t))
         if kind is not None and lo.is_cuda and H % h == 0 and W % w == 0 and H // h == W // w:
-            if task_kind(t) == "edge":  # the constant weight instead of the label statistic
-                return UpsampleLossFn.apply(kind, lo, lab, H // h, 255.0, EDGE_POS_WEIGHT)
+            pw = EDGE_POS_WEIGHT if task_kind(t) == "edge" else None  # the constant weight instead of the label statistic
+            if valid is not None:
+                return UpsampleLossFn.apply(kind, lo, lab, H // h, 255.0, pw, valid)
+            if pw is not None:
+                return UpsampleLossFn.apply(kind, lo, lab, H // h, 255.0, pw)
             return UpsampleLossFn.apply(kind, lo, lab, H // h)
+        if valid is not None:  # (select first: the unlabelled samples' predictions are not upsampled)
+            if lo.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"mtlora_amd: task {t!r} with valid= takes the plain loss path ({(h, w)} -> {(H, W)} is no integer "
+                                   "scale, or the task has no fused kind), which selects the labelled samples on the host: it cannot "
+                                   "be captured")
+            idx = torch.nonzero(valid.reshape(-1) != 0).reshape(-1)
+            if idx.numel() == 0:
+                return lo.float().reshape(-1)[:0].sum()
+            lo, lab = lo.index_select(0, idx.to(lo.device)), lab.index_select(0, idx.to(lab.device))
         return task_loss(t, F.interpolate(lo.permute(0, 3, 1, 2), (H, W), mode="bilinear"), lab)
 
     def combine(self, per):
@@ -341,11 +346,11 @@ class MultiTaskLoss(nn.Module):
         per["total"] = total
         return total, per
 
-    def forward_low(self, low, gt):
-        """same value and gradients as ``forward(upsampled prediction, gt)`` from the LOW-resolution (B, h, w, C)
+    def forward_low(self, low, gt, valid: Optional[Mapping[str, torch.Tensor]] = None):
+        """same value and gradients as ``forward(upsampled prediction, gt, valid)`` from the LOW-resolution (B, h, w, C)
         predictions of ``model(x, upsample=False)``: bilinear upsample + loss + backward fused (csrc/loss.hip).
         Non-integer scales and CPU tensors take the plain path."""
-        return self.combine({t: self.task_low(t, low[t], gt[t]) for t in self.tasks})
+        return self.combine({t: self.task_low(t, low[t], gt[t], (valid or {}).get(t)) for t in self.tasks})
 
 
 # --------------------------------------------------------------------------------------------------
@@ -421,10 +426,14 @@ def build_optimizer(model: nn.Module, lr=5e-4, weight_decay=0.05, fused: Optiona
                              capturable=bool(capturable and fused))
 
 
-def synthetic_batch(B: int, S: int, tasks: Sequence[str], seed: int, device="cpu", num_outputs: Optional[Mapping[str, int]] = None):
+def synthetic_batch(B: int, S: int, tasks: Sequence[str], seed: int, device="cpu", num_outputs: Optional[Mapping[str, int]] = None,
+                    valid: Optional[Mapping[str, Sequence[int]]] = None):
     """SURVEY 8d synthetic inputs: image ~ N(0,1); semseg/human_parts class ids with 5 % 255; sal Bernoulli(.3);
     normals unit vectors with 5 % pixels 255; depth uniform in [0, 10); edge Bernoulli(.1) (edge maps are sparse: about
-    one pixel in ten of a dilated NYUD / PASCAL boundary map is on).  ``num_outputs`` as ``build_model``."""
+    one pixel in ten of a dilated NYUD / PASCAL boundary map is on).  ``num_outputs`` as ``build_model``.
+    ``valid`` (``{task: B flags}``): a partially labelled batch -- the labels of a task's unlabelled samples (flag 0) are
+    overwritten with NaN, so that anything that reads them shows; the labelled samples' values and the random draws are those
+    of the call without ``valid``.  Returns ``(images, targets, {task: uint8 (B,)})`` then, the flags on ``device``."""
     g = torch.Generator(device="cpu").manual_seed(seed)
     img = torch.randn(B, 3, S, S, generator=g)
     tg = {}
@@ -445,7 +454,11 @@ def synthetic_batch(B: int, S: int, tasks: Sequence[str], seed: int, device="cpu
             lab = (torch.rand(B, 1, S, S, generator=g) < 0.1).float()
         else:
             raise NotImplementedError(t)
+        if valid is not None and t in valid:
+            lab[torch.as_tensor(valid[t]).reshape(B) == 0] = float("nan")
         tg[t] = lab.to(device)
+    if valid is not None:
+        return img.to(device), tg, {t: torch.as_tensor(v).reshape(B).ne(0).to(torch.uint8).to(device) for t, v in valid.items()}
     return img.to(device), tg
 
 
@@ -482,9 +495,14 @@ def _factor_packer(model):
     return pk
 
 
+def _task_low(criterion, t, lo, lab, valid):
+    """``criterion.task_low`` with the flags only where there are some: a criterion without partial labels keeps its signature"""
+    return criterion.task_low(t, lo, lab) if valid is None else criterion.task_low(t, lo, lab, valid)
+
+
 def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 5.0, reducer=None,
                amp_dtype: Optional[torch.dtype] = torch.bfloat16, fused_loss: bool = True, loss_scaler=None,
-               update_grad: bool = True, meters=None):
+               update_grad: bool = True, meters=None, valid: Optional[Mapping[str, torch.Tensor]] = None):
     """one reference train step (main.py:329-354): autocast fwd + weighted multi-task loss, backward,
     [gradient all-reduce], clip_grad_norm_(5.0), AdamW, zero_grad.  bf16 autocast needs no GradScaler
     (the reference's scaler exists for its fp16 default: ``loss_scaler``, an ``optim.LossScaler``, scales the loss before
@@ -493,7 +511,11 @@ def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 
     ``FusedAdamW`` the clip, the step and the scaler update are ``clip_and_step``'s three launches.  ``meters`` (a
     ``meters.TrainMeters.for_train_step``): after the update, or after the backward of an accumulating micro-step, the loss, the
     per-task losses and -- on an update step -- the norm are written into the meters' device sources by one small kernel and
-    ``meters.update()`` is launched; nothing is read back, and the step computes what it computes without them."""
+    ``meters.update()`` is launched; nothing is read back, and the step computes what it computes without them.
+    ``valid`` (``{task: uint8 (B,)}`` on the device, non-zero: the sample carries a label for that task; a task without an entry is
+    labelled everywhere): a partially labelled batch.  Each task's loss is its criterion over its labelled samples
+    (``MultiTaskLoss.forward``), 0 with a zero gradient when it has none; the heads still run on all B samples."""
+    valid = valid or {}
     fused_opt = isinstance(optimizer, FusedOptimizer)
     if loss_scaler is not None and not fused_opt:
         raise TypeError("train_step: loss_scaler needs the HIP optimizer (build_optimizer(impl='hip'))")
@@ -501,9 +523,10 @@ def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 
         if fused_loss:  # final upsample + losses (+ their backward) as one kernel per task, inside the task's stream
             if isinstance(model, MultiTaskSwin):
                 return criterion.combine(model(images, upsample=False,
-                                               per_task_fn=lambda t, lo: criterion.task_low(t, lo, targets[t])))
-            return criterion.forward_low(model(images, upsample=False), targets)
-        return criterion(model(images), targets)
+                                               per_task_fn=lambda t, lo: _task_low(criterion, t, lo, targets[t], valid.get(t))))
+            low = model(images, upsample=False)
+            return criterion.forward_low(low, targets, valid) if valid else criterion.forward_low(low, targets)
+        return criterion(model(images), targets, valid) if valid else criterion(model(images), targets)
 
     if images.is_cuda:
         Fn.droppath_begin_step(images.device)  # DropPath factors of the whole step from one draw (functional._DropPathPool)
@@ -648,6 +671,12 @@ class GraphedTrainStep:
       by a captured add at the start of every replay and added to the seeds by the kernels at run time; DropPath
       uses torch's graph-safe generator;
     * data: ``images`` / ``targets`` are static buffers -- ``copy_`` the next batch into them before calling;
+    * ``valid`` (``{task: uint8 (B,)}`` on the device, as ``train_step``'s): static buffers like the targets -- ``copy_`` the next batch's
+      flags into them before calling.  The fused loss kernels read them on the device, so one capture serves every mask: a replay
+      never re-captures.  Needs ``fused_loss`` on a GPU, and every task named in ``valid`` must reach the fused kernel (a fused kind
+      and an integer scale between head output and label, ``MultiTaskLoss.task_low``): the plain path selects on the host, which a
+      graph cannot follow.  The constructor checks the kinds; a non-integer scale shows at capture time, and the step then runs
+      eagerly (correctly) with the reason in ``self.why``, like any other capture problem;
     * optimizer: must be ``capturable`` (``build_optimizer(..., capturable=True)``).  With ``impl="hip"`` the update is
       ``FusedAdamW.clip_and_step``'s three launches inside the graph, ``loss_scaler`` (an ``optim.LossScaler``: the fp16 recipe)
       is allowed, the learning rate follows ``optimizer.param_groups`` from replay to replay (the values are pushed to the
@@ -685,11 +714,19 @@ class GraphedTrainStep:
 
     def __init__(self, model, criterion, optimizer, images, targets, clip_grad: float = 5.0, reducer=None,
                  amp_dtype: Optional[torch.dtype] = torch.bfloat16, fused_loss: bool = True, warmup: int = 3, loss_scaler=None,
-                 accumulation_steps: int = 1, lr_scheduler=None, meters=None):
+                 accumulation_steps: int = 1, lr_scheduler=None, meters=None, valid: Optional[Mapping[str, torch.Tensor]] = None):
+        self.valid = dict(valid) if valid else {}
         self.accumulation_steps = accumulation_steps_of(accumulation_steps)
         if self.accumulation_steps > 1 and reducer is not None:
             raise ValueError("GraphedTrainStep: accumulation_steps > 1 with a reducer is not supported (the all-reduce would have to "
                              "sit between two graphs on every k-th call only); use train_step(..., reducer=, update_grad=)")
+        if self.valid and not (fused_loss and images.is_cuda):
+            raise ValueError("GraphedTrainStep: valid= needs fused_loss=True on a GPU: the fused loss kernels read the flags on the "
+                             "device at replay time; the plain losses select the labelled samples on the host")
+        plain = [t for t in self.valid if MultiTaskLoss.FUSED_KIND.get(task_kind(t)) is None]
+        if plain:
+            raise ValueError(f"GraphedTrainStep: valid= names {plain}, which have no fused loss kind: their losses would select the "
+                             "labelled samples on the host")
         self.fused_opt = isinstance(optimizer, FusedOptimizer)
         if self.accumulation_steps > 1 and not self.fused_opt:
             raise TypeError("GraphedTrainStep: accumulation_steps > 1 needs the HIP optimizer (build_optimizer(impl='hip', "
@@ -827,7 +864,10 @@ class GraphedTrainStep:
         with ctx:
             if self.fused_loss and isinstance(self.model, MultiTaskSwin):  # as train_step: each loss inside its task's stream
                 loss, per = self.criterion.combine(self.model(
-                    self.images, upsample=False, per_task_fn=lambda t, lo: self.criterion.task_low(t, lo, self.targets[t])))
+                    self.images, upsample=False,
+                    per_task_fn=lambda t, lo: _task_low(self.criterion, t, lo, self.targets[t], self.valid.get(t))))
+            elif self.fused_loss and self.valid:
+                loss, per = self.criterion.forward_low(self.model(self.images, upsample=False), self.targets, self.valid)
             elif self.fused_loss:
                 loss, per = self.criterion.forward_low(self.model(self.images, upsample=False), self.targets)
             else:
