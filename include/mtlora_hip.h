@@ -563,6 +563,28 @@ int mtlora_upsample_metrics(int kind, const void* low, const float* label, const
                             void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Partially labelled batches at the validation end (additive under ABI 12): the same launch with the per-sample validity flag
+ * of mtlora_upsample_loss_valid.  `valid` is a device array of B bytes, non-zero = sample b carries a label for this task;
+ * V = the labelled samples.  The result is what mtlora_upsample_metrics gives for the sub-batch (low[V], label[V]):
+ *   stat[0]  the statistic of mtlora_upsample_metrics over the samples of V only -- what mtlora_label_stat_valid writes to
+ *            out[0] (kind 4: pos_weight), so the loss is the sub-batch's criterion
+ *   |V|      as a float (out[1] of mtlora_label_stat_valid), in the word behind those of the unmasked launch: stat[1] for kinds
+ *            0, 1, 3 (not read) and 4, stat[35] for kind 2, whose thresholds keep stat[1..35).  Kinds 2 and 4 normalise the loss
+ *            (kind 4: and the meter's value) by |V| H W
+ * A tile belongs to one sample.  A tile of an unlabelled sample decides on its flag before it loads anything: it adds nothing
+ * to `counts` (kind 2: that image's [15][3] rows stay as they were), writes +0.0 to its partial of every float quantity and
+ * reads neither low[b] nor label[b] (any bits, NaN and Inf included, may stand there).  Every element of `fpartials` is still
+ * written exactly once; sizes and layouts are those of mtlora_upsample_metrics_sizes for the whole batch B, image b of kind 2
+ * keeps row b.  With V empty, `counts` is unchanged and every partial is +0.0.  With every sample labelled, `counts` and
+ * `fpartials` have the bits of mtlora_upsample_metrics fed by mtlora_label_stat.  `valid` is read by the kernel, at launch or
+ * replay time: a captured launch follows the buffer's content.  No float atomics, no memset.  Checks and return codes as
+ * mtlora_upsample_metrics; valid == NULL with B > 0 is MTLORA_ERR_NULL.
+ * ------------------------------------------------------------------------------------------ */
+int mtlora_upsample_metrics_valid(int kind, const void* low, const float* label, const unsigned char* valid, const float* stat,
+                                  int64_t* counts, float* fpartials, int64_t B, int h, int w, int C, int scale, int dtype,
+                                  float ignore_index, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Full-resolution predictions, fused (ABI v11): replaces, for one task and one batch, the final
  * F.interpolate(pred, img_size, mode="bilinear") of models/swin_mtl.py:245 TOGETHER WITH get_output
  * (evaluation/evaluate_utils.py:20-38) -- what utils.py:405-439 save_imgs_mtl and any offline scoring (the edge benchmark)

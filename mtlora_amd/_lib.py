@@ -265,6 +265,8 @@ _SIGS = {
     "mtlora_upsample_metrics_sizes": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "mtlora_upsample_metrics": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                         c_int, c_int, ctypes.c_float, c_void_p]),
+    "mtlora_upsample_metrics_valid": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                              c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p]),
     "mtlora_upsample_predict": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mtlora_upsample_cl_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int64, c_int, c_void_p]),
     "mtlora_upsample_cl_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int64, c_int, c_void_p]),

@@ -36,6 +36,12 @@
 //                         sum (log gt - log p)^2 over label != ignore (eval_depth.py:71-89)
 //   kind 4  edge          floats: loss (kind 2's formula with the constant stat[0]), and the meter's value, which is the same
 //                         formula applied to q (eval_edge.py:31-37 feeds the PROCESSED prediction to the loss)
+//
+// Partially labelled batches (mtlora_upsample_metrics_valid, VAL): a byte per sample says whether it carries a label, as in
+// loss.hip.  A tile belongs to one sample, so the decision is wave-uniform: a tile of an unlabelled sample writes +0 to its
+// float partials, adds to no counter and leaves before it loads anything of that sample.  stat holds the statistics over the
+// labelled samples, and their number |V| behind the words of the unmasked launch (kinds 2 and 4 normalise by |V| H W).  VAL is
+// a template parameter: the unmasked entry runs the code it ran before.
 #include "dispatch.h"
 #include "up_pixel.h"
 
@@ -47,6 +53,7 @@ struct UpMetParams {
     const float* stat;           // device scalars, see above
     unsigned long long* counts;  // added to
     float* fpart;                // [NF][tiles]
+    const unsigned char* valid;  // (B) non-zero: the sample has a label (VAL kernels only; NULL otherwise)
     int B, h, w, C, S, TR;
     int tiles;
     float ignore;
@@ -55,6 +62,8 @@ struct UpMetParams {
 constexpr int MET_SAL_T1 = 15, MET_SAL_T2 = 19;
 constexpr int MET_SAL_NC = 2 * MET_SAL_T1 + 1 + 2 * MET_SAL_T2 + 1;  // per-lane counters of the saliency kind
 constexpr float MET_DEG = 57.29577951308232f;                          // 180 / pi
+// VAL: the stat word that carries |V| -- behind the words of the unmasked launch
+static __host__ __device__ constexpr int met_nv_word(int kind) { return kind == 2 ? 1 + MET_SAL_T1 + MET_SAL_T2 : 1; }
 
 static __host__ __device__ inline int met_nfloat(int kind) { return kind == 1 || kind == 3 ? 3 : (kind == 4 ? 2 : 1); }
 static inline int64_t met_nint(int kind, int64_t B, int C) {
@@ -86,7 +95,7 @@ __device__ __forceinline__ int wave_sum(int v) {
     return v;
 }
 
-template <typename T, int MK, int CMAX, int SC>
+template <typename T, int MK, int CMAX, int SC, bool VAL>
 __global__ __launch_bounds__(64) void k_up_metrics(const UpMetParams p) {
     extern __shared__ float sm[];
     constexpr int LK = MK == 4 ? 2 : MK;      // the loss formula of up_pixel
@@ -106,6 +115,13 @@ __global__ __launch_bounds__(64) void k_up_metrics(const UpMetParams p) {
     const T* low = reinterpret_cast<const T*>(p.low);
     const float rs = (float)p.h / (float)H;  // in / out, exactly 1/S
 
+    // a sample without a label (wave-uniform: b comes from blockIdx): +0 to the tile's partial of every float quantity, nothing
+    // to any counter; neither low[b] nor label[b] is loaded
+    if (VAL && __builtin_amdgcn_readfirstlane((int)p.valid[b]) == 0) {
+        if (lane < met_nfloat(MK)) p.fpart[(int64_t)lane * p.tiles + blockIdx.x] = 0.f;
+        return;
+    }
+
     for (int i = lane; i < (TR + 2) * (TQ + 2) * C; i += 64) {
         const int pix = i / C, c = i - pix * C;
         const int py = pix / (TQ + 2), px = pix - py * (TQ + 2);
@@ -117,15 +133,17 @@ __global__ __launch_bounds__(64) void k_up_metrics(const UpMetParams p) {
     if (MK == 0)
         for (int i = lane; i < 3 * C; i += 64) xl[i] = 0;
 
-    float norm;  // 1 / normaliser of the mean, as k_up_loss
+    // 1 / normaliser of the mean, as k_up_loss.  VAL: stat[0] runs over the labelled samples; the formula of kinds 2 and 4 takes
+    // |V| where it took B (the same expression: all labelled gives the same bits), and kind 0 guards a count of 0 as k_up_loss
+    float norm;
     if (LK == 0)
-        norm = 1.f / p.stat[0];
+        norm = (VAL && p.stat[0] == 0.f) ? 0.f : 1.f / p.stat[0];
     else if (LK == 1)
         norm = 1.f / fmaxf(p.stat[0], 1e-6f);
     else if (LK == 3)
         norm = 1.f / fmaxf(p.stat[0], 1.f);
     else
-        norm = 1.f / ((float)p.B * (float)H * (float)W);
+        norm = 1.f / ((VAL ? p.stat[met_nv_word(MK)] : (float)p.B) * (float)H * (float)W);
     const float wneg = LK == 2 ? p.stat[0] : 0.f;
     float th1[MK == 2 ? MET_SAL_T1 : 1], th2[MK == 2 ? MET_SAL_T2 : 1];  // (wave-uniform: scalar registers)
     if (MK == 2) {
@@ -385,37 +403,37 @@ __global__ __launch_bounds__(64) void k_up_metrics(const UpMetParams p) {
     }
 }
 
-template <typename T, int MK, int CMAX>
+template <typename T, int MK, int CMAX, bool VAL>
 static void launch_met(const UpMetParams& p, hipStream_t s) {
     const size_t lds = met_lds_bytes(MK, p.C, p.S, p.TR);
     if (p.S == 8)  // the scale of the models' heads
-        hipLaunchKernelGGL((k_up_metrics<T, MK, CMAX, 8>), dim3((unsigned)p.tiles), dim3(64), lds, s, p);
+        hipLaunchKernelGGL((k_up_metrics<T, MK, CMAX, 8, VAL>), dim3((unsigned)p.tiles), dim3(64), lds, s, p);
     else
-        hipLaunchKernelGGL((k_up_metrics<T, MK, CMAX, 0>), dim3((unsigned)p.tiles), dim3(64), lds, s, p);
+        hipLaunchKernelGGL((k_up_metrics<T, MK, CMAX, 0, VAL>), dim3((unsigned)p.tiles), dim3(64), lds, s, p);
 }
 
-template <typename T>
+template <typename T, bool VAL>
 static int dispatch_met(int kind, const UpMetParams& p, hipStream_t s) {
     if (kind == 0) {
         if (p.C <= 8)
-            launch_met<T, 0, 8>(p, s);
+            launch_met<T, 0, 8, VAL>(p, s);
         else if (p.C <= 24)
-            launch_met<T, 0, 24>(p, s);
+            launch_met<T, 0, 24, VAL>(p, s);
         else if (p.C <= 48)
-            launch_met<T, 0, 48>(p, s);
+            launch_met<T, 0, 48, VAL>(p, s);
         else
             return MTLORA_ERR_UNSUPPORTED;
     } else if (kind == 1) {
         if (p.C > 4) return MTLORA_ERR_UNSUPPORTED;
-        launch_met<T, 1, 4>(p, s);
+        launch_met<T, 1, 4, VAL>(p, s);
     } else {
         if (p.C != 1) return MTLORA_ERR_UNSUPPORTED;
         if (kind == 2)
-            launch_met<T, 2, 1>(p, s);
+            launch_met<T, 2, 1, VAL>(p, s);
         else if (kind == 3)
-            launch_met<T, 3, 1>(p, s);
+            launch_met<T, 3, 1, VAL>(p, s);
         else
-            launch_met<T, 4, 1>(p, s);
+            launch_met<T, 4, 1, VAL>(p, s);
     }
     return MTLORA_OK;
 }
@@ -439,14 +457,17 @@ int mtlora_upsample_metrics_sizes(int kind, int64_t B, int h, int w, int C, int 
     return MTLORA_OK;
 }
 
-int mtlora_upsample_metrics(int kind, const void* low, const float* label, const float* stat, int64_t* counts, float* fpartials,
-                            int64_t B, int h, int w, int C, int scale, int dtype, float ignore_index, void* stream) {
+// the launch behind both entries: mtlora_upsample_metrics hands in valid == NULL (need_valid false) and runs the VAL = false
+// kernels
+static int up_metrics_launch(int kind, const void* low, const float* label, const unsigned char* valid, bool need_valid,
+                             const float* stat, int64_t* counts, float* fpartials, int64_t B, int h, int w, int C, int scale,
+                             int dtype, float ignore_index, void* stream) {
     int64_t ni = 0, nfp = 0;
     const int rc0 = mtlora_upsample_metrics_sizes(kind, B, h, w, C, scale, &ni, &nfp);
     if (rc0 != MTLORA_OK) return rc0;
     if (!mtl_dtype_in(dtype, MTL_DT_F32_BF16)) return MTLORA_ERR_DTYPE;
     if (B == 0) return MTLORA_OK;
-    if (mtl_any_null({low, label, stat, fpartials}) || (ni > 0 && !counts)) return MTLORA_ERR_NULL;
+    if (mtl_any_null({low, label, stat, fpartials}) || (ni > 0 && !counts) || (need_valid && !valid)) return MTLORA_ERR_NULL;
     const int64_t tiles = met_tiles(kind, B, h, w, C, scale);
     if (tiles >= ((int64_t)1 << 31) || (int64_t)h * scale * (int64_t)w * scale >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
     UpMetParams p;
@@ -455,6 +476,7 @@ int mtlora_upsample_metrics(int kind, const void* low, const float* label, const
     p.stat = stat;
     p.counts = reinterpret_cast<unsigned long long*>(counts);
     p.fpart = fpartials;
+    p.valid = need_valid ? valid : nullptr;
     p.B = (int)B;
     p.h = h;
     p.w = w;
@@ -464,12 +486,28 @@ int mtlora_upsample_metrics(int kind, const void* low, const float* label, const
     p.tiles = (int)tiles;
     p.ignore = ignore_index;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (need_valid) mtl_prof_tag("valid metrics k%d B%lld h%d w%d C%d S%d", kind, (long long)B, h, w, C, scale);
     MtlProfScope prof(PK_LOSS, (double)B * h * w * C * mtl_elem_size(dtype) +
                                    (double)B * h * scale * w * scale * 4.0 * (kind == 1 ? C : 1), s);
-    const int rc = mtl_dispatch_f32_bf16(dtype, [&](auto t) { return dispatch_met<typename decltype(t)::type>(kind, p, s); });
+    const int rc = mtl_dispatch_f32_bf16(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return need_valid ? dispatch_met<T, true>(kind, p, s) : dispatch_met<T, false>(kind, p, s);
+    });
     if (rc != MTLORA_OK) return rc;
     MTL_CHECK_LAUNCH();
     return MTLORA_OK;
+}
+
+int mtlora_upsample_metrics(int kind, const void* low, const float* label, const float* stat, int64_t* counts, float* fpartials,
+                            int64_t B, int h, int w, int C, int scale, int dtype, float ignore_index, void* stream) {
+    return up_metrics_launch(kind, low, label, nullptr, false, stat, counts, fpartials, B, h, w, C, scale, dtype, ignore_index,
+                             stream);
+}
+
+int mtlora_upsample_metrics_valid(int kind, const void* low, const float* label, const unsigned char* valid, const float* stat,
+                                  int64_t* counts, float* fpartials, int64_t B, int h, int w, int C, int scale, int dtype,
+                                  float ignore_index, void* stream) {
+    return up_metrics_launch(kind, low, label, valid, true, stat, counts, fpartials, B, h, w, C, scale, dtype, ignore_index, stream);
 }
 
 }  // extern "C"

@@ -88,6 +88,22 @@ class _Meter:
         elif self.counts.device != device:
             self.counts, self.sums = self.counts.to(device), self.sums.to(device)
 
+    @staticmethod
+    def _labelled(pred, gt, valid):
+        """the portable definition of ``update(pred, gt, valid)``: the labelled samples index-selected (``valid`` (B,), non-zero:
+        the sample carries a label for this task; read on the host, as ``functional.upsample_loss_valid_torch`` does).  Returns
+        ``(pred, gt)`` as they are when every sample is labelled, the sub-batch otherwise, ``None`` when there is none."""
+        B = gt.shape[0]
+        flags = torch.as_tensor(valid).reshape(-1)
+        if flags.numel() != B:
+            raise RuntimeError(f"mtlora_amd: valid must have one flag per sample ({B}), got {flags.numel()}")
+        idx = torch.nonzero(flags != 0).reshape(-1)
+        if idx.numel() == B:
+            return pred, gt
+        if idx.numel() == 0:
+            return None
+        return pred.index_select(0, idx.to(pred.device)), gt.index_select(0, idx.to(gt.device))
+
     def _host(self):
         if self.counts is None:
             raise RuntimeError("mtlora_amd: get_score() of a meter that has seen no batch")
@@ -103,7 +119,12 @@ class SegmentationMeter(_Meter):
         super().__init__()
 
     @torch.no_grad()
-    def update(self, pred, gt):
+    def update(self, pred, gt, valid=None):
+        if valid is not None:
+            sel = self._labelled(pred, gt, valid)
+            if sel is None:
+                return
+            pred, gt = sel
         C = self.n_classes
         self._state(gt.device)
         g = gt.reshape(-1)
@@ -116,12 +137,12 @@ class SegmentationMeter(_Meter):
         self.counts.index_add_(0, gi + 2 * C, g_in.long())
         self.counts[3 * C] += valid.sum()
 
-    def update_fused(self, low, gt, scale):
+    def update_fused(self, low, gt, scale, valid=None):
         from . import functional as Fn
         if low.shape[-1] != self.n_classes:
             raise RuntimeError(f"mtlora_amd: {self.name} meter has {self.n_classes} classes, the prediction {low.shape[-1]}")
         self._state(low.device)
-        _, sums = Fn.upsample_metrics("softmax", low, gt, scale, counts=self.counts)
+        _, sums = Fn.upsample_metrics("softmax", low, gt, scale, counts=self.counts, valid=valid)
         return sums[0]
 
     def get_score(self, verbose=True):
@@ -147,7 +168,12 @@ class NormalsMeter(_Meter):
         return torch.where(zero.expand_as(x), torch.zeros_like(x), x / torch.where(zero, torch.ones_like(n), n))
 
     @torch.no_grad()
-    def update(self, pred, gt):
+    def update(self, pred, gt, valid=None):
+        if valid is not None:
+            sel = self._labelled(pred, gt, valid)
+            if sel is None:
+                return
+            pred, gt = sel
         self._state(gt.device)
         p = (2 * pred / 255 - 1).permute(0, 3, 1, 2)
         ok = gt != 255
@@ -161,10 +187,10 @@ class NormalsMeter(_Meter):
         self.counts += torch.stack([m1.sum(), (m1 & (d1 < 11.25)).sum(), (m1 & (d1 < 22.5)).sum(), (m1 & (d1 < 30)).sum(), m2.sum()])
         self.sums += torch.stack([torch.where(m1, d1, z).sum(dtype=torch.float64), torch.where(m2, d2, z).sum(dtype=torch.float64)])
 
-    def update_fused(self, low, gt, scale):
+    def update_fused(self, low, gt, scale, valid=None):
         from . import functional as Fn
         self._state(low.device)
-        _, sums = Fn.upsample_metrics("normals", low, gt, scale, counts=self.counts)
+        _, sums = Fn.upsample_metrics("normals", low, gt, scale, counts=self.counts, valid=valid)
         self.sums += sums[1:3]
         return sums[0]
 
@@ -182,7 +208,9 @@ class NormalsMeter(_Meter):
 
 class SaliencyMeter(_Meter):
     """SaliencyMeterWithBeta (global counts over 19 thresholds) + SaliencyMeterWithNoBeta (per-image tp / fp / fn over 15).
-    counts: [19][tp, predicted, actual]; ``per_image``: one (B, 15, 3) int64 tensor per batch."""
+    counts: [19][tp, predicted, actual]; ``per_image``: one (B, 15, 3) int64 tensor per batch; ``per_image_valid``: per batch,
+    ``None`` (every row counts) or a device copy of the (B,) flags ``update_fused(valid=)`` was given -- the fused launch leaves
+    an unlabelled image's row at zero, and ``get_score()`` drops it (an all-zero row would score a Jaccard of 1)."""
     n_counts = 57
 
     def __init__(self, beta_squared: float = 0.3):
@@ -194,9 +222,15 @@ class SaliencyMeter(_Meter):
     def reset(self):
         super().reset()
         self.per_image = []
+        self.per_image_valid = []
 
     @torch.no_grad()
-    def update(self, pred, gt):
+    def update(self, pred, gt, valid=None):
+        if valid is not None:
+            sel = self._labelled(pred, gt, valid)
+            if sel is None:
+                return
+            pred, gt = sel
         self._state(gt.device)
         B = gt.shape[0]
         p = pred.float().reshape(B, -1) / 255.
@@ -208,6 +242,7 @@ class SaliencyMeter(_Meter):
             tp = (m & gpos).sum(1)
             rows.append(torch.stack([tp, m.sum(1) - tp, gpos.sum(1) - tp], 1))
         self.per_image.append(torch.stack(rows, 1))
+        self.per_image_valid.append(None)
         q = torch.sigmoid(p)
         valid = g != 255
         tg = torch.where(valid, g.long(), torch.zeros_like(g, dtype=torch.long))
@@ -218,14 +253,24 @@ class SaliencyMeter(_Meter):
             cols.append(torch.stack([(f * tg).sum(), f.sum(), ap]))
         self.counts += torch.stack(cols).reshape(-1)
 
-    def update_fused(self, low, gt, scale):
+    def update_fused(self, low, gt, scale, valid=None):
         from . import functional as Fn
         self._state(low.device)
         B = low.shape[0]
-        counts, sums = Fn.upsample_metrics("saliency", low, gt, scale)
+        counts, sums = Fn.upsample_metrics("saliency", low, gt, scale, valid=valid)
         self.counts += counts[:57]
         self.per_image.append(counts[57:57 + 45 * B].view(B, 15, 3))
+        self.per_image_valid.append(None if valid is None else valid.clone())  # (the caller may rewrite its buffer)
         return sums[0]
+
+    def _per_image_rows(self):
+        """(N, 15, 3) on the host: the rows of the labelled images of every batch"""
+        im = torch.cat(self.per_image).cpu()
+        if any(v is not None for v in self.per_image_valid):
+            keep = torch.cat([torch.ones(r.shape[0], dtype=torch.bool) if v is None else v.cpu() != 0
+                              for r, v in zip(self.per_image, self.per_image_valid)])
+            im = im[keep]
+        return im.numpy()
 
     def get_score(self, verbose=True):
         c, _ = self._host()
@@ -234,7 +279,7 @@ class SaliencyMeter(_Meter):
         precision, recall = tp / pp, tp / ap
         fscore = (1 + self.beta_squared) * precision * recall / (self.beta_squared * precision + recall)
         fscore[fscore != fscore] = 0
-        im = torch.cat(self.per_image).cpu().numpy()  # (N, 15, 3)
+        im = self._per_image_rows()  # (N, 15, 3)
         tp, fp, fn = im[..., 0], im[..., 1], im[..., 2]
         union = (tp + fp + fn).astype(float)
         jac = np.where(union == 0, 1.0, tp / np.where(union == 0, 1.0, union))  # jaccard.py:27-28: nothing there, nothing found
@@ -253,7 +298,12 @@ class DepthMeter(_Meter):
     n_counts, n_sums = 1, 2
 
     @torch.no_grad()
-    def update(self, pred, gt):
+    def update(self, pred, gt, valid=None):
+        if valid is not None:
+            sel = self._labelled(pred, gt, valid)
+            if sel is None:
+                return
+            pred, gt = sel
         self._state(gt.device)
         g = gt.reshape(-1)
         p = torch.clamp(pred.reshape(-1), min=1e-9)
@@ -263,10 +313,10 @@ class DepthMeter(_Meter):
         self.sums += torch.stack([torch.where(mask, torch.pow(g - p, 2), z).sum(dtype=torch.float64),
                                   torch.where(mask, torch.pow(torch.log(g) - torch.log(p), 2), z).sum(dtype=torch.float64)])
 
-    def update_fused(self, low, gt, scale):
+    def update_fused(self, low, gt, scale, valid=None):
         from . import functional as Fn
         self._state(low.device)
-        _, sums = Fn.upsample_metrics("l1_masked", low, gt, scale, counts=self.counts)
+        _, sums = Fn.upsample_metrics("l1_masked", low, gt, scale, counts=self.counts, valid=valid)
         self.sums += sums[1:3]
         return sums[0]
 
@@ -282,7 +332,8 @@ class DepthMeter(_Meter):
 
 class EdgeMeter(_Meter):
     """the edge loss on the processed prediction, weighted by the batch's element count (the true edge score, seism's odsF, is
-    computed offline in the reference as well).  sums: numel * loss; ``n``: elements seen."""
+    computed offline in the reference as well).  sums: numel * loss; ``n``: elements seen (a host integer); ``n_dev``: the
+    elements of the batches ``update_fused(valid=)`` saw, |V| H W each, counted on the device and read in ``get_score()``."""
     n_sums = 1
 
     def __init__(self, pos_weight: float = EDGE_POS_WEIGHT):
@@ -292,9 +343,15 @@ class EdgeMeter(_Meter):
     def reset(self):
         super().reset()
         self.n = 0
+        self.n_dev: Optional[torch.Tensor] = None
 
     @torch.no_grad()
-    def update(self, pred, gt):
+    def update(self, pred, gt, valid=None):
+        if valid is not None:
+            sel = self._labelled(pred, gt, valid)
+            if sel is None:
+                return
+            pred, gt = sel
         self._state(gt.device)
         g = gt.reshape(-1).float()
         o = pred.float().reshape(-1) / 255.
@@ -306,17 +363,23 @@ class EdgeMeter(_Meter):
         self.n += g.numel()
         self.sums += loss.double() * g.numel()
 
-    def update_fused(self, low, gt, scale):
+    def update_fused(self, low, gt, scale, valid=None):
         from . import functional as Fn
         self._state(low.device)
-        _, sums = Fn.upsample_metrics("edge", low, gt, scale, pos_weight=self.pos_weight)
-        self.n += gt.numel()
-        self.sums += sums[1:2] * gt.numel()
+        _, sums = Fn.upsample_metrics("edge", low, gt, scale, pos_weight=self.pos_weight, valid=valid)
+        if valid is None:
+            self.n += gt.numel()
+            self.sums += sums[1:2] * gt.numel()
+        else:  # the launch normalised by |V| H W
+            n = (valid != 0).sum() * (gt.numel() // max(gt.shape[0], 1))
+            self.n_dev = n if self.n_dev is None else self.n_dev + n
+            self.sums += sums[1:2] * n
         return sums[0]
 
     def get_score(self, verbose=True):
         _, s = self._host()
-        res = {"loss": s[0] / self.n}
+        n = self.n + (0 if self.n_dev is None else int(self.n_dev.item()))
+        res = {"loss": s[0] / n if n else float("nan")}  # (only batches without a labelled sample: no score)
         if verbose:
             print("\nEdge Detection Evaluation")
             print("Edge Detection Loss %.3f" % res["loss"])
@@ -354,26 +417,41 @@ class PerformanceMeter:
         for t in self.tasks:
             self.meters[t].reset()
 
-    def update(self, pred: Mapping[str, torch.Tensor], gt: Mapping[str, torch.Tensor]):
+    def update(self, pred: Mapping[str, torch.Tensor], gt: Mapping[str, torch.Tensor],
+               valid: Optional[Mapping[str, torch.Tensor]] = None):
+        """``valid`` (partially labelled batches): ``{task: uint8 (B,)}``, non-zero: the sample carries a label for the task; a
+        task without an entry is labelled everywhere.  A task's meter then sees its labelled samples only."""
         for t in self.tasks:
-            self.meters[t].update(pred[t], gt[t])
+            v = None if valid is None else valid.get(t)
+            if v is None:
+                self.meters[t].update(pred[t], gt[t])
+            else:
+                self.meters[t].update(pred[t], gt[t], v)
 
-    def update_task_low(self, t: str, lo: torch.Tensor, lab: torch.Tensor) -> torch.Tensor:
+    def update_task_low(self, t: str, lo: torch.Tensor, lab: torch.Tensor, valid: Optional[torch.Tensor] = None) -> torch.Tensor:
         """one task's meter from its LOW-resolution (B, h, w, C) prediction; returns the task's loss (a device scalar).  Fused
-        under the conditions of ``MultiTaskLoss.task_low`` (GPU, integer scale), else ``update(get_output(interpolate))``."""
+        under the conditions of ``MultiTaskLoss.task_low`` (GPU, integer scale), else ``update(get_output(interpolate))``.
+        ``valid``: this task's uint8 (B,) flags; meter and loss then cover the labelled samples only (fused: the flags are read
+        on the device, nothing comes back to the host)."""
         h, w = lo.shape[1:3]
         H, W = lab.shape[-2:]
         if lo.is_cuda and H % h == 0 and W % w == 0 and H // h == W // w:
-            return self.meters[t].update_fused(lo, lab, H // h)
+            if valid is None:
+                return self.meters[t].update_fused(lo, lab, H // h)
+            return self.meters[t].update_fused(lo, lab, H // h, valid)
         from .mtl_harness import task_loss
         up = F.interpolate(lo.permute(0, 3, 1, 2).float(), (H, W), mode="bilinear")
-        self.meters[t].update(get_output(up, t), lab)
-        return task_loss(t, up, lab)
+        if valid is None:
+            self.meters[t].update(get_output(up, t), lab)
+            return task_loss(t, up, lab)
+        self.meters[t].update(get_output(up, t), lab, valid)
+        return task_loss(t, up, lab, valid=valid)
 
-    def update_low(self, low: Mapping[str, torch.Tensor], gt: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    def update_low(self, low: Mapping[str, torch.Tensor], gt: Mapping[str, torch.Tensor],
+                   valid: Optional[Mapping[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """the fused path: ``low`` is the dict of (B, h, w, C) head outputs of ``model(x, upsample=False)``.  One launch per
-        task, no host sync; returns the per-task losses."""
-        return {t: self.update_task_low(t, low[t], gt[t]) for t in self.tasks}
+        task, no host sync; returns the per-task losses.  ``valid``: ``{task: uint8 (B,)}`` as ``update``."""
+        return {t: self.update_task_low(t, low[t], gt[t], None if valid is None else valid.get(t)) for t in self.tasks}
 
     def get_score(self, verbose: bool = True):
         return {t: self.meters[t].get_score(verbose) for t in self.tasks}

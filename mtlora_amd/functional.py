@@ -1965,11 +1965,19 @@ def upsample_metrics_sizes(kind: str, B: int, h: int, w: int, C: int, scale: int
 
 
 @torch.no_grad()
-def upsample_metrics(kind: str, low, label, scale: int, counts=None, ignore_index: float = 255.0, pos_weight: float = 0.95):
+def upsample_metrics(kind: str, low, label, scale: int, counts=None, ignore_index: float = 255.0, pos_weight: float = 0.95,
+                     valid=None):
     """meter counters and loss of ``F.interpolate(low.permute(0,3,1,2), scale_factor=scale, mode="bilinear")`` against ``label``
     in ONE launch (csrc/metrics.hip; layouts in include/mtlora_hip.h).  ``low`` (B, h, w, C) channels-last fp32 / bf16.
     Returns ``(counts, sums)``: ``counts`` int64 -- the given tensor, ADDED to in place, or a fresh zeroed one -- and ``sums``
-    the kind's float quantities as fp64 (loss first), summed over the tiles' partials in a fixed order.  No host sync."""
+    the kind's float quantities as fp64 (loss first), summed over the tiles' partials in a fixed order.  No host sync.
+
+    ``valid`` (uint8 (B,) on the device, non-zero: the sample carries a label for this task): counters, sums and loss of the
+    labelled sub-batch ``(low[V], label[V])`` through ``mtlora_upsample_metrics_valid`` fed by ``label_stat_valid``; layouts
+    and sizes stay those of the whole batch (an unlabelled image's saliency rows receive nothing).  The kernels read the flags
+    on the device -- a captured call follows the tensor's content at replay time -- and never read the prediction or the label
+    of an unlabelled sample; with no labelled sample ``counts`` is unchanged and every sum is +0.0.  ``None``: today's launch,
+    bit for bit."""
     L.require_gpu(low, label)
     B, h, w, C = low.shape
     H, W = h * scale, w * scale
@@ -1980,7 +1988,19 @@ def upsample_metrics(kind: str, low, label, scale: int, counts=None, ignore_inde
     lo = low.detach().contiguous()
     if lo.dtype not in (torch.float32, torch.bfloat16):
         lo = lo.float()
-    if kind in ("softmax", "normals", "l1_masked"):
+    vflags = None if valid is None else _valid_flags(valid, B, lo.device)
+    if kind not in METRIC_KINDS:
+        raise RuntimeError(f"mtlora_amd: unknown fused metrics kind {kind!r}")
+    if vflags is not None:  # the unmasked launch's words over the labelled samples, then their number |V|
+        if kind == "saliency":
+            sv = label_stat_valid(lab, vflags, 1, ignore_index)
+            stat = torch.cat([sv[:1], saliency_thresholds(lab.device), sv[1:]])
+        elif kind == "edge":
+            stat = torch.cat([torch.full((1,), float(pos_weight), dtype=torch.float32, device=lab.device),
+                              label_stat_valid(lab, vflags, 2, ignore_index)[1:]])
+        else:
+            stat = label_stat_valid(lab, vflags, 0, ignore_index)
+    elif kind in ("softmax", "normals", "l1_masked"):
         stat = label_stat(lab, 0, ignore_index)
     elif kind == "saliency":
         stat = torch.cat([label_stat(lab, 1, ignore_index), saliency_thresholds(lab.device)])
@@ -1995,9 +2015,15 @@ def upsample_metrics(kind: str, low, label, scale: int, counts=None, ignore_inde
         raise RuntimeError(f"mtlora_amd: counts must be a contiguous int64 tensor of at least {ni} elements on {lo.device}")
     nq = METRIC_FLOATS[kind]
     part = torch.empty(max(nfp, nq), dtype=torch.float32, device=lo.device)
-    st = L.lib().mtlora_upsample_metrics(METRIC_KINDS[kind], L.ptr(lo), L.ptr(lab), L.ptr(stat), L.ptr(counts), L.ptr(part), B, h,
-                                         w, C, int(scale), L.dtype_code(lo), float(ignore_index), L.stream_ptr())
-    L.check(st, "mtlora_upsample_metrics")
+    if vflags is None:
+        st = L.lib().mtlora_upsample_metrics(METRIC_KINDS[kind], L.ptr(lo), L.ptr(lab), L.ptr(stat), L.ptr(counts), L.ptr(part), B,
+                                             h, w, C, int(scale), L.dtype_code(lo), float(ignore_index), L.stream_ptr())
+        L.check(st, "mtlora_upsample_metrics")
+    else:
+        st = L.lib().mtlora_upsample_metrics_valid(METRIC_KINDS[kind], L.ptr(lo), L.ptr(lab), L.ptr(vflags), L.ptr(stat),
+                                                   L.ptr(counts), L.ptr(part), B, h, w, C, int(scale), L.dtype_code(lo),
+                                                   float(ignore_index), L.stream_ptr())
+        L.check(st, "mtlora_upsample_metrics_valid")
     if nfp == 0:
         return counts, torch.zeros(nq, dtype=torch.float64, device=lo.device)
     return counts, part[:nfp].view(nq, nfp // nq).sum(1, dtype=torch.float64)

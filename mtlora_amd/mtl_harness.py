@@ -502,7 +502,8 @@ def _task_low(criterion, t, lo, lab, valid):
 
 def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 5.0, reducer=None,
                amp_dtype: Optional[torch.dtype] = torch.bfloat16, fused_loss: bool = True, loss_scaler=None,
-               update_grad: bool = True, meters=None, valid: Optional[Mapping[str, torch.Tensor]] = None):
+               update_grad: bool = True, meters=None, valid: Optional[Mapping[str, torch.Tensor]] = None,
+               performance_meter=None):
     """one reference train step (main.py:329-354): autocast fwd + weighted multi-task loss, backward,
     [gradient all-reduce], clip_grad_norm_(5.0), AdamW, zero_grad.  bf16 autocast needs no GradScaler
     (the reference's scaler exists for its fp16 default: ``loss_scaler``, an ``optim.LossScaler``, scales the loss before
@@ -514,19 +515,42 @@ def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 
     ``meters.update()`` is launched; nothing is read back, and the step computes what it computes without them.
     ``valid`` (``{task: uint8 (B,)}`` on the device, non-zero: the sample carries a label for that task; a task without an entry is
     labelled everywhere): a partially labelled batch.  Each task's loss is its criterion over its labelled samples
-    (``MultiTaskLoss.forward``), 0 with a zero gradient when it has none; the heads still run on all B samples."""
+    (``MultiTaskLoss.forward``), 0 with a zero gradient when it has none; the heads still run on all B samples.
+    ``performance_meter`` (an ``evaluation.PerformanceMeter``): the reference's EVAL_TRAINING (main.py:403-408) -- this step's own
+    outputs, in train mode, also score.  With ``fused_loss`` each task's low-resolution head output goes to
+    ``performance_meter.update_task_low(t, lo.detach(), targets[t], valid.get(t))`` under ``torch.no_grad()``: one more launch per
+    task on that task's stream, whose loss value is discarded; without it the full-resolution predictions go to
+    ``performance_meter.update``.  Loss, gradients, norm and the parameter update are those of the step without a meter, bit for
+    bit."""
     valid = valid or {}
+
+    def scored(t, lo):  # (inside the task's stream)
+        with torch.no_grad():
+            performance_meter.update_task_low(t, lo.detach(), targets[t], valid.get(t))
+        return lo
+
+    if performance_meter is None:  # (the step without a meter issues exactly what it issued)
+        per_task = lambda t, lo: _task_low(criterion, t, lo, targets[t], valid.get(t))
+    else:
+        per_task = lambda t, lo: _task_low(criterion, t, scored(t, lo), targets[t], valid.get(t))
     fused_opt = isinstance(optimizer, FusedOptimizer)
     if loss_scaler is not None and not fused_opt:
         raise TypeError("train_step: loss_scaler needs the HIP optimizer (build_optimizer(impl='hip'))")
     def fwd():
         if fused_loss:  # final upsample + losses (+ their backward) as one kernel per task, inside the task's stream
             if isinstance(model, MultiTaskSwin):
-                return criterion.combine(model(images, upsample=False,
-                                               per_task_fn=lambda t, lo: _task_low(criterion, t, lo, targets[t], valid.get(t))))
+                return criterion.combine(model(images, upsample=False, per_task_fn=per_task))
             low = model(images, upsample=False)
+            for t in (criterion.tasks if performance_meter is not None else ()):
+                scored(t, low[t])
             return criterion.forward_low(low, targets, valid) if valid else criterion.forward_low(low, targets)
-        return criterion(model(images), targets, valid) if valid else criterion(model(images), targets)
+        pred = model(images)
+        if performance_meter is not None:
+            from .evaluation import get_output
+            with torch.no_grad():
+                performance_meter.update({t: get_output(pred[t].detach().float(), t) for t in criterion.tasks}, targets,
+                                         valid or None)
+        return criterion(pred, targets, valid) if valid else criterion(pred, targets)
 
     if images.is_cuda:
         Fn.droppath_begin_step(images.device)  # DropPath factors of the whole step from one draw (functional._DropPathPool)
@@ -571,12 +595,17 @@ def train_step(model, criterion, optimizer, images, targets, clip_grad: float = 
     return loss.detach(), norm
 
 
-def validate_step(model, criterion, meter, images, targets, amp_dtype: Optional[torch.dtype] = torch.bfloat16):
+def validate_step(model, criterion, meter, images, targets, amp_dtype: Optional[torch.dtype] = torch.bfloat16,
+                  valid: Optional[Mapping[str, torch.Tensor]] = None):
     """one batch of the reference's ``validate()`` (main.py:439-528): eval-mode forward under ``torch.no_grad()``, the weighted
     multi-task loss and the meter update.  On a GPU each task's head runs on its side stream as in ``MultiTaskSwin.forward``
     and ends in ONE launch (``meter.update_task_low``: final upsample + get_output + meter + loss, csrc/metrics.hip); the
     full-resolution predictions never exist and nothing is copied to the host.  Returns ``(weighted loss, per-task losses)``
-    as device tensors.  ``model.training`` is restored; parameters, buffers, hooks and the merged state are not touched."""
+    as device tensors.  ``model.training`` is restored; parameters, buffers, hooks and the merged state are not touched.
+    ``valid`` (``{task: uint8 (B,)}`` on the device, as ``train_step``'s; a task without an entry is labelled everywhere): a
+    partially labelled batch.  Each task's meter and loss cover its labelled samples only; the same launch reads the flags on the
+    device, never the prediction or the label of an unlabelled sample, and still nothing comes back to the host."""
+    valid = valid or {}
     was_training = model.training
     model.eval()
     try:
@@ -587,10 +616,10 @@ def validate_step(model, criterion, meter, images, targets, amp_dtype: Optional[
                 if isinstance(model, MultiTaskSwin):
                     conc = images.is_cuda and _TASK_STREAMS and len(model.tasks) > 1 and _streams_allowed()
                     per = model(images, upsample=False, concurrent=conc,
-                                per_task_fn=lambda t, lo: meter.update_task_low(t, lo, targets[t]))
+                                per_task_fn=lambda t, lo: meter.update_task_low(t, lo, targets[t], valid.get(t)))
                 else:
                     low = model(images, upsample=False)
-                    per = {t: meter.update_task_low(t, low[t], targets[t]) for t in criterion.tasks}
+                    per = {t: meter.update_task_low(t, low[t], targets[t], valid.get(t)) for t in criterion.tasks}
             return criterion.combine({t: per[t].float() for t in criterion.tasks})
     finally:
         model.train(was_training)
@@ -598,15 +627,20 @@ def validate_step(model, criterion, meter, images, targets, amp_dtype: Optional[
 
 def validate(model, batches, criterion=None, meter=None, database: str = "PASCALContext",
              amp_dtype: Optional[torch.dtype] = torch.bfloat16, verbose: bool = False):
-    """the reference's ``validate()`` over ``batches`` (an iterable of ``(images, targets)``): ``validate_step`` per batch,
-    ONE ``meter.get_score()`` -- the only device-to-host copy -- at the end.  Returns ``(scores, mean weighted loss)``."""
+    """the reference's ``validate()`` over ``batches`` (an iterable of ``(images, targets)`` or, for partially labelled
+    batches, ``(images, targets, valid)`` with ``valid`` as ``validate_step``'s -- a ``data.DeviceLoader`` batch's
+    ``batch["valid"]``; both forms may mix): ``validate_step`` per batch, ONE ``meter.get_score()`` -- the only device-to-host
+    copy -- at the end.  Returns ``(scores, mean weighted loss)``."""
     from .evaluation import PerformanceMeter
     tasks = list(model.tasks)
     criterion = criterion if criterion is not None else MultiTaskLoss(tasks)
     meter = meter if meter is not None else PerformanceMeter(tasks, database)
     total, n = None, 0
-    for images, targets in batches:
-        loss, _ = validate_step(model, criterion, meter, images, targets, amp_dtype)
+    for batch in batches:
+        if len(batch) not in (2, 3):
+            raise ValueError(f"validate: a batch is (images, targets) or (images, targets, valid), got {len(batch)} items")
+        images, targets = batch[0], batch[1]
+        loss, _ = validate_step(model, criterion, meter, images, targets, amp_dtype, batch[2] if len(batch) == 3 else None)
         total = loss.double() if total is None else total + loss.double()
         n += 1
     scores = meter.get_score(verbose)

@@ -10,6 +10,13 @@ full-res: interpolate + get_output + meter.update + task_loss).  HIP events afte
 
     python tools/bench_eval.py [--config c2] [--batch 32] [--steps 10] [--warmup 3] [--tasks a,b,..] [--out FILE]
 
+    python tools/bench_eval.py --masked [--batch 32] [--steps 10] [--warmup 3] [--inner 20] [--out FILE]
+
+--masked times, instead, `functional.upsample_metrics` alone (label statistic + the k_up_metrics launch + the sum of its partials)
+per task on synthetic bf16 head outputs at the heads' geometry (B x 56 x 56 at scale 8): the unmasked call, `valid=` with every
+sample labelled and `valid=` with every second sample labelled.  Each timed window is --inner calls between two HIP events; the
+three variants alternate inside every one of the --steps rounds, and the median, the minimum and the maximum per call are reported.
+
 Prints one JSON line.  Under `rocprofv3 --kernel-trace --stats -- python tools/bench_eval.py --steps 3` the k_up_metrics
 launches appear next to everything else.
 """
@@ -43,6 +50,58 @@ def timed(fn, steps, warmup):
     return statistics.median(ms), min(ms)
 
 
+MASKED_TASKS = ("semseg", "human_parts", "normals", "sal", "depth", "edge")
+
+
+def masked(a):
+    """the partially labelled launch next to the unmasked one, per task, at the heads' geometry"""
+    from mtlora_amd import functional as Fn
+    from mtlora_amd.evaluation import FUSED_KIND
+    dev = torch.device("cuda:0")
+    B, h, w, S = a.batch or 32, 56, 56, 8
+    tasks = tuple(a.tasks.split(",")) if a.tasks else MASKED_TASKS
+    _, tg = H.synthetic_batch(B, h * S, tasks, seed=1, device=dev)
+    g = torch.Generator().manual_seed(2)
+    flags = {"unmasked": None, "valid_all": torch.ones(B, dtype=torch.uint8, device=dev),
+             "valid_half": (torch.arange(B) % 2 == 0).to(torch.uint8).to(dev)}
+    res = {"mode": "masked", "batch": B, "h": h, "w": w, "scale": S, "dtype": "bf16", "steps": a.steps, "inner": a.inner,
+           "device": torch.cuda.get_device_name(0), "per_task_us": {}}
+    for t in tasks:
+        kind = FUSED_KIND[t]
+        low = torch.randn(B, h, w, H.num_output(t), generator=g).to(dev).to(torch.bfloat16)
+        ni, _ = Fn.upsample_metrics_sizes(kind, B, h, w, low.shape[-1], S)
+        counts = torch.zeros(max(ni, 1), dtype=torch.int64, device=dev)
+
+        def run(v):
+            for _ in range(a.inner):
+                Fn.upsample_metrics(kind, low, tg[t], S, counts=counts, valid=v)
+
+        for v in flags.values():
+            for _ in range(a.warmup):
+                run(v)
+        torch.cuda.synchronize()
+        us = {k: [] for k in flags}
+        for _ in range(a.steps):
+            for k, v in flags.items():  # alternating: a drift of the machine hits the three alike
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                run(v)
+                e1.record()
+                torch.cuda.synchronize()
+                us[k].append(1e3 * e0.elapsed_time(e1) / a.inner)
+        res["per_task_us"][t] = {k: {"median": statistics.median(x), "min": min(x), "max": max(x)} for k, x in us.items()}
+    return res
+
+
+def emit(res, out):
+    line = json.dumps(res)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as fh:
+            fh.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2")
@@ -51,7 +110,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--tasks", default=None)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--masked", action="store_true", help="time upsample_metrics with and without valid= at the heads' geometry")
+    ap.add_argument("--inner", type=int, default=20, help="--masked: calls per timed window")
     a = ap.parse_args()
+    if a.masked:
+        emit(masked(a), a.out)
+        return
     cfg = H.config(a.config)
     tasks = tuple(a.tasks.split(",")) if a.tasks else cfg["tasks"]
     B = a.batch or cfg["batch"]
@@ -98,12 +162,7 @@ def main():
         fused_meter.reset()
         plain_meter.reset()
     res["per_task"] = per
-    line = json.dumps(res)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
-    print(line)
+    emit(res, a.out)
 
 
 if __name__ == "__main__":
