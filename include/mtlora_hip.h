@@ -1161,6 +1161,31 @@ int mtlora_snapshot_pack(const void* dev_table, int64_t n, int64_t n_chunks, voi
 int mtlora_snapshot_unpack(const void* dev_table, int64_t n, int64_t n_chunks, const void* packed, int64_t packed_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rank-aware dense update (added under ABI v12, additive): an update of rank r > min(K, N) is applied as the N x K matrix it is
+ * (reference lora.py:253-284 states the low-rank form  y += s (x A^T) B^T = x (s B A)^T).  For the n <= 1 + MTLORA_MAX_TASKS
+ * updates of one layer, update i with A_i (r_i x K), B_i (N x r_i), all row-major contiguous fp32, and the effective scale
+ *     s_i = scale[i] * (scale_dev && scale_dev[i] ? *scale_dev[i] : 1)
+ * (`scale`: host floats; `scale_dev`: null, or a host array of null-or-device pointers to one float each, read by the kernel --
+ * no host read ever happens):
+ *
+ *   forward    out_i (N x K)   = s_i B_i A_i                    out_i[n][k]   = s_i sum_p B_i[n][p] A_i[p][k]
+ *   backward   dA_i (r_i x K)  = s_i B_i^T Z_i                  dA_i[p][k]    = s_i sum_n B_i[n][p] Z_i[n][k]
+ *              dB_i (N x r_i)  = s_i Z_i A_i^T                  dB_i[n][p]    = s_i sum_k Z_i[n][k] A_i[p][k]
+ *   with Z_i (N x K) the gradient that reached out_i.  A null dA[i] or dB[i] skips that output (the arrays themselves are required).
+ *
+ * One launch per call whatever n and the ranks, which may differ between updates.  Every output element is the fp32 MFMA sum of its
+ * products in a fixed order, scaled once: no atomics, no workspace, no memset, bit-reproducible.  Non-finite inputs propagate as in
+ * a plain fp32 matmul.  Rejected before any launch, in this order: a null array other than scale_dev (MTLORA_ERR_NULL); n outside
+ * 1 .. 1 + MTLORA_MAX_TASKS, N or K outside 1 .. 2^31 - 1, K % 4 != 0, an r_i < 1, 2^31 or more output tiles (MTLORA_ERR_SHAPE); a
+ * null A_i, B_i, out_i or Z_i (MTLORA_ERR_NULL); an A_i, Z_i, out_i or dA_i off 16 bytes, a B_i, dB_i or scale pointer off 4
+ * (MTLORA_ERR_ALIGN); an output that overlaps an input of the call (MTLORA_ERR_UNSUPPORTED).
+ * ------------------------------------------------------------------------------------------ */
+int mtlora_delta_fwd(int n, int64_t N, int64_t K, const int32_t* r, const float* const* A, const float* const* B, const float* scale,
+                     const float* const* scale_dev, float* const* out, void* stream);
+int mtlora_delta_bwd(int n, int64_t N, int64_t K, const int32_t* r, const float* const* A, const float* const* B, const float* scale,
+                     const float* const* scale_dev, const float* const* Z, float* const* dA, float* const* dB, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hardware self-test: writes the lane->element maps of the MFMA / LDS-transpose primitives the
  * kernels rely on into `out` (int32[4096]) so a GPU test can assert them (tests/test_gpu_layouts.py).
  * ------------------------------------------------------------------------------------------ */

@@ -314,6 +314,11 @@ _SIGS = {
     "mtlora_snapshot_check": (c_int, [c_void_p, c_int64, c_int64]),
     "mtlora_snapshot_pack": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "mtlora_snapshot_unpack": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    # rank-aware dense update: n, N, K, r[n], A[n], B[n], scale[n] (host floats), scale_dev[n] (nullable), then the outputs
+    "mtlora_delta_fwd": (c_int, [c_int, c_int64, c_int64, POINTER(c_int32), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_float),
+                                 POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
+    "mtlora_delta_bwd": (c_int, [c_int, c_int64, c_int64, POINTER(c_int32), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_float),
+                                 POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
     "mtlora_selftest_layouts": (c_int, [c_void_p, c_void_p]),
     "mtlora_prof_begin": (c_int, [c_int]),
     "mtlora_prof_end": (c_int, [POINTER(ProfSummary)]),

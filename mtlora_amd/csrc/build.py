@@ -11,9 +11,11 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["window_process.hip", "linear.hip", "attention.hip", "glue.hip", "act_dropout.hip", "layernorm.hip", "loss.hip", "metrics.hip", "predict.hip", "upsample.hip", "reduce.hip", "weight_grad.hip", "selftest.hip", "block.hip", "hid.hip", "optim.hip", "ingest.hip", "augment.hip", "meter.hip", "snapshot.hip"]
+SOURCES = ["window_process.hip", "linear.hip", "attention.hip", "glue.hip", "act_dropout.hip", "layernorm.hip", "loss.hip", "metrics.hip", "predict.hip", "upsample.hip", "reduce.hip", "weight_grad.hip", "selftest.hip", "block.hip", "hid.hip", "optim.hip", "ingest.hip", "augment.hip", "meter.hip", "snapshot.hip", "delta.hip"]
 LIB = os.path.join(HERE, "libmtlora_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
+# per-source additions.  delta.hip: no packed fp32 VALU forms (v_pk_*_f32) -- its epilogue is plain per-element fp32 multiplies
+EXTRA_FLAGS = {"delta.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc():
@@ -39,7 +41,7 @@ def build(force=False, verbose=True):
         o = os.path.join(HERE, src.replace(".hip", ".o"))
         objs.append(o)
         if force or _stale(o, [s] + hdrs):
-            jobs.append([_hipcc()] + FLAGS + ["-c", s, "-o", o])
+            jobs.append([_hipcc()] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-c", s, "-o", o])
     if jobs:
         def run(cmd):
             if verbose:

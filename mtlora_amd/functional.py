@@ -491,6 +491,101 @@ def weight_grad_torch(x: torch.Tensor, dys) -> torch.Tensor:
     return G.t() @ x2
 
 
+# ----------------------------------------------------------------------------------------------
+# rank-aware dense update (lora.py "rank-aware association"): Delta W_i = s_i B_i A_i for the 1 + T updates of a layer, one launch
+# ----------------------------------------------------------------------------------------------
+def delta_torch(As, Bs, scales, scale_devs=None):
+    """portable definition of ``mtlora_delta_fwd``: [s_i B_i A_i], each (N, K), with s_i = scales[i] times the 1-element tensor
+    scale_devs[i] where one is given.  Plain torch in the factors' dtype, any device, differentiable."""
+    out = []
+    for i, (a, b) in enumerate(zip(As, Bs)):
+        s = scales[i] if (scale_devs is None or scale_devs[i] is None) else scales[i] * scale_devs[i].to(a.dtype).reshape(())
+        out.append((b @ a) * s)
+    return out
+
+
+def delta_bwd_torch(As, Bs, scales, Zs, scale_devs=None):
+    """portable definition of ``mtlora_delta_bwd``: ([dA_i], [dB_i]) = ([s_i B_i^T Z_i], [s_i Z_i A_i^T]) for the gradients Z_i (N, K)
+    of the updates (the scales as in ``delta_torch``; they get no gradient here)."""
+    dA, dB = [], []
+    for i, (a, b, z) in enumerate(zip(As, Bs, Zs)):
+        s = scales[i] if (scale_devs is None or scale_devs[i] is None) else scales[i] * scale_devs[i].detach().to(a.dtype).reshape(())
+        dA.append((b.t() @ z) * s)
+        dB.append((z @ a.t()) * s)
+    return dA, dB
+
+
+def delta_ok(As, Bs, scale_devs=None) -> bool:
+    """may the HIP path form these updates?  1 .. MAX_TASKS + 1 of them, every factor (and device scale) a CUDA fp32 contiguous
+    tensor of matching shape, K a multiple of 4, the rows of every A on 16 bytes"""
+    if not 1 <= len(As) <= L.MAX_TASKS + 1 or len(As) != len(Bs):
+        return False
+    K, N = As[0].shape[-1], Bs[0].shape[0]
+    ok = lambda t: t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    return (K % 4 == 0 and all(a.dim() == 2 and b.dim() == 2 and ok(a) and ok(b) and a.shape[0] >= 1 and a.shape == (b.shape[1], K)
+                               and b.shape[0] == N and a.data_ptr() % 16 == 0 for a, b in zip(As, Bs))
+            and all(s is None or (ok(s) and s.numel() == 1) for s in (scale_devs or ())))
+
+
+def _delta_args(As, Bs, scales, scale_devs):
+    n = len(As)
+    return (n, Bs[0].shape[0], As[0].shape[1], (ctypes.c_int32 * n)(*[a.shape[0] for a in As]), L.ptr_array9(As), L.ptr_array9(Bs),
+            (ctypes.c_float * n)(*scales), L.ptr_array9(scale_devs))
+
+
+def delta_fwd(As, Bs, scales, scale_devs=None):
+    """[s_i B_i A_i] by ONE ``mtlora_delta_fwd`` launch (``delta_ok`` inputs): fp32 (N, K) tensors allocated here.  A scale tensor
+    is read on the device -- no host synchronisation, and a captured launch follows it."""
+    L.require_gpu(*As, *Bs, *(scale_devs or ()))
+    if not delta_ok(As, Bs, scale_devs):
+        raise RuntimeError("mtlora_amd: delta_fwd takes 1 .. MAX_TASKS + 1 pairs of contiguous fp32 CUDA factors A (r, K), B (N, r) with "
+                           "K % 4 == 0 and 1-element fp32 scale tensors")
+    N, K = Bs[0].shape[0], As[0].shape[1]
+    out = [torch.empty((N, K), dtype=torch.float32, device=As[0].device) for _ in As]
+    L.check(L.lib().mtlora_delta_fwd(*_delta_args(As, Bs, scales, scale_devs), L.ptr_array9(out), L.stream_ptr()), "mtlora_delta_fwd")
+    return out
+
+
+class DeltaFn(torch.autograd.Function):
+    """(Delta W_0 .. Delta W_n-1) = (s_i B_i A_i), one launch each way (``mtlora_delta_fwd`` / ``_bwd``).  Backward returns dA_i = s_i
+    B_i^T Z_i and dB_i = s_i Z_i A_i^T for the factors that need a gradient, nulls for the rest; an update whose Delta W got no
+    gradient is left out of the launch.  A scale tensor enters the product on the device and gets NO gradient here (the rank-aware
+    form is limited to constant scales, ``MTLoRALinear._rank_aware``).
+    args: n, scales (n floats), scale_devs (n 1-element tensors / None, or None), A_0 .. A_n-1, B_0 .. B_n-1"""
+
+    @staticmethod
+    def forward(ctx, n: int, scales, scale_devs, *factors):
+        As, Bs = [f.detach() for f in factors[:n]], [f.detach() for f in factors[n:]]
+        sd = None if scale_devs is None else [None if s is None else s.detach() for s in scale_devs]
+        out = delta_fwd(As, Bs, scales, sd)
+        ctx.save_for_backward(*As, *Bs, *[s for s in (sd or ()) if s is not None])
+        ctx.n, ctx.scales, ctx.sd_at = n, tuple(scales), [i for i, s in enumerate(sd or ()) if s is not None]
+        ctx.set_materialize_grads(False)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        n = ctx.n
+        saved = ctx.saved_tensors
+        As, Bs = saved[:n], saved[n:2 * n]
+        sd = [None] * n
+        for j, i in enumerate(ctx.sd_at):
+            sd[i] = saved[2 * n + j]
+        need = ctx.needs_input_grad[3:]
+        idx = [i for i in range(n) if gs[i] is not None and (need[i] or need[n + i])]
+        dA, dB = [None] * n, [None] * n
+        if idx:
+            sub = lambda xs: [xs[i] for i in idx]
+            Zs = [_canon_grad(gs[i], (Bs[i].shape[0], As[i].shape[1]), torch.float32) for i in idx]
+            Zs = [z if z.data_ptr() % 16 == 0 else z.clone() for z in Zs]  # (a contiguous view at an odd offset: the kernel reads 16-byte rows)
+            for i in idx:
+                dA[i] = torch.empty_like(As[i]) if need[i] else None
+                dB[i] = torch.empty_like(Bs[i]) if need[n + i] else None
+            L.check(L.lib().mtlora_delta_bwd(*_delta_args(sub(As), sub(Bs), sub(ctx.scales), sub(sd)), L.ptr_array9(Zs),
+                                             L.ptr_array9(sub(dA)), L.ptr_array9(sub(dB)), L.stream_ptr()), "mtlora_delta_bwd")
+        return (None, None, None) + tuple(dA) + tuple(dB)
+
+
 _SG_BYTES = None
 
 

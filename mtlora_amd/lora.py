@@ -49,18 +49,31 @@ class LoRALayer(nn.Module):
 # (Z = dB' or dA', the N x K gradient the library returns) come out of autograd; the identity side gets no gradient (and the
 # library skips that reduction).  MTLORA_RANK_AWARE=0 keeps the low-rank form everywhere (A/B runs).
 RANK_AWARE = os.environ.get("MTLORA_RANK_AWARE", "1") != "0"
+# Delta W and its two gradients can be formed by the library (Fn.DeltaFn: one launch each way for all updates of a layer,
+# csrc/delta.h) wherever the factors qualify (Fn.delta_ok): MTLORA_DELTA_HIP=1, or ``lora.DELTA_HIP = True``.  The ATen matmuls below
+# stay the default of the TRAINING path for now: the kernels are as accurate (tests/test_gpu_delta.py) but round differently, and in
+# fp32 that moves the kink-dominated gradient population of the whole-model c5:256 parity test across its threshold.
+# merge() / unmerge() / state_dict() use the kernel regardless (``_shared_delta``).
+DELTA_HIP = os.environ.get("MTLORA_DELTA_HIP", "0") == "1"
 _eyes: Dict[Any, torch.Tensor] = {}
 
 
+def _delta_hip(As, Bs) -> bool:
+    return DELTA_HIP and Fn.delta_ok(As, Bs)
+
+
 def _delta_factors(As, Bs, scales, K: int, N: int):
-    """effective (A', B') of updates s_i B_i A_i, each N x K: one batched matmul when the ranks agree"""
+    """effective (A', B') of updates s_i B_i A_i, each N x K: one ``Fn.DeltaFn`` launch whatever the ranks where the factors qualify
+    for the HIP path, else one batched matmul when the ranks agree"""
     dev = As[0].device
     key = (min(K, N), dev)
     eye = _eyes.get(key)
     if eye is None:
         eye = _eyes[key] = torch.eye(min(K, N), dtype=torch.float32, device=dev)
     with torch.autocast(dev.type, enabled=False):
-        if len(As) > 1 and len({a.shape[0] for a in As}) == 1:
+        if _delta_hip(As, Bs):
+            dW = list(Fn.DeltaFn.apply(len(As), tuple(float(s) for s in scales), None, *As, *Bs))
+        elif len(As) > 1 and len({a.shape[0] for a in As}) == 1:
             sc = torch.tensor(scales, dtype=torch.float32, device=dev).view(-1, 1, 1) if len(set(scales)) > 1 else scales[0]
             dW = list((torch.bmm(torch.stack([b.float() for b in Bs]), torch.stack([a.float() for a in As])) * sc).unbind(0))
         else:
@@ -183,6 +196,12 @@ class MTLoRALinear(LoRALayer):
 
     def _shared_delta(self) -> torch.Tensor:
         s = self.lora_shared_scale
+        A, B = self.lora_shared_A.detach(), self.lora_shared_B.detach()
+        sd = [s.detach()] if isinstance(s, torch.Tensor) else None
+        if Fn.delta_ok([A], [B], sd):
+            # one launch; a trainable scale is read on the device (no host read: merge / unmerge / state_dict can be captured)
+            with torch.cuda.device(A.device):
+                return Fn.delta_fwd([A], [B], [1.0 if sd else float(s)], sd)[0]
         s = float(s.detach().item()) if isinstance(s, torch.Tensor) else float(s)
         return (self.lora_shared_B.detach().float() @ self.lora_shared_A.detach().float()) * s
 
@@ -405,10 +424,17 @@ class MTLoRALinear(LoRALayer):
         vs, vt = val(ss), [val(s) for s in st]
         if ra_s or any(ra_t):
             K_, N_ = self.linear.in_features, self.linear.out_features
-            if ra_s:
+            idx = [i for i, f in enumerate(ra_t) if f]
+            ra_A, ra_B = ([A_s] if ra_s else []) + [A_t[i] for i in idx], ([B_s] if ra_s else []) + [B_t[i] for i in idx]
+            if ra_s and idx and _delta_hip(ra_A, ra_B):  # the shared update and the tasks' go out as ONE DeltaFn call
+                Ae, Be = _delta_factors(ra_A, ra_B, [vs] + [vt[i] for i in idx], K_, N_)
+                A_s, B_s, r_s, vs = Ae[0], Be[0], min(K_, N_), 1.0
+                for j, i in enumerate(idx):
+                    A_t[i], B_t[i], r_t[i], vt[i] = Ae[1 + j], Be[1 + j], min(K_, N_), 1.0
+                idx = []
+            elif ra_s:
                 (A_s,), (B_s,) = _delta_factors([A_s], [B_s], [vs], K_, N_)
                 r_s, vs = min(K_, N_), 1.0
-            idx = [i for i, f in enumerate(ra_t) if f]
             if idx:
                 Ae, Be = _delta_factors([A_t[i] for i in idx], [B_t[i] for i in idx], [vt[i] for i in idx], K_, N_)
                 for j, i in enumerate(idx):
