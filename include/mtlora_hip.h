@@ -1186,6 +1186,32 @@ int mtlora_delta_bwd(int n, int64_t N, int64_t K, const int32_t* r, const float*
                      const float* const* scale_dev, const float* const* Z, float* const* dA, float* const* dB, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Decoder head in eval mode (added under ABI v12, additive): the whole tail of the reference's HighResolutionHead
+ * (models/seg_hrnet.py:498-526: Conv2d 1x1 -> BatchNorm2d -> ReLU -> Conv2d 1x1) on the (pixels, channels) matrix with the
+ * BatchNorm's RUNNING statistics, where it is the per-channel affine map h -> h * a + c, as one launch:
+ *
+ *     O (M x ncp) = act((X W1^T) .* a + c) W2^T + b2          act = ReLU (relu != 0) or the identity
+ *
+ *   X   (M x ldx)   16-bit (`dtype`: MTLORA_BF16 or MTLORA_F16), row-major, ldx % 8 == 0 (the padded concatenated pixel matrix)
+ *   W1  (Hd x ldx)  dtype of X; columns that meet padding columns of X are zero
+ *   a,c (Hd)        fp32: a = gamma / sqrt(running_var + eps), c = beta + (b1 - running_mean) * a, b1 the first conv's bias
+ *   W2  (ncp x Hd)  dtype of X; ncp = classes rounded up to a multiple of 8, the padding rows zero
+ *   b2  (ncp)       fp32, zero in the padding
+ *   O   (M x ncp)   dtype of X, the layout of the second linear's output
+ *
+ * The Hd-wide intermediate stays on chip (fp32 accumulators, rounded once to `dtype` as the k operand of the second product); X is
+ * read once, O written once.  No atomics, workspace or memset: bit-reproducible and capturable.  A non-finite value in a row of X
+ * makes that row of O non-finite and no other; ReLU keeps a NaN.  Checked in this order, before any launch: dtype outside the three
+ * codes (MTLORA_ERR_DTYPE), MTLORA_F32 (MTLORA_ERR_UNSUPPORTED: fp32 callers keep the separate steps); M == 0 returns MTLORA_OK
+ * without looking further; a null pointer (MTLORA_ERR_NULL); a pointer off 16 bytes (MTLORA_ERR_ALIGN); M < 0, ldx, Hd or ncp < 1,
+ * ldx % 8 or ncp % 8 != 0 (MTLORA_ERR_SHAPE); ldx > 512, Hd % 8 != 0, ncp > 64, 2^38 or more rows (MTLORA_ERR_UNSUPPORTED).
+ * mtlora_head_eval_supported: 1 if the kernel takes the shape and type, else 0 (a pure host call).
+ * ------------------------------------------------------------------------------------------ */
+int mtlora_head_eval_supported(int64_t M, int ldx, int Hd, int ncp, int dtype);
+int mtlora_head_eval_fwd(const void* X, const void* W1, const float* a, const float* c, const void* W2, const float* b2, void* O, int64_t M,
+                         int ldx, int Hd, int ncp, int relu, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hardware self-test: writes the lane->element maps of the MFMA / LDS-transpose primitives the
  * kernels rely on into `out` (int32[4096]) so a GPU test can assert them (tests/test_gpu_layouts.py).
  * ------------------------------------------------------------------------------------------ */

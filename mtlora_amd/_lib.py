@@ -319,6 +319,10 @@ _SIGS = {
                                  POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
     "mtlora_delta_bwd": (c_int, [c_int, c_int64, c_int64, POINTER(c_int32), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_float),
                                  POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
+    # eval-mode decoder head: X, W1, a, c, W2, b2, O, M, ldx, Hd, ncp, relu, dtype, stream
+    "mtlora_head_eval_supported": (c_int, [c_int64, c_int, c_int, c_int, c_int]),
+    "mtlora_head_eval_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                     c_int, c_int, c_void_p]),
     "mtlora_selftest_layouts": (c_int, [c_void_p, c_void_p]),
     "mtlora_prof_begin": (c_int, [c_int]),
     "mtlora_prof_end": (c_int, [POINTER(ProfSummary)]),

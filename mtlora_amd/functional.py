@@ -2491,6 +2491,75 @@ class ConcatUpsampleFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------------------------
+# HRNet head in eval mode: conv1x1 -> BatchNorm (running statistics) -> ReLU -> conv1x1 as ONE launch (csrc/head_eval.hip)
+# ----------------------------------------------------------------------------------------------
+HEAD_EVAL_MAX_LDX, HEAD_EVAL_MAX_NCP = 512, 64
+
+
+def head_eval_torch(x, w1p, a, c, w2p, b2, relu: bool = True):
+    """portable definition of ``mtlora_head_eval_fwd``: act((x w1p^T) * a + c) w2p^T + b2 with a = gamma / sqrt(running_var + eps),
+    c = beta + (b1 - running_mean) a -- the eval-mode BatchNorm of seg_hrnet.py:498-526 as the affine map it is.  Plain torch in the
+    dtype of ``x``, any device."""
+    h = (x @ w1p.t()) * a.to(x.dtype) + c.to(x.dtype)
+    if relu:
+        h = torch.relu(h)
+    return h @ w2p.t() + b2.to(x.dtype)
+
+
+def head_eval_affine(bn, b1, out=None):
+    """(a, c) fp32 of an eval-mode BatchNorm that follows a layer with bias ``b1`` (None: no bias), formed on the device without a
+    host read; ``out``: a pair of buffers to refill in place"""
+    a, c = out if out is not None else (torch.empty_like(bn.running_var, dtype=torch.float32) for _ in range(2))
+    torch.add(bn.running_var.detach().float(), bn.eps, out=a)
+    a.rsqrt_()
+    if bn.weight is not None:
+        a.mul_(bn.weight.detach().float())
+    c.copy_(bn.running_mean.detach())
+    c.neg_()
+    if b1 is not None:
+        c.add_(b1.detach().float())
+    c.mul_(a)
+    if bn.bias is not None:
+        c.add_(bn.bias.detach().float())
+    return a, c
+
+
+def head_eval_ok(x, bn, hd: int, ncp: int, params=()) -> bool:
+    """may ``head_eval`` serve this head?  ``x`` a contiguous 16-bit CUDA (M, ldx) matrix within the kernel's limits (ldx % 8 == 0,
+    ldx <= 512, hd % 8 == 0, ncp % 8 == 0, ncp <= 64), the BatchNorm ``bn`` in eval mode with running statistics, and no gradient
+    wanted: grad mode off, or neither ``x`` nor any of ``params`` requires one"""
+    if not (x.is_cuda and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and x.is_contiguous() and x.data_ptr() % 16 == 0):
+        return False
+    if bn.training or not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or any(q is not None and q.requires_grad for q in params)):
+        return False
+    ldx = x.shape[1]
+    return ldx % 8 == 0 and 0 < ldx <= HEAD_EVAL_MAX_LDX and hd > 0 and hd % 8 == 0 and ncp % 8 == 0 and 0 < ncp <= HEAD_EVAL_MAX_NCP
+
+
+def head_eval(x, w1p, a, c, w2p, b2, relu: bool = True):
+    """O (M, ncp) = act((x w1p^T) * a + c) w2p^T + b2 by ONE ``mtlora_head_eval_fwd`` launch: x (M, ldx) and the weights w1p (Hd, ldx),
+    w2p (ncp, Hd) in one 16-bit dtype, a, c (Hd) and b2 (ncp) fp32, all contiguous CUDA tensors.  The Hd-wide intermediate stays on
+    chip.  A plain call, not an autograd node: it raises if an input requires grad while grad mode is on."""
+    ts = (x, w1p, a, c, w2p, b2)
+    L.require_gpu(*ts)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise RuntimeError("mtlora_amd: head_eval is forward-only (eval mode): call it under torch.no_grad() or with detached inputs")
+    M, ldx = x.shape
+    Hd, ncp = w1p.shape[0], w2p.shape[0]
+    if (x.dtype not in (torch.bfloat16, torch.float16) or w1p.dtype != x.dtype or w2p.dtype != x.dtype or w1p.shape != (Hd, ldx)
+            or w2p.shape != (ncp, Hd) or any(t.dtype != torch.float32 for t in (a, c, b2)) or a.shape != (Hd,) or c.shape != (Hd,)
+            or b2.shape != (ncp,) or not all(t.is_contiguous() for t in ts)):
+        raise RuntimeError("mtlora_amd: head_eval takes contiguous x (M, ldx), w1p (Hd, ldx), w2p (ncp, Hd) of one 16-bit dtype and fp32 "
+                           "a, c (Hd), b2 (ncp)")
+    out = torch.empty((M, ncp), dtype=x.dtype, device=x.device)
+    L.check(L.lib().mtlora_head_eval_fwd(L.ptr(x), L.ptr(w1p), L.ptr(a), L.ptr(c), L.ptr(w2p), L.ptr(b2), L.ptr(out), M, ldx, Hd, ncp,
+                                         int(bool(relu)), L._DT[x.dtype], L.stream_ptr()), "mtlora_head_eval_fwd")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # a run of SwinTransformerBlocks without task outputs: ONE autograd node, one library call per block and direction
 # (mtlora_block_fwd / mtlora_block_bwd, ABI v7)
 # ----------------------------------------------------------------------------------------------

@@ -114,6 +114,9 @@ def mtlora_namespace(tasks: Sequence[str], r_shared=64, r_task=4, scale=4.0, dro
 
 
 # --------------------------------------------------------------------------------------------------
+# the decoder heads in eval mode as one launch each (Fn.head_eval, csrc/head_eval.hip) wherever Fn.head_eval_ok holds:
+# MTLORA_HEAD_EVAL=0, or ``mtl_harness.HEAD_EVAL = False``, keeps the four separate steps
+HEAD_EVAL = os.environ.get("MTLORA_HEAD_EVAL", "1") != "0"
 _TASK_STREAMS = os.environ.get("MTLORA_TASK_STREAMS", "1") != "0"
 # side streams (per-task heads, factor gradients) also while a HIP graph is being captured: the fork / join events become graph
 # dependencies and the replay runs the branches concurrently.  MTLORA_GRAPH_STREAMS=0 captures a single-stream graph.
@@ -159,6 +162,48 @@ class HighResolutionHead(nn.Module):
         self.last_layer = nn.Sequential(nn.Conv2d(c, 4 * c, 1), nn.BatchNorm2d(4 * c, momentum=0.1),
                                         nn.ReLU(inplace=False), nn.Conv2d(4 * c, num_outputs, 1))
 
+    def _head_eval_operands(self, t, col_idx):
+        """(w1p, a, c, w2p, b2) of ``Fn.head_eval`` for the pixel matrix ``t``: the first conv's weight with its columns scattered to
+        the padded channel positions, the eval-mode BatchNorm as the affine pair (a, c), the classifier's weight and bias padded to
+        a multiple of 8 classes.  One set of buffers per (dtype, device, layout), never freed and refilled IN PLACE (a captured
+        HIP graph may hold their addresses: the MTLoRALinear._wcache policy) when a source tensor's ``_version`` or address moved --
+        ``num_batches_tracked`` stands for the running statistics, which the fused training BatchNorm writes through raw pointers
+        -- and on every call while a source is trainable (FusedAdamW moves no ``_version`` either)."""
+        c0, bn, _, c3 = self.last_layer
+        hd, k, nc, ld = c0.out_channels, c0.in_channels, c3.out_channels, t.shape[1]
+        src = (c0.weight, c0.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, c3.weight, c3.bias)
+        ver = tuple(None if q is None else (q._version, q.data_ptr()) for q in src) + (bn.eps, None if col_idx is None else col_idx.data_ptr())
+        key = (t.dtype, t.device, ld)
+        cache = self.__dict__.setdefault("_he_cache", {})
+        hit = cache.get(key)
+        if hit is not None and hit[1][0].is_inference() and not torch.is_inference_mode_enabled():
+            hit = None  # (buffers made under torch.inference_mode() cannot be refilled outside it)
+        if hit is not None and hit[0] == ver and not any(q is not None and q.requires_grad for q in src):
+            return hit[1]
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):
+            if hit is None:
+                ncp = nc + (-nc) % 8
+                z = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=t.device)
+                ops = (z(hd, ld, dt=t.dtype), z(hd), z(hd), z(ncp, hd, dt=t.dtype), z(ncp))
+            else:
+                ops = hit[1]
+            w1p, a, c, w2p, b2 = ops
+            w1 = c0.weight.detach().view(hd, k).to(t.dtype)
+            if col_idx is None:
+                w1p.copy_(w1)
+            else:
+                w1p.index_copy_(1, col_idx, w1)
+            Fn.head_eval_affine(bn, c0.bias, out=(a, c))
+            w2p[:nc].copy_(c3.weight.detach().view(nc, hd))
+            if c3.bias is not None:
+                b2[:nc].copy_(c3.bias.detach())
+        cache[key] = (ver, ops)
+        return ops
+
+    def _apply(self, fn, *a, **k):  # .to() / .cuda(): the operands live on the old device
+        self.__dict__.pop("_he_cache", None)
+        return super()._apply(fn, *a, **k)
+
     def forward(self, x, channels_last_out: bool = False):
         B, _, Hh, Ww = x[0].shape
         c0, bn, _, c3 = self.last_layer
@@ -180,6 +225,13 @@ class HighResolutionHead(nn.Module):
                     self._col_idx = torch.cat([torch.arange(o, o + c) for o, c in zip(offs, chans)]).to(w2d.device)
                     self._col_key = key
                 col_idx = self._col_idx
+            nc = c3.out_channels
+            if HEAD_EVAL and Fn.head_eval_ok(t, bn, c0.out_channels, nc + (-nc) % 8,
+                                             (c0.weight, c0.bias, bn.weight, bn.bias, c3.weight, c3.bias)):
+                # eval mode, no gradient wanted: conv -> BatchNorm (running statistics) -> ReLU -> conv as one launch (csrc/head_eval.hip)
+                o = Fn.head_eval(t, *self._head_eval_operands(t, col_idx), relu=getattr(self, "relu", True))
+                o = (o if o.shape[1] == nc else o[:, :nc].contiguous()).view(B, Hh, Ww, nc)
+                return o if channels_last_out else o.permute(0, 3, 1, 2)
         else:
             cat = torch.cat([x[0]] + [F.interpolate(m, (Hh, Ww), mode="bilinear") for m in x[1:]], 1)
             t = cat.permute(0, 2, 3, 1).reshape(B * Hh * Ww, cat.shape[1])
