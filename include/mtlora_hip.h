@@ -286,7 +286,8 @@ int mtlora_gemm_tn(const void* a, const void* b, float* out, int64_t M, int Na, 
  * out has the same token order as qkv, (.., C).  bias: dense (num_heads, N, N) fp32
  * (table[index] gathered by the host, :202-206).  mask: (nW_per_image, N, N) fp32 or NULL (:209-213).
  * N = ws*ws <= 144 (window sizes up to 12; N <= 64 runs one wave per (window, head), larger windows one workgroup),
- * head_dim == 32 (every Swin variant).  Larger windows return MTLORA_ERR_UNSUPPORTED.
+ * head_dim == 32 (every Swin variant).  Larger windows return MTLORA_ERR_UNSUPPORTED here: 144 < N <= 256 has the
+ * mtlora_window_attn_xl_* entry points below.
  * ------------------------------------------------------------------------------------------ */
 typedef struct mtlora_attn_desc {
     int64_t B;            /* images */
@@ -313,6 +314,27 @@ int mtlora_window_attn_fwd(const mtlora_attn_desc* d, const void* qkv, const flo
 int mtlora_window_attn_bwd(const mtlora_attn_desc* d, const void* qkv, const float* bias, const float* mask,
                            const int32_t* mask_ids, const void* dout, void* dqkv, float* dbias, void* scratch,
                            int64_t scratch_bytes, void* stream);
+
+/* Windows of 13 x 13 to 16 x 16 tokens (144 < N <= 256; window 14 is the natural one for 448 px inputs) have entry points of their
+ * own, with the descriptor, arguments and statuses of the three above: one workgroup of eight waves per (window, head) in the forward,
+ * two launches in the backward (query-owner: dQ, dbias partials, row statistics; key-owner: dK, dV).  The scratch holds the dbias
+ * partials and 3 N floats of row statistics per (window, head).  N <= 144 (served above), window sizes from 17 and head_dim != 32
+ * return MTLORA_ERR_UNSUPPORTED.  There is no attention-dropout form of these kernels. */
+int64_t mtlora_window_attn_xl_bwd_scratch_bytes(const mtlora_attn_desc* d);
+int mtlora_window_attn_xl_fwd(const mtlora_attn_desc* d, const void* qkv, const float* bias, const float* mask,
+                              const int32_t* mask_ids, void* out, void* stream);
+int mtlora_window_attn_xl_bwd(const mtlora_attn_desc* d, const void* qkv, const float* bias, const float* mask,
+                              const int32_t* mask_ids, const void* dout, void* dqkv, float* dbias, void* scratch,
+                              int64_t scratch_bytes, void* stream);
+
+/* The dense bias of such a window without a one-hot matrix.  gather: bias[h][p] = table[index[p]][h] for the N * N positions p = i * N + j
+ * (table: (entries, num_heads) fp32, index: int32).  scatter: dtable[e][h] = sum of dbias[h][p] over the positions with index[p] == e,
+ * given as CSR lists (csr_offsets: entries + 1, csr_positions: N * N, each list in ascending order); the sums are formed in a fixed
+ * order without atomics and every element of dtable is written. */
+int mtlora_rel_bias_gather(const float* table, const int32_t* index, float* bias, int32_t entries, int32_t num_heads, int32_t N,
+                           void* stream);
+int mtlora_rel_bias_scatter(const float* dbias, const int32_t* csr_offsets, const int32_t* csr_positions, float* dtable, int32_t entries,
+                            int32_t num_heads, int32_t N, void* stream);
 
 /* Attention dropout (swin_transformer_mtlora.py:216, `attn_drop` on the softmax output):  P' = keep . P / (1 - p),  out = P' V.
  * The keep bits are generated inside the kernels, forward and backward alike; no mask is stored.  Element (window w, head h,

@@ -185,6 +185,13 @@ _SIGS = {
     "mtlora_window_attn_fwd": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mtlora_window_attn_bwd": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_int64, c_void_p]),
+    # 144 < N <= 256 (windows 13..16): same arguments as the three above
+    "mtlora_window_attn_xl_bwd_scratch_bytes": (c_int64, [POINTER(AttnDesc)]),
+    "mtlora_window_attn_xl_fwd": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mtlora_window_attn_xl_bwd": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_int64, c_void_p]),
+    "mtlora_rel_bias_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mtlora_rel_bias_scatter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mtlora_window_attn_drop_fwd": (c_int, [POINTER(AttnDesc), POINTER(AttnDropout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p]),
     "mtlora_window_attn_drop_bwd": (c_int, [POINTER(AttnDesc), POINTER(AttnDropout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

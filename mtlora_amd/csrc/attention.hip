@@ -930,11 +930,13 @@ __global__ __launch_bounds__(256) void k_dbias_reduce(const float* part, float* 
 
 constexpr int WIDE_MAX_N = 144;  // 64 < N <= 144 (ws 9..12): the multi-wave kernels of attention_wide.h
 
-int check(const mtlora_attn_desc* d) {
+// min_n < N <= max_n: the range of the entry point (the 13 x 13 .. 16 x 16 windows of attention_xl.h have entry points of their own)
+int check(const mtlora_attn_desc* d, int min_n = 0, int max_n = WIDE_MAX_N) {
     if (!d) return MTLORA_ERR_NULL;
     if (!mtl_dtype_in(d->dtype, MTL_DT_ALL)) return MTLORA_ERR_DTYPE;
     if (d->head_dim != HD) return MTLORA_ERR_UNSUPPORTED;
-    if (d->window_size <= 0 || d->window_size * d->window_size > WIDE_MAX_N) return MTLORA_ERR_UNSUPPORTED;
+    if (d->window_size <= 0 || d->window_size > max_n) return MTLORA_ERR_UNSUPPORTED;
+    if (d->window_size * d->window_size > max_n || d->window_size * d->window_size <= min_n) return MTLORA_ERR_UNSUPPORTED;
     if (d->B < 0 || d->H <= 0 || d->W <= 0 || d->num_heads <= 0) return MTLORA_ERR_SHAPE;
     if (d->H % d->window_size || d->W % d->window_size) return MTLORA_ERR_SHAPE;
     if (d->shift < 0 || d->shift >= d->window_size) return MTLORA_ERR_SHAPE;
@@ -993,6 +995,7 @@ AttnParams make_params(const mtlora_attn_desc* d) {
 }
 
 #include "attention_wide.h"
+#include "attention_xl.h"
 
 // the one-wave kernel of a parameter block: plain (AttnParams) or attention dropout (AttnDropParams)
 template <typename T, bool DENSE>
@@ -1113,9 +1116,98 @@ static int attn_bwd_entry(const mtlora_attn_desc* d, const mtlora_attn_dropout* 
     return drop_on ? attn_bwd_run(d, p, dbias, s) : attn_bwd_run(d, static_cast<AttnParams&>(p), dbias, s);
 }
 
+// ---- 144 < N <= 256: the entry points of attention_xl.h ----
+static int xl_check(const mtlora_attn_desc* d) { return check(d, WIDE_MAX_N, XL_MAX_N); }
+
+static void xl_fill(AttnParams& p, const mtlora_attn_desc* d, const void* qkv, const float* bias, const float* mask, const int32_t* mask_ids) {
+    p = make_params(d);
+    p.qkv = qkv;
+    p.bias = bias;
+    p.mask = mask;
+    p.mask_ids = mask_ids;
+    p.mask_value = d->mask_value;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t mtlora_window_attn_xl_bwd_scratch_bytes(const mtlora_attn_desc* d) {
+    if (xl_check(d) != MTLORA_OK) return -1;
+    return xl_part_bytes(d) + xl_stats_bytes(d) + 256;
+}
+
+int mtlora_window_attn_xl_fwd(const mtlora_attn_desc* d, const void* qkv, const float* bias, const float* mask,
+                              const int32_t* mask_ids, void* out, void* stream) {
+    const int st = xl_check(d);
+    if (st != MTLORA_OK) return st;
+    if (mtl_any_null({qkv, bias, out})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({qkv, out})) return MTLORA_ERR_ALIGN;
+    AttnParams p;
+    xl_fill(p, d, qkv, bias, mask, mask_ids);
+    if (p.n_windows == 0) return MTLORA_OK;
+    p.out = out;
+    hipStream_t s = (hipStream_t)stream;
+    const double ab = 4.0 * mtl_elem_size(d->dtype) * (double)p.n_windows * p.N * p.C;
+    MtlProfScope prof(PK_ATTN_FWD, ab, s, ab, 4.0 * (double)p.n_windows * p.N * p.N * p.C);
+    const int wst = xl_fwd(d, p, s);
+    if (wst != MTLORA_OK) return wst;
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
+int mtlora_window_attn_xl_bwd(const mtlora_attn_desc* d, const void* qkv, const float* bias, const float* mask,
+                              const int32_t* mask_ids, const void* dout, void* dqkv, float* dbias, void* scratch,
+                              int64_t scratch_bytes, void* stream) {
+    const int st = xl_check(d);
+    if (st != MTLORA_OK) return st;
+    if (mtl_any_null({qkv, bias, dout, dqkv, dbias, scratch})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({qkv, dout, dqkv, scratch})) return MTLORA_ERR_ALIGN;
+    if (scratch_bytes < xl_part_bytes(d) + xl_stats_bytes(d)) return MTLORA_ERR_WORKSPACE;
+    XlParams p;
+    xl_fill(p, d, qkv, bias, mask, mask_ids);
+    hipStream_t s = (hipStream_t)stream;
+    if (p.n_windows == 0) {
+        mtl_zero_async(dbias, (size_t)p.nH * p.N * p.N * 4, s);
+        return MTLORA_OK;
+    }
+    p.dout = dout;
+    p.dqkv = dqkv;
+    p.dbias_part = reinterpret_cast<float*>(scratch);
+    p.stats = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(scratch) + xl_part_bytes(d));
+    {
+        const double ab = 7.0 * mtl_elem_size(d->dtype) * (double)p.n_windows * p.N * p.C;
+        MtlProfScope prof(PK_ATTN_BWD, ab, s, ab, 10.0 * (double)p.n_windows * p.N * p.N * p.C);
+        const int wst = xl_bwd(d, p, s);
+        if (wst != MTLORA_OK) return wst;
+    }
+    const int total = p.nH * p.N * p.N;
+    hipLaunchKernelGGL(k_dbias_reduce, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, s, (const float*)p.dbias_part, dbias, p.G,
+                       p.nH, p.N);
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
+int mtlora_rel_bias_gather(const float* table, const int32_t* index, float* bias, int32_t entries, int32_t num_heads, int32_t N,
+                           void* stream) {
+    if (mtl_any_null({table, index, bias})) return MTLORA_ERR_NULL;
+    if (entries <= 0 || num_heads <= 0 || N <= 0 || (int64_t)N * N * num_heads >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
+    const int NN = N * N;
+    hipLaunchKernelGGL(k_rel_bias_gather, dim3((unsigned)((NN + 255) / 256)), dim3(256), 0, (hipStream_t)stream, table, index, bias,
+                       entries, num_heads, NN);
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
+int mtlora_rel_bias_scatter(const float* dbias, const int32_t* csr_offsets, const int32_t* csr_positions, float* dtable, int32_t entries,
+                            int32_t num_heads, int32_t N, void* stream) {
+    if (mtl_any_null({dbias, csr_offsets, csr_positions, dtable})) return MTLORA_ERR_NULL;
+    if (entries <= 0 || num_heads <= 0 || N <= 0 || (int64_t)N * N * num_heads >= ((int64_t)1 << 31)) return MTLORA_ERR_SHAPE;
+    hipLaunchKernelGGL(k_rel_bias_scatter, dim3((unsigned)entries), dim3(64), 0, (hipStream_t)stream, dbias, csr_offsets, csr_positions,
+                       dtable, num_heads, N * N);
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
 
 int64_t mtlora_window_attn_bwd_scratch_bytes(const mtlora_attn_desc* d) {
     if (check(d) != MTLORA_OK) return -1;

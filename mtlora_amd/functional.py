@@ -1022,6 +1022,21 @@ class AttnMeta:
         return d
 
 
+ATTN_MAX_N = 256       # tokens per window the attention kernels take (window sizes up to 16)
+ATTN_DROP_MAX_N = 144  # ... and the attention-dropout kernels (window sizes up to 12)
+
+
+def _attn_xl(meta: AttnMeta) -> bool:
+    """windows of 13 x 13 to 16 x 16 tokens run the mtlora_window_attn_xl_* entry points (csrc/attention_xl.h)"""
+    return meta.window_size * meta.window_size > ATTN_DROP_MAX_N
+
+
+def window_attention_supported(window_size: int, head_dim: int, attn_drop: float = 0.0) -> bool:
+    """can the window attention kernels take this shape (with attention dropout ``attn_drop`` in training)?"""
+    n = window_size * window_size
+    return head_dim == 32 and 0 < n <= (ATTN_DROP_MAX_N if attn_drop > 0.0 else ATTN_MAX_N)
+
+
 class WindowAttentionFn(torch.autograd.Function):
     """out = softmax(scale * q k^T + bias[h] + mask[w]) v per (window, head)  (swin_transformer_mtlora.py:194-220).
     qkv: (..., 3C) [3][nH][hd]; bias: (nH, N, N) fp32 dense.  The shift mask is either ``mask_ids`` (nW, N) int32
@@ -1046,6 +1061,9 @@ class WindowAttentionFn(torch.autograd.Function):
         C = meta.num_heads * meta.head_dim
         out = torch.empty(qkv_c.shape[:-1] + (C,), dtype=dt, device=qkv.device)
         d = meta.desc(dt)
+        if p > 0.0 and _attn_xl(meta):
+            raise RuntimeError(f"mtlora_amd: attention dropout (attn_drop = {p}) is limited to windows of at most {ATTN_DROP_MAX_N} tokens "
+                               f"(window size 12); window size {meta.window_size} has {meta.window_size ** 2}.  Set ATTN_DROP_RATE to 0")
         if p > 0.0:
             dr = L.AttnDropout()
             dr.p, dr.seed, dr.seed_offset = p, seed, (0 if _seed_offset is None else _seed_offset.data_ptr())
@@ -1054,9 +1072,10 @@ class WindowAttentionFn(torch.autograd.Function):
             L.check(st, "mtlora_window_attn_drop_fwd")
         else:
             dr = None
-            st = L.lib().mtlora_window_attn_fwd(ctypes.byref(d), L.ptr(qkv_c), L.ptr(bias_c), L.ptr(mask), L.ptr(mask_ids),
-                                                L.ptr(out), L.stream_ptr())
-            L.check(st, "mtlora_window_attn_fwd")
+            name = "mtlora_window_attn_xl_fwd" if _attn_xl(meta) else "mtlora_window_attn_fwd"
+            st = getattr(L.lib(), name)(ctypes.byref(d), L.ptr(qkv_c), L.ptr(bias_c), L.ptr(mask), L.ptr(mask_ids), L.ptr(out),
+                                        L.stream_ptr())
+            L.check(st, name)
         ctx.meta, ctx.drop, ctx.n_drop = meta, dr, len(drop)
         ctx.save_for_backward(qkv_c, bias_c, mask, mask_ids)
         return out
@@ -1068,7 +1087,8 @@ class WindowAttentionFn(torch.autograd.Function):
         dout = dout.to(qkv.dtype).contiguous()
         d = meta.desc(qkv.dtype)
         lib = L.lib()
-        sb = lib.mtlora_window_attn_bwd_scratch_bytes(ctypes.byref(d))
+        xl = "xl_" if _attn_xl(meta) else ""
+        sb = getattr(lib, f"mtlora_window_attn_{xl}bwd_scratch_bytes")(ctypes.byref(d))
         scratch = _scratch(sb, qkv.device, "window attention geometry (B, H, W, window)", meta.B, meta.H, meta.W, meta.window_size)
         dqkv = torch.empty_like(qkv)
         dbias = torch.empty_like(bias)
@@ -1078,10 +1098,53 @@ class WindowAttentionFn(torch.autograd.Function):
                                                  L.stream_ptr())
             L.check(st, "mtlora_window_attn_drop_bwd")
         else:
-            st = lib.mtlora_window_attn_bwd(ctypes.byref(d), L.ptr(qkv), L.ptr(bias), L.ptr(mask), L.ptr(mask_ids),
-                                            L.ptr(dout), L.ptr(dqkv), L.ptr(dbias), L.ptr(scratch), sb, L.stream_ptr())
-            L.check(st, "mtlora_window_attn_bwd")
+            name = f"mtlora_window_attn_{xl}bwd"
+            st = getattr(lib, name)(ctypes.byref(d), L.ptr(qkv), L.ptr(bias), L.ptr(mask), L.ptr(mask_ids), L.ptr(dout), L.ptr(dqkv),
+                                    L.ptr(dbias), L.ptr(scratch), sb, L.stream_ptr())
+            L.check(st, name)
         return (None, dqkv, dbias, None, None) + (None,) * ctx.n_drop
+
+
+def rel_bias_csr(index: torch.Tensor, entries: int):
+    """CSR lists of a ``relative_position_index`` buffer (N, N): ``positions[offsets[e]:offsets[e + 1]]`` are the flat positions
+    i * N + j whose index is ``e``, ascending (a stable sort).  Both int32, on the index's device.  An index outside
+    [0, entries) is an error."""
+    flat = index.reshape(-1).to(torch.int64)
+    if flat.numel() and (int(flat.min()) < 0 or int(flat.max()) >= entries):
+        raise RuntimeError(f"mtlora_amd: relative_position_index has entries outside the bias table's {entries} rows")
+    positions = torch.sort(flat, stable=True).indices
+    offsets = torch.zeros(entries + 1, dtype=torch.int64, device=flat.device)
+    offsets[1:] = torch.cumsum(torch.bincount(flat, minlength=entries), 0)
+    return offsets.to(torch.int32), positions.to(torch.int32)
+
+
+class RelBiasFn(torch.autograd.Function):
+    """bias (nH, N, N) fp32 = table[index] (reference :202-206) by ``mtlora_rel_bias_gather``; the backward sums dbias into the table's
+    rows over the CSR lists of :func:`rel_bias_csr` in a fixed order (``mtlora_rel_bias_scatter``): no one-hot matrix, no atomics.
+    index: (N, N) int32; table: (entries, nH)."""
+
+    @staticmethod
+    def forward(ctx, table, index, offsets, positions):
+        L.require_gpu(table, index, offsets, positions)
+        t = _f32_param(table)
+        entries, nH = t.shape
+        n = index.shape[0]
+        bias = torch.empty(nH, n, n, dtype=torch.float32, device=t.device)
+        st = L.lib().mtlora_rel_bias_gather(L.ptr(t), L.ptr(index), L.ptr(bias), entries, nH, n, L.stream_ptr())
+        L.check(st, "mtlora_rel_bias_gather")
+        ctx.save_for_backward(offsets, positions)
+        ctx.shape, ctx.dtype, ctx.n = (entries, nH), table.dtype, n
+        return bias
+
+    @staticmethod
+    def backward(ctx, dbias):
+        offsets, positions = ctx.saved_tensors
+        entries, nH = ctx.shape
+        g = dbias.float().contiguous()
+        dtable = torch.empty(entries, nH, dtype=torch.float32, device=g.device)
+        st = L.lib().mtlora_rel_bias_scatter(L.ptr(g), L.ptr(offsets), L.ptr(positions), L.ptr(dtable), entries, nH, ctx.n, L.stream_ptr())
+        L.check(st, "mtlora_rel_bias_scatter")
+        return dtable.to(ctx.dtype), None, None, None
 
 
 # ----------------------------------------------------------------------------------------------

@@ -408,7 +408,8 @@ class MultiTaskLoss(nn.Module):
 # --------------------------------------------------------------------------------------------------
 def build_model(img_size=448, tasks=("semseg", "normals", "sal", "human_parts"), embed_dim=96, depths=(2, 2, 6, 2),
                 num_heads=(3, 6, 12, 24), r_shared=64, r_task=4, drop_path_rate=0.2, lora_b_std=0.02, seed=0,
-                freeze=True, num_outputs: Optional[Mapping[str, int]] = None, bias: str = "none", **mt_over) -> MultiTaskSwin:
+                freeze=True, num_outputs: Optional[Mapping[str, int]] = None, bias: str = "none", window_size: int = 7,
+                **mt_over) -> MultiTaskSwin:
     """random-init model of the BASELINE configs: trunc_normal(.02) weights (reference :717-724),
     lora_*_B ~ N(0, lora_b_std) so that the LoRA paths are numerically live, and the reference's
     trainable set (mark_only_lora_as_trainable with every freeze flag False, main.py:257-262).
@@ -420,7 +421,7 @@ def build_model(img_size=448, tasks=("semseg", "normals", "sal", "human_parts"),
     torch.manual_seed(seed)
     mt = mtlora_namespace(tasks, r_shared, r_task, n_stages=len(depths), **mt_over)
     bb = SwinTransformerMTLoRA(img_size=img_size, patch_size=4, in_chans=3, num_classes=0, embed_dim=embed_dim,
-                               depths=list(depths), num_heads=list(num_heads), window_size=7, mlp_ratio=4.0,
+                               depths=list(depths), num_heads=list(num_heads), window_size=window_size, mlp_ratio=4.0,
                                qkv_bias=True, drop_rate=0.0, drop_path_rate=drop_path_rate, ape=False, patch_norm=True,
                                tasks=list(tasks), mtlora=mt)
     model = MultiTaskSwin(bb, tasks, {t: int((num_outputs or {}).get(t, num_output(t))) for t in tasks})

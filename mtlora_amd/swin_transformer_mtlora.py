@@ -288,12 +288,19 @@ class WindowAttention(nn.Module):
         """(nH, N, N) = table[index] (reference :202-206); autograd routes the kernel's dbias into the table.
         On the GPU the gather is a product with a constant one-hot matrix (fp32, outside autocast): same values, and the
         backward is ONE deterministic GEMM  d table^T = dbias (nH x N^2) @ onehot^T  instead of index_put's sort +
-        segmented-reduce kernels."""
+        segmented-reduce kernels.  Windows above 12 x 12 use ``Fn.RelBiasFn`` (a gather kernel and a fixed-order segmented sum)."""
         n = self.window_size[0] * self.window_size[1]
         table = self.relative_position_bias_table
         if not table.is_cuda:
             b = table[self.relative_position_index.view(-1)]
             return b.view(n, n, -1).permute(2, 0, 1).float()
+        if n > Fn.ATTN_DROP_MAX_N:  # windows 13..16: the one-hot matrix would be 112 MB (14) to 252 MB (16) -- two small kernels instead
+            csr = getattr(self, "_rpi_csr", None)
+            if csr is None or csr[0].device != table.device:
+                index = self.relative_position_index.to(table.device)
+                csr = (index.to(torch.int32).contiguous(),) + Fn.rel_bias_csr(index, table.shape[0])
+                self._rpi_csr = csr  # plain attribute, built once per module from ITS index buffer (an edited one keeps working)
+            return Fn.RelBiasFn.apply(table, *csr)
         oh = getattr(self, "_rpi_onehot", None)
         if oh is None or oh.device != table.device:
             oh = _shared_rpi_onehot(self.relative_position_index, self.window_size[0], self.window_size[1], table.shape[0], table.device)
@@ -421,7 +428,8 @@ class SwinTransformerBlock(nn.Module):
                 and type(self.mlp.act) is nn.GELU and getattr(self.mlp.act, "approximate", "none") == "none"
                 and all(isinstance(d, nn.Dropout) for d in (self.mlp.drop, self.attn.proj_drop, self.attn.attn_drop))
                 and C % 8 == 0 and self.mlp.fc1.linear.out_features % 8 == 0
-                and C // self.num_heads == 32 and self.window_size * self.window_size <= 144)
+                and C // self.num_heads == 32 and self.window_size * self.window_size <= 144)  # (the block call's own limit: windows
+        #                                                                     13..16 run on the per-layer path)
 
     def _block_call(self, has_norm1: bool, next_norm, cdtype, x):
         """(BlockCall, flat tensor list) of this block for a ``SwinBlockRunFn`` call, or None when the block cannot run fused NOW.

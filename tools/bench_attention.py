@@ -5,6 +5,10 @@ of its own.
 
     python tools/bench_attention.py [--batch 16] [--iters 20] [--out profiles/attention_wide_bench.txt]   (--out: relative to the repository)
 
+    python tools/bench_attention.py --window 14 [--batch 32] [--out profiles/attention_xl_bench.txt]
+        the window-14 stage shapes of Swin-T / 448 (csrc/attention_xl.h; the 14 x 14 last stage is one unshifted window), and the
+        dense_bias paths at that window: the gather / scatter kernels against the one-hot product
+
     python tools/bench_attention.py --attn-drop 0.1 [--batch 16] [--out profiles/attention_dropout_bench.txt]
         the attention-dropout kernels (csrc/attention_dropout.h) next to the plain ones (p = 0) at the C2 stage shapes (Swin-T / 448,
         window 7) and at one window-12 shape, forward and backward, bf16
@@ -25,7 +29,28 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STAGES = [(96, 4), (48, 8), (24, 16), (12, 32)]  # (H = W, heads) of Swin-B patch4_window12_384
-WS = 12
+STAGES_BY_WINDOW = {12: (STAGES, "Swin-B/384"), 14: ([(112, 3), (56, 6), (28, 12), (14, 24)], "Swin-T/448")}
+WS = 12  # (--window replaces both)
+
+
+def run_bias(iters, rounds):
+    """dense_bias of a window-WS attention module, forward and forward + backward: the module's own path and the one-hot product"""
+    from mtlora_amd import swin_transformer_mtlora as S
+    from oracle import mtlora_oracle as O
+    dev = torch.device("cuda:0")
+    nH, n = STAGES[-1][1], WS * WS
+    m = S.WindowAttention(nH * 32, (WS, WS), nH, mtlora=O.mtlora_config([], r_shared=8, r_task=4, dropout=0.0), layer_idx=0).to(dev)
+    table = m.relative_position_bias_table
+    oh = S._shared_rpi_onehot(m.relative_position_index, WS, WS, table.shape[0], dev)
+    g = torch.randn(nH, n, n, device=dev)
+    row = {"heads": nH}
+    for tag, fn in (("module", m.dense_bias), ("onehot", lambda: (table.float().t() @ oh).view(-1, n, n))):
+        def both():
+            table.grad = None
+            fn().backward(g)
+        row[tag + "_fwd_us"] = _span(lambda: fn().detach(), iters, rounds)
+        row[tag + "_fwd_bwd_us"] = _span(both, iters, rounds)
+    return row
 
 
 def _span(fn, iters, rounds, warmup=3):
@@ -166,9 +191,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=os.path.join("profiles", "attention_wide_bench.txt"))
     ap.add_argument("--child-timeout", type=float, default=150.0, help="seconds each of the two measuring processes may take")
-    ap.add_argument("--child", choices=["hip", "eager", "drop"])
+    ap.add_argument("--child", choices=["hip", "eager", "drop", "bias"])
+    ap.add_argument("--window", type=int, default=12, choices=sorted(STAGES_BY_WINDOW), help="12: Swin-B/384 stages; 14: Swin-T/448 stages")
     ap.add_argument("--attn-drop", type=float, default=0.0, help="time the attention-dropout kernels with this p next to the plain ones")
     a = ap.parse_args()
+    global WS, STAGES
+    WS, (STAGES, model) = a.window, STAGES_BY_WINDOW[a.window]
     if not torch.cuda.is_available():
         raise SystemExit("bench_attention: needs a GPU")
     if a.child == "drop":
@@ -176,14 +204,18 @@ def main():
         return
     if a.attn_drop > 0.0:
         return main_drop(a)
+    if a.child == "bias":
+        print("ROWS " + json.dumps(run_bias(a.iters, a.rounds)))
+        return
     if a.child:
         print("ROWS " + json.dumps(run(a.child, a.batch, a.iters, a.rounds)))
         return
     res = {}
-    for which in ("hip", "eager"):  # one process each, one after the other
+    for which in ("hip", "eager") + (("bias",) if WS > 12 else ()):  # one process each, one after the other
         try:  # a child that does not finish is killed: nothing else is started on the GPU after it
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", which, "--batch", str(a.batch), "--iters", str(a.iters),
-                                "--rounds", str(a.rounds)], capture_output=True, text=True, cwd=ROOT, timeout=a.child_timeout)
+                                "--rounds", str(a.rounds), "--window", str(WS)], capture_output=True, text=True, cwd=ROOT,
+                               timeout=a.child_timeout)
         except subprocess.TimeoutExpired:
             raise SystemExit(f"bench_attention: {which} child did not finish within {a.child_timeout} s")
         line = [l for l in p.stdout.splitlines() if l.startswith("ROWS ")]
@@ -191,7 +223,7 @@ def main():
             raise SystemExit(f"bench_attention: {which} child failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
         res[which] = json.loads(line[0][5:])
     lines = [
-        f"bench_attention: window {WS} x {WS} attention, Swin-B/384 stage shapes, batch {a.batch}, bf16, shifted (stage 3: one window, no shift)",
+        f"bench_attention: window {WS} x {WS} attention, {model} stage shapes, batch {a.batch}, bf16, shifted (stage 3: one window, no shift)",
         f"box: {torch.cuda.get_device_name(0)}, torch {torch.__version__}, HIP {torch.version.hip}; device time by HIP events, "
         f"median of {a.rounds} spans of {a.iters} calls; backward = (forward + backward) - forward",
         "stage  HxW    heads      M      C |  hip fwd us  TB/s(4MC) |  hip bwd us  TB/s(7MC) | eager fwd us  eager bwd us | eager/hip fwd  bwd",
@@ -202,6 +234,11 @@ def main():
         hb, eb = h["fwd_bwd_us"] - h["fwd_us"], e["fwd_bwd_us"] - e["fwd_us"]
         lines.append(f"{k:5d}  {HW:3d}x{HW:<3d} {nH:5d} {M:6d} {C:6d} | {h['fwd_us']:10.1f} {4 * M * C * 2 / h['fwd_us'] / 1e6:10.3f} | "
                      f"{hb:10.1f} {7 * M * C * 2 / hb / 1e6:10.3f} | {e['fwd_us']:12.1f} {eb:12.1f} | {e['fwd_us'] / h['fwd_us']:13.2f} {eb / hb:4.2f}")
+    if "bias" in res:
+        r = res["bias"]
+        mb, ob = r["module_fwd_bwd_us"] - r["module_fwd_us"], r["onehot_fwd_bwd_us"] - r["onehot_fwd_us"]
+        lines.append(f"dense_bias, {r['heads']} heads: gather kernel {r['module_fwd_us']:.1f} us, scatter kernel {mb:.1f} us | one-hot product "
+                     f"{r['onehot_fwd_us']:.1f} us, its backward {ob:.1f} us")
     text = "\n".join(lines) + "\n"
     print(text, end="")
     out = a.out if os.path.isabs(a.out) else os.path.join(ROOT, a.out)  # (relative to the repository, like the children's cwd)
