@@ -1234,6 +1234,54 @@ int mtlora_head_eval_fwd(const void* X, const void* W1, const float* a, const fl
                          int ldx, int Hd, int ncp, int relu, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Patch embedding -- replaces PatchEmbed.forward (reference swin_transformer.py PatchEmbed: Conv2d(kernel = stride = 4) -> flatten
+ * -> transpose -> LayerNorm) and its backward: gather, GEMM and LayerNorm in one launch each way (csrc/patch_embed.hip).
+ *
+ *     y[m, :] = LN(W patch(m) + b)      token m = (b, py, px), patch(m)[c 16 + dy 4 + dx] = img[b, c, 4 py + dy, 4 px + dx]
+ *
+ *   img          (B, in_chans, H, W) contiguous NCHW, `img_dtype`: fp32 or the compute dtype
+ *   W, bias      (E, 16 in_chans), (E): the fp32 masters; W and the image are rounded to the compute dtype `dtype` inside the launch
+ *   gamma, beta  (E) fp32, read when has_norm; without a norm layer y is the biased product
+ *   y            (B H/4 W/4, E) row-major, `out_dtype`: fp32 or the compute dtype
+ *   mean, rstd   per token, fp32, written when has_norm: all the backward needs besides the image and the parameters
+ *
+ * Products accumulate in fp32 (MFMA), bias, mean and variance (two passes) in fp32 on the unrounded accumulators; one rounding to
+ * out_dtype.  The backward has no input gradient.  It forms the pre-norm tile again from the image, then
+ *     dz = rstd (g - mean(g) - xhat mean(g xhat)),  g = dy gamma;   dW = dz^T X,  db = sum dz,  dgamma = sum dy xhat,  dbeta = sum dy
+ * (dz = dy without a norm layer; dz enters the dW product rounded to the compute dtype, the sums are fp32).  grad_flags selects the
+ * outputs: MTLORA_PE_GRAD_PROJ dW and db, MTLORA_PE_GRAD_NORM dgamma and dbeta; outputs not selected are not touched and may be
+ * null; with no flag set the call launches nothing.  dy is (M, E) in out_dtype; dW, db, dgamma, dbeta fp32.  Each workgroup leaves one
+ * partial set in `scratch` and a second launch sums the sets in index order: no atomics, no memset, bit-reproducible, capturable.
+ * max_groups: 0 = the library's grid, else a cap on the workgroups of either launch.
+ *
+ * Supported: patch 4, in_chans <= 4, E a multiple of 32 and at most 256, H and W multiples of 4, fewer than 2^31 tokens (element
+ * offsets are 64-bit).  Checked in this order, before any launch: a null descriptor (MTLORA_ERR_NULL); a dtype field outside the
+ * three codes (MTLORA_ERR_DTYPE); B < 0, another size < 1, max_groups < 0, grad_flags outside 0..3 (MTLORA_ERR_SHAPE); a shape
+ * outside the list above, or an image / output dtype that is neither fp32 nor `dtype` (MTLORA_ERR_UNSUPPORTED); B == 0 returns
+ * MTLORA_OK; a null pointer that the call reads or writes (MTLORA_ERR_NULL); a pointer off 16 bytes (MTLORA_ERR_ALIGN); scratch
+ * smaller than the size query's answer (MTLORA_ERR_WORKSPACE).  The size query answers -1 for a descriptor the entries refuse;
+ * the `supported` query answers 1 or 0 (a pure host call).
+ * ------------------------------------------------------------------------------------------ */
+#define MTLORA_PE_GRAD_PROJ 1
+#define MTLORA_PE_GRAD_NORM 2
+typedef struct mtlora_patch_embed_desc {
+    int64_t B;
+    int32_t in_chans, H, W, patch, E;
+    int32_t img_dtype, dtype, out_dtype; /* mtlora_dtype codes: image, compute, output (and incoming gradient) */
+    int32_t has_norm;
+    float eps;
+    int32_t grad_flags; /* backward: MTLORA_PE_GRAD_* */
+    int32_t max_groups; /* 0 = default grid */
+} mtlora_patch_embed_desc;
+int mtlora_patch_embed_supported(const mtlora_patch_embed_desc* d);
+int mtlora_patch_embed_fwd(const mtlora_patch_embed_desc* d, const void* img, const float* W, const float* bias, const float* gamma,
+                           const float* beta, void* y, float* mean, float* rstd, void* stream);
+int64_t mtlora_patch_embed_bwd_scratch_bytes(const mtlora_patch_embed_desc* d);
+int mtlora_patch_embed_bwd(const mtlora_patch_embed_desc* d, const void* img, const float* W, const float* bias, const float* gamma,
+                           const float* mean, const float* rstd, const void* dy, float* dW, float* db, float* dgamma, float* dbeta,
+                           void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hardware self-test: writes the lane->element maps of the MFMA / LDS-transpose primitives the
  * kernels rely on into `out` (int32[4096]) so a GPU test can assert them (tests/test_gpu_layouts.py).
  * ------------------------------------------------------------------------------------------ */
@@ -1246,7 +1294,7 @@ int mtlora_selftest_layouts(int32_t* out, void* stream);
  * were synchronised.  A process-wide diagnostic switch -- the only global state in the library; the
  * compute entry points stay re-entrant.
  * ------------------------------------------------------------------------------------------ */
-#define MTLORA_PROF_KINDS 24
+#define MTLORA_PROF_KINDS 26
 typedef struct mtlora_prof_summary {
     int64_t count[MTLORA_PROF_KINDS];
     double ms[MTLORA_PROF_KINDS];        /* sum of launch durations */

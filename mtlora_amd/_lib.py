@@ -107,6 +107,14 @@ class MeterSource(Structure):
     _fields_ = [("src", c_void_p), ("dtype", c_int32), ("reserved", c_int32), ("weight", c_double), ("period", c_int64)]
 
 
+class PatchEmbedDesc(Structure):
+    """mtlora_patch_embed_desc: one patch embedding (image -> tokens) call; the dtype fields are F32 / BF16 / F16 codes"""
+    _fields_ = [("B", c_int64), ("in_chans", c_int32), ("H", c_int32), ("W", c_int32), ("patch", c_int32), ("E", c_int32),
+                ("img_dtype", c_int32), ("dtype", c_int32), ("out_dtype", c_int32), ("has_norm", c_int32), ("eps", c_float),
+                ("grad_flags", c_int32), ("max_groups", c_int32)]
+
+
+PE_GRAD_PROJ, PE_GRAD_NORM = 1, 2
 METER_MAX_SLOTS, METER_F32, METER_F64 = 64, 0, 1
 INGEST_MAX_JOBS = 8
 AUGMENT_IMAGE_CUBIC_U8, AUGMENT_CLASS_NEAREST_U8, AUGMENT_NORMALS_CUBIC_F32, AUGMENT_DEPTH_NEAREST_F32 = 0, 1, 2, 3
@@ -124,7 +132,7 @@ LR_COSINE, LR_STEP, LR_LINEAR, LR_MULTISTEP = 1, 2, 3, 4
 ADAMW_SCHED_COUNT_OFFSET, ADAMW_SCHED_LR_OFFSET, ADAMW_SCHED_DEV_BYTES = 344, 352, 480
 SNAPSHOT_CHUNK = 32768  # bytes of the packed buffer one workgroup of mtlora_snapshot_pack / _unpack owns
 
-PROF_KINDS = 24
+PROF_KINDS = 26
 
 
 class ProfSummary(Structure):
@@ -330,6 +338,14 @@ _SIGS = {
     "mtlora_head_eval_supported": (c_int, [c_int64, c_int, c_int, c_int, c_int]),
     "mtlora_head_eval_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                      c_int, c_int, c_void_p]),
+    # patch embedding: desc, img, W, bias, gamma, beta, y, mean, rstd, stream / desc, img, W, bias, gamma, mean, rstd, dy, dW, db,
+    # dgamma, dbeta, scratch, scratch_bytes, stream
+    "mtlora_patch_embed_supported": (c_int, [POINTER(PatchEmbedDesc)]),
+    "mtlora_patch_embed_fwd": (c_int, [POINTER(PatchEmbedDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
+    "mtlora_patch_embed_bwd_scratch_bytes": (c_int64, [POINTER(PatchEmbedDesc)]),
+    "mtlora_patch_embed_bwd": (c_int, [POINTER(PatchEmbedDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mtlora_selftest_layouts": (c_int, [c_void_p, c_void_p]),
     "mtlora_prof_begin": (c_int, [c_int]),
     "mtlora_prof_end": (c_int, [POINTER(ProfSummary)]),

@@ -432,7 +432,9 @@ enum MtlProfKind {
     PK_SUM_LN_ADD_FWD = 21,  // k_sum_ln_add_fwd: n task outputs + y in, out                        (n + 2) tensors of M*N
     PK_SUM_LN_ADD_BWD = 22,  // k_sum_ln_add_bwd (+ k_ln_reduce): dout, n y_t, addends in, n dy_t out
     PK_LABEL_STAT_VALID = 23,  // k_label_stat_valid_part / _combine: label statistic over the labelled samples of a batch
-    PK_COUNT = 24
+    PK_PATCH_EMBED_FWD = 24,   // k_patch_embed_fwd: image in, tokens (+ mean, rstd) out
+    PK_PATCH_EMBED_BWD = 25,   // k_patch_embed_bwd + k_patch_embed_reduce: image, token gradient (+ mean, rstd) in
+    PK_COUNT = 26
 };
 int mtl_prof_start(int kind, double alg_bytes, hipStream_t s, double s8d_bytes = 0.0, double flops = 0.0);
 void mtl_prof_tag(const char* fmt, ...);  // shape note attached to the NEXT record (MTLORA_PROF_DUMP=<file> lists records)

@@ -190,6 +190,8 @@ extern "C" const char* mtlora_prof_kind_name(int kind) {
         case PK_SUM_LN_ADD_FWD: return "k_sum_ln_add_fwd";
         case PK_SUM_LN_ADD_BWD: return "k_sum_ln_add_bwd";
         case PK_LABEL_STAT_VALID: return "k_label_stat_valid";
+        case PK_PATCH_EMBED_FWD: return "k_patch_embed_fwd";
+        case PK_PATCH_EMBED_BWD: return "k_patch_embed_bwd";
         default: return "";
     }
 }

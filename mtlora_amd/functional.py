@@ -2623,6 +2623,129 @@ def head_eval(x, w1p, a, c, w2p, b2, relu: bool = True):
 
 
 # ----------------------------------------------------------------------------------------------
+# patch embedding: gather + GEMM + LayerNorm as ONE launch each way, straight from the NCHW image (csrc/patch_embed.hip)
+# ----------------------------------------------------------------------------------------------
+PATCH_EMBED_MAX_E, PATCH_EMBED_MAX_CHANS = 256, 4
+
+
+def patch_embed_torch(img, weight, bias, gamma, beta, eps, cdtype, out_dtype):
+    """The portable definition of ``mtlora_patch_embed_fwd``: LayerNorm(W patch + b) over the 4 x 4 patches of ``img`` (B, C, H, W),
+    ``weight`` (E, C, 4, 4) or (E, 16 C); ``gamma`` None: no norm layer.  The image and the weight are rounded to ``cdtype``,
+    everything after that is carried in fp32 (in fp64 for an fp64 image) and rounded to ``out_dtype`` once.  Plain torch, any device,
+    differentiable."""
+    acc = torch.float64 if img.dtype == torch.float64 else torch.float32
+    B, C, H, W = img.shape
+    E = weight.shape[0]
+    p = img.to(cdtype).to(acc).reshape(B, C, H // 4, 4, W // 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(B, -1, C * 16)
+    z = p @ weight.to(cdtype).to(acc).reshape(E, -1).t() + bias.to(acc)
+    if gamma is not None:
+        d = z - z.mean(-1, keepdim=True)
+        z = d * torch.rsqrt((d * d).mean(-1, keepdim=True) + eps) * gamma.to(acc) + beta.to(acc)
+    return z.to(out_dtype)
+
+
+def _module_hooked(mod: torch.nn.Module) -> bool:
+    return bool(mod._forward_hooks or mod._forward_pre_hooks or mod._backward_hooks or mod._backward_pre_hooks)
+
+
+def patch_embed_ok(img: torch.Tensor, proj: torch.nn.Module, norm: Optional[torch.nn.Module]) -> bool:
+    """may ``patch_embed`` serve this call?  Answered without a library call: a contiguous CUDA image (B, C <= 4, H, W) in a hot-path
+    dtype that is fp32 or the compute dtype, H and W multiples of 4, fewer than 2^31 tokens; ``proj`` a plain 4 x 4 / stride 4
+    ``nn.Conv2d`` with a bias, fp32 parameters and E a multiple of 32 up to 256; ``norm`` None or an affine ``nn.LayerNorm`` over
+    E; no hooks on either; the image wants no gradient."""
+    if not (img.is_cuda and img.dim() == 4 and img.dtype in _HOT_DTYPES and img.is_contiguous() and img.data_ptr() % 16 == 0):
+        return False
+    if img.requires_grad and torch.is_grad_enabled():  # the kernels form no input gradient: the separate steps do
+        return False
+    if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") not in _HOT_DTYPES:
+        return False
+    B, C, H, W = img.shape
+    if not (type(proj) is torch.nn.Conv2d and proj.kernel_size == (4, 4) and proj.stride == (4, 4) and proj.padding == (0, 0)
+            and proj.dilation == (1, 1) and proj.groups == 1 and proj.bias is not None and proj.in_channels == C
+            and proj.weight.is_cuda and proj.weight.dtype == torch.float32 and proj.bias.dtype == torch.float32
+            and proj.weight.is_contiguous() and not _module_hooked(proj)):
+        return False
+    E = proj.out_channels
+    if norm is not None and not (_ln_module_ok(norm, last_dim_only=True) and norm.normalized_shape[0] == E and norm.weight.is_cuda
+                                 and not _module_hooked(norm)):
+        return False
+    return (img.dtype in (torch.float32, compute_dtype(img)) and 1 <= C <= PATCH_EMBED_MAX_CHANS and H % 4 == 0 and W % 4 == 0
+            and H > 0 and W > 0 and E % 32 == 0 and E <= PATCH_EMBED_MAX_E and B * (H // 4) * (W // 4) < 2 ** 31)
+
+
+def _patch_embed_desc(img, E: int, cdtype, out_dtype, has_norm: bool, eps: float, max_groups: int) -> "L.PatchEmbedDesc":
+    d = L.PatchEmbedDesc()
+    d.B, d.in_chans, d.H, d.W = img.shape
+    d.patch, d.E = 4, E
+    d.img_dtype, d.dtype, d.out_dtype = L._DT[img.dtype], L._DT[cdtype], L._DT[out_dtype]
+    d.has_norm, d.eps, d.max_groups = int(has_norm), float(eps), max_groups
+    return d
+
+
+class PatchEmbedFn(torch.autograd.Function):
+    """y (B, H/4 * W/4, E) = LayerNorm(W patch + b) by one ``mtlora_patch_embed_fwd`` launch; ``gamma`` / ``beta`` None: no norm
+    layer.  ``weight`` (E, C, 4, 4), ``bias``, ``gamma``, ``beta`` are the fp32 masters; their gradients come back in fp32 from
+    ``mtlora_patch_embed_bwd`` (two launches, no atomics, no host read; the scratch is sized by the library's query).  The image gets
+    no gradient.  Saves the image, mean and rstd per token, and the parameters.  ``max_groups``: a cap on the workgroups (0: none).
+    args: img, weight, bias, gamma, beta, eps, cdtype, out_dtype, max_groups"""
+
+    @staticmethod
+    def forward(ctx, img, weight, bias, gamma, beta, eps: float, cdtype, out_dtype, max_groups: int = 0):
+        L.require_gpu(img, weight, bias, gamma, beta)
+        img = img.contiguous()
+        B, _, H, W = img.shape
+        E, M = weight.shape[0], B * (H // 4) * (W // 4)
+        has_norm = gamma is not None
+        w, b = _f32_param(weight), _f32_param(bias)
+        g, be = _ln_affine(gamma, beta) if has_norm else (None, None)
+        d = _patch_embed_desc(img, E, cdtype, out_dtype, has_norm, eps, max_groups)
+        y = torch.empty((B, M // B if B else 0, E), dtype=out_dtype, device=img.device)
+        stats = torch.empty((2, M), dtype=torch.float32, device=img.device) if has_norm else None
+        st = L.lib().mtlora_patch_embed_fwd(ctypes.byref(d), L.ptr(img), L.ptr(w), L.ptr(b), L.ptr(g), L.ptr(be), L.ptr(y),
+                                            L.ptr(stats), L.ptr(None if stats is None else stats[1]), L.stream_ptr())
+        L.check(st, "mtlora_patch_embed_fwd")
+        ctx.save_for_backward(img, w, b, g, stats)
+        ctx.desc, ctx.ME, ctx.wshape = d, (M, E), weight.shape
+        ctx.dtypes = (weight.dtype, bias.dtype, out_dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        img, w, b, g, stats = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d, (M, E) = ctx.desc, ctx.ME
+        want_w, want_n = need[1] or need[2], g is not None and (need[3] or need[4])
+        if not (want_w or want_n):
+            return (None,) * 9
+        d.grad_flags = (L.PE_GRAD_PROJ if want_w else 0) | (L.PE_GRAD_NORM if want_n else 0)
+        dy = _canon_grad(gy, (M, E), ctx.dtypes[2])
+        lib = L.lib()
+        sb = lib.mtlora_patch_embed_bwd_scratch_bytes(ctypes.byref(d))
+        scratch = _scratch(sb, dy.device, "patch embedding shape (B, C, H, W, E)", *img.shape, E, floor=16)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dy.device)  # noqa: E731
+        dw, db = (new(E, w.numel() // E), new(E)) if want_w else (None, None)
+        dg, dbe = (new(E), new(E)) if want_n else (None, None)
+        st = lib.mtlora_patch_embed_bwd(ctypes.byref(d), L.ptr(img), L.ptr(w), L.ptr(b), L.ptr(g), L.ptr(stats),
+                                        L.ptr(None if stats is None else stats[1]), L.ptr(dy), L.ptr(dw), L.ptr(db), L.ptr(dg), L.ptr(dbe),
+                                        L.ptr(scratch), sb, L.stream_ptr())
+        L.check(st, "mtlora_patch_embed_bwd")
+        wdt, bdt, _ = ctx.dtypes
+        return (None, dw.view(ctx.wshape).to(wdt) if need[1] else None, db.to(bdt) if need[2] else None,
+                dg if need[3] else None, dbe if need[4] else None, None, None, None, None)
+
+
+def patch_embed(img: torch.Tensor, proj: torch.nn.Module, norm: Optional[torch.nn.Module], max_groups: int = 0) -> torch.Tensor:
+    """``norm(proj(img).flatten(2).transpose(1, 2))`` for a call ``patch_embed_ok`` accepts.  The compute dtype is the autocast
+    dtype, else the image's; the output dtype is what the separate steps produce: with a norm layer fp32 under autocast (autocast
+    runs layer_norm in fp32) and the image's dtype otherwise, without one the compute dtype."""
+    cdtype = compute_dtype(img)
+    if norm is None:
+        return PatchEmbedFn.apply(img, proj.weight, proj.bias, None, None, 0.0, cdtype, cdtype, max_groups)
+    out_dtype = torch.float32 if torch.is_autocast_enabled() else img.dtype
+    return PatchEmbedFn.apply(img, proj.weight, proj.bias, norm.weight, norm.bias, norm.eps, cdtype, out_dtype, max_groups)
+
+
+# ----------------------------------------------------------------------------------------------
 # a run of SwinTransformerBlocks without task outputs: ONE autograd node, one library call per block and direction
 # (mtlora_block_fwd / mtlora_block_bwd, ABI v7)
 # ----------------------------------------------------------------------------------------------
