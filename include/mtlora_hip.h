@@ -1282,6 +1282,60 @@ int mtlora_patch_embed_bwd(const mtlora_patch_embed_desc* d, const void* img, co
                            void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Decoder front end (added under ABI v12, additive) -- the fixed arithmetic every task's decoder starts with (reference
+ * models/swin_mtl.py:88-135 and models/seg_hrnet.py:498-510): a bias-free 1x1 convolution of each stage's tokens, bilinear
+ * upsampling (align_corners=False) of the coarse maps to the finest resolution, concatenation along channels
+ * (csrc/decoder_front.hip).  Convolution and interpolation commute: the stages are projected at THEIR resolution and interpolated
+ * on chip; the coarse maps never reach memory.
+ *
+ *     out[(b, y, x), off_i + j] = sum_{(qy, qx)} U_i[(y, x), (qy, qx)] sum_k x_i[(b, qy, qx), k] W_i[j, k]        i < n, j < c_i
+ *
+ *   x_i    (B h_i w_i, C_i)  contiguous 16-bit tokens (`dtype`: MTLORA_BF16 or MTLORA_F16), H = s_i h_i, W = s_i w_i, s_0 = 1
+ *   W_i    (c_i, C_i)        the fp32 masters, rounded to `dtype` inside the launch
+ *   U_i                      the bilinear map of integer scale s_i with the clamped source index of mtlora_upsample_cl_fwd
+ *   out    (B H W, ld)       `dtype`; off / ld are the layout of the separate steps (every slice starts at a multiple of 4 channels,
+ *                            c_i rounded up to 4 apart, ld the total rounded up to 8); every column outside the slices is written +0
+ *
+ * Products accumulate in fp32 (MFMA), the taps are applied in fp32, one rounding to `dtype`.  The forward is one launch.  The
+ * backward reads dout (B H W, ld; the columns outside the slices are ignored, whatever they hold), forms gz_i = U_i^T dout_i in
+ * fp32 on chip and, as grad_flags selects, dx_i = gz_i W_i (`dtype`; gz enters the product as a 16-bit pair hi + lo, so that it
+ * is carried to 2^-17) and dW_i = gz_i^T x_i (fp32; gz rounded once to `dtype`, written to `scratch`, summed over row splits in a
+ * fixed order by a second and a third launch).  A null dx[i] skips that stage's input gradient.  Outputs not selected are not
+ * touched and may be null.  No atomics, no memset, no allocation: bit-reproducible and capturable.
+ * band_rows: 0 = the library's choice, else the fine rows per workgroup asked for (the library rounds it to what the scales and
+ * the LDS allow).
+ *
+ * Checked in this order, before any launch: a null descriptor (MTLORA_ERR_NULL); dtype outside the three codes
+ * (MTLORA_ERR_DTYPE); B < 0, n < 2, a size < 1, H or W not s_i h_i / s_i w_i, grad_flags outside 0..3, band_rows < 0
+ * (MTLORA_ERR_SHAPE); MTLORA_F32, n > 4, s_0 != 1, C_i % 16 != 0, c_i % 4 != 0 for i >= 1, c_i > 160, a scale above 8, off / ld
+ * other than the layout above, an LDS image that does not fit, 2^31 or more fine pixels (MTLORA_ERR_UNSUPPORTED); B == 0 returns
+ * MTLORA_OK; a null pointer that the call reads or writes (MTLORA_ERR_NULL); a pointer off 16 bytes (MTLORA_ERR_ALIGN); scratch
+ * smaller than the size query's answer (MTLORA_ERR_WORKSPACE).  The size query answers -1 for a descriptor the entries refuse,
+ * the `supported` query 1 or 0 (a pure host call).
+ * ------------------------------------------------------------------------------------------ */
+#define MTLORA_DF_MAX_STAGES 4
+#define MTLORA_DF_GRAD_X 1
+#define MTLORA_DF_GRAD_W 2
+typedef struct mtlora_decoder_front_desc {
+    int64_t B;
+    int32_t n;     /* stages, 2 .. MTLORA_DF_MAX_STAGES */
+    int32_t dtype; /* compute dtype: MTLORA_BF16 or MTLORA_F16 */
+    int32_t h[MTLORA_DF_MAX_STAGES], w[MTLORA_DF_MAX_STAGES]; /* token grid of stage i */
+    int32_t C[MTLORA_DF_MAX_STAGES], c[MTLORA_DF_MAX_STAGES]; /* channels in, channels out */
+    int32_t s[MTLORA_DF_MAX_STAGES];                          /* integer scale to the finest grid, s[0] = 1 */
+    int32_t off[MTLORA_DF_MAX_STAGES];                        /* first output column of stage i */
+    int32_t ld;                                               /* elements per output row */
+    int32_t grad_flags;                                       /* backward: MTLORA_DF_GRAD_* */
+    int32_t band_rows;                                        /* 0 = default */
+    int32_t reserved;
+} mtlora_decoder_front_desc;
+int mtlora_decoder_front_supported(const mtlora_decoder_front_desc* d);
+int mtlora_decoder_front_fwd(const mtlora_decoder_front_desc* d, const void* const* x, const float* const* W, void* out, void* stream);
+int64_t mtlora_decoder_front_bwd_scratch_bytes(const mtlora_decoder_front_desc* d);
+int mtlora_decoder_front_bwd(const mtlora_decoder_front_desc* d, const void* const* x, const float* const* W, const void* dout,
+                             void* const* dx, float* const* dW, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hardware self-test: writes the lane->element maps of the MFMA / LDS-transpose primitives the
  * kernels rely on into `out` (int32[4096]) so a GPU test can assert them (tests/test_gpu_layouts.py).
  * ------------------------------------------------------------------------------------------ */

@@ -114,7 +114,20 @@ class PatchEmbedDesc(Structure):
                 ("grad_flags", c_int32), ("max_groups", c_int32)]
 
 
+DF_MAX_STAGES = 4
+
+
+class DecoderFrontDesc(Structure):
+    """mtlora_decoder_front_desc: the 1x1 convs + upsample + concat of one decoder; per stage the token grid (h, w), channels in / out
+    (C, c), the integer scale s to the finest grid and the first output column; ld elements per output row"""
+    _fields_ = [("B", c_int64), ("n", c_int32), ("dtype", c_int32), ("h", c_int32 * DF_MAX_STAGES), ("w", c_int32 * DF_MAX_STAGES),
+                ("C", c_int32 * DF_MAX_STAGES), ("c", c_int32 * DF_MAX_STAGES), ("s", c_int32 * DF_MAX_STAGES),
+                ("off", c_int32 * DF_MAX_STAGES), ("ld", c_int32), ("grad_flags", c_int32), ("band_rows", c_int32),
+                ("reserved", c_int32)]
+
+
 PE_GRAD_PROJ, PE_GRAD_NORM = 1, 2
+DF_GRAD_X, DF_GRAD_W = 1, 2
 METER_MAX_SLOTS, METER_F32, METER_F64 = 64, 0, 1
 INGEST_MAX_JOBS = 8
 AUGMENT_IMAGE_CUBIC_U8, AUGMENT_CLASS_NEAREST_U8, AUGMENT_NORMALS_CUBIC_F32, AUGMENT_DEPTH_NEAREST_F32 = 0, 1, 2, 3
@@ -346,6 +359,12 @@ _SIGS = {
     "mtlora_patch_embed_bwd_scratch_bytes": (c_int64, [POINTER(PatchEmbedDesc)]),
     "mtlora_patch_embed_bwd": (c_int, [POINTER(PatchEmbedDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    # decoder front end: desc, x[n], W[n], out, stream / desc, x[n], W[n], dout, dx[n], dW[n], scratch, scratch_bytes, stream
+    "mtlora_decoder_front_supported": (c_int, [POINTER(DecoderFrontDesc)]),
+    "mtlora_decoder_front_fwd": (c_int, [POINTER(DecoderFrontDesc), POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_void_p]),
+    "mtlora_decoder_front_bwd_scratch_bytes": (c_int64, [POINTER(DecoderFrontDesc)]),
+    "mtlora_decoder_front_bwd": (c_int, [POINTER(DecoderFrontDesc), POINTER(c_void_p), POINTER(c_void_p), c_void_p, POINTER(c_void_p),
+                                         POINTER(c_void_p), c_void_p, c_int64, c_void_p]),
     "mtlora_selftest_layouts": (c_int, [c_void_p, c_void_p]),
     "mtlora_prof_begin": (c_int, [c_int]),
     "mtlora_prof_end": (c_int, [POINTER(ProfSummary)]),

@@ -2746,6 +2746,121 @@ def patch_embed(img: torch.Tensor, proj: torch.nn.Module, norm: Optional[torch.n
 
 
 # ----------------------------------------------------------------------------------------------
+# decoder front end: the 1x1 convs of the stages' tokens + bilinear upsample + concat as ONE launch (csrc/decoder_front.hip)
+# ----------------------------------------------------------------------------------------------
+def decoder_front_torch(xs, ws, grids):
+    """The portable definition of ``mtlora_decoder_front_fwd``: ``xs[i]`` (B, h_i w_i, C_i) tokens, ``ws[i]`` (c_i, C_i[, 1, 1])
+    weights, ``grids[i]`` = (h_i, w_i), the first the finest.  ``F.linear`` per stage, ``F.interpolate`` (bilinear) of the coarse maps
+    to grids[0], and a ``cat`` along channels in the layout of ``ConcatUpsampleFn.layout`` with zero pad columns: the
+    (B H W, ld) pixel matrix.  Plain torch in the dtype of ``xs[0]``, any device, differentiable."""
+    B, (H, W) = xs[0].shape[0], grids[0]
+    chans = [w.shape[0] for w in ws]
+    offs, ld = ConcatUpsampleFn.layout(chans)
+    parts, end = [], 0
+    for x, w, (h, wd), o, c in zip(xs, ws, grids, offs, chans):
+        m = torch.nn.functional.linear(x, w.reshape(c, -1).to(x.dtype)).view(B, h, wd, c)
+        if (h, wd) != (H, W):
+            m = torch.nn.functional.interpolate(m.permute(0, 3, 1, 2), (H, W), mode="bilinear").permute(0, 2, 3, 1)
+        parts += [m.new_zeros(B, H, W, o - end), m]
+        end = o + c
+    return torch.cat(parts + [parts[-1].new_zeros(B, H, W, ld - end)], 3).reshape(B * H * W, ld)
+
+
+def decoder_front_desc(B: int, grids, Cs, cs, cdtype, band_rows: int = 0) -> Optional["L.DecoderFrontDesc"]:
+    """the descriptor of a decoder front end with the output layout of ``ConcatUpsampleFn.layout(cs)``; None where the descriptor
+    cannot even state the call (stage count, non-integer or unequal scales, a compute dtype outside the library's)"""
+    n = len(grids)
+    if not (2 <= n <= L.DF_MAX_STAGES and len(Cs) == n and len(cs) == n and cdtype in L._DT) or min(min(g) for g in grids) < 1:
+        return None
+    (H, W), d = grids[0], L.DecoderFrontDesc()
+    if any(H % h or W % w or H // h != W // w for h, w in grids):
+        return None
+    offs, ld = ConcatUpsampleFn.layout(cs)
+    d.B, d.n, d.dtype, d.ld, d.band_rows = B, n, L._DT[cdtype], ld, band_rows
+    for i, (h, w) in enumerate(grids):
+        d.h[i], d.w[i], d.C[i], d.c[i], d.s[i], d.off[i] = h, w, Cs[i], cs[i], H // h, offs[i]
+    return d
+
+
+def decoder_front_ok(xs, convs, grids) -> bool:
+    """may ``decoder_front`` serve this call?  ``xs[i]`` CUDA (B, h_i w_i, C_i) token tensors in a hot-path dtype with a 16-bit
+    compute dtype (their own, or autocast's); ``convs[i]`` plain bias-free 1x1 ``nn.Conv2d`` with contiguous fp32 CUDA weights and
+    no hooks; and a shape ``mtlora_decoder_front_supported`` takes: 2 to 4 stages, equal power-of-two scales up to 8 in x and y,
+    C_i % 16 == 0, c_i % 4 == 0 past the first stage, c_i <= 160, LDS images that fit."""
+    if len(xs) != len(convs) or len(xs) != len(grids) or not xs:
+        return False
+    if not all(x.is_cuda and x.dim() == 3 and x.dtype in _HOT_DTYPES and x.shape[0] == xs[0].shape[0] for x in xs):
+        return False
+    if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") not in _HOT_DTYPES:
+        return False
+    cdtype = compute_dtype(xs[0])
+    if cdtype == torch.float32 or any(x.shape[1] != h * w for x, (h, w) in zip(xs, grids)):
+        return False
+    for x, conv in zip(xs, convs):
+        if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+                and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.in_channels == x.shape[2]
+                and conv.weight.is_cuda and conv.weight.dtype == torch.float32 and conv.weight.is_contiguous()
+                and not _module_hooked(conv)):
+            return False
+    d = decoder_front_desc(xs[0].shape[0], grids, [x.shape[2] for x in xs], [c.out_channels for c in convs], cdtype)
+    return d is not None and L.lib().mtlora_decoder_front_supported(ctypes.byref(d)) == 1
+
+
+class DecoderFrontFn(torch.autograd.Function):
+    """The (B H W, ld) pixel matrix [W_0 x_0 | pad | up(W_1 x_1) | ...] of ``decoder_front_torch`` by ONE ``mtlora_decoder_front_fwd``
+    launch: tokens ``xs[i]`` (B, h_i w_i, C_i) and the fp32 master weights ``ws[i]`` (c_i, C_i[, 1, 1]) in, 16-bit matrix out; the
+    coarse maps stay on chip.  Backward: ``mtlora_decoder_front_bwd`` (three launches, no atomics, no host read) returns dx_i in the
+    dtype of x_i for the tokens that want one and dW_i in the weights' dtype.  Saves the tokens and the weights.
+    args: grids, cdtype, band_rows, x_0 .. x_n-1, w_0 .. w_n-1"""
+
+    @staticmethod
+    def forward(ctx, grids, cdtype, band_rows: int, *args):
+        n = len(grids)
+        L.require_gpu(*args)
+        xs, ws = [_flat(x.detach(), cdtype) for x in args[:n]], [_f32_param(w) for w in args[n:]]
+        B, (H, W) = xs[0].shape[0], grids[0]
+        d = decoder_front_desc(B, grids, [x.shape[2] for x in xs], [w.shape[0] for w in ws], cdtype, band_rows)
+        if d is None:
+            raise RuntimeError(f"mtlora_amd: decoder_front cannot take the grids {tuple(grids)} in {cdtype}")
+        out = torch.empty((B * H * W, d.ld), dtype=cdtype, device=xs[0].device)
+        st = L.lib().mtlora_decoder_front_fwd(ctypes.byref(d), L.ptr_array(xs), L.ptr_array(ws), L.ptr(out), L.stream_ptr())
+        L.check(st, "mtlora_decoder_front_fwd")
+        ctx.save_for_backward(*xs, *ws)
+        ctx.desc, ctx.n, ctx.cdtype = d, n, cdtype
+        ctx.in_meta = [(a.shape, a.dtype) for a in args]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        n, d = ctx.n, ctx.desc
+        xs, ws = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
+        need = ctx.needs_input_grad[3:]
+        want_x, want_w = any(need[:n]), any(need[n:])
+        if not (want_x or want_w):
+            return (None,) * (3 + 2 * n)
+        d.grad_flags = (L.DF_GRAD_X if want_x else 0) | (L.DF_GRAD_W if want_w else 0)
+        dout = _canon_grad(g, (g.numel() // d.ld, d.ld), ctx.cdtype)
+        lib = L.lib()
+        dx = [torch.empty_like(x) if need[i] else None for i, x in enumerate(xs)]
+        dw = [torch.empty_like(w) if want_w else None for w in ws]
+        sb = lib.mtlora_decoder_front_bwd_scratch_bytes(ctypes.byref(d)) if want_w else 0
+        scratch = _scratch(sb, dout.device, "decoder front end (B, n)", d.B, n, floor=16) if want_w else None
+        st = lib.mtlora_decoder_front_bwd(ctypes.byref(d), L.ptr_array(xs), L.ptr_array(ws), L.ptr(dout), L.ptr_array(dx), L.ptr_array(dw),
+                                          L.ptr(scratch), sb, L.stream_ptr())
+        L.check(st, "mtlora_decoder_front_bwd")
+        grads = [None if t is None or not need[i] else t.view(ctx.in_meta[i][0]).to(ctx.in_meta[i][1]) for i, t in enumerate(dx + dw)]
+        return (None, None, None) + tuple(grads)
+
+
+def decoder_front(xs, convs, grids, band_rows: int = 0) -> torch.Tensor:
+    """the concatenated (B H W, ld) pixel matrix of a decoder from the stages' tokens, for a call ``decoder_front_ok`` accepts;
+    the compute dtype is the autocast dtype, else the tokens'.  ``band_rows``: fine rows per workgroup (0: the library's choice)."""
+    cdtype = compute_dtype(xs[0])
+    with torch.autocast("cuda", enabled=False):
+        return DecoderFrontFn.apply(tuple(tuple(g) for g in grids), cdtype, band_rows, *xs, *[c.weight for c in convs])
+
+
+# ----------------------------------------------------------------------------------------------
 # a run of SwinTransformerBlocks without task outputs: ONE autograd node, one library call per block and direction
 # (mtlora_block_fwd / mtlora_block_bwd, ABI v7)
 # ----------------------------------------------------------------------------------------------

@@ -117,6 +117,11 @@ def mtlora_namespace(tasks: Sequence[str], r_shared=64, r_task=4, scale=4.0, dro
 # the decoder heads in eval mode as one launch each (Fn.head_eval, csrc/head_eval.hip) wherever Fn.head_eval_ok holds:
 # MTLORA_HEAD_EVAL=0, or ``mtl_harness.HEAD_EVAL = False``, keeps the four separate steps
 HEAD_EVAL = os.environ.get("MTLORA_HEAD_EVAL", "1") != "0"
+# MTLORA_DECODER_FRONT=1, or ``mtl_harness.DECODER_FRONT = True``: a task's Downsampler hands its head the concatenated pixel matrix
+# from ONE launch (Fn.decoder_front, csrc/decoder_front.hip: 1x1 convs at the stages' resolution, interpolation on chip) wherever
+# Fn.decoder_front_ok holds, with or without a gradient.  Off by default: the coarse maps are then no longer rounded to
+# 16 bits before the interpolation, and the existing suite's bounds were calibrated on the separate steps.
+DECODER_FRONT = os.environ.get("MTLORA_DECODER_FRONT", "0") == "1"
 _TASK_STREAMS = os.environ.get("MTLORA_TASK_STREAMS", "1") != "0"
 # side streams (per-task heads, factor gradients) also while a HIP graph is being captured: the fork / join events become graph
 # dependencies and the replay runs the branches concurrently.  MTLORA_GRAPH_STREAMS=0 captures a single-stream graph.
@@ -125,6 +130,14 @@ _GRAPH_STREAMS = os.environ.get("MTLORA_GRAPH_STREAMS", "1") != "0"
 
 def _streams_allowed() -> bool:
     return _GRAPH_STREAMS or not torch.cuda.is_current_stream_capturing()
+
+
+class DecoderFront:
+    """what a Downsampler hands its head when ``Fn.decoder_front`` has already formed the head's input: the (B H W, ld) pixel matrix
+    ``t`` in the layout of ``Fn.ConcatUpsampleFn.layout(chans)``"""
+
+    def __init__(self, t, B, H, W, chans):
+        self.t, self.B, self.H, self.W, self.chans = t, B, H, W, list(chans)
 
 
 class Downsampler(nn.Module):
@@ -141,6 +154,10 @@ class Downsampler(nn.Module):
                 setattr(self, f"downsample_{i}", nn.Conv2d(d, c, 1, bias=bias))
 
     def forward(self, feats):
+        if DECODER_FRONT and self.enabled and len(feats) == len(self.input_res):
+            convs, grids = [getattr(self, f"downsample_{i}") for i in range(len(feats))], [(r, r) for r in self.input_res]
+            if Fn.decoder_front_ok(feats, convs, grids):
+                return DecoderFront(Fn.decoder_front(feats, convs, grids), feats[0].shape[0], *grids[0], [c.out_channels for c in convs])
         maps = []
         for i, (f, r, d) in enumerate(zip(feats, self.input_res, self.dims)):
             if self.enabled:
@@ -205,18 +222,23 @@ class HighResolutionHead(nn.Module):
         return super()._apply(fn, *a, **k)
 
     def forward(self, x, channels_last_out: bool = False):
-        B, _, Hh, Ww = x[0].shape
         c0, bn, _, c3 = self.last_layer
         w2d = c0.weight.view(c0.out_channels, c0.in_channels)
-        xc = [m.permute(0, 2, 3, 1) for m in x]  # the Downsampler's maps are channels-last views
-        chans = [t.shape[3] for t in xc]
-        if (x[0].is_cuda and all(t.is_contiguous() for t in xc) and all(c % 4 == 0 for c in chans[1:])
+        front = x if isinstance(x, DecoderFront) else None  # the Downsampler formed the concatenated matrix already (DECODER_FRONT)
+        if front is not None:
+            B, Hh, Ww, chans = front.B, front.H, front.W, front.chans
+        else:
+            B, _, Hh, Ww = x[0].shape
+            xc = [m.permute(0, 2, 3, 1) for m in x]  # the Downsampler's maps are channels-last views
+            chans = [t.shape[3] for t in xc]
+        if front is not None or (
+                x[0].is_cuda and all(t.is_contiguous() for t in xc) and all(c % 4 == 0 for c in chans[1:])
                 and len({t.dtype for t in xc}) == 1 and xc[0].dtype in (torch.float32, torch.bfloat16, torch.float16)
                 and all(Hh % t.shape[1] == 0 and Ww % t.shape[2] == 0 and Hh // t.shape[1] == Ww // t.shape[2] for t in xc)):
             # upsample kernels write straight into the channel slices of the concatenated pixel matrix (padded so that
             # every slice starts at a multiple of 4 channels and rows are 16-byte aligned); the 1x1 conv weight gets the
             # matching zero columns
-            t = Fn.ConcatUpsampleFn.apply(*xc)
+            t = front.t if front is not None else Fn.ConcatUpsampleFn.apply(*xc)
             offs, ld = Fn.ConcatUpsampleFn.layout(chans)
             col_idx = None
             if ld != w2d.shape[1]:  # the weight's columns are scattered to the padded channel positions INSIDE the linear Function
