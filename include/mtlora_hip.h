@@ -1336,6 +1336,51 @@ int mtlora_decoder_front_bwd(const mtlora_decoder_front_desc* d, const void* con
                              void* const* dx, float* const* dW, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Patch merging (added under ABI v12, additive) -- PatchMerging.forward (reference swin_transformer_mtlora.py:429-481: 2x2
+ * neighbourhood concat -> LayerNorm(4C) -> bias-free Linear(4C -> 2C)) of n independent token streams and its backward; the
+ * normalised (rows, 4C) matrix and its gradient never reach memory (csrc/patch_merge.hip).
+ *
+ *     y[m, :] = round(LN_{4C}(row(m)) gamma + beta) W^T        merged row m = (stream, b, i, j), stream-major;
+ *     row(m) = [x(2i, 2j), x(2i+1, 2j), x(2i, 2j+1), x(2i+1, 2j+1)]: four contiguous C-vectors of the stream's (B, H W, C) tensor
+ *
+ *   x[k]         n contiguous (B, H W, C) token tensors, `x_dtype`: fp32 or the compute dtype
+ *   gamma, beta  (4C) fp32;  W (2C, 4C) fp32, the master, rounded to `dtype` inside the launches
+ *   y            (n B H/2 W/2, 2C) row-major in `dtype` (MTLORA_BF16 or MTLORA_F16)
+ *   mean, rstd   per merged row, fp32 (two passes over the row in registers): all the backward needs besides x and the parameters
+ *
+ * The statistics are fp32, the normalised row is rounded to `dtype` once, the product accumulates in fp32 (MFMA), one rounding to
+ * `dtype`.  The forward is one launch.  The backward is three: dx[k] (x_dtype, every element of every stream written once) =
+ * rstd (g gamma - mean(g gamma) - xhat mean(g gamma xhat)) with g = dy W formed on chip, and the per-workgroup column sums of
+ * dgamma = sum g xhat, dbeta = sum g; the row-split partials of dW = dy^T z with z rebuilt as the forward rounded it; a last launch
+ * that sums both sets of partials in index order.  dy is (rows, 2C) in `dtype`; dW, dgamma, dbeta are fp32 and may each be null
+ * (not formed / not written).  No atomics, no memset, no allocation: bit-reproducible and capturable.
+ * max_groups: 0 = the library's grids, else a cap on the workgroups of the persistent launches (and one row split for dW).
+ *
+ * Supported: C a multiple of 32 with 4C <= 2048, H and W even, n <= MTLORA_PM_MAX_STREAMS, fewer than 2^31 - 4096 merged rows.
+ * Checked in this order, before any launch: a null descriptor (MTLORA_ERR_NULL); a dtype field outside the three codes
+ * (MTLORA_ERR_DTYPE); B < 0, n or another size < 1, max_groups < 0 (MTLORA_ERR_SHAPE); `dtype` MTLORA_F32, x_dtype neither fp32
+ * nor `dtype`, a shape outside the list above (MTLORA_ERR_UNSUPPORTED); zero rows return MTLORA_OK; a null pointer that the call
+ * reads or writes (MTLORA_ERR_NULL); a pointer off 16 bytes (MTLORA_ERR_ALIGN); scratch smaller than the size query's answer
+ * (MTLORA_ERR_WORKSPACE).  The size query answers -1 for a descriptor the entries refuse.
+ * ------------------------------------------------------------------------------------------ */
+#define MTLORA_PM_MAX_STREAMS 9
+typedef struct mtlora_patch_merge_desc {
+    int64_t B;        /* images per stream */
+    int32_t n;        /* streams, 1 .. MTLORA_PM_MAX_STREAMS */
+    int32_t H, W, C;  /* token grid and channels of the input */
+    int32_t x_dtype, dtype; /* mtlora_dtype codes: input rows (and dx), compute (y, dy) */
+    float eps;
+    int32_t max_groups; /* 0 = default grids */
+    int32_t reserved;
+} mtlora_patch_merge_desc;
+int mtlora_patch_merge_fwd(const mtlora_patch_merge_desc* d, const void* const* x, const float* gamma, const float* beta, const float* W,
+                           void* y, float* mean, float* rstd, void* stream);
+int64_t mtlora_patch_merge_bwd_scratch_bytes(const mtlora_patch_merge_desc* d);
+int mtlora_patch_merge_bwd(const mtlora_patch_merge_desc* d, const void* const* x, const float* gamma, const float* beta, const float* W,
+                           const float* mean, const float* rstd, const void* dy, void* const* dx, float* dW, float* dgamma, float* dbeta,
+                           void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hardware self-test: writes the lane->element maps of the MFMA / LDS-transpose primitives the
  * kernels rely on into `out` (int32[4096]) so a GPU test can assert them (tests/test_gpu_layouts.py).
  * ------------------------------------------------------------------------------------------ */

@@ -114,6 +114,12 @@ class PatchEmbedDesc(Structure):
                 ("grad_flags", c_int32), ("max_groups", c_int32)]
 
 
+class PatchMergeDesc(Structure):
+    """mtlora_patch_merge_desc: PatchMerging of n streams of (B, H W, C) tokens; x_dtype fp32 or the compute dtype ``dtype``"""
+    _fields_ = [("B", c_int64), ("n", c_int32), ("H", c_int32), ("W", c_int32), ("C", c_int32), ("x_dtype", c_int32),
+                ("dtype", c_int32), ("eps", c_float), ("max_groups", c_int32), ("reserved", c_int32)]
+
+
 DF_MAX_STAGES = 4
 
 
@@ -365,6 +371,13 @@ _SIGS = {
     "mtlora_decoder_front_bwd_scratch_bytes": (c_int64, [POINTER(DecoderFrontDesc)]),
     "mtlora_decoder_front_bwd": (c_int, [POINTER(DecoderFrontDesc), POINTER(c_void_p), POINTER(c_void_p), c_void_p, POINTER(c_void_p),
                                          POINTER(c_void_p), c_void_p, c_int64, c_void_p]),
+    # patch merging: desc, x[n], gamma, beta, W, y, mean, rstd, stream / desc, x[n], gamma, beta, W, mean, rstd, dy, dx[n], dW, dgamma,
+    # dbeta, scratch, scratch_bytes, stream
+    "mtlora_patch_merge_fwd": (c_int, [POINTER(PatchMergeDesc), POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
+    "mtlora_patch_merge_bwd_scratch_bytes": (c_int64, [POINTER(PatchMergeDesc)]),
+    "mtlora_patch_merge_bwd": (c_int, [POINTER(PatchMergeDesc), POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mtlora_selftest_layouts": (c_int, [c_void_p, c_void_p]),
     "mtlora_prof_begin": (c_int, [c_int]),
     "mtlora_prof_end": (c_int, [POINTER(ProfSummary)]),

@@ -2746,6 +2746,118 @@ def patch_embed(img: torch.Tensor, proj: torch.nn.Module, norm: Optional[torch.n
 
 
 # ----------------------------------------------------------------------------------------------
+# patch merging: 2x2 gather + LayerNorm(4C) + Linear(4C -> 2C) of n streams as ONE launch, three backward (csrc/patch_merge.hip)
+# ----------------------------------------------------------------------------------------------
+PATCH_MERGE_MAX_K, PATCH_MERGE_MAX_STREAMS = 2048, 9
+
+
+def patch_merge_torch(xs, gamma, beta, weight, eps, H, W, cdtype):
+    """The portable definition of ``mtlora_patch_merge_fwd``: per stream ``xs[k]`` (B, H*W, C) the rows [x(2i, 2j), x(2i+1, 2j),
+    x(2i, 2j+1), x(2i+1, 2j+1)], LayerNorm over 4C, the result and ``weight`` (2C, 4C) rounded to ``cdtype``, their product rounded
+    to ``cdtype``; the n outputs stacked stream-major: (n*B, H*W/4, 2C).  Carried in fp32, in fp64 for fp64 streams (the output
+    then stays fp64).  Plain torch, any device, differentiable."""
+    acc = torch.float64 if xs[0].dtype == torch.float64 else torch.float32
+    B, _, C = xs[0].shape
+    x = torch.stack([t.to(acc) for t in xs]).view(len(xs) * B, H // 2, 2, W // 2, 2, C)
+    rows = x.permute(0, 1, 3, 4, 2, 5).reshape(len(xs) * B, (H // 2) * (W // 2), 4 * C)  # (.., dx, dy, C): the reference's cat order
+    d = rows - rows.mean(-1, keepdim=True)
+    z = d * torch.rsqrt((d * d).mean(-1, keepdim=True) + eps) * gamma.to(acc) + beta.to(acc)
+    if acc == torch.float64:  # rounding is not differentiable: the fp64 form is the exact map
+        return z @ weight.to(acc).t()
+    y = z.to(cdtype).to(acc) @ weight.to(cdtype).to(acc).t()
+    return y.to(cdtype)
+
+
+def patch_merge_ok(xs, norm: torch.nn.Module, reduction: torch.nn.Module, H: int, W: int) -> bool:
+    """may ``PatchMergeFn`` serve this call?  Answered without a library call: 1 .. 9 contiguous CUDA streams (B, H*W, C) of one shape
+    and dtype, fp32 or the 16-bit compute dtype; C a multiple of 32 with 4C <= 2048, H and W even, fewer than 2^31 - 4096 merged rows;
+    ``norm`` an affine ``nn.LayerNorm`` over 4C and ``reduction`` a bias-free linear (2C, 4C), both with fp32 CUDA parameters and
+    without hooks."""
+    x = xs[0]
+    if not (1 <= len(xs) <= PATCH_MERGE_MAX_STREAMS and x.dim() == 3
+            and all(t.is_cuda and t.dtype == x.dtype and t.shape == x.shape and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in xs)):
+        return False
+    if x.dtype not in _HOT_DTYPES or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") not in _HOT_DTYPES):
+        return False
+    cdtype = compute_dtype(x)
+    B, Lt, C = x.shape
+    if cdtype == torch.float32 or x.dtype not in (torch.float32, cdtype):
+        return False
+    if not (_ln_module_ok(norm, last_dim_only=True) and norm.normalized_shape[0] == 4 * C and norm.weight.is_cuda
+            and not _module_hooked(norm)):
+        return False
+    w = getattr(reduction, "weight", None)
+    if not (isinstance(reduction, torch.nn.Linear) and reduction.bias is None and w is not None and w.is_cuda
+            and w.dtype == torch.float32 and w.shape == (2 * C, 4 * C) and w.is_contiguous() and not _module_hooked(reduction)):
+        return False
+    return (Lt == H * W and H % 2 == 0 and W % 2 == 0 and H > 0 and W > 0 and C % 32 == 0 and 4 * C <= PATCH_MERGE_MAX_K
+            and len(xs) * B * (H // 2) * (W // 2) < 2 ** 31 - 4096)
+
+
+def _patch_merge_desc(n: int, B: int, H: int, W: int, C: int, x_dtype, cdtype, eps: float, max_groups: int) -> "L.PatchMergeDesc":
+    d = L.PatchMergeDesc()
+    d.B, d.n, d.H, d.W, d.C = B, n, H, W, C
+    d.x_dtype, d.dtype, d.eps, d.max_groups = L._DT[x_dtype], L._DT[cdtype], float(eps), max_groups
+    return d
+
+
+def _ptr_list(ts) -> "ctypes.Array":
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+class PatchMergeFn(torch.autograd.Function):
+    """stacked (n*B, H*W/4, 2C) = PatchMerging of the n streams (B, H*W, C) by one ``mtlora_patch_merge_fwd`` launch, in ``cdtype``.
+    ``gamma``, ``beta`` (4C) and ``weight`` (2C, 4C) are the fp32 masters; their gradients come back in fp32 from
+    ``mtlora_patch_merge_bwd`` (three launches, no atomics, no host read; the scratch is sized by the library's query), the streams'
+    gradients in the streams' dtype.  Saves the streams, mean and rstd per merged row, and the parameters.  ``max_groups``: a cap on
+    the workgroups (0: none).  args: gamma, beta, weight, eps, H, W, cdtype, max_groups, *streams"""
+
+    @staticmethod
+    def forward(ctx, gamma, beta, weight, eps: float, H: int, W: int, cdtype, max_groups: int, *xs):
+        L.require_gpu(gamma, beta, weight, *xs)
+        xs = [x.contiguous() for x in xs]
+        n, (B, Lt, C) = len(xs), xs[0].shape
+        M = n * B * Lt // 4
+        g, be = _ln_affine(gamma, beta)
+        w = _f32_param(weight)
+        d = _patch_merge_desc(n, B, H, W, C, xs[0].dtype, cdtype, eps, max_groups)
+        y = torch.empty((n * B, Lt // 4, 2 * C), dtype=cdtype, device=xs[0].device)
+        stats = torch.empty((2, M), dtype=torch.float32, device=xs[0].device)
+        st = L.lib().mtlora_patch_merge_fwd(ctypes.byref(d), _ptr_list(xs), L.ptr(g), L.ptr(be), L.ptr(w), L.ptr(y), L.ptr(stats),
+                                            L.ptr(stats[1]), L.stream_ptr())
+        L.check(st, "mtlora_patch_merge_fwd")
+        ctx.save_for_backward(g, be, w, stats, *xs)
+        ctx.desc, ctx.MC, ctx.dtypes = d, (M, C), (gamma.dtype, beta.dtype, weight.dtype, cdtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        g, be, w, stats, *xs = ctx.saved_tensors
+        d, (M, C) = ctx.desc, ctx.MC
+        need = ctx.needs_input_grad
+        dy = _canon_grad(gy, (M, 2 * C), ctx.dtypes[3])
+        lib = L.lib()
+        sb = lib.mtlora_patch_merge_bwd_scratch_bytes(ctypes.byref(d))
+        scratch = _scratch(sb, dy.device, "patch merging shape (n, B, H, W, C)", d.n, d.B, d.H, d.W, C, floor=16)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dy.device)  # noqa: E731
+        dw = new(2 * C, 4 * C) if need[2] else None
+        dg, dbe = new(4 * C), new(4 * C)
+        dxs = [torch.empty_like(x) for x in xs]
+        st = lib.mtlora_patch_merge_bwd(ctypes.byref(d), _ptr_list(xs), L.ptr(g), L.ptr(be), L.ptr(w), L.ptr(stats), L.ptr(stats[1]),
+                                        L.ptr(dy), _ptr_list(dxs), L.ptr(dw), L.ptr(dg), L.ptr(dbe), L.ptr(scratch), sb, L.stream_ptr())
+        L.check(st, "mtlora_patch_merge_bwd")
+        gdt, bdt, wdt, _ = ctx.dtypes
+        return (dg.to(gdt) if need[0] else None, dbe.to(bdt) if need[1] else None, dw.to(wdt) if need[2] else None,
+                None, None, None, None, None, *dxs)
+
+
+def patch_merge(xs, norm: torch.nn.Module, reduction: torch.nn.Module, H: int, W: int, max_groups: int = 0) -> torch.Tensor:
+    """stacked ``reduction(norm(2x2 concat))`` of the streams for a call ``patch_merge_ok`` accepts, in the compute dtype (what
+    the separate steps return)"""
+    return PatchMergeFn.apply(norm.weight, norm.bias, reduction.weight, norm.eps, H, W, compute_dtype(xs[0]), max_groups, *xs)
+
+
+# ----------------------------------------------------------------------------------------------
 # decoder front end: the 1x1 convs of the stages' tokens + bilinear upsample + concat as ONE launch (csrc/decoder_front.hip)
 # ----------------------------------------------------------------------------------------------
 def decoder_front_torch(xs, ws, grids):

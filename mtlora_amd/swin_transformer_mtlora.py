@@ -46,6 +46,11 @@ _FUSED_BLOCKS = os.environ.get("MTLORA_FUSED_BLOCKS", "1") != "0"
 # are set from the separate steps' own error, miss them with it on
 PATCH_EMBED = os.environ.get("MTLORA_PATCH_EMBED", "0") == "1"
 
+# MTLORA_PATCH_MERGE=1: PatchMerging (2x2 gather, LayerNorm, reduction) through the one-launch kernel (functional.PatchMergeFn) when the
+# reduction is the plain linear; module attribute, read at every call.  Ships OFF, as PATCH_EMBED does: the oracle-parity tests are
+# calibrated on the separate steps
+PATCH_MERGE = os.environ.get("MTLORA_PATCH_MERGE", "0") == "1"
+
 
 def set_fused_blocks(on: bool) -> bool:
     """switch the one-call-per-block path (functional.SwinBlockRunFn) on / off; returns the previous setting"""
@@ -587,14 +592,25 @@ class PatchMerging(nn.Module):
         assert H % 2 == 0 and W % 2 == 0, f"x size ({H}*{W}) are not even."
         # rows of the normalised matrix = 2x2 neighbourhoods, channel order [x(0,0), x(1,0), x(0,1), x(1,1)] as the
         # reference's cat; gathered by the LayerNorm kernel itself (no strided copy forward, no scatter copy backward)
+        if self._fused([x]):
+            return Fn.patch_merge([x], self.norm, self.reduction, H, W)
         y, _ = self.reduction(Fn.layer_norm_merge(self.norm, x, H, W))
         return y
+
+    def _fused(self, xs) -> bool:
+        """gather, LayerNorm and reduction of the streams in one launch (``Fn.PatchMergeFn``): the switch is on, the reduction is the
+        plain bias-free linear, and the kernels take the call"""
+        H, W = self.input_resolution
+        return (PATCH_MERGE and type(self.reduction) is CompatLinear and self.reduction.bias is None and not Fn._module_hooked(self)
+                and Fn.patch_merge_ok(xs, self.norm, self.reduction, H, W))
 
     def forward_residual_multi(self, res, branches, drop_prob, training, drop=None):
         """merging of (res_k + DropPath(branches_k)) for the shared + task streams: residual, 2x2 gather and LayerNorm in one
         launch, one reduction GEMM; falls back to residual kernel + ``forward_multi``.  ``drop``: a pending activation dropout of the
         branches (``Fn.residual_droppath``): the residual kernel applies it, then ``forward_multi``."""
         H, W = self.input_resolution
+        if self._fused(list(res)):  # the residuals first (their own kernel), then the one-launch merge of ``forward_multi``
+            return self.forward_multi(Fn.residual_droppath(list(res), list(branches), drop_prob, training, drop))
         stacked = None if drop is not None else Fn.residual_merge_norm_streams(self.norm, res, branches, H, W, drop_prob, training)
         if stacked is None:
             return self.forward_multi(Fn.residual_droppath(list(res), list(branches), drop_prob, training, drop))
@@ -605,6 +621,10 @@ class PatchMerging(nn.Module):
         """the shared tensor and the task tensors through the same merging in ONE LayerNorm launch and ONE reduction GEMM
         (stacked along the batch); falls back to per-tensor calls when the fused kernel does not apply."""
         H, W = self.input_resolution
+        xs = list(xs)
+        if self._fused(xs):
+            y = Fn.patch_merge(xs, self.norm, self.reduction, H, W)
+            return list(y.view(len(xs), -1, *y.shape[1:]).unbind(0))
         stacked = Fn.layer_norm_merge_multi(self.norm, xs, H, W) if len(xs) > 1 else None
         if stacked is None:
             return [self.forward(x) for x in xs]
