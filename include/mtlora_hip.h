@@ -265,6 +265,20 @@ int mtlora_mlp_hid_bwd(const mtlora_linear_desc* d1, const mtlora_linear_desc* d
                        const void* ctx1, const void* ctx2, const void* scratch2, void* scratch1, void* g, float* const* dB1_t,
                        float* const* dA2_t, void* part, int64_t part_bytes, void* stream);
 
+/* The same Mlp for task ranks 16 .. 128 (csrc/hid_wide.h): the ranks are the k steps and n tiles of v_mfma_f32_32x32x16.  Same call
+ * sequence, arguments and results as the mtlora_mlp_hid_* entries above, with these in their place.  Supported: 16-bit dtype, mode
+ * 'matrix', has_x_tasks on both layers, 1 <= T <= 8, d1->N == d2->K a multiple of 128 (any width), every r_t of both layers a multiple
+ * of 16 in [16, 128] (they may differ between tasks and layers); anything else: MTLORA_ERR_UNSUPPORTED (-1 from the size queries)
+ * before any launch.  Deterministic (fixed-order partial sums, no atomics). */
+int mtlora_mlp_hidr_supported(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2);
+int64_t mtlora_mlp_hidr_fwd_scratch_bytes(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2);
+int64_t mtlora_mlp_hidr_bwd_scratch_bytes(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2);
+int mtlora_mlp_hidr_proj(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2, const void* h_base, const void* ctx1,
+                         void* ctx2, void* scratch, int64_t scratch_bytes, void* stream);
+int mtlora_mlp_hidr_bwd(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2, const void* h_base, const void* dh_s,
+                        const void* ctx1, const void* ctx2, const void* scratch2, void* scratch1, void* g, float* const* dB1_t,
+                        float* const* dA2_t, void* part, int64_t part_bytes, void* stream);
+
 /* Weight gradient of a plain linear layer with a NARROW output (the decoder heads' final 1x1 convolutions,
  * models/seg_hrnet.py:518-526: nn.Conv2d(1080, num_classes, 1) on B*H*W pixels; autograd's dW = dY^T X):
  *   out (Na x Nb, fp32, row-major) = a^T b,  a = (M x Na, row stride lda), b = (M x Nb, row stride ldb).

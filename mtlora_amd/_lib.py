@@ -208,6 +208,12 @@ _SIGS = {
     "mtlora_mlp_hid_proj": (c_int, [POINTER(LinearDesc), POINTER(LinearDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mtlora_mlp_hid_bwd": (c_int, [POINTER(LinearDesc), POINTER(LinearDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int64, c_void_p]),
+    "mtlora_mlp_hidr_supported": (c_int, [POINTER(LinearDesc), POINTER(LinearDesc)]),
+    "mtlora_mlp_hidr_fwd_scratch_bytes": (c_int64, [POINTER(LinearDesc), POINTER(LinearDesc)]),
+    "mtlora_mlp_hidr_bwd_scratch_bytes": (c_int64, [POINTER(LinearDesc), POINTER(LinearDesc)]),
+    "mtlora_mlp_hidr_proj": (c_int, [POINTER(LinearDesc), POINTER(LinearDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mtlora_mlp_hidr_bwd": (c_int, [POINTER(LinearDesc), POINTER(LinearDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int64, c_void_p]),
     "mtlora_window_attn_bwd_scratch_bytes": (c_int64, [POINTER(AttnDesc)]),
     "mtlora_window_attn_fwd": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mtlora_window_attn_bwd": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

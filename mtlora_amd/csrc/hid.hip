@@ -895,3 +895,5 @@ MTL_INTERNAL void mtli_hid_rows_finish(int dtype, const float* rowpart, int n_ch
 MTL_INTERNAL void mtli_hid_reduce(const HidRedParams* r, int64_t per, void* stream) {
     hipLaunchKernelGGL(k_hid_reduce, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *r);
 }
+
+#include "hid_wide.h"  // k_hidr_*: task ranks 16 .. 128

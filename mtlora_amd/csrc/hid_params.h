@@ -64,3 +64,40 @@ struct HidLaunch {
     int nthr, n_wg;  // threads per workgroup, workgroups
     size_t lds;      // dynamic LDS bytes (MFMA forms)
 };
+
+// ---- wide ranks (hid_wide.h, k_hidr_*): every r_t a multiple of 16 in [16, 128]; the ranks are MFMA k steps / n tiles
+constexpr int HIDR_MAXT = 8;      // tasks of one forward launch (MTLORA_MAX_TASKS)
+constexpr int HIDR_HC = 128;      // backward: hidden columns per workgroup (4 waves x 32)
+constexpr int HIDR_RS = 132;      // backward: fp32 row stride of the Q1 table in LDS (128 rank columns + 4: 16-byte rows off the bank period)
+
+struct HidrFwdParams {
+    const void* hbase;    // (M x H)
+    const void* p1;       // (M x ld1)  P of fc1
+    void* p2;             // (M x ld2)  P of fc2: task t owns columns [off2[t], off2[t] + r2[t])
+    const void* b1;       // (H x ld1)  b_cat of fc1: row c = B1[c, :], unscaled
+    const void* a2;       // (ld2 x H)  a_cat of fc2: row rr = A2[rr, :], unscaled
+    const float* alpha2;  // (ld2)
+    int64_t M;
+    int H, nt, ld1, ld2;
+    int off1[HIDR_MAXT], r1[HIDR_MAXT], off2[HIDR_MAXT], r2[HIDR_MAXT];
+};
+struct HidrBwdParams {    // ONE task per launch
+    const void* hbase;    // (M x H)
+    const void* p1;       // (M x ld1)  P of fc1
+    const void* q2;       // (M x ld2)  Q of fc2
+    const void* gsrc;     // (M x H) dH_s for the first task, the running G after it
+    void* g;              // (M x H) out
+    const void* b1;       // (H x ld1)  b_cat of fc1
+    const void* b1t;      // (ld1 x H)  bt_cat of fc1
+    const void* a2t;      // (H x ld2)  at_cat of fc2
+    float* part;          // [chunk][workgroup][r1 + r2][HIDR_HC]: rows < r1 dB1^T, the rest dA2
+    float* rowpart;       // [chunk][M][r1]: unscaled Q1 row sums of the chunk's columns
+    int64_t M;
+    int H, ld1, ld2, off1, r1, off2, r2;
+};
+struct HidrRedParams {
+    const float* part;
+    int n_wg, H, r1, r2;
+    float* dB1;           // (H x r1) row-major, nullable
+    float* dA2;           // (r2 x H) row-major, nullable
+};

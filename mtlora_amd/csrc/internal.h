@@ -31,3 +31,13 @@ MTL_INTERNAL void mtli_hid_launch(const HidLaunch* L, const HidParams* q, void* 
 MTL_INTERNAL void mtli_hid_rows_finish(int dtype, const float* rowpart, int n_chunk, int64_t M, int nt, const float* alpha, const int* off,
                                        void* out, int ldo, void* stream);
 MTL_INTERNAL void mtli_hid_reduce(const HidRedParams* r, int64_t per, void* stream);
+
+// k_hidr_* (hid_wide.h, compiled into hid.hip): the same streams for task ranks 16 .. 128
+struct HidrFwdParams;
+struct HidrBwdParams;
+struct HidrRedParams;
+MTL_INTERNAL void mtli_hidr_fwd(int dtype, const HidrFwdParams* q, int n_wg, void* stream);
+MTL_INTERNAL void mtli_hidr_bwd(int dtype, const HidrBwdParams* q, int n_wg, int n_chunk, void* stream);
+MTL_INTERNAL void mtli_hidr_rows_finish(int dtype, const float* rowpart, int n_chunk, int64_t M, int r1, const float* alpha, void* out, int ldo,
+                                        void* stream);
+MTL_INTERNAL void mtli_hidr_reduce(const HidrRedParams* r, void* stream);

@@ -1942,9 +1942,198 @@ static int hid_bwd_impl(const mtlora_linear_desc* d1, const mtlora_linear_desc* 
     return MTLORA_OK;
 }
 
+// ---- the same Mlp with task ranks 16 .. 128 (hid_wide.h): shape rules, launch geometry, the two entries.  hid_check and the entries
+// above keep their shape rules; these are reached through their own exports (mtlora_mlp_hidr_*).
+static int hidr_check(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2) {
+    int st = check_desc(d1);
+    if (st != MTLORA_OK) return st;
+    st = check_desc(d2);
+    if (st != MTLORA_OK) return st;
+    if (!mtl_dtype_in(d1->dtype, MTL_DT_16) || d1->dtype != d2->dtype) return MTLORA_ERR_UNSUPPORTED;
+    if (d1->M != d2->M || d1->N != d2->K || d1->T != d2->T || d1->T < 1 || d1->T > HIDR_MAXT) return MTLORA_ERR_UNSUPPORTED;
+    if (d1->mode != 0 || d2->mode != 0 || !d1->has_x_tasks || !d2->has_x_tasks) return MTLORA_ERR_UNSUPPORTED;
+    if (d1->N % HIDR_HC != 0 || d1->M <= 0) return MTLORA_ERR_UNSUPPORTED;
+    for (int t = 0; t < d1->T; ++t)
+        for (int r : {d1->r_t[t], d2->r_t[t]})
+            if (r < 16 || r > 128 || r % 16 != 0) return MTLORA_ERR_UNSUPPORTED;
+    return MTLORA_OK;
+}
+struct HidrPlan {
+    int n_chunk, n_wg_f, n_wg_b, rmax1, rrmax;
+    int64_t part_bytes, rowpart_bytes;
+};
+static HidrPlan hidr_plan(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2) {
+    HidrPlan pl = {};
+    const Tune tu = make_tune(d1);
+    const int64_t nblk = (d1->M + 31) / 32;
+    pl.n_chunk = (int)(d1->N / HIDR_HC);
+    // forward: one wave per workgroup, up to 8 per CU (~150 registers each).  backward: one 4-wave workgroup per CU (its accumulators
+    // take the whole register file), at least four row blocks each so that the fp32 factor partials stay a small part of the traffic
+    pl.n_wg_f = (int)std::min<int64_t>(nblk, (int64_t)num_cu(tu) * 8);
+    pl.n_wg_b = (int)std::max<int64_t>(1, std::min<int64_t>((nblk + 3) / 4, num_cu(tu) / pl.n_chunk));
+    for (int t = 0; t < d1->T; ++t) {
+        pl.rmax1 = std::max(pl.rmax1, d1->r_t[t]);
+        pl.rrmax = std::max(pl.rrmax, d1->r_t[t] + d2->r_t[t]);
+    }
+    pl.part_bytes = mtl_round_up((int64_t)pl.n_chunk * pl.n_wg_b * pl.rrmax * HIDR_HC * 4, 256);
+    pl.rowpart_bytes = mtl_round_up((int64_t)pl.n_chunk * d1->M * pl.rmax1 * 4, 256);
+    return pl;
+}
+
+template <typename T>
+static int hidr_proj_impl(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2, const void* h_base, const void* ctx1, void* ctx2,
+                          hipStream_t s) {
+    const Segs s1 = make_segs(d1), s2 = make_segs(d2);
+    const CtxLayout L1 = ctx_layout(d1, s1), L2 = ctx_layout(d2, s2);
+    const unsigned char* c1 = reinterpret_cast<const unsigned char*>(ctx1);
+    const unsigned char* pk1 = d1->packed ? reinterpret_cast<const unsigned char*>(d1->packed) : c1;
+    const unsigned char* pk2 = reinterpret_cast<const unsigned char*>(d2->packed);
+    const HidrPlan pl = hidr_plan(d1, d2);
+    HidrFwdParams q = {};
+    q.hbase = h_base;
+    q.p1 = c1 + L1.p;
+    q.p2 = reinterpret_cast<unsigned char*>(ctx2) + L2.p;
+    q.b1 = pk1 + L1.b_cat;
+    q.a2 = pk2 + L2.a_cat;
+    q.alpha2 = reinterpret_cast<const float*>(pk2 + L2.alpha);
+    q.M = d1->M;
+    q.H = (int)d1->N;
+    q.nt = d1->T;
+    q.ld1 = s1.R;
+    q.ld2 = s2.R;
+    double rsum = 0.0;
+    for (int t = 0; t < d1->T; ++t) {
+        q.off1[t] = s1.off[1 + t];
+        q.r1[t] = d1->r_t[t];
+        q.off2[t] = s2.off[1 + t];
+        q.r2[t] = d2->r_t[t];
+        rsum += q.r1[t] + q.r2[t];
+    }
+    mtl_prof_tag("hidr_fwd M%lld H%d T%d", (long long)d1->M, q.H, d1->T);
+    // (bytes: h_base once per task, P1 in, P2 out; flops: the two rank products)
+    MtlProfScope prof(PK_NT_FWD_P, (double)sizeof(T) * d1->M * ((double)d1->T * q.H + rsum), s, (double)sizeof(T) * d1->M * (double)d1->T * q.H,
+                      2.0 * d1->M * (double)q.H * rsum);
+    mtli_hidr_fwd(d1->dtype, &q, pl.n_wg_f, s);
+    return MTLORA_OK;
+}
+
+template <typename T>
+static int hidr_bwd_impl(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2, const void* h_base, const void* dh_s, const void* ctx1,
+                         const void* ctx2, const void* scratch2, void* scratch1, void* g, float* const* dB1_t, float* const* dA2_t, void* part,
+                         hipStream_t s) {
+    const Segs s1 = make_segs(d1), s2 = make_segs(d2);
+    const CtxLayout L1 = ctx_layout(d1, s1), L2 = ctx_layout(d2, s2);
+    const BwdScratch S1 = bwd_scratch(d1, s1), S2 = bwd_scratch(d2, s2);
+    const unsigned char* c1 = reinterpret_cast<const unsigned char*>(ctx1);
+    const unsigned char* c2 = reinterpret_cast<const unsigned char*>(ctx2);
+    const unsigned char* pk1 = d1->packed ? reinterpret_cast<const unsigned char*>(d1->packed) : c1;
+    const unsigned char* pk2 = d2->packed ? reinterpret_cast<const unsigned char*>(d2->packed) : c2;
+    const HidrPlan pl = hidr_plan(d1, d2);
+    const int H = (int)d1->N;
+    for (int t = 0; t < d1->T; ++t) {  // one task per launch: its factor accumulators fill the registers; G is carried in place
+        HidrBwdParams q = {};
+        q.hbase = h_base;
+        q.p1 = c1 + L1.p;
+        q.q2 = reinterpret_cast<const unsigned char*>(scratch2) + S2.q;
+        q.gsrc = t == 0 ? dh_s : g;
+        q.g = g;
+        q.b1 = pk1 + L1.b_cat;
+        q.b1t = pk1 + L1.bt_cat;
+        q.a2t = pk2 + L2.at_cat;
+        q.part = reinterpret_cast<float*>(part);
+        q.rowpart = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(part) + pl.part_bytes);
+        q.M = d1->M;
+        q.H = H;
+        q.ld1 = s1.R;
+        q.ld2 = s2.R;
+        q.off1 = s1.off[1 + t];
+        q.r1 = d1->r_t[t];
+        q.off2 = s2.off[1 + t];
+        q.r2 = d2->r_t[t];
+        {
+            mtl_prof_tag("hidr_bwd M%lld H%d t%d r%d/%d", (long long)d1->M, H, t, q.r1, q.r2);
+            const double hb = (double)sizeof(T) * d1->M * H;
+            MtlProfScope prof(PK_NT_BWD_DX, 3.0 * hb + 4.0 * pl.n_chunk * d1->M * q.r1, s, hb, 2.0 * d1->M * (double)H * (3.0 * q.r1 + 2.0 * q.r2));
+            mtli_hidr_bwd(d1->dtype, &q, pl.n_wg_b, pl.n_chunk, s);
+        }
+        {
+            mtl_prof_tag("hidr_rows_finish M%lld chunks%d r%d", (long long)d1->M, pl.n_chunk, q.r1);
+            MtlProfScope prof(PK_REDUCE, 0.0, s);
+            const float* alpha1 = reinterpret_cast<const float*>(pk1 + L1.alpha) + q.off1;
+            T* q1 = reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(scratch1) + S1.q) + q.off1;
+            mtli_hidr_rows_finish(d1->dtype, q.rowpart, pl.n_chunk, d1->M, q.r1, alpha1, q1, s1.R, s);
+        }
+        HidrRedParams r = {};
+        r.part = q.part;
+        r.n_wg = pl.n_wg_b;
+        r.H = H;
+        r.r1 = q.r1;
+        r.r2 = q.r2;
+        r.dB1 = dB1_t ? dB1_t[t] : nullptr;
+        r.dA2 = dA2_t ? dA2_t[t] : nullptr;
+        if (r.dB1 || r.dA2) {
+            mtl_prof_tag("hidr_reduce H%d wg%d r%d/%d", H, pl.n_wg_b, q.r1, q.r2);
+            MtlProfScope prof(PK_REDUCE, 0.0, s);
+            mtli_hidr_reduce(&r, s);
+        }
+    }
+    return MTLORA_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mtlora_mlp_hidr_supported(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2) {
+    return (d1 && d2 && hidr_check(d1, d2) == MTLORA_OK) ? 1 : 0;
+}
+
+int64_t mtlora_mlp_hidr_fwd_scratch_bytes(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2) {
+    if (!d1 || !d2 || hidr_check(d1, d2) != MTLORA_OK) return -1;
+    return 256;  // (the forward kernel finishes its rows in registers; the argument is kept for the shared call shape)
+}
+
+int64_t mtlora_mlp_hidr_bwd_scratch_bytes(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2) {
+    if (!d1 || !d2 || hidr_check(d1, d2) != MTLORA_OK) return -1;
+    const HidrPlan pl = hidr_plan(d1, d2);
+    return pl.part_bytes + pl.rowpart_bytes + 256;
+}
+
+int mtlora_mlp_hidr_proj(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2, const void* h_base, const void* ctx1, void* ctx2,
+                         void* scratch, int64_t scratch_bytes, void* stream) {
+    if (!d1 || !d2) return MTLORA_ERR_NULL;
+    const int st = hidr_check(d1, d2);
+    if (st != MTLORA_OK) return st;
+    if (mtl_any_null({h_base, ctx1, ctx2, d2->packed, scratch})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({h_base, ctx1, ctx2, d2->packed, d1->packed, scratch})) return MTLORA_ERR_ALIGN;
+    if (scratch_bytes < 256) return MTLORA_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int r = mtl_dispatch_dtype16(d1->dtype, [&](auto t) { return hidr_proj_impl<typename decltype(t)::type>(d1, d2, h_base, ctx1, ctx2, s); });
+    if (r != MTLORA_OK) return r;
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
+
+int mtlora_mlp_hidr_bwd(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2, const void* h_base, const void* dh_s, const void* ctx1,
+                        const void* ctx2, const void* scratch2, void* scratch1, void* g, float* const* dB1_t, float* const* dA2_t, void* part,
+                        int64_t part_bytes, void* stream) {
+    if (!d1 || !d2) return MTLORA_ERR_NULL;
+    const int st = hidr_check(d1, d2);
+    if (st != MTLORA_OK) return st;
+    if (mtl_any_null({h_base, ctx1, ctx2, scratch1, scratch2, g, part})) return MTLORA_ERR_NULL;
+    if (mtl_any_misaligned({h_base, dh_s, ctx1, ctx2, scratch1, scratch2, g, part, d1->packed, d2->packed}, d1->T,
+                           {mtl_arr(dB1_t), mtl_arr(dA2_t)}))
+        return MTLORA_ERR_ALIGN;
+    const HidrPlan pl = hidr_plan(d1, d2);
+    if (part_bytes < pl.part_bytes + pl.rowpart_bytes + 256) return MTLORA_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int r = mtl_dispatch_dtype16(d1->dtype, [&](auto t) {
+        return hidr_bwd_impl<typename decltype(t)::type>(d1, d2, h_base, dh_s, ctx1, ctx2, scratch2, scratch1, g, dB1_t, dA2_t, part, s);
+    });
+    if (r != MTLORA_OK) return r;
+    MTL_CHECK_LAUNCH();
+    return MTLORA_OK;
+}
 
 int mtlora_mlp_hid_supported(const mtlora_linear_desc* d1, const mtlora_linear_desc* d2) {
     return (d1 && d2 && hid_check(d1, d2) == MTLORA_OK) ? 1 : 0;

@@ -823,6 +823,26 @@ def mlp_hid_supported(meta1: "LinearMeta", meta2: "LinearMeta", M: int) -> bool:
     return bool(_size_query("hid_ok", L.lib().mtlora_mlp_hid_supported, meta1.desc(M), meta2.desc(M)))
 
 
+# task ranks 16 .. 128 (csrc/hid_wide.h, mtlora_mlp_hidr_*): opt-in -- the whole-model references of the configurations with such ranks
+# were calibrated on the per-layer path
+_MLP_HID_WIDE = os.environ.get("MTLORA_MLP_HID_WIDE", "0") == "1"
+
+
+def mlp_hid_wide_enabled() -> bool:
+    return _MLP_HID_WIDE
+
+
+def set_mlp_hid_wide(on: bool) -> bool:
+    """switch the implicit-task-hiddens path for task ranks 16 .. 128 on / off (default off); returns the old value"""
+    global _MLP_HID_WIDE
+    old, _MLP_HID_WIDE = _MLP_HID_WIDE, bool(on)
+    return old
+
+
+def mlp_hidr_supported(meta1: "LinearMeta", meta2: "LinearMeta", M: int) -> bool:
+    return bool(_size_query("hidr_ok", L.lib().mtlora_mlp_hidr_supported, meta1.desc(M), meta2.desc(M)))
+
+
 def _ensure_packed(meta: "LinearMeta", A_s, B_s, A_t, B_t, device) -> None:
     """the k_hid kernels read the layers' packed factors: a layer without a current FactorPacker buffer packs into a per-call one"""
     if meta.packed is not None:
@@ -883,11 +903,13 @@ class MlpHidFn(torch.autograd.Function):
         L.check(st, "mtlora_linear_fwd_gelu (fc1, implicit task hiddens)")
         d1.hid, d1.hid_ptr = 0, 0
         # the task columns of fc2's P straight from h_base and P1
-        fb = _size_query("hid_fwd", lib.mtlora_mlp_hid_fwd_scratch_bytes, d1, d2)
+        wide = _MLP_HID_WIDE and bool(_size_query("hidr_ok", lib.mtlora_mlp_hidr_supported, d1, d2))  # (ranks 16 .. 128: hid_wide.h)
+        f_bytes, f_proj = ((lib.mtlora_mlp_hidr_fwd_scratch_bytes, lib.mtlora_mlp_hidr_proj) if wide else
+                           (lib.mtlora_mlp_hid_fwd_scratch_bytes, lib.mtlora_mlp_hid_proj))
+        fb = _size_query("hidr_fwd" if wide else "hid_fwd", f_bytes, d1, d2)
         fscr = _scratch(fb, dev, "Mlp shape (M, K, hidden, N) for implicit task hiddens", M, meta1.K, H, meta2.N)
-        st = lib.mtlora_mlp_hid_proj(ctypes.byref(d1), ctypes.byref(d2), L.ptr(h_base), L.ptr(ctx1), L.ptr(ctx2), L.ptr(fscr), fb,
-                                     L.stream_ptr())
-        L.check(st, "mtlora_mlp_hid_proj")
+        st = f_proj(ctypes.byref(d1), ctypes.byref(d2), L.ptr(h_base), L.ptr(ctx1), L.ptr(ctx2), L.ptr(fscr), fb, L.stream_ptr())
+        L.check(st, "mtlora_mlp_hidr_proj" if wide else "mtlora_mlp_hid_proj")
         oshape = (*lead, meta2.N)
         ys = torch.empty(oshape, dtype=dt, device=dev)
         yt = [torch.empty(oshape, dtype=dt, device=dev) for _ in range(T)]
@@ -895,7 +917,7 @@ class MlpHidFn(torch.autograd.Function):
         st = lib.mtlora_linear_fwd(ctypes.byref(d2), L.ptr(a_s), L.ptr_array(None), L.ptr(W2c), L.ptr(b2), L.ptr(f2[0]), L.ptr(f2[1]),
                                    L.ptr_array(f2[2]), L.ptr_array(f2[3]), L.ptr(ys), L.ptr_array(yt), L.ptr(ctx2), cb2, L.stream_ptr())
         L.check(st, "mtlora_linear_fwd (fc2, implicit task hiddens)")
-        ctx.meta1, ctx.meta2, ctx.lead, ctx.M = meta1, meta2, lead, M
+        ctx.meta1, ctx.meta2, ctx.lead, ctx.M, ctx.wide = meta1, meta2, lead, M, wide
         ctx.in_dtypes = [x.dtype] + [t.dtype for t in x_t]
         ctx.save_for_backward(x2, W1t, W2t, ctx1, ctx2, h_s, a_s, h_base, *xt2)
         ctx.factor_params = (A1_s, B1_s, *A1_t, *B1_t, A2_s, B2_s, *A2_t, *B2_t)
@@ -917,7 +939,9 @@ class MlpHidFn(torch.autograd.Function):
         d1, d2 = meta1.desc(M), meta2.desc(M)
         sb1 = _size_query("bwd", lib.mtlora_linear_bwd_scratch_bytes, d1)
         sb2 = _size_query("bwd", lib.mtlora_linear_bwd_scratch_bytes, d2)
-        pb = _size_query("hid_bwd", lib.mtlora_mlp_hid_bwd_scratch_bytes, d1, d2)
+        b_bytes, b_hid = ((lib.mtlora_mlp_hidr_bwd_scratch_bytes, lib.mtlora_mlp_hidr_bwd) if ctx.wide else
+                          (lib.mtlora_mlp_hid_bwd_scratch_bytes, lib.mtlora_mlp_hid_bwd))
+        pb = _size_query("hidr_bwd" if ctx.wide else "hid_bwd", b_bytes, d1, d2)
         scratch1 = _scratch(sb1, dev, "Mlp backward shape (M, K, hidden)", M, meta1.K, H)
         scratch2 = _scratch(sb2, dev, "Mlp backward shape (M, hidden, N)", M, H, meta2.N)
         part = _scratch(pb, dev, "Mlp backward shape (M, K, hidden, N) for implicit task hiddens", M, meta1.K, H, meta2.N)
@@ -950,10 +974,9 @@ class MlpHidFn(torch.autograd.Function):
             L.check(st, "mtlora_linear_bwd_gelu (fc2, implicit task hiddens)")
 
         def hid(stream_ptr):  # G = dh_s + sum_t dH_t, Q1 task columns, dB1_t, dA2_t
-            st = lib.mtlora_mlp_hid_bwd(ctypes.byref(d1), ctypes.byref(d2), L.ptr(h_base), L.ptr(dh_s), L.ptr(ctx1), L.ptr(ctx2),
-                                        L.ptr(scratch2), L.ptr(scratch1), L.ptr(G), L.ptr_array(dB1_t), L.ptr_array(dA2_t), L.ptr(part), pb,
-                                        stream_ptr)
-            L.check(st, "mtlora_mlp_hid_bwd")
+            st = b_hid(ctypes.byref(d1), ctypes.byref(d2), L.ptr(h_base), L.ptr(dh_s), L.ptr(ctx1), L.ptr(ctx2), L.ptr(scratch2),
+                       L.ptr(scratch1), L.ptr(G), L.ptr_array(dB1_t), L.ptr_array(dA2_t), L.ptr(part), pb, stream_ptr)
+            L.check(st, "mtlora_mlp_hidr_bwd" if ctx.wide else "mtlora_mlp_hid_bwd")
 
         def fc1(phase, stream_ptr):  # dx, dx_t [phase 1]; dA1_s, dB1_s, dA1_t [phase 2]
             d1.bwd_phase = phase

@@ -155,7 +155,10 @@ class Mlp(nn.Module):
             return None
         # (shape rules first: ``hid_call`` draws the layers' dropout seeds)
         H, r1, r2 = self.fc1.linear.out_features, self.fc1._ranks, self.fc2._ranks
-        if H % 128 or any(not (1 <= r1.get(t, 0) <= 8 and 1 <= r2.get(t, 0) <= 8) for t in tasks):  # (width limits: mlp_hid_supported)
+        narrow = all(1 <= r1.get(t, 0) <= 8 and 1 <= r2.get(t, 0) <= 8 for t in tasks)  # (width limits: mlp_hid_supported)
+        wide = (Fn.mlp_hid_wide_enabled() and len(tasks) <= 8  # (ranks 16 .. 128, opt-in: mlp_hidr_supported)
+                and all(r.get(t, 0) % 16 == 0 and 16 <= r.get(t, 0) <= 128 for r in (r1, r2) for t in tasks))
+        if H % 128 or not (narrow or wide):
             return None
         c1 = self.fc1.hid_call(dtype, x.device)
         c2 = self.fc2.hid_call(dtype, x.device) if c1 is not None else None
@@ -163,7 +166,7 @@ class Mlp(nn.Module):
             return None
         (m1, (W1c, W1t, b1), f1), (m2, (W2c, W2t, b2), f2) = c1, c2
         M = x.numel() // m1.K
-        if not Fn.mlp_hid_supported(m1, m2, M):
+        if not (Fn.mlp_hidr_supported(m1, m2, M) if wide else Fn.mlp_hid_supported(m1, m2, M)):
             return None
         outs = Fn.MlpHidFn.apply(m1, m2, x, W1c, W1t, b1, W2c, W2t, b2, f1[0], f1[1], f2[0], f2[1], *xt, *f1[2], *f1[3], *f2[2], *f2[3])
         return outs[0], {t: outs[1 + i] for i, t in enumerate(tasks)}
